@@ -12,10 +12,12 @@ the rank's batch: samples already resident in HBM -> STFT -> KL-NMF -> GCC-PHAT 
 GCC-NMF masks -> reconstruction -> iSTFT/OLA -> separated waveforms in HBM.  Files are independent,
 so ranks share nothing on the data path (weak scaling, no collective inside the timed region).
 
-Prints ONE JSON line (rank 0).  `value` is the bench contract's rate (inputs resident in HBM when the timed region starts);
-`sec8d_host_to_host` is SURVEY 8(d)'s metric (host samples in -> host waveforms out, 8 batches pipelined); `roofline` times the
-dominant kernel live with HIP events on the launch stream; `cpu_baseline` times the NumPy oracle (a port of the reference) on
-one file at the best of a few BLAS thread counts.
+Prints ONE JSON line (rank 0).  `value` is the bench contract's rate (inputs resident in HBM when the timed region starts).
+A plain run only sets up, warms up, times the steps and prints that line.  With `--full` the line also carries everything else
+the benchmark measures: `sec8d_host_to_host` is SURVEY 8(d)'s metric (host samples in -> host waveforms out, 8 batches pipelined);
+`roofline` times the dominant kernel live with HIP events on the launch stream; `cpu_baseline` times the NumPy oracle (a port of
+the reference) on one file at the best of a few BLAS thread counts; the other BASELINE configurations are timed in sub-records.
+`--dump-outputs DIR` writes what the last timed step computed as .npy files (see dump_outputs).
 """
 import argparse
 import json
@@ -55,7 +57,46 @@ def parse():
     p.add_argument('--h-updates', type=int, default=2, help='streaming mode: KL-NMF coefficient updates per frame (W fixed)')
     p.add_argument('--mode', choices=['separate', 'shared-dictionary', 'streaming', 'time-sharded'], default='separate',
                    help="'separate' = the headline path (independent dictionary per file); 'shared-dictionary' = BASELINE config 4; 'streaming' = config 5; 'time-sharded' = ONE long mixture (--seconds, default 160 s there) sharded over frame windows, strong scaling")
-    return p.parse_args()
+    p.add_argument('--full', action='store_true',
+                   help='also run every measurement and check beyond the headline figure (roofline kernel, host-to-host, single file, drop-in, '
+                        'mixed lengths, the other BASELINE configurations, CPU baseline, live HBM traffic); the --skip-* options prune these')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help="after the timed steps, write what the last one computed as DIR/<name>.npy ('separate' mode; rank 0's files)")
+    a = p.parse_args()
+    if a.steps < 1:
+        p.error('--steps must be at least 1')
+    if a.dump_outputs and a.mode != 'separate':
+        p.error("--dump-outputs writes the outputs of the 'separate' mode only")
+    return a
+
+
+DUMP_BUDGET_BYTES = 40 << 20          # the waveform sample of --dump-outputs; with the index files it writes well under 64 MB
+
+
+def dump_outputs(d, e, seed=0):
+    """--dump-outputs: what the timed path handed its caller in the last step -- the separated waveforms `e.y` (files, targets, 2, samples)
+    and the TDOA indexes -- as .npy files in `d`, well under 64 MB in all:
+      waveforms.npy        float32, the waveforms of the files listed in waveform_files.npy, all of them if they fit in DUMP_BUDGET_BYTES,
+                           else a fixed seeded choice of files (and, should one file alone not fit, of sample positions: waveform_samples.npy)
+      waveform_files.npy   float64, which files (index in the batch) waveforms.npy holds
+      waveform_rms.npy     float64 (files, targets, 2), RMS of every waveform of the batch
+      tdoa_indexes.npy     float64 (files, targets), the target TDOA indexes of every file"""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    y = e.y
+    B, per_file = y.shape[0], y[0].numel() * y.element_size()
+    files = np.arange(B) if B * per_file <= DUMP_BUDGET_BYTES else np.sort(rng.choice(B, max(1, DUMP_BUDGET_BYTES // per_file), replace=False))
+    sample = y[torch.from_numpy(files).to(y.device)]
+    if per_file > DUMP_BUDGET_BYTES:
+        L = y.shape[-1]
+        cols = np.sort(rng.choice(L, DUMP_BUDGET_BYTES // (per_file // L), replace=False))
+        sample = sample[..., torch.from_numpy(cols).to(y.device)]
+        np.save(os.path.join(d, 'waveform_samples.npy'), cols.astype(np.float64))
+    np.save(os.path.join(d, 'waveforms.npy'), sample.float().cpu().numpy())
+    np.save(os.path.join(d, 'waveform_files.npy'), files.astype(np.float64))
+    np.save(os.path.join(d, 'waveform_rms.npy'), y.double().square().mean(dim=-1).sqrt().cpu().numpy())
+    np.save(os.path.join(d, 'tdoa_indexes.npy'), e.get_tdoa_indexes().astype(np.float64))
 
 
 def live_traffic(a, timeout_s=150, chained=False):
@@ -632,7 +673,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     e.check_status()
-    idx_ok = bool((e.get_tdoa_indexes() == np.array([27, 59, 91])).all()) if a.seconds == 10.0 else None
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, e)
 
     frames = world * B * g.T * a.steps
     out = {
@@ -641,14 +683,16 @@ def main():
         'ms_per_step': 1e3 * elapsed / a.steps, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
         'dtype': 'f32', 'data': 'synthetic',
         'config': {'workload': 'HBM-resident (float32 samples in HBM -> separated float32 waveforms in HBM; the host-to-host rates are '
-                               'the host_to_host_* fields): %d x %.0f s stereo @16 kHz synthetic mixtures per GPU (SURVEY 8d recipe), '
+                               'the host_to_host_* fields of a --full run): %d x %.0f s stereo @16 kHz synthetic mixtures per GPU (SURVEY 8d recipe), '
                                '1024-pt FFT hop %d (F=513, T=%d/file), K=%d, %d KL-NMF iters, 128 TDOAs, 3 targets, independent '
                                'dictionary per file' % (B, a.seconds, a.hop, g.T, K, iters),
                    'files_per_gpu': B, 'frames_per_file': g.T, 'dictionary_size': K, 'nmf_iterations': iters,
                    'parallelism': 'file-sharded x%d, no data-path collective' % world,
                    'nmf_file_groups_per_gpu': e.nmf_groups},
-        'tdoa_indexes_as_expected': idx_ok, 'ranks_seen': ranks_seen,
+        'ranks_seen': ranks_seen,
     }
+    if a.full:
+        out['tdoa_indexes_as_expected'] = bool((e.get_tdoa_indexes() == np.array([27, 59, 91])).all()) if a.seconds == 10.0 else None
     # the whole path against the f32-MFMA roofline -- algorithmic flop per stereo frame (NMF 16 F K iters + STFT,
     # angular spectrum, scores, reconstruction, iSTFT) / peak; per GPU, so the fraction holds at any N
     flop_per_frame = 16.0 * g.F * K * iters + 2 * 5 * 1024 * 10 + 2.0 * 128 * 2 * g.F + 3 * 2.0 * g.F * K + 3 * 2 * 2.0 * g.F * K + 3 * 2 * 5 * 1024 * 10
@@ -656,7 +700,9 @@ def main():
     out['end_to_end_vs_mfma_roofline'] = {'flop_per_frame': flop_per_frame, 'ceiling_frames_per_s_per_gpu': ceiling,
                                           'frac': frames / elapsed / world / ceiling}
 
-    if rank == 0 and not a.skip_extras:
+    # --full: everything beyond the headline figure, after it is measured (and after --dump-outputs has saved the timed step's results)
+    extras, roofline = a.full and not a.skip_extras, a.full and not a.skip_roofline
+    if rank == 0 and extras:
         # host float32 samples in -> host float32 waveforms out (PCIe both ways); reported beside `value`, never as `value`
         e.separate(xs)                                           # allocates the page-locked staging buffers (slow, once per engine)
         t1 = time.perf_counter()
@@ -678,7 +724,7 @@ def main():
                                      'single_batch_unpipelined': out['host_to_host_frames_per_s'],
                                      'hbm_resident': frames / elapsed / world}
 
-    if rank == 0 and not a.skip_roofline:
+    if rank == 0 and roofline:
         traffic_file = os.path.join(REPO, 'profiles', 'pmc_traffic.json')
         pmc = json.load(open(traffic_file)) if os.path.exists(traffic_file) else None
         iter_ms, k3_ms, chain_call_ms = kernel_timings(e)
@@ -726,7 +772,7 @@ def main():
         out['nmf_iteration_one_stream'] = {'ms': float(iter_ms), 'tflops': 4 * gemm_flop / (iter_ms * 1e-3) / 1e12,
                                            'frac_of_peak': 4 * gemm_flop / (iter_ms * 1e-3) / 1e12 / F32_MFMA_PEAK_TFLOPS}
 
-    if rank == 0 and world == 1 and not a.skip_extras:
+    if rank == 0 and world == 1 and extras:
         # the same parameters on ONE mixture (BASELINE config 2's shape): latency-bound, small-batch GEMM tile
         e1 = GCCNMFEngine(n, sampleRate=sr, windowSize=1024, hopSize=a.hop, numTDOAs=128, microphoneSeparationInMetres=1.0,
                           numTargets=3, dictionarySize=K, numIterations=iters, batch=1, device='cuda:%d' % local_rank)
@@ -744,7 +790,7 @@ def main():
                               # different GEMM tile (launch-size dependent) -> different summation grouping, not bitwise equal
                               'waveform_rms_vs_in_batch': float(np.sqrt(np.mean((e1.y[0].cpu().numpy().astype(np.float64) - e.y[0].cpu().numpy()) ** 2)))}
 
-    if rank == 0 and world == 1 and not a.skip_extras:
+    if rank == 0 and world == 1 and extras:
         # the drop-in route: the reference-named host-array function (NumPy V in -> NumPy W, H out), as runGCCNMF.py calls it
         from gcc_nmf_amd import gccNMFFunctions as G
         V0 = e.get_V()[0]
@@ -755,7 +801,7 @@ def main():
                                       'what': 'gcc_nmf_amd.gccNMFFunctions.performKLNMF(V (%d, %d) ndarray, %d, %d, 0): host arrays in and out'
                                               % (g.F, g.N, K, iters)}
 
-    if rank == 0 and world == 1 and not a.skip_extras and (K, a.hop) != (128, 128):
+    if rank == 0 and world == 1 and extras and (K, a.hop) != (128, 128):
         # the reference driver's OWN call (gccNMF/runGCCNMF.py:41,60: dictionarySize = 128, hopSize = 128 -> performKLNMF(V (513, 2486), 128, 100, 0)),
         # one mixture alone, next to the headline shape: what `python runGCCNMF.py` on top of dropin.install() spends on the device
         e2 = GCCNMFEngine(n, sampleRate=sr, windowSize=1024, hopSize=128, numTDOAs=128, microphoneSeparationInMetres=1.0,
@@ -778,7 +824,7 @@ def main():
                                          'dropin_performKLNMF_ms': 1e3 * (time.perf_counter() - t1)}
         del e2
 
-    if rank == 0 and world == 1 and not a.skip_extras and (K, iters, a.seconds) == (1024, 100, 10.0):
+    if rank == 0 and world == 1 and extras and (K, iters, a.seconds) == (1024, 100, 10.0):
         # the whole drop-in sequence, function by function, host arrays in and out: the reference driver's own shape and BASELINE config 2's,
         # in the default (copying) mode and in the opt-in resident mode of dropin.install(resident=True)
         out['dropin_sequence'] = {
@@ -787,7 +833,7 @@ def main():
             'driver_shape_hop128_K128': {'copying': dropin_sequence(dev1_mixture(), sr, 128, 128), 'resident': dropin_sequence(dev1_mixture(), sr, 128, 128, resident=True)},
             'config2_hop256_K1024': {'copying': dropin_sequence(dev1_mixture(), sr, 256, 1024), 'resident': dropin_sequence(dev1_mixture(), sr, 256, 1024, resident=True)}}
 
-    if rank == 0 and world == 1 and not a.skip_extras and (K, iters, a.hop, a.seconds) == (1024, 100, 256, 10.0):
+    if rank == 0 and world == 1 and extras and (K, iters, a.hop, a.seconds) == (1024, 100, 256, 10.0):
         # mixtures of DIFFERENT lengths in one batch (runGCCNMF.py:30-36 takes a file of any length): 21 x 5 s + 21 x 10 s + 22 x 15 s, KL-NMF over
         # all 64 files in one ragged chained launch, against the equal-length rate of this run at (nearly) the same total frames
         from gcc_nmf_amd.engine import RaggedGCCNMFEngine
@@ -813,12 +859,12 @@ def main():
                                         '(gccnmf_klnmf_ragged: per-file column tiles, files dealt out to the XCDs by length), the one-shot stages per length'}
         del er
 
-    if rank == 0 and world == 1 and not a.skip_extras and not a.skip_config_lines and (K, iters, a.hop, a.seconds) == (1024, 100, 256, 10.0):
+    if rank == 0 and world == 1 and extras and not a.skip_config_lines and (K, iters, a.hop, a.seconds) == (1024, 100, 256, 10.0):
         t1 = time.perf_counter()
         out.update(config_lines(a, e, xs, sr, n, local_rank))
         out['config_lines_seconds'] = time.perf_counter() - t1
 
-    if rank == 0 and world == 1 and not a.skip_cpu_baseline and not a.skip_extras:
+    if rank == 0 and world == 1 and not a.skip_cpu_baseline and extras:
         from oracle import gccnmf_oracle as O                                # the checker, timed as the CPU baseline
         from threadpoolctl import threadpool_info, threadpool_limits
         threads = max([i.get('num_threads', 1) for i in threadpool_info()] or [1])
@@ -867,7 +913,7 @@ def main():
         out['gpu_vs_cpu_waveform_rms'] = float(np.sqrt(np.mean((y0.astype(np.float64) - r['y']) ** 2)))
         out['gpu_vs_cpu_tdoa_equal'] = bool(e.get_tdoa_indexes()[0].tolist() == r['idx'])
 
-    if rank == 0 and world == 1 and 'roofline' in out and not slabs and not a.skip_extras and not a.no_live_traffic:
+    if rank == 0 and world == 1 and 'roofline' in out and not slabs and extras and not a.no_live_traffic:
         # LAST, with every other number already in `out` and this process idle on the device: the kernel's HBM traffic from the counters
         torch.cuda.synchronize()
         rec, note = live_traffic(a, chained='k3_alone' in out['roofline'])

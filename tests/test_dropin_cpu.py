@@ -1,6 +1,6 @@
 """The reference's own driver, byte-for-byte unchanged, running on top of this package's module names
-(SURVEY.md 8b).  Needs the reference checkout, so it runs only in the build container; the hot functions are
-stubbed with the oracle here (no GPU in this container) -- what is under test is the interception mechanics:
+(SURVEY.md 8b).  Needs the reference's driver, which build() stages under oracle/_ref/ where a checkout is readable; the hot
+functions are stubbed with the oracle here (no GPU in this container) -- what is under test is the interception mechanics:
 every hot-path call of runGCCNMF.py must land in gcc_nmf_amd.gccNMFFunctions.  The same driver run with the
 real HIP functions is tests/test_gpu_kernels.py::test_reference_call_sequence_dropin's call sequence."""
 import os
@@ -9,14 +9,15 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import golden
+from conftest import REPO, golden
 
-REF = os.environ.get('GCCNMF_REFERENCE_ROOT', '/root/reference')
+# the copy build() stages in git-ignored oracle/_ref/ (oracle/stage_reference.py), as test_gpu_pipeline.py's driver test
+REF = os.environ.get('GCCNMF_REFERENCE_ROOT', os.path.join(REPO, 'oracle', '_ref', 'reference_checkout'))
 HOT = ['computeComplexMixtureSpectrogram', 'performKLNMF', 'getAngularSpectrogram', 'estimateTargetTDOAIndexesFromAngularSpectrum',
        'getTargetTDOAGCCNMFs', 'getTargetCoefficientMasks', 'getTargetSpectrogramEstimates', 'getTargetSignalEstimates']
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF, 'gccNMF', 'runGCCNMF.py')), reason='reference checkout not present')
+@pytest.mark.skipif(not os.path.exists(os.path.join(REF, 'gccNMF', 'runGCCNMF.py')), reason='no staged reference driver (build() stages it where a reference checkout is readable)')
 def test_unmodified_reference_driver_lands_in_this_package(tmp_path, monkeypatch):
     pytest.importorskip('matplotlib')
     from scipy.io import wavfile

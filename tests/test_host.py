@@ -338,12 +338,45 @@ def test_bench_contract_defaults_and_loud_failure_without_gpu(monkeypatch):
     a = bench.parse()
     assert (a.gpus, a.files, a.dictionary_size, a.iterations, a.hop, a.seconds, a.mode) == (1, 64, 1024, 100, 256, 10.0, 'separate')
     assert 1 <= a.steps <= 10 and a.warmup >= 1 and a.nmf_groups is None
+    assert not a.full and a.dump_outputs is None                 # a plain run measures the headline figure only
     assert bench.F32_MFMA_PEAK_TFLOPS == 157.3
     if not torch.cuda.is_available():
         from gcc_nmf_amd._hip import HipLibraryError
         from gcc_nmf_amd.engine import GCCNMFEngine
         with pytest.raises(HipLibraryError):
             GCCNMFEngine(160000, dictionarySize=1024, batch=1)
+
+
+def test_bench_dump_outputs_are_seeded_and_bounded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the last step's waveforms (all files when they fit the budget, else the same seeded choice of files on
+    every run, else of sample positions too) plus every file's waveform RMS and TDOA indexes, as float32 / float64 .npy files."""
+    import importlib
+    import sys
+    import types
+    import torch
+    monkeypatch.setattr(sys, 'argv', ['bench.py'])
+    bench = importlib.import_module('bench')
+    y = torch.randn(5, 3, 2, 1000, generator=torch.Generator().manual_seed(3))
+    idx = np.arange(15, dtype=np.int32).reshape(5, 3)
+    e = types.SimpleNamespace(y=y, get_tdoa_indexes=lambda: idx)
+    per_file = 3 * 2 * 1000 * 4
+
+    def dump(d, budget):
+        monkeypatch.setattr(bench, 'DUMP_BUDGET_BYTES', budget)
+        bench.dump_outputs(str(tmp_path / d), e)
+        return dict((f[:-4], np.load(str(tmp_path / d / f))) for f in os.listdir(str(tmp_path / d)))
+    full, a, b, c = dump('full', 5 * per_file), dump('a', 2 * per_file), dump('b', 2 * per_file), dump('c', per_file // 4)
+    for out in (full, a, b, c):
+        assert out['waveforms'].dtype == np.float32 and all(v.dtype == np.float64 for k, v in out.items() if k != 'waveforms')
+        assert np.allclose(out['waveform_rms'], y.double().square().mean(-1).sqrt().numpy()) and np.array_equal(out['tdoa_indexes'], idx)
+    assert full['waveform_files'].tolist() == [0, 1, 2, 3, 4] and np.array_equal(full['waveforms'], y.numpy()) and 'waveform_samples' not in full
+    files = a['waveform_files'].astype(int)
+    assert len(files) == 2 and list(files) == sorted(set(files)) and all(np.array_equal(a[k], b[k]) for k in a)
+    assert np.array_equal(a['waveforms'], y.numpy()[files])
+    cols = c['waveform_samples'].astype(int)
+    assert c['waveforms'].shape == (1, 3, 2, 250) and np.array_equal(c['waveforms'][0], y.numpy()[int(c['waveform_files'][0])][..., cols])
+    # the headline shape (64 files x 3 targets x 2 x 158976 samples): what --dump-outputs writes stays below 64 MB
+    assert bench.DUMP_BUDGET_BYTES + 8 * (64 + 2 * 64 * 3 * 2) + 8 * bench.DUMP_BUDGET_BYTES // 24 < 64 << 20
 
 
 def test_fft_size_limits_are_named():
