@@ -38,7 +38,9 @@ __global__ __launch_bounds__(256) void ang_mean_kernel(const float* __restrict__
 }
 
 // Strict local maxima (scipy.signal.argrelmax, order 1: edges never qualify, NaN never compares greater),
-// keep the S largest, ascending index order.  One 64-thread block per file; D <= 4096.
+// keep the S largest, ascending index order.  Among peaks of equal height the LARGER index is kept: the reference keeps
+// peakIndexes[argsort(values)[-S:]], and a stable ascending sort puts the larger of two equal values last.
+// One 64-thread block per file; D <= 4096.
 __global__ __launch_bounds__(64) void pick_peaks_kernel(const double* __restrict__ mean_ang, int D, int Dp, int S,
                                                         int* __restrict__ tdoa_idx, int* __restrict__ status) {
     __shared__ double v[4096];
@@ -49,8 +51,8 @@ __global__ __launch_bounds__(64) void pick_peaks_kernel(const double* __restrict
     __syncthreads();
     for (int i = threadIdx.x; i < D; i += 64) is_peak[i] = (i > 0 && i < D - 1 && v[i] > v[i - 1] && v[i] > v[i + 1]) ? 1 : 0;
     __syncthreads();
-    // top-S peaks: S rounds of a 64-lane arg-max over the peaks still standing (largest value, smallest index on ties -- the order
-    // the serial scan this replaces produced; that scan cost 33 us of a single-mixture run)
+    // top-S peaks: S rounds of a 64-lane arg-max over the peaks still standing (largest value, largest index on ties; a serial scan
+    // cost 33 us of a single-mixture run)
     __shared__ int s_found;
     if (threadIdx.x == 0) s_found = 0;
     __syncthreads();
@@ -58,7 +60,7 @@ __global__ __launch_bounds__(64) void pick_peaks_kernel(const double* __restrict
         double bv = 0.0;
         int bi = -1;
         for (int i = 1 + threadIdx.x; i < D - 1; i += 64)
-            if (is_peak[i] == 1 && (bi < 0 || v[i] > bv)) {
+            if (is_peak[i] == 1 && (bi < 0 || v[i] >= bv)) {
                 bv = v[i];
                 bi = i;
             }
@@ -66,7 +68,7 @@ __global__ __launch_bounds__(64) void pick_peaks_kernel(const double* __restrict
         for (int o = 32; o > 0; o >>= 1) {
             const double ov = __shfl_xor(bv, o);
             const int oi = __shfl_xor(bi, o);
-            if (oi >= 0 && (bi < 0 || ov > bv || (ov == bv && oi < bi))) {
+            if (oi >= 0 && (bi < 0 || ov > bv || (ov == bv && oi > bi))) {
                 bv = ov;
                 bi = oi;
             }

@@ -234,7 +234,7 @@ int gccnmf_angular_spectrogram(const float* CC, const float* trig, int F, int T,
                                double* mean_ang, void* stream);
 
 /* Peak picking on the mean angular spectrum: strict local maxima (edges excluded), keep the
- * S largest, ascending order.  Replaces estimateTargetTDOAIndexesFromAngularSpectrum
+ * S largest (the larger index among equal heights), ascending order.  Replaces estimateTargetTDOAIndexesFromAngularSpectrum
  * (gccNMFFunctions.py:94-116) for numSources > 0.
  *   tdoa_idx [batch][S] int32 out; status [batch] int32 out (0 ok, 1 = fewer than S peaks) */
 int gccnmf_pick_tdoa_peaks(const double* mean_ang, int D, int Dp, int S, int batch, int* tdoa_idx, int* status,

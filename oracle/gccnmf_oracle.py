@@ -203,7 +203,9 @@ def estimateTargetTDOAIndexesFromAngularSpectrum(angularSpectrum, microphoneSepa
     peakIndexes = argrelmax(angularSpectrum)[0]
     if not numSources:
         raise ValueError('numSources must be given (the reference KMeans branch is a NameError)')
-    sourcePeakIndexes = peakIndexes[np.argsort(angularSpectrum[peakIndexes])[-numSources:]]
+    # kind='stable': the default argsort promises no order among equal values (a SIMD sort on some hosts), so it does not define which
+    # of two tied peaks is kept; a stable sort keeps the larger index, as the reference did with the numpy it was written for
+    sourcePeakIndexes = peakIndexes[np.argsort(angularSpectrum[peakIndexes], kind='stable')[-numSources:]]
     if len(sourcePeakIndexes) != numSources:
         raise ValueError('found %d peaks, need %d' % (len(sourcePeakIndexes), numSources))
     return sorted(sourcePeakIndexes)

@@ -106,22 +106,28 @@ class GCCNMFProcessorOracle(object):
         self.targetTDOAIndex, self.targetTDOAEpsilon = np.float32(targetTDOAIndex), np.float32(targetTDOAEpsilon)
         self.targetTDOABeta, self.targetTDOANoiseFloor = np.float32(targetTDOABeta), np.float32(targetTDOANoiseFloor)
 
-    def coefficientMask(self, realGCC):
-        """:259-265 -- GCC-NMF scores (TDOA, time, atom), arg-max over TDOA, soft or boxcar window around the target."""
-        gccNMF = np.dot(realGCC.T, self.W)                               # (D, Tc, K) float32
-        argmaxTDOA = np.argmax(gccNMF, axis=0).T                         # (K, Tc) int64, first maximum wins
+    def coefficientMask(self, realGCC, argmax_override=None):
+        """:259-265 -- GCC-NMF scores (TDOA, time, atom), arg-max over TDOA, soft or boxcar window around the target.
+        ``argmax_override`` (K, Tc): evaluate the mask under another implementation's arg-max instead (tests: the stages after a
+        near-tie decision, conditioned on the device's own decision)."""
+        if argmax_override is None:
+            gccNMF = np.dot(realGCC.T, self.W)                           # (D, Tc, K) float32
+            argmaxTDOA = np.argmax(gccNMF, axis=0).T                     # (K, Tc) int64, first maximum wins
+        else:
+            argmaxTDOA = np.asarray(argmax_override).astype(np.int64)
         distance = np.abs(argmaxTDOA - self.targetTDOAIndex)             # int64 - float32 -> float64
         if self.targetMode == TARGET_MODE_BOXCAR:
             return np.where(distance < self.targetTDOAEpsilon, 1.0, 0.0), argmaxTDOA
         return np.exp(-(distance / self.targetTDOAEpsilon) ** self.targetTDOABeta) / (1 + self.targetTDOANoiseFloor) + self.targetTDOANoiseFloor, argmaxTDOA
 
-    def processFrames(self, windowedSamples, return_intermediates=False):
-        """:201-231.  windowedSamples (2, windowSize, Tc) -> processed frames (2, windowSize, Tc)."""
+    def processFrames(self, windowedSamples, return_intermediates=False, argmax_override=None):
+        """:201-231.  windowedSamples (2, windowSize, Tc) -> processed frames (2, windowSize, Tc).  argmax_override: see
+        coefficientMask."""
         X = rfft(windowedSamples * self.windowFunction, axis=1).astype(np.complex64)                # :202 (no conjugate)
         coherenceV = X[0] * X[1].conj() / np.abs(X[0]) / np.abs(X[1])                                # :253
         realGCC = (coherenceV[:, :, np.newaxis] * self.expJOmegaTau[:, np.newaxis]).real             # :254,206 (F, Tc, D)
         if self.separationEnabled:
-            HMask, argmaxTDOA = self.coefficientMask(realGCC)                                        # (K, Tc)
+            HMask, argmaxTDOA = self.coefficientMask(realGCC, argmax_override)                       # (K, Tc)
             if self.numHUpdates == 0:
                 recSource = np.dot(self.W, HMask)                                                    # :267
                 recV = np.sum(self.W, axis=-1)                                                       # :268

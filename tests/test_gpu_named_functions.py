@@ -6,7 +6,7 @@ import pytest
 
 from conftest import golden, mask_flips
 from oracle import gccnmf_oracle as O
-from test_gpu_pipeline import TIE_LIMIT, live_gaps, rel
+from test_gpu_pipeline import TIE_LIMIT, check_after_masks, live_gaps, rel
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
@@ -100,8 +100,7 @@ def test_named_functions_with_non_default_parameters(dropin_mode):
     assert np.abs(r['G'] - o['G']).max() < 1e-4 * np.abs(o['G']).max()
     flipped = np.argmax(r['M'], 0) != np.argmax(o['M'], 0)
     assert (live_gaps(o['G'])[flipped] < TIE_LIMIT).all(), int(flipped.sum())
-    if not flipped.any():
-        assert np.abs(r['S'] - o['S']).max() < 1e-4 * np.abs(o['S']).max()
+    check_after_masks(r['S'], r['y'], np.argmax(r['M'], 0), r['X'], r['W'], r['H'], o, 1024, 256)
     assert r['y'].shape == o['y'].shape == (2, 2, 256 * (r['X'].shape[2] - 1))
     rms = np.sqrt(np.mean((r['y'].astype(np.float64) - o['y']) ** 2))
     assert rms < 1e-6, rms

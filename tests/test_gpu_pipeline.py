@@ -3,6 +3,7 @@ live oracle, and size-independent properties at the benchmark shape."""
 import numpy as np
 import pytest
 
+import gcc_checks
 from conftest import golden, golden_wav, mask_flips
 from oracle import gccnmf_oracle as O
 
@@ -22,8 +23,10 @@ TIE_LIMIT = 1e-4
 
 
 def live_gaps(G):
-    """relative top-2 gap of oracle scores G (S, K, T) -> (K, T)"""
+    """relative top-2 gap of oracle scores G (S, K, T) -> (K, T); inf with one target (nothing to flip to)"""
     srt = np.sort(np.asarray(G, np.float64), axis=0)
+    if len(srt) < 2:
+        return np.full(srt.shape[1:], np.inf)
     return (srt[-1] - srt[-2]) / np.maximum(np.abs(srt[-1]), 1e-300)
 
 
@@ -39,6 +42,24 @@ def rel(a, b):
 def engine(n, **kw):
     from gcc_nmf_amd.engine import GCCNMFEngine
     return GCCNMFEngine(n, **kw)
+
+
+def check_after_masks(spec, y, argmax, X, W, H, ref, windowSize, hopSize, spec_tol=1e-4, y_tol=1e-6):
+    """The stages after the coefficient masks of one file, compared twice, both always:
+    (a) under the device's own decisions and intermediates: the oracle's getTargetSpectrogramEstimates of the device's arg-max (one-hot),
+        X, W and H against the device's spectrogram, and the oracle's inverse STFT of the device's spectrogram against its waveforms;
+    (b) against the oracle's own run ``ref`` on every frame where no atom's target flipped -- and most frames must be compared.
+    spec (S, 2, F, T), y (S, 2, L), argmax (K, T), X (2, F, T), W (F, K), H (K, 2T)."""
+    S = spec.shape[0]
+    onehot = np.stack([(argmax == i) for i in range(S)]).astype(np.float32)
+    est = O.getTargetSpectrogramEstimates(onehot, X, W, np.array(np.hsplit(H, 2)))
+    assert np.abs(spec - est).max() < spec_tol * np.abs(est).max()
+    yc = O.getTargetSignalEstimates(spec, windowSize, hopSize, np.hanning)
+    rms = np.sqrt(np.mean((y.astype(np.float64) - yc) ** 2))
+    assert rms < y_tol, rms
+    ok = ~(argmax != np.argmax(ref['M'], 0)).any(axis=0)
+    assert 2 * ok.sum() > ok.size, (int(ok.sum()), ok.size)
+    assert np.abs(spec[..., ok] - ref['S'][..., ok]).max() < spec_tol * np.abs(ref['S']).max()
 
 
 @pytest.mark.parametrize('K', [128, 1024])
@@ -195,9 +216,44 @@ def test_synthetic_against_oracle_stagewise():
         assert np.abs(e.get_scores()[0] - r['G']).max() < 1e-4 * np.abs(r['G']).max()
         flipped = e.get_argmax()[0] != np.argmax(r['M'], 0)
         assert (live_gaps(r['G'])[flipped] < TIE_LIMIT).all(), (int(flipped.sum()), live_gaps(r['G'])[flipped].max())
-        if not flipped.any():
-            assert np.abs(e.get_spec()[0] - r['S']).max() < 1e-4 * np.abs(r['S']).max()
+        check_after_masks(e.get_spec()[0], y, e.get_argmax()[0], e.get_X()[0], W[0], H[0], r, 1024, 256)
         assert np.sqrt(np.mean((y.astype(np.float64) - r['y']) ** 2)) < 1e-6
+
+
+# windowSize (F = 129 ... 2049), numTDOAs, numTargets and K off the n_fft = 1024 / 128 TDOAs / 3 targets path: every value twice
+OFF_PATH = [  # (windowSize, hopSize, numTDOAs, numTargets, K)
+    (256, 128, 33, 1, 64), (256, 128, 200, 4, 200), (512, 256, 200, 1, 200), (512, 256, 33, 4, 64),
+    (2048, 512, 33, 4, 200), (2048, 512, 200, 1, 64), (4096, 1024, 200, 4, 64), (4096, 1024, 33, 1, 200),
+]
+
+
+@pytest.mark.parametrize('ws,hop,D,S,K', OFF_PATH, ids=['ws%d-hop%d-D%d-S%d-K%d' % c for c in OFF_PATH])
+def test_engine_against_oracle_off_the_1024_path(ws, hop, D, S, K):
+    """GCCNMFEngine against O.runGCCNMF (1.5 s, four sources, 10 iterations): TDOA indexes exact, W / H <= 1e-4, masks exact up to the
+    oracle's near-ties, the localisation GEMM on the device's own coherence, the stages after the masks both ways (check_after_masks)."""
+    n = 24000
+    x = O.synthetic_mixture(17, numSamples=n, delays=(-30, -12, 5, 24))
+    r = O.runGCCNMF(x, 16000, ws, hop, D, 1.0, S, dictionarySize=K, numIterations=10, return_intermediates=True)
+    e = engine(n, windowSize=ws, hopSize=hop, numTDOAs=D, numTargets=S, dictionarySize=K, numIterations=10)
+    y = e.separate(x)[0]
+    assert e.get_tdoa_indexes()[0].tolist() == r['idx']
+    W, H = e.get_WH()
+    assert rel(W[0], r['W']) < 1e-4 and rel(H[0], r['H']) < 1e-4, (rel(W[0], r['W']), rel(H[0], r['H']))
+    ang, meanA = e.get_angular()
+    C = e.get_C()[0].astype(np.complex128)
+    E = np.exp(np.outer(e.frequenciesInHz, -(2j * np.pi) * e.tdoasInSeconds))
+    absA = np.dot(np.abs(E.real).T, np.abs(C.real)) + np.dot(np.abs(E.imag).T, np.abs(C.imag))
+    gcc_checks.check_gemm_like(ang[0], np.dot(E.T, C).real, absA, 2 * (ws // 2 + 1), what='angular spectrogram')
+    gcc_checks.check_mean(meanA[0], ang[0])
+    G = e.get_scores()[0]
+    assert G.shape == r['G'].shape == (S, K, r['X'].shape[2])
+    am = e.get_argmax()[0]
+    flipped = am != np.argmax(r['M'], 0)
+    assert (live_gaps(r['G'])[flipped] < TIE_LIMIT).all(), (int(flipped.sum()), live_gaps(r['G'])[flipped].max())
+    check_after_masks(e.get_spec()[0], y, am, e.get_X()[0], W[0], H[0], r, ws, hop)
+    assert y.shape == r['y'].shape
+    rms = np.sqrt(np.mean((y.astype(np.float64) - r['y']) ** 2))
+    assert rms < 1e-5, rms
 
 
 def test_benchmark_batch_against_oracle():
