@@ -14,13 +14,31 @@
 //   rt_localize   gccPHAT[tau] = nanmean_f G, history ring, target = argmax nanmean(last L columns)   (:214-222)
 // NaN semantics follow the reference here (a zero-magnitude bin makes the frame's GCC-NMF scores NaN and its arg-max 0;
 // nanmean skips it), because the localisation history depends on them.
+//
+// Stream bank (frames_mode bit 3, include/gccnmf_hip.h): S independent streams of one configuration in the same launches, so that
+// one GPU serves many real-time sessions with the same six launches and one host sync per block (StreamingGCCNMFBank; config 5 at
+// S = 256: 0.59 ms per 4 ms block for all streams, 0.042 of one stream's device cost per stream; LABBOOK R7.1).  Stream s is
+// blockIdx.z of every kernel; each per-stream buffer holds S consecutive single-stream images and a kernel first moves its base pointers
+// to image s (64-bit offsets), so the arithmetic of one stream is that of the single-stream call, which is the S = 1 case.  The
+// per-stream switches are words 4 (separation) and 5 (localisation) of the stream's 8-word target row.
 #include "fft_core.h"
 
 typedef float rt_f32x16 __attribute__((ext_vector_type(16)));
 
-// ---- rt_shift: single workgroup, in-place left shift by B of both 8-block buffers ---------------------------
+#define RT_ROW 8                                           // bank layout: target row {index, eps, beta, noiseFloor, sep, loc, 0, 0}
+
+// rows = the bank's [S][RT_ROW] target rows, NULL outside the bank layout: true when this workgroup's stream has `word` switched off
+__device__ __forceinline__ bool rt_switched_off(const float* rows, int word) {
+    return rows && rows[(long)blockIdx.z * RT_ROW + word] == 0.f;
+}
+
+// ---- rt_shift: one workgroup per stream, in-place left shift by B of both 8-block buffers ---------------------------
 __global__ __launch_bounds__(1024) void rt_shift_kernel(float* __restrict__ in_ring, float* __restrict__ out_ring,
                                                         const float* __restrict__ block_in, int B, int ring) {
+    const long sid = blockIdx.z;
+    in_ring += sid * 2 * ring;
+    out_ring += sid * 2 * ring;
+    block_in += sid * 2 * B;
     // ring = 8*B samples per channel, 2 channels.  Chunks of 8192 values in ascending order, every thread loading everything it
     // will store before the barrier: a chunk reads at or above the positions it writes (never below), so no later chunk's stores can
     // reach what an earlier one still has to read -- any block size, one workgroup (the reference's buffers have no size limit,
@@ -51,7 +69,7 @@ __global__ __launch_bounds__(1024) void rt_shift_kernel(float* __restrict__ in_r
     }
 }
 
-// ---- rt_frames: grid = Tc, one analysis window per workgroup ----------------------------------------------------
+// ---- rt_frames: grid = (Tc, 1, S), one analysis window per workgroup ----------------------------------------------------
 __global__ __launch_bounds__(FFT_NT) void rt_frames_kernel(const float* __restrict__ in_ring, int ring, int N, int logN, int start0,
                                                            int start_step, int Tc, const float* __restrict__ window,
                                                            const float2* __restrict__ twiddle, float2* __restrict__ X,
@@ -62,6 +80,7 @@ __global__ __launch_bounds__(FFT_NT) void rt_frames_kernel(const float* __restri
     const int t = blockIdx.x;
     const int F = N / 2 + 1;
     const int start = start0 + t * start_step;            // ring mode: utils.py:105; frames mode: t * N
+    in_ring += (long)blockIdx.z * 2 * ring;
     for (int i = threadIdx.x; i < N / 2; i += FFT_NT) tw[i] = twiddle[i];
     for (int n = threadIdx.x; n < N; n += FFT_NT) {
         const float w = window[n];
@@ -69,19 +88,20 @@ __global__ __launch_bounds__(FFT_NT) void rt_frames_kernel(const float* __restri
     }
     __syncthreads();
     fft_stages<false, 1>(z, tw, N, logN, N);
+    const long cr0 = (long)blockIdx.z * F, xr0 = 2 * cr0;           // first row of this stream's image
     for (int f = threadIdx.x; f < F; f += FFT_NT) {
         const float2 zk = z[f], zn = z[(N - f) & (N - 1)];
         const float2 XL = make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y));     // rfft, NOT conjugated (:202)
         const float2 XR = make_float2(0.5f * (zk.y + zn.y), -0.5f * (zk.x - zn.x));
-        X[(long)f * Tc + t] = XL;
-        X[((long)F + f) * Tc + t] = XR;
+        X[(xr0 + f) * Tc + t] = XL;
+        X[(xr0 + F + f) * Tc + t] = XR;
         const float aL = hypotf(XL.x, XL.y), aR = hypotf(XR.x, XR.y);
         float re = XL.x * XR.x + XL.y * XR.y, im = XL.y * XR.x - XL.x * XR.y;
-        C[(long)f * Tc + t] = make_float2(re / aL / aR, im / aL / aR);                   // 0/0 -> NaN like the reference (:253)
+        C[(cr0 + f) * Tc + t] = make_float2(re / aL / aR, im / aL / aR);                   // 0/0 -> NaN like the reference (:253)
     }
 }
 
-// ---- rt_gccnmf: grid = (Kp/32, Tc); 32 atoms per workgroup, the 4 waves split the reduction over f ------------------------------
+// ---- rt_gccnmf: grid = (Kp/32, Tc, S); 32 atoms per workgroup, the 4 waves split the reduction over f ------------------------------
 // MFMA 32x32x2: A[i = tau][k = f] = G[f][tau] built on the fly from the steering tables, B[k = f][j = atom] = W[f][atom].
 // Latency matters here, not throughput (33.7 MFLOP per frame): the first version ran 16 workgroups with a 129-step chain of
 // dependent global loads (31 us).  Now each of 8 waves owns an eighth of the frequency rows (17 steps at n_fft = 512: ONE batch of
@@ -92,8 +112,14 @@ __global__ __launch_bounds__(FFT_NT) void rt_frames_kernel(const float* __restri
 __global__ __launch_bounds__(64 * RT_G_WAVES) void rt_gccnmf_kernel(const float2* __restrict__ C, const float* __restrict__ cosT,
                                                         const float* __restrict__ sinT, const float* __restrict__ W, int F, int K,
                                                         int Kp, int D, int Dp, int Tc, const float* __restrict__ target,
-                                                        int target_mode, float* __restrict__ HMask, int* __restrict__ argmaxTDOA) {
+                                                        int target_mode, int bank, float* __restrict__ HMask, int* __restrict__ argmaxTDOA) {
     __shared__ float s_part[RT_G_WAVES - 1][32][64];      // partial accumulators (two TDOA tiles) of the other waves
+    const long sid = blockIdx.z;
+    target += sid * RT_ROW;
+    if (bank && target[4] == 0.f) return;                 // this stream's separation is off
+    C += sid * F * Tc;
+    HMask += sid * Kp * Tc;
+    if (argmaxTDOA) argmaxTDOA += sid * Kp * Tc;
     const int t = blockIdx.y, k0 = blockIdx.x * 32;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, hh = lane >> 5;
@@ -189,12 +215,19 @@ __global__ __launch_bounds__(64 * RT_G_WAVES) void rt_gccnmf_kernel(const float2
     }
 }
 
-// ---- rt_tfmask: one wave per frequency row; grid = ceil(F/4) ------------------------------------------------------
+// ---- rt_tfmask: one wave per frequency row; grid = (ceil(F/4), 1, S) ------------------------------------------------------
+// (tfMask's per-stream image is [2][F][Tc] here too, the size the coefficient-inference mask needs)
 __global__ __launch_bounds__(256) void rt_tfmask_kernel(const float* __restrict__ W, const float* __restrict__ HMask, int F, int K,
-                                                        int Kp, int Tc, const float2* __restrict__ X, float2* __restrict__ Y, float* __restrict__ tfMask) {
+                                                        int Kp, int Tc, const float2* __restrict__ X, float2* __restrict__ Y, float* __restrict__ tfMask,
+                                                        const float* __restrict__ rows) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int f = blockIdx.x * 4 + wave;
-    if (f >= F) return;
+    if (f >= F || rt_switched_off(rows, 4)) return;
+    const long sid = blockIdx.z;
+    HMask += sid * Kp * Tc;
+    X += sid * 2 * F * Tc;
+    Y += sid * 2 * F * Tc;
+    tfMask += sid * 2 * F * Tc;
     const float* Wr = W + (long)f * Kp;
     float rec = 0.f;
     for (int k = lane; k < K; k += 64) rec += Wr[k];
@@ -215,15 +248,22 @@ __global__ __launch_bounds__(256) void rt_tfmask_kernel(const float* __restrict_
     }
 }
 
-// ---- rt_synth: single workgroup; frames in order (their output ranges overlap) ----------------------------------------
+// ---- rt_synth: one workgroup per stream; frames in order (their output ranges overlap) ----------------------------------------
+// Y = the spectra to synthesise; in the bank layout (rows != NULL) a stream whose separation is off takes X instead
 __global__ __launch_bounds__(FFT_NT) void rt_synth_kernel(const float2* __restrict__ Y, int N, int logN, int start0, int start_step,
                                                           int accumulate, int Tc, int ring, int B, int out_delay,
                                                           const float* __restrict__ window, const float2* __restrict__ twiddle,
-                                                          float* __restrict__ out_ring, float* __restrict__ block_out) {
+                                                          float* __restrict__ out_ring, float* __restrict__ block_out,
+                                                          const float2* __restrict__ X, const float* __restrict__ rows) {
     extern __shared__ __attribute__((aligned(16))) float2 rt_smem[];
     float2* z = rt_smem;
     float2* tw = rt_smem + N;
     const int F = N / 2 + 1;
+    const long sid = blockIdx.z;
+    if (rt_switched_off(rows, 4)) Y = X;
+    Y += sid * 2 * F * Tc;
+    out_ring += sid * 2 * ring;
+    block_out += sid * 2 * B;
     const float invN = 1.f / (float)N;
     for (int i = threadIdx.x; i < N / 2; i += FFT_NT) tw[i] = twiddle[i];
     for (int t = 0; t < Tc; ++t) {
@@ -264,7 +304,7 @@ __global__ __launch_bounds__(FFT_NT) void rt_synth_kernel(const float2* __restri
 // Off the powers of two the transform is evaluated as the sum it is, against a full-circle table (cos, sin)(2 pi k / N), k < N, computed
 // in float64 on the host: a frame is 2 x (N/2 + 1) x N complex MACs (N = 1000: 4 MFLOP) -- nothing on this chip, and no mixed-radix
 // machinery for a path whose defaults are powers of two.  The angle index f * n mod N advances by one addition and one compare.
-// rt_frames_dft: grid = (ceil(F / 64), Tc), 256 threads = 64 frequencies x 4 segments of n (partial sums added in segment order).
+// rt_frames_dft: grid = (ceil(F / 64), Tc, S), 256 threads = 64 frequencies x 4 segments of n (partial sums added in segment order).
 __global__ __launch_bounds__(256) void rt_frames_dft_kernel(const float* __restrict__ in_ring, int ring, int N, int start0, int start_step,
                                                             int Tc, const float* __restrict__ window, const float2* __restrict__ table,
                                                             float2* __restrict__ X, float2* __restrict__ C) {
@@ -274,6 +314,10 @@ __global__ __launch_bounds__(256) void rt_frames_dft_kernel(const float* __restr
     __shared__ float4 s_part[4][64];
     const int t = blockIdx.y, F = N / 2 + 1;
     const int start = start0 + t * start_step;
+    const long sid = blockIdx.z;
+    in_ring += sid * 2 * ring;
+    X += sid * 2 * F * Tc;
+    C += sid * F * Tc;
     for (int n = threadIdx.x; n < N; n += 256) {
         const float w = window[n];
         xw[n] = make_float2(w * in_ring[start + n], w * in_ring[ring + start + n]);
@@ -311,16 +355,23 @@ __global__ __launch_bounds__(256) void rt_frames_dft_kernel(const float* __restr
 }
 
 // rt_synth_dft: one thread per OUTPUT position of the buffer (both channels), frames in ascending order -- the reference's accumulation
-// order (utils.py:113-114), and no two threads ever add into the same sample.  grid = ceil(positions / 256); s_lo = first position.
+// order (utils.py:113-114), and no two threads ever add into the same sample.  grid = (ceil(positions / 256), 1, S); s_lo = first position.
+// X / rows: as for rt_synth.
 __global__ __launch_bounds__(256) void rt_synth_dft_kernel(const float2* __restrict__ Y, int N, int start0, int start_step, int accumulate,
                                                            int Tc, int ring, int B, int out_delay, int s_lo, const float* __restrict__ window,
                                                            const float2* __restrict__ table, float* __restrict__ out_ring,
-                                                           float* __restrict__ block_out) {
+                                                           float* __restrict__ block_out, const float2* __restrict__ X,
+                                                           const float* __restrict__ rows) {
     extern __shared__ __attribute__((aligned(16))) float2 rt_smem[];
     float2* tb = rt_smem;                  // [N]
     float2* ya = rt_smem + N;              // [F] left
     float2* yb = ya + (N / 2 + 1);         // [F] right
     const int F = N / 2 + 1, H = N / 2;
+    const long sid = blockIdx.z;
+    if (rt_switched_off(rows, 4)) Y = X;
+    Y += sid * 2 * F * Tc;
+    out_ring += sid * 2 * ring;
+    block_out += sid * 2 * B;
     const float invN = 1.f / (float)N;
     const int s = s_lo + blockIdx.x * 256 + threadIdx.x;
     const bool live = s < ring;
@@ -370,15 +421,23 @@ __global__ __launch_bounds__(256) void rt_synth_dft_kernel(const float2* __restr
     }
 }
 
-// ---- rt_localize: single workgroup of 1024 threads = Dq TDOAs x 1024/Dq frequency phases ---------------------------
-// hist is a [D][Lh] float ring with write position hist_pos[0]; target[0] is updated for the NEXT block (:216-222).
+// ---- rt_localize: one workgroup of 1024 threads per stream = Dq TDOAs x 1024/Dq frequency phases ---------------------------
+// hist is a [D][Lh] float ring with write position hist_pos[0]; target[0] is updated for the NEXT block (:216-222).  In the bank layout
+// a stream whose row word 5 is 0 fills its history and leaves its target index alone.
 __global__ __launch_bounds__(1024) void rt_localize_kernel(const float2* __restrict__ C, const float* __restrict__ cosT,
                                                            const float* __restrict__ sinT, int F, int D, int Dp, int Dq, int Tc,
                                                            float* __restrict__ hist, int Lh, int* __restrict__ hist_pos,
                                                            int loc_enabled, int loc_window, float* __restrict__ target,
-                                                           float* __restrict__ gccphat_out) {
+                                                           float* __restrict__ gccphat_out, int bank) {
     __shared__ float s_sum[1024];
     __shared__ int s_cnt[1024];
+    const long sid = blockIdx.z;
+    C += sid * F * Tc;
+    hist += sid * D * Lh;
+    hist_pos += sid;
+    target += sid * RT_ROW;
+    if (gccphat_out) gccphat_out += sid * D * Tc;
+    if (bank && target[5] == 0.f) loc_enabled = 0;
     const int tau = threadIdx.x % Dq, g = threadIdx.x / Dq, G = 1024 / Dq;
     int pos = hist_pos[0];
     for (int t = 0; t < Tc; ++t) {
@@ -467,14 +526,19 @@ __global__ __launch_bounds__(256) void rt_fill_kernel(float* __restrict__ p, flo
     if (i < n) p[i] = v;
 }
 
-// r[f][col] = |X_c[f][t]| / sum_k W[f][k] h[k][col]; one wave per frequency row, grid = ceil(F/4)
+// r[f][col] = |X_c[f][t]| / sum_k W[f][k] h[k][col]; one wave per frequency row, grid = (ceil(F/4), 1, S)
 // first != 0: h is still all ones (no fill pass: the first update reads no coefficients and WRITES them)
 __global__ __launch_bounds__(256) void rt_wh_kernel(const float* __restrict__ W, const float* __restrict__ Hc, const float2* __restrict__ X,
-                                                    float* __restrict__ Rv, int F, int K, int Kp, int Tc, int first) {
+                                                    float* __restrict__ Rv, int F, int K, int Kp, int Tc, int first,
+                                                    const float* __restrict__ rows) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int f = blockIdx.x * 4 + wave;
-    if (f >= F) return;
+    if (f >= F || rt_switched_off(rows, 4)) return;
     const int ncol = 2 * Tc;
+    const long sid = blockIdx.z;
+    Hc += sid * Kp * ncol;
+    X += sid * 2 * F * Tc;
+    Rv += sid * F * ncol;
     const float* Wr = W + (long)f * Kp;
     for (int t = 0; t < Tc; ++t) {                         // both channels of a frame in one pass over the row of W
         float s0 = 0.f, s1 = 0.f;
@@ -503,14 +567,19 @@ __global__ __launch_bounds__(256) void rt_wh_kernel(const float* __restrict__ W,
 }
 
 // h[k][col] *= (sum_f W[f][k] r[f][col]) / colsumW[k]; 16 atoms x 16 frequency phases per workgroup, grid = Kp/16 (the first version
-// had 64 x 4: 16 workgroups with a 65-step chain of dependent loads, 17 us; now 64 workgroups, 17 independent loads per thread)
+// had 64 x 4: 16 workgroups with a 65-step chain of dependent loads, 17 us; now 64 workgroups, 17 independent loads per thread);
+// grid = (Kp/16, 1, S)
 __global__ __launch_bounds__(256) void rt_hupdate_kernel(const float* __restrict__ W, const float* __restrict__ Rv,
                                                          const float* __restrict__ colsumW, float* __restrict__ Hc, int F, int K, int Kp,
-                                                         int Tc, int first) {
+                                                         int Tc, int first, const float* __restrict__ rows) {
     __shared__ float red[4][16];
+    if (rt_switched_off(rows, 4)) return;                 // the whole workgroup: before any barrier
     const int c = threadIdx.x & 15, q = threadIdx.x >> 4, wave = threadIdx.x >> 6;
     const int k = blockIdx.x * 16 + c;
     const int ncol = 2 * Tc;
+    const long sid = blockIdx.z;
+    Rv += sid * F * ncol;
+    Hc += sid * Kp * ncol;
     for (int col = 0; col < ncol; ++col) {
         float s = 0.f;
 #pragma unroll 4
@@ -528,14 +597,22 @@ __global__ __launch_bounds__(256) void rt_hupdate_kernel(const float* __restrict
     }
 }
 
-// per-channel mask with inferred coefficients: m_c[f][t] = sum_k W h_c HMask / sum_k W h_c;  Y_c = m_c X_c;  tfMask [2][F][Tc]
+// per-channel mask with inferred coefficients: m_c[f][t] = sum_k W h_c HMask / sum_k W h_c;  Y_c = m_c X_c;  tfMask [2][F][Tc];
+// grid = (ceil(F/4), 1, S)
 __global__ __launch_bounds__(256) void rt_tfmask_h_kernel(const float* __restrict__ W, const float* __restrict__ HMask,
                                                           const float* __restrict__ Hc, int F, int K, int Kp, int Tc,
-                                                          const float2* __restrict__ X, float2* __restrict__ Y, float* __restrict__ tfMask) {
+                                                          const float2* __restrict__ X, float2* __restrict__ Y, float* __restrict__ tfMask,
+                                                          const float* __restrict__ rows) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int f = blockIdx.x * 4 + wave;
-    if (f >= F) return;
+    const int f = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
+    if (f >= F || rt_switched_off(rows, 4)) return;
     const int ncol = 2 * Tc;
+    const long sid = blockIdx.z;
+    HMask += sid * Kp * Tc;
+    Hc += sid * Kp * ncol;
+    X += sid * 2 * F * Tc;
+    Y += sid * 2 * F * Tc;
+    tfMask += sid * 2 * F * Tc;
     const float* Wr = W + (long)f * Kp;
     for (int t = 0; t < Tc; ++t) {                         // both channels of a frame in one pass over the row of W
         float n0 = 0.f, d0 = 0.f, n1 = 0.f, d1 = 0.f;
@@ -573,6 +650,7 @@ extern "C" {
 //   frames_mode = 0: streaming.  block_in [2][B] -> 8-block input buffer -> Tc windows -> ... -> overlap-add -> block_out [2][B]
 //   frames_mode = 1: the reference's GCCNMFProcessor.processFrames on its own: in_ring = windowed-sample frames [2][Tc][N]
 //                    in, out_ring = processed frames [2][Tc][N] out, no shift / overlap-add (block_in, block_out unused).
+//   bit 3 + bits 8..19 = S - 1: a bank of S streams in one set of launches (the layout is documented in include/gccnmf_hip.h).
 int gccnmf_rt_process_block_ll(const float* block_in, float* block_out, float* in_ring, float* out_ring, float* X, float* Y, float* C,
                                float* HMask, int* argmaxTDOA, float* tfMask, float* hist, int* hist_pos, float* target,
                                float* gccphat, const float* W, const float* cosT, const float* sinT, const float* window,
@@ -582,9 +660,14 @@ int gccnmf_rt_process_block_ll(const float* block_in, float* block_out, float* i
                                int frames_mode_bits, int numHUpdates, int out_delay_blocks, void* stream) {
     GCCNMF_ENTER();
     // frames_mode_bits: 1 = frames mode (above); 2 = leave the localisation kernel out of this call; 4 = ONLY the localisation kernel
-    // (2 then 4 = the same work in two calls, so that a host can fetch block_out before the tracking update has run)
+    // (2 then 4 = the same work in two calls, so that a host can fetch block_out before the tracking update has run); 8 = bank layout
+    // of S = bits 8..19 + 1 streams (streaming only); any bit above 19, or S bits without the bank layout, is an error
     const int frames_mode = frames_mode_bits & 1;
     const bool skip_localize = frames_mode_bits & 2, only_localize = frames_mode_bits & 4;
+    const int bank = (frames_mode_bits >> 3) & 1;
+    const int S = ((frames_mode_bits >> 8) & 0xfff) + 1;
+    if ((frames_mode_bits & ~0xfffff) || (bank && frames_mode) || (!bank && S > 1)) return GCCNMF_ERR_ARG;
+    const float* rows = bank ? target : nullptr;          // the per-stream switches the mask and synthesis kernels read
     // powers of two from 64 up: the radix-2 LDS transform (twiddle = N/2 values of exp(-2 pi j k / N)); every other even size: the direct
     // sums above (twiddle = the N-entry table (cos, sin)(2 pi k / N))
     const bool pow2 = windowSize >= 64 && (windowSize & (windowSize - 1)) == 0;
@@ -606,13 +689,13 @@ int gccnmf_rt_process_block_ll(const float* block_in, float* block_out, float* i
     int Dq = 64;
     while (Dq < D) Dq *= 2;                 // power of two so that 1024 % Dq == 0
     if (only_localize) {
-        hipLaunchKernelGGL(rt_localize_kernel, dim3(1), dim3(1024), 0, s, (const float2*)C, cosT, sinT, F, D, Dp, Dq, Tc, hist,
-                           numTDOAHistory, hist_pos, localization_enabled, localization_window, target, gccphat);
+        hipLaunchKernelGGL(rt_localize_kernel, dim3(1, 1, S), dim3(1024), 0, s, (const float2*)C, cosT, sinT, F, D, Dp, Dq, Tc, hist,
+                           numTDOAHistory, hist_pos, localization_enabled, localization_window, target, gccphat, bank);
         GCCNMF_CHECK_LAUNCH();
         return GCCNMF_OK;
     }
     if (!frames_mode) {
-        hipLaunchKernelGGL(rt_shift_kernel, dim3(1), dim3(1024), 0, s, in_ring, out_ring, block_in, blockSize, ring);
+        hipLaunchKernelGGL(rt_shift_kernel, dim3(1, 1, S), dim3(1024), 0, s, in_ring, out_ring, block_in, blockSize, ring);
         GCCNMF_CHECK_LAUNCH();
     }
     const size_t lds_dft = sizeof(float2) * (2 * windowSize + 2);
@@ -623,50 +706,51 @@ int gccnmf_rt_process_block_ll(const float* block_in, float* block_out, float* i
             return GCCNMF_ERR_LAUNCH;
     }
     if (pow2) {
-        hipLaunchKernelGGL(rt_frames_kernel, dim3(Tc), dim3(FFT_NT), lds, s, in_ring, ring, windowSize, logN, start0, start_step, Tc,
+        hipLaunchKernelGGL(rt_frames_kernel, dim3(Tc, 1, S), dim3(FFT_NT), lds, s, in_ring, ring, windowSize, logN, start0, start_step, Tc,
                            window, (const float2*)twiddle, (float2*)X, (float2*)C);
     } else {
-        hipLaunchKernelGGL(rt_frames_dft_kernel, dim3(gccnmf_ceil_div(F, 64), Tc), dim3(256), lds_dft, s, in_ring, ring, windowSize, start0,
+        hipLaunchKernelGGL(rt_frames_dft_kernel, dim3(gccnmf_ceil_div(F, 64), Tc, S), dim3(256), lds_dft, s, in_ring, ring, windowSize, start0,
                            start_step, Tc, window, (const float2*)twiddle, (float2*)X, (float2*)C);
     }
     GCCNMF_CHECK_LAUNCH();
     if (separation_enabled) {
-        hipLaunchKernelGGL(rt_gccnmf_kernel, dim3(Kp / 32, Tc), dim3(64 * RT_G_WAVES), 0, s, (const float2*)C, cosT, sinT, W, F, K, Kp, D, Dp, Tc,
-                           target, target_mode, HMask, argmaxTDOA);
+        hipLaunchKernelGGL(rt_gccnmf_kernel, dim3(Kp / 32, Tc, S), dim3(64 * RT_G_WAVES), 0, s, (const float2*)C, cosT, sinT, W, F, K, Kp, D, Dp,
+                           Tc, target, target_mode, bank, HMask, argmaxTDOA);
         GCCNMF_CHECK_LAUNCH();
         if (numHUpdates == 0) {
-            hipLaunchKernelGGL(rt_tfmask_kernel, dim3(gccnmf_ceil_div(F, 4)), dim3(256), 0, s, W, HMask, F, K, Kp, Tc, (const float2*)X,
-                               (float2*)Y, tfMask);
+            hipLaunchKernelGGL(rt_tfmask_kernel, dim3(gccnmf_ceil_div(F, 4), 1, S), dim3(256), 0, s, W, HMask, F, K, Kp, Tc, (const float2*)X,
+                               (float2*)Y, tfMask, rows);
             GCCNMF_CHECK_LAUNCH();
         } else {
             for (int it = 0; it < numHUpdates; ++it) {      // h0 = 1 is implicit in the first update (no fill pass)
-                hipLaunchKernelGGL(rt_wh_kernel, dim3(gccnmf_ceil_div(F, 4)), dim3(256), 0, s, W, Hcoef, (const float2*)X, Rv, F, K, Kp, Tc,
-                                   it == 0 ? 1 : 0);
+                hipLaunchKernelGGL(rt_wh_kernel, dim3(gccnmf_ceil_div(F, 4), 1, S), dim3(256), 0, s, W, Hcoef, (const float2*)X, Rv, F, K, Kp,
+                                   Tc, it == 0 ? 1 : 0, rows);
                 GCCNMF_CHECK_LAUNCH();
-                hipLaunchKernelGGL(rt_hupdate_kernel, dim3(Kp / 16), dim3(256), 0, s, W, Rv, colsumW, Hcoef, F, K, Kp, Tc, it == 0 ? 1 : 0);
+                hipLaunchKernelGGL(rt_hupdate_kernel, dim3(Kp / 16, 1, S), dim3(256), 0, s, W, Rv, colsumW, Hcoef, F, K, Kp, Tc, it == 0 ? 1 : 0,
+                                   rows);
                 GCCNMF_CHECK_LAUNCH();
             }
-            hipLaunchKernelGGL(rt_tfmask_h_kernel, dim3(gccnmf_ceil_div(F, 4)), dim3(256), 0, s, W, HMask, Hcoef, F, K, Kp, Tc,
-                               (const float2*)X, (float2*)Y, tfMask);
+            hipLaunchKernelGGL(rt_tfmask_h_kernel, dim3(gccnmf_ceil_div(F, 4), 1, S), dim3(256), 0, s, W, HMask, Hcoef, F, K, Kp, Tc,
+                               (const float2*)X, (float2*)Y, tfMask, rows);
             GCCNMF_CHECK_LAUNCH();
         }
     }
     if (pow2) {
-        hipLaunchKernelGGL(rt_synth_kernel, dim3(1), dim3(FFT_NT), lds, s, (const float2*)(separation_enabled ? Y : X), windowSize, logN,
+        hipLaunchKernelGGL(rt_synth_kernel, dim3(1, 1, S), dim3(FFT_NT), lds, s, (const float2*)(separation_enabled ? Y : X), windowSize, logN,
                            start0, start_step, frames_mode ? 0 : 1, Tc, ring, blockSize, out_delay_blocks, synthesis_window,
-                           (const float2*)twiddle, out_ring, block_out);
+                           (const float2*)twiddle, out_ring, block_out, (const float2*)X, rows);
     } else {
         // positions that receive a frame this call, plus the block handed out (it may lie in front of them)
         const int h0 = ring - (out_delay_blocks + 1) * blockSize;
         const int s_lo = frames_mode ? 0 : (start0 < h0 ? start0 : (h0 > 0 ? h0 : 0));
-        hipLaunchKernelGGL(rt_synth_dft_kernel, dim3(gccnmf_ceil_div(ring - s_lo, 256)), dim3(256), lds_dft, s,
+        hipLaunchKernelGGL(rt_synth_dft_kernel, dim3(gccnmf_ceil_div(ring - s_lo, 256), 1, S), dim3(256), lds_dft, s,
                            (const float2*)(separation_enabled ? Y : X), windowSize, start0, start_step, frames_mode ? 0 : 1, Tc, ring, blockSize,
-                           out_delay_blocks, s_lo, synthesis_window, (const float2*)twiddle, out_ring, block_out);
+                           out_delay_blocks, s_lo, synthesis_window, (const float2*)twiddle, out_ring, block_out, (const float2*)X, rows);
     }
     GCCNMF_CHECK_LAUNCH();
     if (skip_localize) return GCCNMF_OK;
-    hipLaunchKernelGGL(rt_localize_kernel, dim3(1), dim3(1024), 0, s, (const float2*)C, cosT, sinT, F, D, Dp, Dq, Tc, hist,
-                       numTDOAHistory, hist_pos, localization_enabled, localization_window, target, gccphat);
+    hipLaunchKernelGGL(rt_localize_kernel, dim3(1, 1, S), dim3(1024), 0, s, (const float2*)C, cosT, sinT, F, D, Dp, Dq, Tc, hist,
+                       numTDOAHistory, hist_pos, localization_enabled, localization_window, target, gccphat, bank);
     GCCNMF_CHECK_LAUNCH();
     return GCCNMF_OK;
 }

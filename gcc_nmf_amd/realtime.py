@@ -5,6 +5,8 @@
 ``GCCNMFProcessor`` keeps the reference's constructor arguments, attributes and methods
 (``processFrames(windowedSamples)``, ``setTargetTDOARange``, ``reset``); ``StreamingGCCNMF`` is the fused
 block-in / block-out path (input ring, frames, mask, synthesis, overlap-add and TDOA tracking all on device).
+``StreamingGCCNMFBank`` runs S such streams of one configuration in the same device call per block, each bit for bit a
+``StreamingGCCNMF`` of its own.
 No CPU fallback: without the library / a device the constructor raises ``HipLibraryError``.
 """
 import numpy as np
@@ -225,6 +227,30 @@ class GCCNMFProcessor(object):
                     gccPHAT=self.dGccPhat.cpu().numpy(), targetTDOAIndex=self.targetTDOAIndex)
 
 
+def _check_stream_shape(processor, hopSize, blockSize, outputDelayBlocks):
+    """The block / hop / hand-out checks of a streaming path over ``processor``; returns outputDelayBlocks as an int."""
+    # outputDelayBlocks: 2 = the reference's hand-out (utils.py:116); 1 is complete when the synthesis window spans two hops
+    if outputDelayBlocks not in (1, 2, 3, 4, 5, 6, 7):
+        raise ValueError('outputDelayBlocks must be 1..7')
+    outputDelayBlocks = int(outputDelayBlocks)
+    # The block handed out is complete only when no later frame adds into it: the synthesis window's non-zero support (first
+    # non-zero sample to the end of the frame) must fit in outputDelayBlocks * blockSize + hopSize samples.  2 is the reference's
+    # hand-out whatever the window (utils.py:116 -- with its own 512 / 64 low-latency setting it hands out partial sums, and
+    # the goldens pin that); any other delay must be complete.
+    if outputDelayBlocks != 2:
+        nz = np.nonzero(np.asarray(processor.synthesisWindowFunction).reshape(-1))[0]
+        support = processor.windowSize - int(nz[0]) if len(nz) else 0
+        if support > outputDelayBlocks * int(blockSize) + int(hopSize):
+            raise ValueError('outputDelayBlocks=%d hands a block out before it is complete: the synthesis window spans %d samples, '
+                             'at most %d fit (use asymmetricWindows, or the reference\'s delay of 2)'
+                             % (outputDelayBlocks, support, outputDelayBlocks * int(blockSize) + int(hopSize)))
+    if blockSize % hopSize or blockSize // hopSize != processor.numTimePerChunk:
+        raise ValueError('blockSize/hopSize must equal the processor\'s numTimePerChunk')
+    if 8 * blockSize < processor.windowSize + (processor.numTimePerChunk - 1) * hopSize:
+        raise ValueError('blockSize=%d is not supported: the 8-block buffers (utils.py:87-92) must cover one block\'s windows' % blockSize)
+    return outputDelayBlocks
+
+
 class StreamingGCCNMF(object):
     """``OverlapAddProcessor.processFrames(GCCNMFProcessor.processFrames)`` (utils.py:99-116) as one device call per block:
     ``process_block((2, blockSize)) -> (2, blockSize)``, output delayed by two blocks like the reference."""
@@ -232,25 +258,7 @@ class StreamingGCCNMF(object):
     def __init__(self, processor, hopSize, blockSize, outputDelayBlocks=2, use_graph=True):
         self.use_graph = bool(use_graph)
         self.capture_error = None          # the exception of a failed HIP-graph capture (process_block then launches directly)
-        # outputDelayBlocks: 2 = the reference's hand-out (utils.py:116); 1 is complete when the synthesis window spans two hops
-        if outputDelayBlocks not in (1, 2, 3, 4, 5, 6, 7):
-            raise ValueError('outputDelayBlocks must be 1..7')
-        self.outputDelayBlocks = int(outputDelayBlocks)
-        # The block handed out is complete only when no later frame adds into it: the synthesis window's non-zero support (first
-        # non-zero sample to the end of the frame) must fit in outputDelayBlocks * blockSize + hopSize samples.  2 is the reference's
-        # hand-out whatever the window (utils.py:116 -- with its own 512 / 64 low-latency setting it hands out partial sums, and
-        # the goldens pin that); any other delay must be complete.
-        if self.outputDelayBlocks != 2:
-            nz = np.nonzero(np.asarray(processor.synthesisWindowFunction).reshape(-1))[0]
-            support = processor.windowSize - int(nz[0]) if len(nz) else 0
-            if support > self.outputDelayBlocks * int(blockSize) + int(hopSize):
-                raise ValueError('outputDelayBlocks=%d hands a block out before it is complete: the synthesis window spans %d samples, '
-                                 'at most %d fit (use asymmetricWindows, or the reference\'s delay of 2)'
-                                 % (self.outputDelayBlocks, support, self.outputDelayBlocks * int(blockSize) + int(hopSize)))
-        if blockSize % hopSize or blockSize // hopSize != processor.numTimePerChunk:
-            raise ValueError('blockSize/hopSize must equal the processor\'s numTimePerChunk')
-        if 8 * blockSize < processor.windowSize + (processor.numTimePerChunk - 1) * hopSize:
-            raise ValueError('blockSize=%d is not supported: the 8-block buffers (utils.py:87-92) must cover one block\'s windows' % blockSize)
+        self.outputDelayBlocks = _check_stream_shape(processor, hopSize, blockSize, outputDelayBlocks)
         self.p, self.hopSize, self.blockSize = processor, int(hopSize), int(blockSize)
         dev = processor.device
         self.in_ring = torch.zeros((2, 8 * blockSize), dtype=torch.float32, device=dev)
@@ -328,3 +336,213 @@ class StreamingGCCNMF(object):
         for b in range(n_blocks):
             self.process_block_device(xb[b], out[b])
         return out.permute(1, 0, 2).reshape(2, n_blocks * B).cpu().numpy()
+
+
+MAX_BANK_STREAMS = 4096                  # frames_mode bits 8..19 (csrc/rt.hip)
+_BANK_LAYOUT = 8
+
+
+class StreamingGCCNMFBank(object):
+    """S independent real-time streams of one configuration, advanced together: one device call per block runs all of them
+    (frames_mode bit 3 of ``gccnmf_rt_process_block_ll``).  Stream s produces bit for bit what a ``StreamingGCCNMF`` over its own
+    ``GCCNMFProcessor`` of the same configuration produces when fed the same blocks.
+
+    ``processor`` is the shared configuration: its dictionary, TDOA grid, windows, twiddles, ``targetMode``, ``numHUpdates`` and
+    ``localizationWindowSize``, and its ``separationEnabled`` / ``localizationEnabled`` as master switches.  The bank allocates its
+    own per-stream state (rings, spectra, masks, history ring, target row) and never touches the processor's.  Each stream has a
+    target row {index, epsilon, beta, noiseFloor, separation, localisation}: a stream separates (localises) when the processor's
+    switch and its own are both on.  After ``processor.reset()`` the next call re-allocates all per-stream state.
+
+    The GUI's host mirrors (``GCCNMFProcessor.fill_histories``) are not produced for a bank."""
+
+    def __init__(self, processor, numStreams, hopSize, blockSize, outputDelayBlocks=2, use_graph=True):
+        if int(numStreams) != numStreams or not 1 <= int(numStreams) <= MAX_BANK_STREAMS:
+            raise ValueError('numStreams=%r: a bank holds 1 to %d streams' % (numStreams, MAX_BANK_STREAMS))
+        self.outputDelayBlocks = _check_stream_shape(processor, hopSize, blockSize, outputDelayBlocks)
+        self.p, self.numStreams, self.hopSize, self.blockSize = processor, int(numStreams), int(hopSize), int(blockSize)
+        self.use_graph = bool(use_graph)
+        self.capture_error = None          # as StreamingGCCNMF.capture_error
+        self.device = processor.device
+        self._generation = None
+        self._graph, self._graph_key = None, None
+        self._alloc()
+
+    # ---- per-stream state ----------------------------------------------------------------------------------------------
+    def _initial_row(self):
+        return np.concatenate([self.p._target_host, np.array([1, 1, 0, 0], np.float32)]).astype(np.float32)
+
+    @_on_device
+    def _alloc(self):
+        p, S, B = self.p, self.numStreams, self.blockSize
+        F, Tc, D, Kp = p.numFrequencies, p.numTimePerChunk, p.numTDOAs, p.Kp
+        z = lambda *shape, **kw: torch.zeros(shape, dtype=kw.get('dtype', torch.float32), device=self.device)
+        self.in_ring, self.out_ring = z(S, 2, 8 * B), z(S, 2, 8 * B)
+        self.block_in, self.block_out = z(S, 2, B), z(S, 2, B)
+        self.dX, self.dY, self.dC = z(S, 2, F, Tc, 2), z(S, 2, F, Tc, 2), z(S, F, Tc, 2)
+        self.dHMask, self.dArgmax = z(S, Kp, Tc), z(S, Kp, Tc, dtype=torch.int32)
+        self.dTfMask, self.dGccPhat = z(S, 2, F, Tc), z(S, D, Tc)
+        self.dHist, self.dHistPos = z(S, D, p.numTDOAHistory), z(S, dtype=torch.int32)
+        self.dHcoef, self.dRv = None, None     # coefficient-inference scratch: allocated with the first call that needs it
+        self._row0 = self._initial_row()
+        self.dTarget = torch.from_numpy(np.tile(self._row0, (S, 1))).to(self.device)
+        self._targets = self._row0[0].repeat(S).astype(np.float32)      # host copy of the tracked indexes
+        self._targets_dirty, self._targets_pin = False, None
+        self._generation = p.generation
+        self._graph, self._graph_key = None, None
+
+    def _ensure_state(self):
+        if self._generation != self.p.generation:           # processor reset(): every table was re-allocated
+            self._alloc()
+        if self.p.numHUpdates and self.dHcoef is None:
+            S, F, Tc, Kp = self.numStreams, self.p.numFrequencies, self.p.numTimePerChunk, self.p.Kp
+            self.dHcoef = torch.zeros((S, Kp, Tc, 2), dtype=torch.float32, device=self.device)
+            self.dRv = torch.zeros((S, F, Tc, 2), dtype=torch.float32, device=self.device)
+
+    def _stream_index(self, s):
+        if int(s) != s or not 0 <= int(s) < self.numStreams:
+            raise IndexError('stream %r of a bank of %d' % (s, self.numStreams))
+        return int(s)
+
+    # ---- per-stream control (none of these re-captures the graph: they only write the target rows) ------------------------
+    @_on_device
+    def setTargetTDOARange(self, s, targetTDOAIndex, targetTDOAEpsilon, targetTDOABeta, targetTDOANoiseFloor):
+        """Words 0-3 of stream s's target row (``GCCNMFProcessor.setTargetTDOARange`` for one stream)."""
+        s = self._stream_index(s)
+        self._ensure_state()
+        v = np.array([targetTDOAIndex, targetTDOAEpsilon, targetTDOABeta, targetTDOANoiseFloor], np.float32)
+        self.dTarget[s, :4].copy_(torch.from_numpy(v))
+        self._targets[s] = v[0]
+
+    @_on_device
+    def setSeparationEnabled(self, s, on):
+        """Word 4 of stream s's row: off = the stream is passed through (synthesised from its unmasked spectrum)."""
+        s = self._stream_index(s)
+        self._ensure_state()
+        self.dTarget[s, 4] = float(bool(on))
+
+    @_on_device
+    def setLocalizationEnabled(self, s, on):
+        """Word 5 of stream s's row: off = the history still fills, the tracked index stays where it is."""
+        s = self._stream_index(s)
+        self._ensure_state()
+        self.dTarget[s, 5] = float(bool(on))
+
+    @_on_device
+    def reset_stream(self, s):
+        """Stream s starts over (a session left, a new one takes its slot): its rings, history, history position and target row
+        (the processor's target, both switches on) are reset; no other stream is touched."""
+        s = self._stream_index(s)
+        self._ensure_state()
+        for t in (self.in_ring, self.out_ring, self.dHist, self.dHistPos):
+            t[s].zero_()
+        row = self._initial_row()
+        self.dTarget[s].copy_(torch.from_numpy(row))
+        self._targets[s] = row[0]
+
+    @property
+    def targetTDOAIndexes(self):
+        """(S,) tracked target TDOA indexes, cached like ``GCCNMFProcessor.targetTDOAIndex``: fetched (one small download of the
+        target rows) only when a call ran with the localisation on since they were last known on the host."""
+        if self._targets_dirty:
+            with torch.cuda.device(self.device):
+                if self._targets_pin is None or self._targets_pin.shape != self.dTarget.shape:
+                    self._targets_pin = torch.zeros(self.dTarget.shape, dtype=torch.float32).pin_memory()
+                self._targets_pin.copy_(self.dTarget, non_blocking=True)
+                torch.cuda.current_stream(self.device).synchronize()
+            self._targets = self._targets_pin.numpy()[:, 0].copy()
+            self._targets_dirty = False
+        return self._targets.copy()
+
+    # ---- device calls -----------------------------------------------------------------------------------------------------
+    @_on_device
+    def _call(self, block_in, block_out, bits):
+        p = self.p
+        if p.localizationEnabled and not bits & 2:
+            self._targets_dirty = True
+        _hip.check(p.lib.gccnmf_rt_process_block_ll(
+            _ptr(block_in), _ptr(block_out), _ptr(self.in_ring), _ptr(self.out_ring), _ptr(self.dX), _ptr(self.dY), _ptr(self.dC),
+            _ptr(self.dHMask), _ptr(self.dArgmax), _ptr(self.dTfMask), _ptr(self.dHist), _ptr(self.dHistPos), _ptr(self.dTarget),
+            _ptr(self.dGccPhat), _ptr(p.dW), _ptr(p.dCos), _ptr(p.dSin), _ptr(p.dWindow), _ptr(p.dSynthWindow), _ptr(p.dTwiddle),
+            _ptr(p.dColsum), _ptr(self.dHcoef), _ptr(self.dRv), p.windowSize, self.hopSize, self.blockSize,
+            p.numAtom, p.Kp, p.numTDOAs, p.Dp, p.numTDOAHistory, int(p.targetMode), int(bool(p.separationEnabled)),
+            int(bool(p.localizationEnabled)), p.localizationWindowSize, bits | _BANK_LAYOUT | ((self.numStreams - 1) << 8),
+            int(p.numHUpdates), self.outputDelayBlocks, _stream()), 'gccnmf_rt_process_block_ll')
+
+    def _check_blocks(self, t):
+        if tuple(t.shape) != (self.numStreams, 2, self.blockSize) or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError('expected a contiguous float32 tensor of shape %s' % ((self.numStreams, 2, self.blockSize),))
+
+    def process_block_device(self, block_in, block_out):
+        """(S, 2, blockSize) device tensors in / out, asynchronous on the current stream."""
+        self._check_blocks(block_in)
+        self._check_blocks(block_out)
+        self._ensure_state()
+        self._call(block_in, block_out, 0)
+
+    def process_block(self, blocks):
+        """(S, 2, blockSize) host blocks in -> (S, 2, blockSize) out, as ``StreamingGCCNMF.process_block``: one captured HIP graph
+        (upload, every kernel but the tracking update, download), the output fetched before the tracking update runs."""
+        blocks = np.ascontiguousarray(blocks, dtype=np.float32)
+        if blocks.shape != (self.numStreams, 2, self.blockSize):
+            raise ValueError('expected blocks of shape %s, got %s' % ((self.numStreams, 2, self.blockSize), blocks.shape))
+        p = self.p
+        with torch.cuda.device(self.device):
+            self._ensure_state()
+            if getattr(self, '_pin_in', None) is None:
+                self._pin_in = torch.zeros((self.numStreams, 2, self.blockSize), dtype=torch.float32).pin_memory()
+                self._pin_out = torch.zeros((self.numStreams, 2, self.blockSize), dtype=torch.float32).pin_memory()
+                self._ev_out = torch.cuda.Event()
+            self._pin_in.copy_(torch.from_numpy(blocks))
+            key = (int(p.targetMode), bool(p.separationEnabled), bool(p.localizationEnabled), int(p.localizationWindowSize),
+                   int(p.numHUpdates), p.dW.data_ptr(), self.dTarget.data_ptr(), p.generation)
+            if self.use_graph and self._graph_key != key:
+                self._graph, self._graph_key = self._capture(), key
+            if self.use_graph and self._graph is not None:
+                self._graph.replay()
+            else:
+                self._launch_front()
+            self._ev_out.record()
+            self._call(self.block_in, self.block_out, 4)
+            self._ev_out.synchronize()
+            return self._pin_out.numpy().copy()
+
+    def _launch_front(self):
+        self.block_in.copy_(self._pin_in, non_blocking=True)
+        self._call(self.block_in, self.block_out, 2)
+        self._pin_out.copy_(self.block_out, non_blocking=True)
+
+    def _capture(self):
+        """upload -> kernels (all but the tracking update) -> download as one HIP graph: a single serial chain on one stream.  A failed
+        capture is kept in ``capture_error``, warned about once, and the block is launched directly."""
+        state = (self.in_ring, self.out_ring, self.dHist, self.dHistPos, self.dTarget)
+        try:
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            saved = [t.clone() for t in state]
+            with torch.cuda.graph(g):
+                self._launch_front()
+            for t, s0 in zip(state, saved):         # capture does not execute on ROCm; restore in case a runtime runs the body once
+                t.copy_(s0)
+            torch.cuda.synchronize()
+            self.capture_error = None
+            return g
+        except Exception as e:
+            import warnings
+            if self.capture_error is None:
+                warnings.warn('StreamingGCCNMFBank: HIP graph capture failed (%s: %s); falling back to direct launches'
+                              % (type(e).__name__, e), RuntimeWarning)
+            self.capture_error = e
+            return None
+
+    def process_streams(self, x):
+        """(S, 2, n) -> (S, 2, n_blocks * blockSize); the whole signal is uploaded once, every block is one device call."""
+        x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(self.device)
+        S, B = self.numStreams, self.blockSize
+        if x.dim() != 3 or x.shape[0] != S or x.shape[1] != 2:
+            raise ValueError('expected signals of shape (%d, 2, n)' % S)
+        n_blocks = x.shape[2] // B
+        xb = x[:, :, :n_blocks * B].reshape(S, 2, n_blocks, B).permute(2, 0, 1, 3).contiguous()      # [block][S][2][B]
+        out = torch.zeros((n_blocks, S, 2, B), dtype=torch.float32, device=self.device)
+        for b in range(n_blocks):
+            self.process_block_device(xb[b], out[b])
+        return out.permute(1, 2, 0, 3).reshape(S, 2, n_blocks * B).cpu().numpy()

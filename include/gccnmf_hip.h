@@ -330,6 +330,15 @@ int gccnmf_rt_process_block(const float* block_in, float* block_out, float* in_r
  *                                  numHUpdates = 0 is exactly gccnmf_rt_process_block (h = 1).
  *   frames_mode bits               1 = frames mode; 2 = everything but the localisation kernel; 4 = only the localisation kernel
  *                                  (2 then 4 on the same stream = one call; lets a host fetch block_out before the tracking update)
+ *                                  8 = stream bank: S = (bits 8..19) + 1 independent streams of this configuration, advanced
+ *                                  together in the same launches (S <= 4096).  Every per-stream buffer holds S consecutive
+ *                                  single-stream images (block_in / block_out, in_ring / out_ring, X, Y, C, HMask, argmaxTDOA,
+ *                                  tfMask as [S][2][F][Tc] whatever numHUpdates, gccphat, hist, Hcoef, Rv); hist_pos is [S];
+ *                                  target is [S][8] = {index, epsilon, beta, noiseFloor, separation, localisation, 0, 0}.  A
+ *                                  stream separates (localises) when separation_enabled (localization_enabled) AND its row word
+ *                                  4 (5) are non-zero; with separation_enabled = 0 no mask kernel is launched.  Stream s computes
+ *                                  bit for bit what a single-stream call on its images computes.  Bits 2 and 4 work as above.
+ *                                  GCCNMF_ERR_ARG: 8 together with 1 (frames mode), bits 8..19 without 8, any bit above 19.
  *   out_delay_blocks               which finished block is handed out: 2 = the reference (utils.py:116); 1 is complete when
  *                                  the synthesis window spans at most two hops */
 int gccnmf_rt_process_block_ll(const float* block_in, float* block_out, float* in_ring, float* out_ring, float* X, float* Y, float* C,
