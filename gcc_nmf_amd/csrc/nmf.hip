@@ -17,6 +17,10 @@
 #ifdef GCCNMF_EXPERIMENTS
 int gccnmf_launch_gemm_stream(GemmArgs a, hipStream_t stream);       // the LDS-free throughput tile (direct.hip)
 #endif
+int gccnmf_klnmf_fixed_launch(const float* V, const float* W, float* H, float* workspace, int F, int N, int K, int batch, int iterations,
+                              float alpha, float eps, bool ones, hipStream_t s);      // fixed dictionary, every iteration in one launch (nmf_fixed.hip)
+bool gccnmf_klnmf_fixed_supported(int F, int K);
+long gccnmf_klnmf_fixed_workspace_floats(int F, int K);
 #include "../../include/gccnmf_hip.h"
 
 #include <atomic>
@@ -1110,12 +1114,17 @@ static int klnmf_stage(int stage, const float* V, float* W, float* H, float* wor
     return GCCNMF_OK;
 }
 
+// GCCNMF_FLAG_FIXED_W alone or with GCCNMF_FLAG_H_ONES, nothing else
+#define GCCNMF_FIXED_BITS (GCCNMF_FLAG_FIXED_W | GCCNMF_FLAG_H_ONES)
+static bool fixed_flags_ok(int flags) { return (flags & GCCNMF_FLAG_FIXED_W) && !(flags & ~GCCNMF_FIXED_BITS); }
+
 // Which launches gccnmf_klnmf would use for this problem under the current tuning: bit 0 the direct latency kernels, bit 1 the fused
 // K1 + K2 launch, bit 2 the fused K3 + K4a slab launch, bit 3 chained launches of the iteration (benchmarks and tests name the kernel they
-// time by this; the engine keeps ONE file group when the library chains).
+// time by this; the engine keeps ONE file group when the library chains), bit 4 the fused fixed-dictionary launch (GCCNMF_FLAG_FIXED_W).
 int gccnmf_klnmf_plan(int F, int N, int K, int batch, int flags) {
     GCCNMF_ENTER();
     if (F < 2 || N < 1 || K < 1 || batch < 1) return -1;
+    if (flags & GCCNMF_FIXED_BITS) return fixed_flags_ok(flags) && gccnmf_klnmf_fixed_supported(F, K) ? 16 : -1;
     const NmfGeom g = make_geom(F, N, K);
     return (direct_path(g, batch) ? 1 : 0) | (fused_wh_updh(g, batch, flags) ? 2 : 0) | (fused_whdiv_rht_files(g, batch, flags) > 0 ? 4 : 0) |
            ((chain_stages(g, batch, flags) || short_chain_group(g, batch, flags)) ? 8 : 0);
@@ -1124,7 +1133,7 @@ int gccnmf_klnmf_plan(int F, int N, int K, int batch, int flags) {
 int gccnmf_klnmf_stage(const float* V, float* W, float* H, float* workspace, int F, int N, int K, int batch,
                        float sparsity_alpha, float epsilon, int flags, int stage, void* stream) {
     GCCNMF_ENTER();
-    if (!V || !W || !H || !workspace || F < 2 || N < 1 || K < 1 || batch < 1) return GCCNMF_ERR_ARG;
+    if (!V || !W || !H || !workspace || F < 2 || N < 1 || K < 1 || batch < 1 || (flags & GCCNMF_FIXED_BITS)) return GCCNMF_ERR_ARG;
     return klnmf_stage(stage, V, W, H, workspace, make_geom(F, N, K), batch, sparsity_alpha, epsilon, flags, (hipStream_t)stream);
 }
 
@@ -1134,6 +1143,17 @@ int gccnmf_klnmf(const float* V, float* W, float* H, float* workspace, int F, in
     if (!V || !W || !H || !workspace || F < 2 || N < 1 || K < 1 || batch < 1 || iterations < 0) return GCCNMF_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     NmfGeom g = make_geom(F, N, K);
+    if (flags & GCCNMF_FIXED_BITS) {
+        // fixed dictionary: W is read only, H holds the initial coefficients (or, with H_ONES, is output only); one launch runs every
+        // iteration.  Nothing chains: the status words of gccnmf_klnmf_chain_status are cleared for this call.
+        if (!fixed_flags_ok(flags)) return GCCNMF_ERR_ARG;
+        if (!gccnmf_klnmf_fixed_supported(F, K) || gccnmf_klnmf_fixed_workspace_floats(F, K) > klnmf_workspace_base_floats(g, batch))
+            return GCCNMF_ERR_UNSUPPORTED;
+        unsigned* status = (unsigned*)(workspace + klnmf_workspace_base_floats(g, batch)) + chain_counter_floats(g, batch) - 32;
+        if (hipMemsetAsync(status, 0, 32 * sizeof(unsigned), s) != hipSuccess) return GCCNMF_ERR_LAUNCH;
+        return gccnmf_klnmf_fixed_launch(V, W, H, workspace, F, N, K, batch, iterations, sparsity_alpha, epsilon,
+                                         (flags & GCCNMF_FLAG_H_ONES) != 0, s);
+    }
     int rc;
     if ((rc = klnmf_stage(0, V, W, H, workspace, g, batch, sparsity_alpha, epsilon, flags, s))) return rc;
     const int chained = chain_stages(g, batch, flags);          // 0 | 2: K1 | K2 in one launch | 4: the whole iteration | 8: the whole call
@@ -1216,7 +1236,8 @@ long gccnmf_klnmf_ragged_workspace_floats(int F, int Nmax, int K, int batch) {
 int gccnmf_klnmf_ragged(const float* V, float* W, float* H, float* workspace, int F, const int* N, int Nmax, int K, int batch, int iterations,
                         float sparsity_alpha, float epsilon, int flags, void* stream) {
     GCCNMF_ENTER();
-    if (!V || !W || !H || !workspace || !N || F < 2 || Nmax < 1 || K < 1 || batch < 1 || iterations < 0) return GCCNMF_ERR_ARG;
+    if (!V || !W || !H || !workspace || !N || F < 2 || Nmax < 1 || K < 1 || batch < 1 || iterations < 0 || (flags & GCCNMF_FIXED_BITS))
+        return GCCNMF_ERR_ARG;
     if (batch > GCCNMF_RAGGED_MAX_BATCH) return GCCNMF_ERR_UNSUPPORTED;
     long tiles = 0;
     for (int f = 0; f < batch; ++f) {

@@ -50,6 +50,57 @@ def klnmf_initial_factors(F, N, K, epsilon=1e-16, seedValue=0):
     return W.astype(np.float32), H.astype(np.float32)
 
 
+GCCNMF_FLAG_FIXED_W = 1 << 16          # include/gccnmf_hip.h
+GCCNMF_FLAG_H_ONES = 1 << 17
+
+
+def check_dictionary(W, F):
+    """A pre-trained dictionary as the fixed-dictionary call takes it: finite, non-negative float32 (F, K) with 1 <= K <= 1024."""
+    W = np.asarray(W)
+    if W.ndim != 2 or W.shape[0] != F or not 1 <= W.shape[1] <= 1024:
+        raise ValueError('dictionaryW must have shape (%d, K) with 1 <= K <= 1024, got %s' % (F, W.shape))
+    W = W.astype(np.float32)
+    if not np.isfinite(W).all() or (W < 0).any():
+        raise ValueError('dictionaryW must be finite and non-negative')
+    return W
+
+
+def inferKLNMFCoefficients(V, W, numIterations, sparsityAlpha=0, epsilon=1e-16, seedValue=0, initialH='random', device='cuda:0'):
+    """H of KL-NMF against the fixed dictionary W -- performKLNMF's H update (gccNMF/gccNMFFunctions.py:76) with W never updated, on
+    the device (gccnmf_klnmf with GCCNMF_FLAG_FIXED_W).  V: (F, N) or (batch, F, N); W: (F, K).  initialH: 'random' = the H0 that
+    performKLNMF draws (klnmf_initial_factors(...)[1]), 'ones' = all ones.  Returns float32 H of shape (K, N) or (batch, K, N)."""
+    V = np.asarray(V, dtype=np.float32)
+    single = V.ndim == 2
+    if single:
+        V = V[None]
+    if V.ndim != 3:
+        raise ValueError('V must be (F, N) or (batch, F, N)')
+    B, F, N = V.shape
+    W = check_dictionary(W, F)
+    K = W.shape[1]
+    if initialH not in ('random', 'ones'):
+        raise ValueError("initialH must be 'random' or 'ones'")
+    lib = _hip.lib()
+    dev = torch.device(device)
+    g = Geometry(F, -(-N // 2), K)
+    Np = -(-N // 64) * 64
+    with torch.cuda.device(dev):
+        Vd = torch.zeros((B, g.Fp, Np), dtype=torch.float32, device=dev)
+        Vd[:, :F, :N] = torch.from_numpy(np.ascontiguousarray(V)).to(dev)
+        Wd = padded(W, (g.Fp, g.Kp), dev)
+        Hd = torch.zeros((B, g.Kp, Np), dtype=torch.float32, device=dev)
+        flags = GCCNMF_FLAG_FIXED_W
+        if initialH == 'ones':
+            flags |= GCCNMF_FLAG_H_ONES
+        else:
+            Hd[:, :K, :N] = torch.from_numpy(klnmf_initial_factors(F, N, K, epsilon, seedValue)[1]).to(dev)
+        ws = torch.zeros(lib.gccnmf_klnmf_workspace_floats(F, N, K, B), dtype=torch.float32, device=dev)
+        _hip.check(lib.gccnmf_klnmf(_ptr(Vd), _ptr(Wd), _ptr(Hd), _ptr(ws), F, N, K, B, int(numIterations), float(sparsityAlpha),
+                                    float(epsilon), flags, _stream()), 'gccnmf_klnmf')
+        H = Hd[:, :K, :N].cpu().numpy()
+    return H[0] if single else H
+
+
 def fft_twiddles(n_fft):
     k = np.arange(n_fft // 2, dtype=np.float64)
     tw = np.exp(-2j * np.pi * k / n_fft).astype(np.complex64)
@@ -92,7 +143,11 @@ def padded(host, shape, device, dtype=torch.float32):
 class GCCNMFEngine(object):
     """All buffers of one batch shape, allocated once; ``separate()`` runs the full path on device.
 
-    ``GCCNMFEngine(lengths=[n_0, n_1, ...], ...)`` -- mixtures of DIFFERENT lengths -- returns a ``RaggedGCCNMFEngine``."""
+    ``GCCNMFEngine(lengths=[n_0, n_1, ...], ...)`` -- mixtures of DIFFERENT lengths -- returns a ``RaggedGCCNMFEngine``.
+
+    ``dictionaryW``: a pre-trained (n_fft/2+1, K) dictionary (e.g. pretraining.loadPretrainedW): KL-NMF then infers only the coefficients
+    against it (gccnmf_klnmf with GCCNMF_FLAG_FIXED_W, every iteration in one launch) and K is the dictionary's.  ``initialH``: 'random'
+    (the H0 performKLNMF draws) or 'ones'."""
 
     def __new__(cls, n_samples=None, *args, **kwargs):
         if cls is GCCNMFEngine and kwargs.get('lengths') is not None:
@@ -101,9 +156,21 @@ class GCCNMFEngine(object):
         return super(GCCNMFEngine, cls).__new__(cls)
 
     def __init__(self, n_samples, sampleRate=16000, windowSize=1024, hopSize=256, numTDOAs=128,
-                 microphoneSeparationInMetres=1.0, numTargets=3, dictionarySize=128, numIterations=100,
+                 microphoneSeparationInMetres=1.0, numTargets=3, dictionarySize=None, numIterations=100,
                  sparsityAlpha=0, epsilon=1e-16, seedValue=0, batch=1, windowFunction=np.hanning,
-                 device='cuda:0', klnmf_flags=0, nmf_groups=None):
+                 device='cuda:0', klnmf_flags=0, nmf_groups=None, dictionaryW=None, initialH='random'):
+        if initialH not in ('random', 'ones'):
+            raise ValueError("initialH must be 'random' or 'ones'")
+        self.initialH = initialH
+        self.dictionaryW = None
+        if dictionaryW is not None:
+            self.dictionaryW = check_dictionary(dictionaryW, int(windowSize) // 2 + 1)
+            K = self.dictionaryW.shape[1]
+            if dictionarySize is not None and int(dictionarySize) != K:
+                raise ValueError('dictionarySize %d conflicts with the %d atoms of dictionaryW' % (dictionarySize, K))
+            dictionarySize, nmf_groups = K, 1
+        elif dictionarySize is None:
+            dictionarySize = 128
         if not torch.cuda.is_available():
             raise _hip.HipLibraryError('no ROCm device visible: the GCC-NMF HIP path has no CPU fallback')
         self.lib = _hip.lib()
@@ -164,6 +231,10 @@ class GCCNMFEngine(object):
             self.CC = z(B, 2, g.Fp, g.Tp)
             self.W = z(B, g.Fp, g.Kp)
             self.H = z(B, g.Kp, g.Np)
+            if self.dictionaryW is not None:
+                # the dictionary never changes: the per-file W that the masks and the reconstruction read is filled once, here
+                self.W0 = padded(self.dictionaryW, (g.Fp, g.Kp), dev)
+                self.W.copy_(self.W0.unsqueeze(0).expand_as(self.W))
             # nmf_groups equal group workspaces (for one group == the whole-batch workspace)
             self.ws_nmf = z(self.nmf_groups * self.lib.gccnmf_klnmf_workspace_floats(F, g.N, g.K, B // self.nmf_groups))
             self.nmf_streams = [torch.cuda.Stream(device=dev) for _ in range(self.nmf_groups)] if self.nmf_groups > 1 else []
@@ -217,6 +288,15 @@ class GCCNMFEngine(object):
     @_on_device
     def klnmf(self):
         g = self.g
+        if self.dictionaryW is not None:
+            flags = GCCNMF_FLAG_FIXED_W
+            if self.initialH == 'ones':
+                flags |= GCCNMF_FLAG_H_ONES                         # H is output only: no H0 broadcast
+            else:
+                self.H.copy_(self.H0.unsqueeze(0).expand_as(self.H))
+            _hip.check(self.lib.gccnmf_klnmf(_ptr(self.V), _ptr(self.W0), _ptr(self.H), _ptr(self.ws_nmf), g.F, g.N, g.K, self.batch,
+                                             self.iters, self.alpha, self.eps, flags, _stream()), 'gccnmf_klnmf')
+            return
         self.W.copy_(self.W0.unsqueeze(0).expand_as(self.W))
         self.H.copy_(self.H0.unsqueeze(0).expand_as(self.H))
         if self.nmf_groups == 1:
@@ -529,8 +609,8 @@ class RaggedGCCNMFEngine(object):
     dictionaries, a handful of files) the files of each length run their KL-NMF as a batch of their own."""
 
     def __init__(self, lengths, sampleRate=16000, windowSize=1024, hopSize=256, numTDOAs=128, microphoneSeparationInMetres=1.0,
-                 numTargets=3, dictionarySize=128, numIterations=100, sparsityAlpha=0, epsilon=1e-16, seedValue=0,
-                 windowFunction=np.hanning, device='cuda:0', klnmf_flags=0):
+                 numTargets=3, dictionarySize=None, numIterations=100, sparsityAlpha=0, epsilon=1e-16, seedValue=0,
+                 windowFunction=np.hanning, device='cuda:0', klnmf_flags=0, dictionaryW=None, initialH='random'):
         if not torch.cuda.is_available():
             raise _hip.HipLibraryError('no ROCm device visible: the GCC-NMF HIP path has no CPU fallback')
         self.lib = _hip.lib()
@@ -544,7 +624,7 @@ class RaggedGCCNMFEngine(object):
         kw = dict(sampleRate=sampleRate, windowSize=windowSize, hopSize=hopSize, numTDOAs=numTDOAs,
                   microphoneSeparationInMetres=microphoneSeparationInMetres, numTargets=numTargets, dictionarySize=dictionarySize,
                   numIterations=numIterations, sparsityAlpha=sparsityAlpha, epsilon=epsilon, seedValue=seedValue,
-                  windowFunction=windowFunction, device=device, klnmf_flags=klnmf_flags)
+                  windowFunction=windowFunction, device=device, klnmf_flags=klnmf_flags, dictionaryW=dictionaryW, initialH=initialH)
         # one ordinary engine per distinct length: its files (caller's indexes, ascending) are its batch
         self.files_of = {}
         for i, n in enumerate(self.lengths):
@@ -557,7 +637,7 @@ class RaggedGCCNMFEngine(object):
         with torch.cuda.device(self.device):
             z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=self.device)
             self.ragged = None
-            if len(self.sub) > 1:
+            if len(self.sub) > 1 and dictionaryW is None:       # a fixed dictionary: each length's engine runs its own one-launch call
                 import ctypes
                 ws = self.lib.gccnmf_klnmf_ragged_workspace_floats(g.F, g.N, g.K, self.batch)
                 if ws > 0:

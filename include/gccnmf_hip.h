@@ -43,6 +43,14 @@ extern "C" {
 #define GCCNMF_FLAG_GROUPS(n) (GCCNMF_FLAG_CONCURRENT_GROUPS | ((n) << 8))   /* ... n equal groups in all (bits 8-15; 0 = two): launch forms that
                                           * are chosen by the size of a launch (tuning keys 16 / 17) are chosen for the groups together, so a
                                           * file's result does not depend on how the batch was split */
+#define GCCNMF_FLAG_FIXED_W (1 << 16)   /* a pre-trained dictionary: W is ONE [Fp][Kp] zero-padded dictionary shared by every file of the call,
+                                          * read only (bit-identical after the call); H [batch][Kp][Np] holds the initial coefficients on entry and
+                                          * the result on exit (h <- h o W^T(v / Wh) / (colsum W + alpha + eps), every iteration of the call in one
+                                          * launch, csrc/nmf_fixed.hip).  V, workspace, sparsity_alpha and epsilon as for the blind call; the
+                                          * chain-status words are left cleared.  F <= 2049 and K <= 1024, else GCCNMF_ERR_UNSUPPORTED.  Not
+                                          * combinable with bits 0-15 (GCCNMF_ERR_ARG); gccnmf_klnmf_stage / gccnmf_klnmf_ragged reject it */
+#define GCCNMF_FLAG_H_ONES (1 << 17)    /* with GCCNMF_FLAG_FIXED_W only (else GCCNMF_ERR_ARG): the initial H is all ones (the streaming
+                                          * processor's h0 = 1); H is output only and is not read */
 
 int gccnmf_version(void);
 
@@ -153,7 +161,8 @@ int gccnmf_klnmf_chain_status(const float* workspace, int F, int N, int K, int b
 
 /* Which launches gccnmf_klnmf uses for this problem under the current tuning: bit 0 = the direct latency kernels (a handful of files),
  * bit 1 = K1 + K2 as one launch of column tiles (tuning key 16), bit 2 = K3 + K4a as one launch of 64-bin slabs (key 17), bit 3 = the whole
- * call as one chained launch (key 21).  -1 on bad arguments.
+ * call as one chained launch (key 21), bit 4 = the fused fixed-dictionary launch (GCCNMF_FLAG_FIXED_W; then no other bit).  -1 on bad
+ * arguments (a flag combination gccnmf_klnmf rejects, or a fixed-dictionary shape outside its envelope).
  * (Benchmarks and tests name the kernel they time by this; the result of gccnmf_klnmf does not depend on it beyond round-off.) */
 int gccnmf_klnmf_plan(int F, int N, int K, int batch, int flags);
 
