@@ -21,23 +21,36 @@
 // blockIdx.z of every kernel; each per-stream buffer holds S consecutive single-stream images and a kernel first moves its base pointers
 // to image s (64-bit offsets), so the arithmetic of one stream is that of the single-stream call, which is the S = 1 case.  The
 // per-stream switches are words 4 (separation) and 5 (localisation) of the stream's 8-word target row.
+//
+// Multiple mode (frames_mode bit 20, TARGET_MODE_MULTIPLE): N <= 8 target TDOA indexes per stream (words 8.. of a 16-word row), one-hot
+// arg-max-over-targets masks from the scores rt_gccnmf already sums, N masked spectra, N synthesis rings (blockIdx.y), the N largest
+// gccPHAT peaks tracked.  Its kernels are new kernels or the `true` / 16-word instantiations of templates whose other instantiation is
+// the single-target kernel unchanged (LABBOOK R7.3).
 #include "fft_core.h"
 
 typedef float rt_f32x16 __attribute__((ext_vector_type(16)));
 
 #define RT_ROW 8                                           // bank layout: target row {index, eps, beta, noiseFloor, sep, loc, 0, 0}
+#define RT_ROW_MULTI 16                                    // multi-target layout (frames_mode bit 20): the 8 words above + tau_0 .. tau_7
+#define RT_MAX_TARGETS 8
 
-// rows = the bank's [S][RT_ROW] target rows, NULL outside the bank layout: true when this workgroup's stream has `word` switched off
+// rows = the bank's [S][ROW] target rows, NULL outside the bank layout: true when this workgroup's stream has `word` switched off
+template <int ROW = RT_ROW>
 __device__ __forceinline__ bool rt_switched_off(const float* rows, int word) {
-    return rows && rows[(long)blockIdx.z * RT_ROW + word] == 0.f;
+    return rows && rows[(long)blockIdx.z * ROW + word] == 0.f;
 }
 
 // ---- rt_shift: one workgroup per stream, in-place left shift by B of both 8-block buffers ---------------------------
+// MULTI (multi-target layout): grid = (1, N, S), out_ring holds N rings per stream; workgroup y shifts ring y, workgroup 0 also the input
+template <bool MULTI>
 __global__ __launch_bounds__(1024) void rt_shift_kernel(float* __restrict__ in_ring, float* __restrict__ out_ring,
                                                         const float* __restrict__ block_in, int B, int ring) {
     const long sid = blockIdx.z;
     in_ring += sid * 2 * ring;
-    out_ring += sid * 2 * ring;
+    if constexpr (MULTI)
+        out_ring += (sid * gridDim.y + blockIdx.y) * 2 * ring;
+    else
+        out_ring += sid * 2 * ring;
     block_in += sid * 2 * B;
     // ring = 8*B samples per channel, 2 channels.  Chunks of 8192 values in ascending order, every thread loading everything it
     // will store before the barrier: a chunk reads at or above the positions it writes (never below), so no later chunk's stores can
@@ -52,7 +65,7 @@ __global__ __launch_bounds__(1024) void rt_shift_kernel(float* __restrict__ in_r
             vin[n] = vout[n] = 0.f;
             if (i < total) {
                 const int c = i / ring, s = i - c * ring;
-                vin[n] = (s + B < ring) ? in_ring[c * ring + s + B] : block_in[c * B + (s + B - ring)];
+                if (!MULTI || blockIdx.y == 0) vin[n] = (s + B < ring) ? in_ring[c * ring + s + B] : block_in[c * B + (s + B - ring)];
                 vout[n] = (s + B < ring) ? out_ring[c * ring + s + B] : 0.f;
             }
         }
@@ -61,7 +74,7 @@ __global__ __launch_bounds__(1024) void rt_shift_kernel(float* __restrict__ in_r
         for (int n = 0; n < 8; ++n) {
             const int i = base + threadIdx.x + 1024 * n;
             if (i < total) {
-                in_ring[i] = vin[n];
+                if (!MULTI || blockIdx.y == 0) in_ring[i] = vin[n];
                 out_ring[i] = vout[n];
             }
         }
@@ -107,18 +120,23 @@ __global__ __launch_bounds__(FFT_NT) void rt_frames_kernel(const float* __restri
 // dependent global loads (31 us).  Now each of 8 waves owns an eighth of the frequency rows (17 steps at n_fft = 512: ONE batch of
 // loads, all issued before the first use, two TDOA tiles per pass sharing the W and C loads), the partial accumulators meet in
 // LDS, and 32 atoms per workgroup double the number of CUs at work.
+// MULTI (frames_mode bit 20): `ntargets` target rows tau_i = words 8.. of the stream's 16-word row.  Wave 0's per-row pass keeps the
+// total of every row that is a target (the same sum the arg-max over tau sees, bit for bit), and the one-hot masks
+// HMask[i][atom][t] = (i == nanargmax_i G[tau_i]) replace the windowed mask; argmaxTDOA is written as in the single-target form.
 #define RT_G_WAVES 8
 #define RT_G_CHUNK 17
+template <bool MULTI>
 __global__ __launch_bounds__(64 * RT_G_WAVES) void rt_gccnmf_kernel(const float2* __restrict__ C, const float* __restrict__ cosT,
                                                         const float* __restrict__ sinT, const float* __restrict__ W, int F, int K,
                                                         int Kp, int D, int Dp, int Tc, const float* __restrict__ target,
-                                                        int target_mode, int bank, float* __restrict__ HMask, int* __restrict__ argmaxTDOA) {
+                                                        int target_mode, int bank, float* __restrict__ HMask, int* __restrict__ argmaxTDOA,
+                                                        int ntargets) {
     __shared__ float s_part[RT_G_WAVES - 1][32][64];      // partial accumulators (two TDOA tiles) of the other waves
     const long sid = blockIdx.z;
-    target += sid * RT_ROW;
+    target += sid * (MULTI ? RT_ROW_MULTI : RT_ROW);
     if (bank && target[4] == 0.f) return;                 // this stream's separation is off
     C += sid * F * Tc;
-    HMask += sid * Kp * Tc;
+    HMask += sid * (MULTI ? ntargets : 1) * Kp * Tc;
     if (argmaxTDOA) argmaxTDOA += sid * Kp * Tc;
     const int t = blockIdx.y, k0 = blockIdx.x * 32;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -130,6 +148,13 @@ __global__ __launch_bounds__(64 * RT_G_WAVES) void rt_gccnmf_kernel(const float2
     const int steps = (f_hi - f_lo + 1) / 2;
     float best_val = -INFINITY;
     int best_idx = 0;
+    int tg[RT_MAX_TARGETS];                               // MULTI: the target rows (-1: no target), uniform over the workgroup
+    float cap[RT_MAX_TARGETS];                            // MULTI: this lane's total of row tg[i] (NaN until seen)
+#pragma unroll
+    for (int i = 0; i < RT_MAX_TARGETS; ++i) {
+        tg[i] = (MULTI && i < ntargets) ? (int)target[8 + i] : -1;
+        cap[i] = NAN;
+    }
     // two TDOA tiles per pass (they share the W and C loads; D = 64 is one pass), 16 steps' loads in flight together
     for (int tt = 0; tt * 32 < Dp; tt += 2) {
         rt_f32x16 acc0, acc1;
@@ -187,6 +212,11 @@ __global__ __launch_bounds__(64 * RT_G_WAVES) void rt_gccnmf_kernel(const float2
                         best_val = v;
                         best_idx = row;
                     }
+                    if constexpr (MULTI) {
+#pragma unroll
+                        for (int i = 0; i < RT_MAX_TARGETS; ++i)
+                            if (row == tg[i]) cap[i] = v;
+                    }
                 }
             }
         }
@@ -199,7 +229,24 @@ __global__ __launch_bounds__(64 * RT_G_WAVES) void rt_gccnmf_kernel(const float2
             best_val = ov;
             best_idx = oi;
         }
-        if (hh == 0 && atom < K) {
+        if constexpr (MULTI) {
+            // row tau lies in lane half (tau >> 2) & 1; nanargmax over the targets: first maximum wins, NaN ignored, all NaN -> 0
+            int bi = 0;
+            float bv = NAN;
+#pragma unroll
+            for (int i = 0; i < RT_MAX_TARGETS; ++i) {
+                const float o = __shfl_xor(cap[i], 32);
+                const float g = (((tg[i] >> 2) & 1) == hh) ? cap[i] : o;
+                if (i < ntargets && g == g && (bv != bv || g > bv)) {
+                    bv = g;
+                    bi = i;
+                }
+            }
+            if (hh == 0 && atom < K) {
+                for (int i = 0; i < ntargets; ++i) HMask[((long)i * Kp + atom) * Tc + t] = (i == bi) ? 1.f : 0.f;
+                if (argmaxTDOA) argmaxTDOA[(long)atom * Tc + t] = (best_val > -INFINITY) ? best_idx : 0;
+            }
+        } else if (hh == 0 && atom < K) {
             int i = best_idx;
             if (!(best_val > -INFINITY)) i = 0;           // every score NaN (or D == 0): numpy.argmax of an all-NaN column is 0
             const float tgt = target[0], eps = target[1], beta = target[2], nf = target[3];
@@ -248,8 +295,63 @@ __global__ __launch_bounds__(256) void rt_tfmask_kernel(const float* __restrict_
     }
 }
 
+// ---- multi-target layout (frames_mode bit 20): HMask [N][Kp][Tc], Y and tfMask [N][2][F][Tc] per stream ------------------------
+// One pass over the row of W makes all N numerators (the loads of W are shared); numerator i is summed in the denominator's order (the
+// lane-strided chain, the same shuffle tree), so with N = 1 (HMask = 1) every quotient is 1.0 exactly.  grid = (ceil(F/4), 1, S)
+__global__ __launch_bounds__(256) void rt_tfmask_multi_kernel(const float* __restrict__ W, const float* __restrict__ HMask, int F, int K,
+                                                              int Kp, int Tc, const float2* __restrict__ X, float2* __restrict__ Y,
+                                                              float* __restrict__ tfMask, const float* __restrict__ rows, int nt) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int f = blockIdx.x * 4 + wave;
+    if (f >= F || rt_switched_off<RT_ROW_MULTI>(rows, 4)) return;
+    const long sid = blockIdx.z;
+    const long hplane = (long)Kp * Tc, yplane = 2L * F * Tc;
+    HMask += sid * nt * hplane;
+    X += sid * yplane;
+    Y += sid * nt * yplane;
+    tfMask += sid * nt * yplane;
+    const float* Wr = W + (long)f * Kp;
+    float rec = 0.f;
+    for (int k = lane; k < K; k += 64) rec += Wr[k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) rec += __shfl_xor(rec, o);
+    for (int t = 0; t < Tc; ++t) {
+        float s[RT_MAX_TARGETS];
+#pragma unroll
+        for (int i = 0; i < RT_MAX_TARGETS; ++i) s[i] = 0.f;
+        for (int k = lane; k < K; k += 64) {
+            const float w = Wr[k];
+#pragma unroll
+            for (int i = 0; i < RT_MAX_TARGETS; ++i)
+                if (i < nt) s[i] = fmaf(w, HMask[i * hplane + (long)k * Tc + t], s[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < RT_MAX_TARGETS; ++i) {
+            if (i < nt) {
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) s[i] += __shfl_xor(s[i], o);
+            }
+        }
+        if (lane == 0) {
+            const float2 a = X[(long)f * Tc + t], b = X[((long)F + f) * Tc + t];
+#pragma unroll
+            for (int i = 0; i < RT_MAX_TARGETS; ++i) {
+                if (i < nt) {
+                    const float m = s[i] / rec;
+                    tfMask[i * yplane + (long)f * Tc + t] = m;
+                    Y[i * yplane + (long)f * Tc + t] = make_float2(m * a.x, m * a.y);
+                    Y[i * yplane + ((long)F + f) * Tc + t] = make_float2(m * b.x, m * b.y);
+                }
+            }
+        }
+    }
+}
+
 // ---- rt_synth: one workgroup per stream; frames in order (their output ranges overlap) ----------------------------------------
 // Y = the spectra to synthesise; in the bank layout (rows != NULL) a stream whose separation is off takes X instead
+// MULTI: grid y = N targets, one overlap-add ring per target (out_ring [N][2][ring], block_out [N][2][B] per stream); Y == X (separation
+// off for the call) or a stream switched off synthesises the mixture into every one of its N rings
+template <bool MULTI>
 __global__ __launch_bounds__(FFT_NT) void rt_synth_kernel(const float2* __restrict__ Y, int N, int logN, int start0, int start_step,
                                                           int accumulate, int Tc, int ring, int B, int out_delay,
                                                           const float* __restrict__ window, const float2* __restrict__ twiddle,
@@ -260,10 +362,17 @@ __global__ __launch_bounds__(FFT_NT) void rt_synth_kernel(const float2* __restri
     float2* tw = rt_smem + N;
     const int F = N / 2 + 1;
     const long sid = blockIdx.z;
-    if (rt_switched_off(rows, 4)) Y = X;
-    Y += sid * 2 * F * Tc;
-    out_ring += sid * 2 * ring;
-    block_out += sid * 2 * B;
+    if constexpr (MULTI) {
+        const long img = sid * gridDim.y + blockIdx.y;
+        Y = (Y == X || rt_switched_off<RT_ROW_MULTI>(rows, 4)) ? X + sid * 2 * F * Tc : Y + img * 2 * F * Tc;
+        out_ring += img * 2 * ring;
+        block_out += img * 2 * B;
+    } else {
+        if (rt_switched_off(rows, 4)) Y = X;
+        Y += sid * 2 * F * Tc;
+        out_ring += sid * 2 * ring;
+        block_out += sid * 2 * B;
+    }
     const float invN = 1.f / (float)N;
     for (int i = threadIdx.x; i < N / 2; i += FFT_NT) tw[i] = twiddle[i];
     for (int t = 0; t < Tc; ++t) {
@@ -357,6 +466,8 @@ __global__ __launch_bounds__(256) void rt_frames_dft_kernel(const float* __restr
 // rt_synth_dft: one thread per OUTPUT position of the buffer (both channels), frames in ascending order -- the reference's accumulation
 // order (utils.py:113-114), and no two threads ever add into the same sample.  grid = (ceil(positions / 256), 1, S); s_lo = first position.
 // X / rows: as for rt_synth.
+// MULTI: as rt_synth (grid y = N targets)
+template <bool MULTI>
 __global__ __launch_bounds__(256) void rt_synth_dft_kernel(const float2* __restrict__ Y, int N, int start0, int start_step, int accumulate,
                                                            int Tc, int ring, int B, int out_delay, int s_lo, const float* __restrict__ window,
                                                            const float2* __restrict__ table, float* __restrict__ out_ring,
@@ -368,10 +479,17 @@ __global__ __launch_bounds__(256) void rt_synth_dft_kernel(const float2* __restr
     float2* yb = ya + (N / 2 + 1);         // [F] right
     const int F = N / 2 + 1, H = N / 2;
     const long sid = blockIdx.z;
-    if (rt_switched_off(rows, 4)) Y = X;
-    Y += sid * 2 * F * Tc;
-    out_ring += sid * 2 * ring;
-    block_out += sid * 2 * B;
+    if constexpr (MULTI) {
+        const long img = sid * gridDim.y + blockIdx.y;
+        Y = (Y == X || rt_switched_off<RT_ROW_MULTI>(rows, 4)) ? X + sid * 2 * F * Tc : Y + img * 2 * F * Tc;
+        out_ring += img * 2 * ring;
+        block_out += img * 2 * B;
+    } else {
+        if (rt_switched_off(rows, 4)) Y = X;
+        Y += sid * 2 * F * Tc;
+        out_ring += sid * 2 * ring;
+        block_out += sid * 2 * B;
+    }
     const float invN = 1.f / (float)N;
     const int s = s_lo + blockIdx.x * 256 + threadIdx.x;
     const bool live = s < ring;
@@ -424,18 +542,22 @@ __global__ __launch_bounds__(256) void rt_synth_dft_kernel(const float2* __restr
 // ---- rt_localize: one workgroup of 1024 threads per stream = Dq TDOAs x 1024/Dq frequency phases ---------------------------
 // hist is a [D][Lh] float ring with write position hist_pos[0]; target[0] is updated for the NEXT block (:216-222).  In the bank layout
 // a stream whose row word 5 is 0 fills its history and leaves its target index alone.
+// MULTI: the window mean then goes through the offline peak rule (gcc.hip pick_peaks_kernel): strict local maxima, edges excluded, NaN
+// never a peak; the `ntargets` largest, the larger index kept among equal heights, written in ascending order to words 8.. of the row.
+// With fewer peaks than targets the indexes stay as they are.
+template <bool MULTI>
 __global__ __launch_bounds__(1024) void rt_localize_kernel(const float2* __restrict__ C, const float* __restrict__ cosT,
                                                            const float* __restrict__ sinT, int F, int D, int Dp, int Dq, int Tc,
                                                            float* __restrict__ hist, int Lh, int* __restrict__ hist_pos,
                                                            int loc_enabled, int loc_window, float* __restrict__ target,
-                                                           float* __restrict__ gccphat_out, int bank) {
+                                                           float* __restrict__ gccphat_out, int bank, int ntargets) {
     __shared__ float s_sum[1024];
     __shared__ int s_cnt[1024];
     const long sid = blockIdx.z;
     C += sid * F * Tc;
     hist += sid * D * Lh;
     hist_pos += sid;
-    target += sid * RT_ROW;
+    target += sid * (MULTI ? RT_ROW_MULTI : RT_ROW);
     if (gccphat_out) gccphat_out += sid * D * Tc;
     if (bank && target[5] == 0.f) loc_enabled = 0;
     const int tau = threadIdx.x % Dq, g = threadIdx.x / Dq, G = 1024 / Dq;
@@ -487,6 +609,28 @@ __global__ __launch_bounds__(1024) void rt_localize_kernel(const float2* __restr
             s_sum[tau] = m;
         }
         __syncthreads();
+        if constexpr (MULTI) {
+            const int i = threadIdx.x;
+            const float v = (i < D) ? s_sum[i] : NAN;
+            const bool peak = i > 0 && i < D - 1 && v > s_sum[i - 1] && v > s_sum[i + 1];
+            __syncthreads();
+            s_sum[i] = peak ? v : NAN;                                                     // peak heights, NaN elsewhere
+            const int npeaks = __syncthreads_count(peak);
+            int rank = 0;                                                                  // peaks ranked above this one
+            if (peak)
+                for (int j = 0; j < D; ++j) {
+                    const float o = s_sum[j];
+                    rank += (o > v || (o == v && j > i)) ? 1 : 0;
+                }
+            const bool keep = peak && rank < ntargets;
+            s_cnt[i] = keep ? 1 : 0;
+            __syncthreads();
+            if (keep && npeaks >= ntargets) {
+                int slot = 0;
+                for (int j = 0; j < i; ++j) slot += s_cnt[j];
+                target[8 + slot] = (float)i;
+            }
+        } else
         // numpy.argmax: NaN counts as the maximum, first occurrence wins.  Tree reduction over (rank, index) pairs: a NaN ranks
         // above every number, equal ranks keep the smaller index (the serial scan this replaces cost ~6 us of the call).
         {
@@ -528,12 +672,13 @@ __global__ __launch_bounds__(256) void rt_fill_kernel(float* __restrict__ p, flo
 
 // r[f][col] = |X_c[f][t]| / sum_k W[f][k] h[k][col]; one wave per frequency row, grid = (ceil(F/4), 1, S)
 // first != 0: h is still all ones (no fill pass: the first update reads no coefficients and WRITES them)
+template <int ROW>
 __global__ __launch_bounds__(256) void rt_wh_kernel(const float* __restrict__ W, const float* __restrict__ Hc, const float2* __restrict__ X,
                                                     float* __restrict__ Rv, int F, int K, int Kp, int Tc, int first,
                                                     const float* __restrict__ rows) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int f = blockIdx.x * 4 + wave;
-    if (f >= F || rt_switched_off(rows, 4)) return;
+    if (f >= F || rt_switched_off<ROW>(rows, 4)) return;
     const int ncol = 2 * Tc;
     const long sid = blockIdx.z;
     Hc += sid * Kp * ncol;
@@ -569,11 +714,12 @@ __global__ __launch_bounds__(256) void rt_wh_kernel(const float* __restrict__ W,
 // h[k][col] *= (sum_f W[f][k] r[f][col]) / colsumW[k]; 16 atoms x 16 frequency phases per workgroup, grid = Kp/16 (the first version
 // had 64 x 4: 16 workgroups with a 65-step chain of dependent loads, 17 us; now 64 workgroups, 17 independent loads per thread);
 // grid = (Kp/16, 1, S)
+template <int ROW>
 __global__ __launch_bounds__(256) void rt_hupdate_kernel(const float* __restrict__ W, const float* __restrict__ Rv,
                                                          const float* __restrict__ colsumW, float* __restrict__ Hc, int F, int K, int Kp,
                                                          int Tc, int first, const float* __restrict__ rows) {
     __shared__ float red[4][16];
-    if (rt_switched_off(rows, 4)) return;                 // the whole workgroup: before any barrier
+    if (rt_switched_off<ROW>(rows, 4)) return;            // the whole workgroup: before any barrier
     const int c = threadIdx.x & 15, q = threadIdx.x >> 4, wave = threadIdx.x >> 6;
     const int k = blockIdx.x * 16 + c;
     const int ncol = 2 * Tc;
@@ -644,6 +790,76 @@ __global__ __launch_bounds__(256) void rt_tfmask_h_kernel(const float* __restric
     }
 }
 
+// multi-target layout: m_{i,c} = sum_k W h_c M_i / sum_k W h_c for all N targets in one pass over the row of W (and h); numerator i
+// in the denominator's order, so N = 1 gives 1.0 exactly (no contraction here: the denominator adds the rounded products w * h as the
+// numerators' fmaf(w * h, 1, .) do).  HMask [N][Kp][Tc], Y and tfMask [N][2][F][Tc] per stream; grid = (ceil(F/4), 1, S)
+__global__ __launch_bounds__(256) void rt_tfmask_h_multi_kernel(const float* __restrict__ W, const float* __restrict__ HMask,
+                                                                const float* __restrict__ Hc, int F, int K, int Kp, int Tc,
+                                                                const float2* __restrict__ X, float2* __restrict__ Y,
+                                                                float* __restrict__ tfMask, const float* __restrict__ rows, int nt) {
+#pragma clang fp contract(off)
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int f = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
+    if (f >= F || rt_switched_off<RT_ROW_MULTI>(rows, 4)) return;
+    const int ncol = 2 * Tc;
+    const long sid = blockIdx.z;
+    const long hplane = (long)Kp * Tc, yplane = 2L * F * Tc;
+    HMask += sid * nt * hplane;
+    Hc += sid * Kp * ncol;
+    X += sid * yplane;
+    Y += sid * nt * yplane;
+    tfMask += sid * nt * yplane;
+    const float* Wr = W + (long)f * Kp;
+    for (int t = 0; t < Tc; ++t) {                         // both channels of a frame in one pass over the row of W
+        float d0 = 0.f, d1 = 0.f, n0[RT_MAX_TARGETS], n1[RT_MAX_TARGETS];
+#pragma unroll
+        for (int i = 0; i < RT_MAX_TARGETS; ++i) n0[i] = n1[i] = 0.f;
+        for (int k = lane; k < K; k += 64) {
+            const float w = Wr[k];
+            const float2 h = *(const float2*)(Hc + (long)k * ncol + 2 * t);
+            const float wh0 = w * h.x, wh1 = w * h.y;
+            d0 += wh0;
+            d1 += wh1;
+#pragma unroll
+            for (int i = 0; i < RT_MAX_TARGETS; ++i) {
+                if (i < nt) {
+                    const float hm = HMask[i * hplane + (long)k * Tc + t];
+                    n0[i] = fmaf(wh0, hm, n0[i]);
+                    n1[i] = fmaf(wh1, hm, n1[i]);
+                }
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            d0 += __shfl_xor(d0, o);
+            d1 += __shfl_xor(d1, o);
+        }
+#pragma unroll
+        for (int i = 0; i < RT_MAX_TARGETS; ++i) {
+            if (i < nt) {
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {
+                    n0[i] += __shfl_xor(n0[i], o);
+                    n1[i] += __shfl_xor(n1[i], o);
+                }
+            }
+        }
+        if (lane == 0) {
+            const float2 a = X[(long)f * Tc + t], b = X[((long)F + f) * Tc + t];
+#pragma unroll
+            for (int i = 0; i < RT_MAX_TARGETS; ++i) {
+                if (i < nt) {
+                    const float m0 = n0[i] / d0, m1 = n1[i] / d1;
+                    tfMask[i * yplane + (long)f * Tc + t] = m0;
+                    tfMask[i * yplane + ((long)F + f) * Tc + t] = m1;
+                    Y[i * yplane + (long)f * Tc + t] = make_float2(m0 * a.x, m0 * a.y);
+                    Y[i * yplane + ((long)F + f) * Tc + t] = make_float2(m1 * b.x, m1 * b.y);
+                }
+            }
+        }
+    }
+}
+
 extern "C" {
 
 // Every buffer is passed explicitly (allocation lives with the host, gcc_nmf_amd/realtime.py).
@@ -651,6 +867,7 @@ extern "C" {
 //   frames_mode = 1: the reference's GCCNMFProcessor.processFrames on its own: in_ring = windowed-sample frames [2][Tc][N]
 //                    in, out_ring = processed frames [2][Tc][N] out, no shift / overlap-add (block_in, block_out unused).
 //   bit 3 + bits 8..19 = S - 1: a bank of S streams in one set of launches (the layout is documented in include/gccnmf_hip.h).
+//   bit 20 + bits 21..23 = N - 1: multi-target layout (target_mode 1): N one-hot masks, N outputs, N tracked peaks per stream.
 int gccnmf_rt_process_block_ll(const float* block_in, float* block_out, float* in_ring, float* out_ring, float* X, float* Y, float* C,
                                float* HMask, int* argmaxTDOA, float* tfMask, float* hist, int* hist_pos, float* target,
                                float* gccphat, const float* W, const float* cosT, const float* sinT, const float* window,
@@ -661,12 +878,16 @@ int gccnmf_rt_process_block_ll(const float* block_in, float* block_out, float* i
     GCCNMF_ENTER();
     // frames_mode_bits: 1 = frames mode (above); 2 = leave the localisation kernel out of this call; 4 = ONLY the localisation kernel
     // (2 then 4 = the same work in two calls, so that a host can fetch block_out before the tracking update has run); 8 = bank layout
-    // of S = bits 8..19 + 1 streams (streaming only); any bit above 19, or S bits without the bank layout, is an error
+    // of S = bits 8..19 + 1 streams (streaming only); 1 << 20 = multi-target layout of NT = bits 21..23 + 1 targets (target_mode 1 only);
+    // any bit above 23, S bits without the bank layout, or target bits without the multi-target layout is an error
     const int frames_mode = frames_mode_bits & 1;
     const bool skip_localize = frames_mode_bits & 2, only_localize = frames_mode_bits & 4;
     const int bank = (frames_mode_bits >> 3) & 1;
     const int S = ((frames_mode_bits >> 8) & 0xfff) + 1;
-    if ((frames_mode_bits & ~0xfffff) || (bank && frames_mode) || (!bank && S > 1)) return GCCNMF_ERR_ARG;
+    const bool multi = (frames_mode_bits >> 20) & 1;
+    const int NT = ((frames_mode_bits >> 21) & 7) + 1;
+    if ((frames_mode_bits & ~0xffffff) || (bank && frames_mode) || (!bank && S > 1)) return GCCNMF_ERR_ARG;
+    if ((multi && target_mode != 1) || (!multi && NT > 1)) return GCCNMF_ERR_ARG;
     const float* rows = bank ? target : nullptr;          // the per-stream switches the mask and synthesis kernels read
     // powers of two from 64 up: the radix-2 LDS transform (twiddle = N/2 values of exp(-2 pi j k / N)); every other even size: the direct
     // sums above (twiddle = the N-entry table (cos, sin)(2 pi k / N))
@@ -688,21 +909,32 @@ int gccnmf_rt_process_block_ll(const float* block_in, float* block_out, float* i
     const size_t lds = sizeof(float2) * (windowSize + windowSize / 2);
     int Dq = 64;
     while (Dq < D) Dq *= 2;                 // power of two so that 1024 % Dq == 0
+    auto localize = [&]() {
+        if (multi)
+            hipLaunchKernelGGL(rt_localize_kernel<true>, dim3(1, 1, S), dim3(1024), 0, s, (const float2*)C, cosT, sinT, F, D, Dp, Dq, Tc, hist,
+                               numTDOAHistory, hist_pos, localization_enabled, localization_window, target, gccphat, bank, NT);
+        else
+            hipLaunchKernelGGL(rt_localize_kernel<false>, dim3(1, 1, S), dim3(1024), 0, s, (const float2*)C, cosT, sinT, F, D, Dp, Dq, Tc, hist,
+                               numTDOAHistory, hist_pos, localization_enabled, localization_window, target, gccphat, bank, 1);
+    };
     if (only_localize) {
-        hipLaunchKernelGGL(rt_localize_kernel, dim3(1, 1, S), dim3(1024), 0, s, (const float2*)C, cosT, sinT, F, D, Dp, Dq, Tc, hist,
-                           numTDOAHistory, hist_pos, localization_enabled, localization_window, target, gccphat, bank);
+        localize();
         GCCNMF_CHECK_LAUNCH();
         return GCCNMF_OK;
     }
     if (!frames_mode) {
-        hipLaunchKernelGGL(rt_shift_kernel, dim3(1, 1, S), dim3(1024), 0, s, in_ring, out_ring, block_in, blockSize, ring);
+        if (multi)
+            hipLaunchKernelGGL(rt_shift_kernel<true>, dim3(1, NT, S), dim3(1024), 0, s, in_ring, out_ring, block_in, blockSize, ring);
+        else
+            hipLaunchKernelGGL(rt_shift_kernel<false>, dim3(1, 1, S), dim3(1024), 0, s, in_ring, out_ring, block_in, blockSize, ring);
         GCCNMF_CHECK_LAUNCH();
     }
     const size_t lds_dft = sizeof(float2) * (2 * windowSize + 2);
     if (!pow2 && lds_dft + 4096 > 64 * 1024) {
         // windows above ~3800 samples: the table + frame image (+ the analysis kernel's 4 KB of static LDS) pass the 64 KB a launch gets by default
         if (hipFuncSetAttribute((const void*)rt_frames_dft_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dft) != hipSuccess ||
-            hipFuncSetAttribute((const void*)rt_synth_dft_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dft) != hipSuccess)
+            hipFuncSetAttribute((const void*)(multi ? rt_synth_dft_kernel<true> : rt_synth_dft_kernel<false>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dft) != hipSuccess)
             return GCCNMF_ERR_LAUNCH;
     }
     if (pow2) {
@@ -714,43 +946,59 @@ int gccnmf_rt_process_block_ll(const float* block_in, float* block_out, float* i
     }
     GCCNMF_CHECK_LAUNCH();
     if (separation_enabled) {
-        hipLaunchKernelGGL(rt_gccnmf_kernel, dim3(Kp / 32, Tc, S), dim3(64 * RT_G_WAVES), 0, s, (const float2*)C, cosT, sinT, W, F, K, Kp, D, Dp,
-                           Tc, target, target_mode, bank, HMask, argmaxTDOA);
+        if (multi)
+            hipLaunchKernelGGL(rt_gccnmf_kernel<true>, dim3(Kp / 32, Tc, S), dim3(64 * RT_G_WAVES), 0, s, (const float2*)C, cosT, sinT, W, F, K,
+                               Kp, D, Dp, Tc, target, target_mode, bank, HMask, argmaxTDOA, NT);
+        else
+            hipLaunchKernelGGL(rt_gccnmf_kernel<false>, dim3(Kp / 32, Tc, S), dim3(64 * RT_G_WAVES), 0, s, (const float2*)C, cosT, sinT, W, F, K,
+                               Kp, D, Dp, Tc, target, target_mode, bank, HMask, argmaxTDOA, 1);
         GCCNMF_CHECK_LAUNCH();
         if (numHUpdates == 0) {
-            hipLaunchKernelGGL(rt_tfmask_kernel, dim3(gccnmf_ceil_div(F, 4), 1, S), dim3(256), 0, s, W, HMask, F, K, Kp, Tc, (const float2*)X,
-                               (float2*)Y, tfMask, rows);
+            if (multi)
+                hipLaunchKernelGGL(rt_tfmask_multi_kernel, dim3(gccnmf_ceil_div(F, 4), 1, S), dim3(256), 0, s, W, HMask, F, K, Kp, Tc,
+                                   (const float2*)X, (float2*)Y, tfMask, rows, NT);
+            else
+                hipLaunchKernelGGL(rt_tfmask_kernel, dim3(gccnmf_ceil_div(F, 4), 1, S), dim3(256), 0, s, W, HMask, F, K, Kp, Tc, (const float2*)X,
+                                   (float2*)Y, tfMask, rows);
             GCCNMF_CHECK_LAUNCH();
         } else {
+            // the coefficient updates do not depend on the targets: the same kernels, reading the switches at the layout's row stride
+            auto wh = multi ? rt_wh_kernel<RT_ROW_MULTI> : rt_wh_kernel<RT_ROW>;
+            auto hupdate = multi ? rt_hupdate_kernel<RT_ROW_MULTI> : rt_hupdate_kernel<RT_ROW>;
             for (int it = 0; it < numHUpdates; ++it) {      // h0 = 1 is implicit in the first update (no fill pass)
-                hipLaunchKernelGGL(rt_wh_kernel, dim3(gccnmf_ceil_div(F, 4), 1, S), dim3(256), 0, s, W, Hcoef, (const float2*)X, Rv, F, K, Kp,
+                hipLaunchKernelGGL(wh, dim3(gccnmf_ceil_div(F, 4), 1, S), dim3(256), 0, s, W, Hcoef, (const float2*)X, Rv, F, K, Kp,
                                    Tc, it == 0 ? 1 : 0, rows);
                 GCCNMF_CHECK_LAUNCH();
-                hipLaunchKernelGGL(rt_hupdate_kernel, dim3(Kp / 16, 1, S), dim3(256), 0, s, W, Rv, colsumW, Hcoef, F, K, Kp, Tc, it == 0 ? 1 : 0,
+                hipLaunchKernelGGL(hupdate, dim3(Kp / 16, 1, S), dim3(256), 0, s, W, Rv, colsumW, Hcoef, F, K, Kp, Tc, it == 0 ? 1 : 0,
                                    rows);
                 GCCNMF_CHECK_LAUNCH();
             }
-            hipLaunchKernelGGL(rt_tfmask_h_kernel, dim3(gccnmf_ceil_div(F, 4), 1, S), dim3(256), 0, s, W, HMask, Hcoef, F, K, Kp, Tc,
-                               (const float2*)X, (float2*)Y, tfMask, rows);
+            if (multi)
+                hipLaunchKernelGGL(rt_tfmask_h_multi_kernel, dim3(gccnmf_ceil_div(F, 4), 1, S), dim3(256), 0, s, W, HMask, Hcoef, F, K, Kp, Tc,
+                                   (const float2*)X, (float2*)Y, tfMask, rows, NT);
+            else
+                hipLaunchKernelGGL(rt_tfmask_h_kernel, dim3(gccnmf_ceil_div(F, 4), 1, S), dim3(256), 0, s, W, HMask, Hcoef, F, K, Kp, Tc,
+                                   (const float2*)X, (float2*)Y, tfMask, rows);
             GCCNMF_CHECK_LAUNCH();
         }
     }
     if (pow2) {
-        hipLaunchKernelGGL(rt_synth_kernel, dim3(1, 1, S), dim3(FFT_NT), lds, s, (const float2*)(separation_enabled ? Y : X), windowSize, logN,
+        hipLaunchKernelGGL(multi ? rt_synth_kernel<true> : rt_synth_kernel<false>, dim3(1, multi ? NT : 1, S), dim3(FFT_NT), lds, s,
+                           (const float2*)(separation_enabled ? Y : X), windowSize, logN,
                            start0, start_step, frames_mode ? 0 : 1, Tc, ring, blockSize, out_delay_blocks, synthesis_window,
                            (const float2*)twiddle, out_ring, block_out, (const float2*)X, rows);
     } else {
         // positions that receive a frame this call, plus the block handed out (it may lie in front of them)
         const int h0 = ring - (out_delay_blocks + 1) * blockSize;
         const int s_lo = frames_mode ? 0 : (start0 < h0 ? start0 : (h0 > 0 ? h0 : 0));
-        hipLaunchKernelGGL(rt_synth_dft_kernel, dim3(gccnmf_ceil_div(ring - s_lo, 256), 1, S), dim3(256), lds_dft, s,
+        hipLaunchKernelGGL(multi ? rt_synth_dft_kernel<true> : rt_synth_dft_kernel<false>, dim3(gccnmf_ceil_div(ring - s_lo, 256), multi ? NT : 1, S),
+                           dim3(256), lds_dft, s,
                            (const float2*)(separation_enabled ? Y : X), windowSize, start0, start_step, frames_mode ? 0 : 1, Tc, ring, blockSize,
                            out_delay_blocks, s_lo, synthesis_window, (const float2*)twiddle, out_ring, block_out, (const float2*)X, rows);
     }
     GCCNMF_CHECK_LAUNCH();
     if (skip_localize) return GCCNMF_OK;
-    hipLaunchKernelGGL(rt_localize_kernel, dim3(1, 1, S), dim3(1024), 0, s, (const float2*)C, cosT, sinT, F, D, Dp, Dq, Tc, hist,
-                       numTDOAHistory, hist_pos, localization_enabled, localization_window, target, gccphat, bank);
+    localize();
     GCCNMF_CHECK_LAUNCH();
     return GCCNMF_OK;
 }

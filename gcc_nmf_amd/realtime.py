@@ -7,6 +7,8 @@
 block-in / block-out path (input ring, frames, mask, synthesis, overlap-add and TDOA tracking all on device).
 ``StreamingGCCNMFBank`` runs S such streams of one configuration in the same device call per block, each bit for bit a
 ``StreamingGCCNMF`` of its own.
+``targetMode = TARGET_MODE_MULTIPLE`` separates ``numSources`` talkers per stream instead of enhancing one (frames_mode bit 20): one-hot
+arg-max-over-targets coefficient masks, one output per target, the N largest peaks of the gccPHAT window mean tracked online.
 No CPU fallback: without the library / a device the constructor raises ``HipLibraryError``.
 """
 import numpy as np
@@ -19,6 +21,8 @@ SPEED_OF_SOUND_IN_METRES_PER_SECOND = 340.29
 TARGET_MODE_BOXCAR = 0                   # gccNMFProcessor.py:35-37
 TARGET_MODE_MULTIPLE = 1
 TARGET_MODE_WINDOW_FUNCTION = 2
+MAX_SOURCES = 8                          # frames_mode bits 21..23 (csrc/rt.hip)
+_MULTI_LAYOUT = 1 << 20
 
 
 def asymmetricWindows(windowSize, synthesisSize):
@@ -46,16 +50,25 @@ def _device():
 class GCCNMFProcessor(object):
     """gccNMF/realtime/gccNMFProcessor.py:167-275.  ``dictionariesW[dictionaryType][dictionarySize]`` is the (F, K) float32
     dictionary (:241).  ``numTDOAs`` is an attribute the reference receives through its parameter queue before ``reset()``;
-    here it is also a constructor keyword."""
+    here it is also a constructor keyword, and so is ``numSources`` (the talkers separated with ``targetMode = TARGET_MODE_MULTIPLE``,
+    1..8; like the reference, :131, a new value takes effect with ``reset()``).
+
+    Multiple mode (parity unpinned: the reference defines the mode, :35-37, and never built it): atom k of frame t goes to the target
+    TDOA index whose GCC-NMF score is largest (``gccNMFFunctions.py:137-143`` on the streaming scores), every target has its own mask,
+    synthesis and output, and the online localisation keeps the ``numSources`` largest peaks of the gccPHAT window mean as the next
+    block's targets, in ascending order -- target identity is left-to-right order, so two talkers that cross swap outputs.  The host
+    mirrors ``gccPHATHistory`` and ``inputSpectrogramHistory`` are filled as in the other modes and ``tdoaHistory`` receives the N
+    indexes as an (N, 1) column; ``outputSpectrogramHistory`` and ``coefficientMaskHistories`` are not filled in this mode."""
 
     def __init__(self, sampleRate, windowSize, numTimePerChunk, dictionariesW, dictionaryType, dictionarySize, numHUpdates,
                  microphoneSeparationInMetres, localizationEnabled, localizationWindowSize, gccPHATHistory=None, tdoaHistory=None,
                  inputSpectrogramHistory=None, outputSpectrogramHistory=None, coefficientMaskHistories=None, numTDOAs=64,
-                 numTDOAHistory=128, analysisWindow=None, synthesisWindow=None):
+                 numTDOAHistory=128, analysisWindow=None, synthesisWindow=None, numSources=2):
         # any even size like the reference (numpy.fft.rfft / irfft, gccNMFProcessor.py:202,:231): powers of two from 64 up take the
         # radix-2 LDS transform, every other even size the direct-sum kernels of csrc/rt.hip
         if int(windowSize) != windowSize or int(windowSize) < 4 or int(windowSize) > 4096 or int(windowSize) % 2:
             raise ValueError('windowSize=%r is not supported by the HIP frame processor: an even size from 4 to 4096' % (windowSize,))
+        _check_num_sources(numSources)
         self.lib = _hip.lib()
         self.device = _device()
         self.sampleRate, self.windowSize, self.numTimePerChunk = sampleRate, int(windowSize), int(numTimePerChunk)
@@ -84,6 +97,7 @@ class GCCNMFProcessor(object):
                 raise ValueError('analysisWindow / synthesisWindow must have windowSize samples')
             self.windowFunction, self.synthesisWindowFunction = a[:, np.newaxis], sy[:, np.newaxis]
         self._target_host = np.array([10.0, 2.0, 1.0, 0.0], np.float32)                                   # :195-198
+        self.numSources = numSources
         self.reset()
 
     # ---- reference API ------------------------------------------------------------------------------------------
@@ -97,6 +111,7 @@ class GCCNMFProcessor(object):
         if self.numFrequencies != self.windowSize // 2 + 1:
             raise ValueError('dictionary has %d rows, window size %d needs %d' % (self.numFrequencies, self.windowSize, self.windowSize // 2 + 1))
         F, K, D, Tc = self.numFrequencies, self.numAtom, self.numTDOAs, self.numTimePerChunk
+        NS = _check_num_sources(self.numSources)
         self.Kp, self.Dp = -(-K // 64) * 64, -(-D // 32) * 32
         self.frequenciesInHz = np.linspace(0, self.sampleRate / 2, F).astype(np.float32)                 # :245
         self.maxTDOA = self.microphoneSeparationInMetres / SPEED_OF_SOUND_IN_METRES_PER_SECOND
@@ -117,7 +132,8 @@ class GCCNMFProcessor(object):
             ang = 2.0 * np.pi * np.arange(N, dtype=np.float64) / N
             self.dTwiddle = torch.from_numpy(np.ascontiguousarray(np.stack([np.cos(ang), np.sin(ang)], axis=1).astype(np.float32)).reshape(-1)).to(dev)
         # what the host mirrors are computed from lives in ONE block, so that they cost one download per call: X | Y | HMask | gccPHAT | target
-        sizes = [2 * F * Tc * 2, 2 * F * Tc * 2, self.Kp * Tc, D * Tc, 4]
+        # (the target row is 16 words: {index, epsilon, beta, noiseFloor, -, -, -, -, tau_0 .. tau_7}; words 8.. are multiple mode's)
+        sizes = [2 * F * Tc * 2, 2 * F * Tc * 2, self.Kp * Tc, D * Tc, 16]
         offs = np.concatenate([[0], np.cumsum([-(-n // 4) * 4 for n in sizes])])
         self.dMirror = z(int(offs[-1]))
         part = lambda i, *shape: self.dMirror[int(offs[i]):int(offs[i]) + sizes[i]].view(*shape)
@@ -125,19 +141,55 @@ class GCCNMFProcessor(object):
         self.dHMask, self.dArgmax = part(2, self.Kp, Tc), z(self.Kp, Tc, dtype=torch.int32)
         self.dTfMask, self.dGccPhat = z(2, F, Tc), part(3, D, Tc)     # tfMask: [F][Tc] used without coefficient inference, [2][F][Tc] with
         self.dHist, self.dHistPos = z(D, self.numTDOAHistory), z(1, dtype=torch.int32)
-        self.dTarget = part(4, 4)
-        self.dTarget.copy_(torch.from_numpy(self._target_host))
+        self.dTarget = part(4, 16)
+        self.dTarget[:4].copy_(torch.from_numpy(self._target_host))
         self._mirror_offs, self._mirror_sizes, self._mirror_host = offs, sizes, None
         # _target_dirty: a device call ran with the online localisation on since the value was last known on the host
         self._calls, self._target_dirty, self._target_value, self._target_pin = 0, False, float(self._target_host[0]), None
         self.dFramesIn, self.dFramesOut = z(2, Tc, self.windowSize), z(2, Tc, self.windowSize)
+        # multiple mode: N masks, masked spectra and frames (the other buffers are shared with the single-target modes)
+        self._sources = NS
+        self.dYm, self.dHMaskm, self.dTfMaskm = z(NS, 2, F, Tc, 2), z(NS, self.Kp, Tc), z(NS, 2, F, Tc)
+        self.dFramesOutM = z(NS, 2, Tc, self.windowSize)
+        self._indexes_host = default_target_indexes(NS, D)
+        self.dTarget[8:8 + NS].copy_(torch.from_numpy(self._indexes_host))
+        self._indexes_dirty, self._indexes_pin = False, None
 
     @_on_device
     def setTargetTDOARange(self, targetTDOAIndex, targetTDOAEpsilon, targetTDOABeta, targetTDOANoiseFloor):
         """:272-275"""
         self._target_host = np.array([targetTDOAIndex, targetTDOAEpsilon, targetTDOABeta, targetTDOANoiseFloor], np.float32)
-        self.dTarget.copy_(torch.from_numpy(self._target_host))
+        self.dTarget[:4].copy_(torch.from_numpy(self._target_host))
         self._target_value, self._target_dirty = float(self._target_host[0]), False
+
+    @_on_device
+    def setTargetTDOAIndexes(self, indexes):
+        """Multiple mode's targets (the reference's ``targetTDOAIndexes`` message, gccNMFProcessor.py:108-111): ``numSources`` integer
+        TDOA indexes in [0, numTDOAs).  The online localisation rewrites them after every block while it is enabled."""
+        v = _check_target_indexes(indexes, self._sources, self.numTDOAs)
+        self.dTarget[8:8 + self._sources].copy_(torch.from_numpy(v))
+        self._indexes_host, self._indexes_dirty = v, False
+
+    @property
+    def targetTDOAIndexes(self):
+        """(numSources,) multiple mode's target indexes, cached like ``targetTDOAIndex`` (fetched only when the tracking ran since the
+        last read)."""
+        if self._indexes_dirty:
+            if self._indexes_pin is None:
+                self._indexes_pin = torch.zeros(16, dtype=torch.float32).pin_memory()
+            with torch.cuda.device(self.device):
+                self._indexes_pin.copy_(self.dTarget, non_blocking=True)
+                torch.cuda.current_stream(self.device).synchronize()
+            self._indexes_host, self._indexes_dirty = self._indexes_pin.numpy()[8:8 + self._sources].copy(), False
+        return self._indexes_host.copy()
+
+    def multiple(self):
+        """True when the next call runs multiple mode; then ``numSources`` must be the value the last ``reset()`` saw."""
+        if int(self.targetMode) != TARGET_MODE_MULTIPLE:
+            return False
+        if int(self.numSources) != self._sources:
+            raise ValueError('numSources changed from %d to %r: call reset() first' % (self._sources, self.numSources))
+        return True
 
     @property
     def targetTDOAIndex(self):
@@ -150,19 +202,27 @@ class GCCNMFProcessor(object):
             if self._target_pin is None:
                 self._target_pin = torch.zeros(4, dtype=torch.float32).pin_memory()
             with torch.cuda.device(self.device):
-                self._target_pin.copy_(self.dTarget, non_blocking=True)
+                self._target_pin.copy_(self.dTarget[:4], non_blocking=True)
                 torch.cuda.current_stream(self.device).synchronize()
             self._target_value, self._target_dirty = float(self._target_pin[0]), False
         return self._target_value
 
     @_on_device
     def _call(self, block_in, block_out, in_ring, out_ring, hop, block, frames_mode, out_delay_blocks=2):
+        """out_ring / block_out: [N][2][...] in multiple mode."""
         self._calls += 1
+        multi = self.multiple()
         if self.localizationEnabled:
-            self._target_dirty = True
+            if multi:
+                self._indexes_dirty = True
+            else:
+                self._target_dirty = True
+        if multi:
+            frames_mode |= _MULTI_LAYOUT | ((self._sources - 1) << 21)
+        Y, HMask, tfMask = (self.dYm, self.dHMaskm, self.dTfMaskm) if multi else (self.dY, self.dHMask, self.dTfMask)
         _hip.check(self.lib.gccnmf_rt_process_block_ll(
-            _ptr(block_in), _ptr(block_out), _ptr(in_ring), _ptr(out_ring), _ptr(self.dX), _ptr(self.dY), _ptr(self.dC), _ptr(self.dHMask),
-            _ptr(self.dArgmax), _ptr(self.dTfMask), _ptr(self.dHist), _ptr(self.dHistPos), _ptr(self.dTarget), _ptr(self.dGccPhat),
+            _ptr(block_in), _ptr(block_out), _ptr(in_ring), _ptr(out_ring), _ptr(self.dX), _ptr(Y), _ptr(self.dC), _ptr(HMask),
+            _ptr(self.dArgmax), _ptr(tfMask), _ptr(self.dHist), _ptr(self.dHistPos), _ptr(self.dTarget), _ptr(self.dGccPhat),
             _ptr(self.dW), _ptr(self.dCos), _ptr(self.dSin), _ptr(self.dWindow), _ptr(self.dSynthWindow), _ptr(self.dTwiddle),
             _ptr(self.dColsum), _ptr(self.dHcoef), _ptr(self.dRv), self.windowSize, hop, block,
             self.numAtom, self.Kp, self.numTDOAs, self.Dp, self.numTDOAHistory, int(self.targetMode), int(bool(self.separationEnabled)),
@@ -171,15 +231,20 @@ class GCCNMFProcessor(object):
 
     @_on_device
     def processFrames(self, windowedSamples):
-        """:201-231.  (2, windowSize, Tc) windowed-sample frames -> (2, windowSize, Tc) processed frames (float32)."""
+        """:201-231.  (2, windowSize, Tc) windowed-sample frames -> (2, windowSize, Tc) processed frames (float32); in multiple mode
+        (numSources, 2, windowSize, Tc), one set of frames per target."""
         ws = np.asarray(windowedSamples, np.float32)
         Tc = self.numTimePerChunk
         if ws.shape != (2, self.windowSize, Tc):
             raise ValueError('expected windowedSamples of shape %s, got %s' % ((2, self.windowSize, Tc), ws.shape))
         self.dFramesIn.copy_(torch.from_numpy(np.ascontiguousarray(ws.transpose(0, 2, 1))))
         # hop = windowSize, block = Tc * windowSize describes Tc back-to-back frames to the kernels' start0/step arithmetic
-        self._call(None, None, self.dFramesIn, self.dFramesOut, self.windowSize, Tc * self.windowSize, 1)
-        out = self.dFramesOut.cpu().numpy().transpose(0, 2, 1)
+        if self.multiple():
+            self._call(None, None, self.dFramesIn, self.dFramesOutM, self.windowSize, Tc * self.windowSize, 1)
+            out = self.dFramesOutM.cpu().numpy().transpose(0, 1, 3, 2)
+        else:
+            self._call(None, None, self.dFramesIn, self.dFramesOut, self.windowSize, Tc * self.windowSize, 1)
+            out = self.dFramesOut.cpu().numpy().transpose(0, 2, 1)
         self.fill_histories()
         return out
 
@@ -200,9 +265,20 @@ class GCCNMFProcessor(object):
         torch.cuda.current_stream(self.device).synchronize()
         m, o, n = self._mirror_host.numpy(), self._mirror_offs, self._mirror_sizes
         self._target_value, self._target_dirty = float(m[o[4]]), False                  # the tracked index came along
+        N = self._sources
+        self._indexes_host, self._indexes_dirty = m[o[4] + 8:o[4] + 8 + N].copy(), False     # ... and multiple mode's
+        multi = self.multiple()
         F, Tc, K, D = self.numFrequencies, self.numTimePerChunk, self.numAtom, self.numTDOAs
         cplx = lambda i: m[o[i]:o[i] + n[i]].reshape(2, F, Tc, 2).copy().view(np.complex64)[..., 0]
         X = cplx(0)
+        if multi:                   # N masks and outputs: no output-spectrogram or coefficient-mask mirror in this mode
+            if self.inputSpectrogramHistory is not None:
+                self.inputSpectrogramHistory.set(-np.mean(np.abs(X), axis=0) ** (1 / 3.0))
+            if self.gccPHATHistory is not None:
+                self.gccPHATHistory.set(m[o[3]:o[3] + n[3]].reshape(D, Tc).copy())
+            if self.tdoaHistory is not None:
+                self.tdoaHistory.set(self._indexes_host.reshape(N, 1).copy())
+            return
         if self.separationEnabled and self.coefficientMaskHistories:
             self.coefficientMaskHistories[self.dictionarySize].set(1 - m[o[2]:o[2] + n[2]].reshape(self.Kp, Tc)[:K])          # :211-212
         if self.inputSpectrogramHistory is not None:
@@ -220,11 +296,42 @@ class GCCNMFProcessor(object):
     @_on_device
     def intermediates(self):
         F, K, D = self.numFrequencies, self.numAtom, self.numTDOAs
+        if self.multiple():         # HMask (N, K, Tc) one-hot; tfMask (N, F, Tc) without coefficient inference, (N, 2, F, Tc) with
+            return dict(X=torch.view_as_complex(self.dX).cpu().numpy(), C=torch.view_as_complex(self.dC).cpu().numpy(),
+                        Y=torch.view_as_complex(self.dYm).cpu().numpy(), HMask=self.dHMaskm[:, :K].cpu().numpy(),
+                        argmaxTDOA=self.dArgmax[:K].cpu().numpy(),
+                        tfMask=self.dTfMaskm.cpu().numpy() if self.numHUpdates else self.dTfMaskm[:, 0].cpu().numpy(),
+                        Hcoef=self.dHcoef[:K].permute(2, 0, 1).contiguous().cpu().numpy(),
+                        gccPHAT=self.dGccPhat.cpu().numpy(), targetTDOAIndexes=self.targetTDOAIndexes)
         return dict(X=torch.view_as_complex(self.dX).cpu().numpy(), C=torch.view_as_complex(self.dC).cpu().numpy(),
                     HMask=self.dHMask[:K].cpu().numpy(), argmaxTDOA=self.dArgmax[:K].cpu().numpy(),
                     tfMask=(self.dTfMask.cpu().numpy() if self.numHUpdates else self.dTfMask.view(-1)[:F * self.numTimePerChunk].view(F, -1).cpu().numpy()),
                     Hcoef=self.dHcoef[:K].permute(2, 0, 1).contiguous().cpu().numpy(),
                     gccPHAT=self.dGccPhat.cpu().numpy(), targetTDOAIndex=self.targetTDOAIndex)
+
+
+def _check_num_sources(n):
+    if isinstance(n, bool) or int(n) != n or not 1 <= int(n) <= MAX_SOURCES:
+        raise ValueError('numSources=%r: multiple mode separates 1 to %d sources' % (n, MAX_SOURCES))
+    return int(n)
+
+
+def default_target_indexes(numSources, numTDOAs):
+    """Initial targets of multiple mode: spread evenly over the TDOA grid, ascending."""
+    return np.array([(i + 1) * numTDOAs // (numSources + 1) for i in range(numSources)], np.float32)
+
+
+def _check_target_indexes(indexes, numSources, numTDOAs):
+    """``numSources`` integer TDOA indexes in [0, numTDOAs) as float32 (the target row's words 8..); ValueError otherwise."""
+    try:
+        v = np.asarray(indexes, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError('target TDOA indexes must be numbers, got %r' % (indexes,))
+    if v.shape != (numSources,):
+        raise ValueError('expected %d target TDOA indexes, got %r' % (numSources, indexes))
+    if not (np.all(np.isfinite(v)) and np.all(v == np.round(v)) and np.all(v >= 0) and np.all(v < numTDOAs)):
+        raise ValueError('target TDOA indexes must be integers in [0, %d), got %r' % (numTDOAs, indexes))
+    return v.astype(np.float32)
 
 
 def _check_stream_shape(processor, hopSize, blockSize, outputDelayBlocks):
@@ -253,7 +360,9 @@ def _check_stream_shape(processor, hopSize, blockSize, outputDelayBlocks):
 
 class StreamingGCCNMF(object):
     """``OverlapAddProcessor.processFrames(GCCNMFProcessor.processFrames)`` (utils.py:99-116) as one device call per block:
-    ``process_block((2, blockSize)) -> (2, blockSize)``, output delayed by two blocks like the reference."""
+    ``process_block((2, blockSize)) -> (2, blockSize)``, output delayed by two blocks like the reference.  In multiple mode
+    (``processor.targetMode = TARGET_MODE_MULTIPLE``) every target has its own output ring: ``(2, blockSize) -> (numSources, 2,
+    blockSize)``; the single-target ring is kept apart, so a stream can switch modes."""
 
     def __init__(self, processor, hopSize, blockSize, outputDelayBlocks=2, use_graph=True):
         self.use_graph = bool(use_graph)
@@ -265,10 +374,25 @@ class StreamingGCCNMF(object):
         self.out_ring = torch.zeros((2, 8 * blockSize), dtype=torch.float32, device=dev)
         self.block_in = torch.zeros((2, blockSize), dtype=torch.float32, device=dev)
         self.block_out = torch.zeros((2, blockSize), dtype=torch.float32, device=dev)
+        self._multi_state = None           # (generation, N, out rings [N][2][8B], block_out [N][2][B]) of multiple mode
+
+    def _outputs(self):
+        """(out_ring, block_out) of the processor's current mode."""
+        p = self.p
+        if not p.multiple():
+            return self.out_ring, self.block_out
+        key = (p.generation, p._sources)
+        if self._multi_state is None or self._multi_state[:2] != key:
+            N, B = p._sources, self.blockSize
+            z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=p.device)
+            self._multi_state = key + (z(N, 2, 8 * B), z(N, 2, B))
+        return self._multi_state[2], self._multi_state[3]
 
     def process_block_device(self, block_in, block_out):
-        """Device tensors in/out, asynchronous on the current stream (what a capture/playback loop would call)."""
-        self.p._call(block_in, block_out, self.in_ring, self.out_ring, self.hopSize, self.blockSize, 0, self.outputDelayBlocks)
+        """Device tensors in/out, asynchronous on the current stream (what a capture/playback loop would call); block_out is
+        [numSources][2][blockSize] in multiple mode."""
+        out_ring = self._outputs()[0]
+        self.p._call(block_in, block_out, self.in_ring, out_ring, self.hopSize, self.blockSize, 0, self.outputDelayBlocks)
 
     def process_block(self, block):
         """Host block in -> host block out.  The finished block is fetched (pinned buffer, its own event) BEFORE the tracking update
@@ -276,15 +400,19 @@ class StreamingGCCNMF(object):
         The fixed launch sequence (upload, kernels, download) is captured once into a HIP graph and replayed per block."""
         if getattr(self, '_pin_in', None) is None:
             self._pin_in = torch.zeros((2, self.blockSize), dtype=torch.float32).pin_memory()
-            self._pin_out = torch.zeros((2, self.blockSize), dtype=torch.float32).pin_memory()
+            self._pin_out = None
             self._ev_out = torch.cuda.Event()
             self._graph, self._graph_key = None, None
         p = self.p
         with torch.cuda.device(p.device):
             self._pin_in.copy_(torch.from_numpy(np.ascontiguousarray(block, dtype=np.float32)))
+            out_ring, block_out = self._outputs()
+            if self._pin_out is None or self._pin_out.shape != block_out.shape:
+                self._pin_out = torch.zeros(block_out.shape, dtype=torch.float32).pin_memory()
             # everything the captured launches depend on besides buffer contents: re-capture when one of them changes
             key = (int(p.targetMode), bool(p.separationEnabled), bool(p.localizationEnabled), int(p.localizationWindowSize),
-                   int(p.numHUpdates), p.dW.data_ptr(), p.dTarget.data_ptr(), p.generation)      # reset() re-allocates every buffer
+                   int(p.numHUpdates), p.dW.data_ptr(), p.dTarget.data_ptr(), p.generation,      # reset() re-allocates every buffer
+                   p._sources if p.multiple() else 0, out_ring.data_ptr(), self._pin_out.data_ptr())
             if self.use_graph and self._graph_key != key:
                 self._graph, self._graph_key = self._capture(), key
             if self._graph is not None:
@@ -292,16 +420,17 @@ class StreamingGCCNMF(object):
             else:
                 self._launch_front()
             self._ev_out.record()
-            p._call(self.block_in, self.block_out, self.in_ring, self.out_ring, self.hopSize, self.blockSize, 4, self.outputDelayBlocks)
+            p._call(self.block_in, block_out, self.in_ring, out_ring, self.hopSize, self.blockSize, 4, self.outputDelayBlocks)
             self._ev_out.synchronize()
             out = self._pin_out.numpy().copy()
             p.fill_histories()                 # host mirrors (only when history objects were given): after the tracking update
         return out
 
     def _launch_front(self):
+        out_ring, block_out = self._outputs()
         self.block_in.copy_(self._pin_in, non_blocking=True)
-        self.p._call(self.block_in, self.block_out, self.in_ring, self.out_ring, self.hopSize, self.blockSize, 2, self.outputDelayBlocks)
-        self._pin_out.copy_(self.block_out, non_blocking=True)
+        self.p._call(self.block_in, block_out, self.in_ring, out_ring, self.hopSize, self.blockSize, 2, self.outputDelayBlocks)
+        self._pin_out.copy_(block_out, non_blocking=True)
 
     def _capture(self):
         """upload -> kernels (all but the tracking update) -> download as one HIP graph.  A failed capture is not silent: it is kept in
@@ -309,11 +438,12 @@ class StreamingGCCNMF(object):
         try:
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
-            state = [t.clone() for t in (self.in_ring, self.out_ring, self.p.dHist, self.p.dHistPos, self.p.dTarget)]
+            held = (self.in_ring, self._outputs()[0], self.p.dHist, self.p.dHistPos, self.p.dTarget)
+            state = [t.clone() for t in held]
             with torch.cuda.graph(g):
                 self._launch_front()
             # capture does not execute on ROCm, but restore the state anyway in case a runtime runs the body once
-            for t, s0 in zip((self.in_ring, self.out_ring, self.p.dHist, self.p.dHistPos, self.p.dTarget), state):
+            for t, s0 in zip(held, state):
                 t.copy_(s0)
             torch.cuda.synchronize()
             self.capture_error = None
@@ -327,15 +457,17 @@ class StreamingGCCNMF(object):
             return None
 
     def process_stream(self, stereoSamples):
-        """(2, n) -> (2, n_blocks*blockSize); the whole signal is uploaded once, every block is one device call."""
+        """(2, n) -> (2, n_blocks*blockSize) (multiple mode: (numSources, 2, n_blocks*blockSize)); the whole signal is uploaded once,
+        every block is one device call."""
         x = torch.from_numpy(np.ascontiguousarray(stereoSamples, dtype=np.float32)).to(self.p.device)
         B = self.blockSize
         n_blocks = x.shape[1] // B
         xb = x[:, :n_blocks * B].reshape(2, n_blocks, B).permute(1, 0, 2).contiguous()      # [block][2][B]
-        out = torch.zeros((n_blocks, 2, B), dtype=torch.float32, device=self.p.device)
+        lead = tuple(self._outputs()[1].shape[:-1])                                        # (2,) or (N, 2)
+        out = torch.zeros((n_blocks,) + lead + (B,), dtype=torch.float32, device=self.p.device)
         for b in range(n_blocks):
             self.process_block_device(xb[b], out[b])
-        return out.permute(1, 0, 2).reshape(2, n_blocks * B).cpu().numpy()
+        return out.movedim(0, -2).reshape(lead + (n_blocks * B,)).cpu().numpy()
 
 
 MAX_BANK_STREAMS = 4096                  # frames_mode bits 8..19 (csrc/rt.hip)
@@ -353,7 +485,11 @@ class StreamingGCCNMFBank(object):
     target row {index, epsilon, beta, noiseFloor, separation, localisation}: a stream separates (localises) when the processor's
     switch and its own are both on.  After ``processor.reset()`` the next call re-allocates all per-stream state.
 
-    The GUI's host mirrors (``GCCNMFProcessor.fill_histories``) are not produced for a bank."""
+    The GUI's host mirrors (``GCCNMFProcessor.fill_histories``) are not produced for a bank.
+
+    Multiple mode (the processor's ``targetMode = TARGET_MODE_MULTIPLE``, N = its ``numSources`` for every stream): target rows are 16
+    words, words 8..8+N-1 the stream's target indexes (``setTargetTDOAIndexes(s, indexes)``; initially the processor's), and
+    ``process_block`` returns (S, N, 2, blockSize).  Switching the processor into or out of multiple mode starts every stream over."""
 
     def __init__(self, processor, numStreams, hopSize, blockSize, outputDelayBlocks=2, use_graph=True):
         if int(numStreams) != numStreams or not 1 <= int(numStreams) <= MAX_BANK_STREAMS:
@@ -369,29 +505,42 @@ class StreamingGCCNMFBank(object):
 
     # ---- per-stream state ----------------------------------------------------------------------------------------------
     def _initial_row(self):
-        return np.concatenate([self.p._target_host, np.array([1, 1, 0, 0], np.float32)]).astype(np.float32)
+        row = np.concatenate([self.p._target_host, np.array([1, 1, 0, 0], np.float32)]).astype(np.float32)
+        if self._multi:                    # + the processor's target indexes (words 8..)
+            tau = np.zeros(8, np.float32)
+            tau[:self._sources] = self.p.targetTDOAIndexes
+            row = np.concatenate([row, tau])
+        return row
+
+    def _layout(self):
+        return (self.p.generation, self.p._sources) if self.p.multiple() else (self.p.generation, 0)
 
     @_on_device
     def _alloc(self):
         p, S, B = self.p, self.numStreams, self.blockSize
         F, Tc, D, Kp = p.numFrequencies, p.numTimePerChunk, p.numTDOAs, p.Kp
+        self._layout_key = self._layout()
+        self._multi, self._sources = self._layout_key[1] > 0, max(self._layout_key[1], 1)
+        N = self._sources if self._multi else 1           # outputs per stream; the mask images carry N targets
+        lead = (S, N) if self._multi else (S,)
         z = lambda *shape, **kw: torch.zeros(shape, dtype=kw.get('dtype', torch.float32), device=self.device)
-        self.in_ring, self.out_ring = z(S, 2, 8 * B), z(S, 2, 8 * B)
-        self.block_in, self.block_out = z(S, 2, B), z(S, 2, B)
-        self.dX, self.dY, self.dC = z(S, 2, F, Tc, 2), z(S, 2, F, Tc, 2), z(S, F, Tc, 2)
-        self.dHMask, self.dArgmax = z(S, Kp, Tc), z(S, Kp, Tc, dtype=torch.int32)
-        self.dTfMask, self.dGccPhat = z(S, 2, F, Tc), z(S, D, Tc)
+        self.in_ring, self.out_ring = z(S, 2, 8 * B), z(*lead, 2, 8 * B)
+        self.block_in, self.block_out = z(S, 2, B), z(*lead, 2, B)
+        self.dX, self.dY, self.dC = z(S, 2, F, Tc, 2), z(*lead, 2, F, Tc, 2), z(S, F, Tc, 2)
+        self.dHMask, self.dArgmax = z(*lead, Kp, Tc), z(S, Kp, Tc, dtype=torch.int32)
+        self.dTfMask, self.dGccPhat = z(*lead, 2, F, Tc), z(S, D, Tc)
         self.dHist, self.dHistPos = z(S, D, p.numTDOAHistory), z(S, dtype=torch.int32)
         self.dHcoef, self.dRv = None, None     # coefficient-inference scratch: allocated with the first call that needs it
         self._row0 = self._initial_row()
         self.dTarget = torch.from_numpy(np.tile(self._row0, (S, 1))).to(self.device)
         self._targets = self._row0[0].repeat(S).astype(np.float32)      # host copy of the tracked indexes
+        self._tindexes = np.tile(self._row0[8:8 + self._sources], (S, 1)) if self._multi else None    # multiple mode's, (S, N)
         self._targets_dirty, self._targets_pin = False, None
         self._generation = p.generation
         self._graph, self._graph_key = None, None
 
     def _ensure_state(self):
-        if self._generation != self.p.generation:           # processor reset(): every table was re-allocated
+        if self._layout_key != self._layout():              # processor reset() (every table re-allocated) or a mode change
             self._alloc()
         if self.p.numHUpdates and self.dHcoef is None:
             S, F, Tc, Kp = self.numStreams, self.p.numFrequencies, self.p.numTimePerChunk, self.p.Kp
@@ -428,9 +577,21 @@ class StreamingGCCNMFBank(object):
         self.dTarget[s, 5] = float(bool(on))
 
     @_on_device
+    def setTargetTDOAIndexes(self, s, indexes):
+        """Multiple mode: words 8.. of stream s's row (``GCCNMFProcessor.setTargetTDOAIndexes`` for one stream)."""
+        s = self._stream_index(s)
+        self._ensure_state()
+        if not self._multi:
+            raise ValueError('setTargetTDOAIndexes needs the processor in TARGET_MODE_MULTIPLE')
+        v = _check_target_indexes(indexes, self._sources, self.p.numTDOAs)
+        self.dTarget[s, 8:8 + self._sources].copy_(torch.from_numpy(v))
+        self._tindexes[s] = v
+
+    @_on_device
     def reset_stream(self, s):
-        """Stream s starts over (a session left, a new one takes its slot): its rings, history, history position and target row
-        (the processor's target, both switches on) are reset; no other stream is touched."""
+        """Stream s starts over (a session left, a new one takes its slot): its rings (all N output rings in multiple mode), history,
+        history position and target row (the processor's target or target indexes, both switches on) are reset; no other stream is
+        touched."""
         s = self._stream_index(s)
         self._ensure_state()
         for t in (self.in_ring, self.out_ring, self.dHist, self.dHistPos):
@@ -438,11 +599,14 @@ class StreamingGCCNMFBank(object):
         row = self._initial_row()
         self.dTarget[s].copy_(torch.from_numpy(row))
         self._targets[s] = row[0]
+        if self._multi:
+            self._tindexes[s] = row[8:8 + self._sources]
 
     @property
     def targetTDOAIndexes(self):
-        """(S,) tracked target TDOA indexes, cached like ``GCCNMFProcessor.targetTDOAIndex``: fetched (one small download of the
-        target rows) only when a call ran with the localisation on since they were last known on the host."""
+        """(S,) tracked target TDOA indexes ((S, numSources) in multiple mode), cached like ``GCCNMFProcessor.targetTDOAIndex``:
+        fetched (one small download of the target rows) only when a call ran with the localisation on since they were last known
+        on the host."""
         if self._targets_dirty:
             with torch.cuda.device(self.device):
                 if self._targets_pin is None or self._targets_pin.shape != self.dTarget.shape:
@@ -450,8 +614,10 @@ class StreamingGCCNMFBank(object):
                 self._targets_pin.copy_(self.dTarget, non_blocking=True)
                 torch.cuda.current_stream(self.device).synchronize()
             self._targets = self._targets_pin.numpy()[:, 0].copy()
+            if self._multi:
+                self._tindexes = self._targets_pin.numpy()[:, 8:8 + self._sources].copy()
             self._targets_dirty = False
-        return self._targets.copy()
+        return (self._tindexes if self._multi else self._targets).copy()
 
     # ---- device calls -----------------------------------------------------------------------------------------------------
     @_on_device
@@ -459,24 +625,26 @@ class StreamingGCCNMFBank(object):
         p = self.p
         if p.localizationEnabled and not bits & 2:
             self._targets_dirty = True
+        multi = (_MULTI_LAYOUT | ((self._sources - 1) << 21)) if self._multi else 0
         _hip.check(p.lib.gccnmf_rt_process_block_ll(
             _ptr(block_in), _ptr(block_out), _ptr(self.in_ring), _ptr(self.out_ring), _ptr(self.dX), _ptr(self.dY), _ptr(self.dC),
             _ptr(self.dHMask), _ptr(self.dArgmax), _ptr(self.dTfMask), _ptr(self.dHist), _ptr(self.dHistPos), _ptr(self.dTarget),
             _ptr(self.dGccPhat), _ptr(p.dW), _ptr(p.dCos), _ptr(p.dSin), _ptr(p.dWindow), _ptr(p.dSynthWindow), _ptr(p.dTwiddle),
             _ptr(p.dColsum), _ptr(self.dHcoef), _ptr(self.dRv), p.windowSize, self.hopSize, self.blockSize,
             p.numAtom, p.Kp, p.numTDOAs, p.Dp, p.numTDOAHistory, int(p.targetMode), int(bool(p.separationEnabled)),
-            int(bool(p.localizationEnabled)), p.localizationWindowSize, bits | _BANK_LAYOUT | ((self.numStreams - 1) << 8),
+            int(bool(p.localizationEnabled)), p.localizationWindowSize, bits | _BANK_LAYOUT | ((self.numStreams - 1) << 8) | multi,
             int(p.numHUpdates), self.outputDelayBlocks, _stream()), 'gccnmf_rt_process_block_ll')
 
-    def _check_blocks(self, t):
-        if tuple(t.shape) != (self.numStreams, 2, self.blockSize) or t.dtype != torch.float32 or not t.is_contiguous():
-            raise ValueError('expected a contiguous float32 tensor of shape %s' % ((self.numStreams, 2, self.blockSize),))
+    def _check_blocks(self, t, shape):
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError('expected a contiguous float32 tensor of shape %s' % (shape,))
 
     def process_block_device(self, block_in, block_out):
-        """(S, 2, blockSize) device tensors in / out, asynchronous on the current stream."""
-        self._check_blocks(block_in)
-        self._check_blocks(block_out)
+        """(S, 2, blockSize) device tensors in, (S, 2, blockSize) ((S, N, 2, blockSize) in multiple mode) out, asynchronous on the
+        current stream."""
         self._ensure_state()
+        self._check_blocks(block_in, (self.numStreams, 2, self.blockSize))
+        self._check_blocks(block_out, tuple(self.block_out.shape))
         self._call(block_in, block_out, 0)
 
     def process_block(self, blocks):
@@ -490,11 +658,14 @@ class StreamingGCCNMFBank(object):
             self._ensure_state()
             if getattr(self, '_pin_in', None) is None:
                 self._pin_in = torch.zeros((self.numStreams, 2, self.blockSize), dtype=torch.float32).pin_memory()
-                self._pin_out = torch.zeros((self.numStreams, 2, self.blockSize), dtype=torch.float32).pin_memory()
+                self._pin_out = None
                 self._ev_out = torch.cuda.Event()
+            if self._pin_out is None or self._pin_out.shape != self.block_out.shape:
+                self._pin_out = torch.zeros(self.block_out.shape, dtype=torch.float32).pin_memory()
             self._pin_in.copy_(torch.from_numpy(blocks))
             key = (int(p.targetMode), bool(p.separationEnabled), bool(p.localizationEnabled), int(p.localizationWindowSize),
-                   int(p.numHUpdates), p.dW.data_ptr(), self.dTarget.data_ptr(), p.generation)
+                   int(p.numHUpdates), p.dW.data_ptr(), self.dTarget.data_ptr(), p.generation, self._layout_key,
+                   self._pin_out.data_ptr())
             if self.use_graph and self._graph_key != key:
                 self._graph, self._graph_key = self._capture(), key
             if self.use_graph and self._graph is not None:
@@ -535,14 +706,17 @@ class StreamingGCCNMFBank(object):
             return None
 
     def process_streams(self, x):
-        """(S, 2, n) -> (S, 2, n_blocks * blockSize); the whole signal is uploaded once, every block is one device call."""
+        """(S, 2, n) -> (S, 2, n_blocks * blockSize) ((S, N, 2, ...) in multiple mode); the whole signal is uploaded once, every block
+        is one device call."""
         x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(self.device)
         S, B = self.numStreams, self.blockSize
         if x.dim() != 3 or x.shape[0] != S or x.shape[1] != 2:
             raise ValueError('expected signals of shape (%d, 2, n)' % S)
+        self._ensure_state()
         n_blocks = x.shape[2] // B
         xb = x[:, :, :n_blocks * B].reshape(S, 2, n_blocks, B).permute(2, 0, 1, 3).contiguous()      # [block][S][2][B]
-        out = torch.zeros((n_blocks, S, 2, B), dtype=torch.float32, device=self.device)
+        lead = tuple(self.block_out.shape[:-1])                                                       # (S, 2) or (S, N, 2)
+        out = torch.zeros((n_blocks,) + lead + (B,), dtype=torch.float32, device=self.device)
         for b in range(n_blocks):
             self.process_block_device(xb[b], out[b])
-        return out.permute(1, 2, 0, 3).reshape(S, 2, n_blocks * B).cpu().numpy()
+        return out.movedim(0, -2).reshape(lead + (n_blocks * B,)).cpu().numpy()

@@ -347,7 +347,18 @@ int gccnmf_rt_process_block(const float* block_in, float* block_out, float* in_r
  *                                  stream separates (localises) when separation_enabled (localization_enabled) AND its row word
  *                                  4 (5) are non-zero; with separation_enabled = 0 no mask kernel is launched.  Stream s computes
  *                                  bit for bit what a single-stream call on its images computes.  Bits 2 and 4 work as above.
- *                                  GCCNMF_ERR_ARG: 8 together with 1 (frames mode), bits 8..19 without 8, any bit above 19.
+ *                                  GCCNMF_ERR_ARG: 8 together with 1 (frames mode), bits 8..19 without 8, any bit above 23.
+ *                                  1 << 20 = multi-target layout (separation of N = (bits 21..23) + 1 talkers, N <= 8; needs
+ *                                  target_mode 1 = TARGET_MODE_MULTIPLE).  The target row is 16 floats per stream (single-stream
+ *                                  call and bank): words 0..7 as above (0..3 unused), words 8..8+N-1 = target TDOA indexes
+ *                                  tau_0..tau_N-1 in [0, D), rewritten by the localisation (the N largest strict local maxima of
+ *                                  the window mean, ascending; unchanged with fewer than N peaks).  Atom k of frame t goes to the
+ *                                  target whose GCC-NMF score at tau_i is largest (one-hot, first index on ties, NaN ignored, all
+ *                                  NaN -> target 0).  Per-stream images: Y, tfMask [N][2][F][Tc]; HMask [N][Kp][Tc] (0 / 1);
+ *                                  out_ring [N][2][8*blockSize] (frames mode: [N][2][Tc][windowSize]); block_out [N][2][blockSize];
+ *                                  every other buffer as above.  With separation off every output is the unmasked mixture.
+ *                                  GCCNMF_ERR_ARG: 1 << 20 with target_mode != 1, bits 21..23 without 1 << 20.  Without bit 20 a
+ *                                  call computes what it computed before the layout existed (target_mode 1 = window function).
  *   out_delay_blocks               which finished block is handed out: 2 = the reference (utils.py:116); 1 is complete when
  *                                  the synthesis window spans at most two hops */
 int gccnmf_rt_process_block_ll(const float* block_in, float* block_out, float* in_ring, float* out_ring, float* X, float* Y, float* C,
