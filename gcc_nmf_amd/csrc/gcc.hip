@@ -8,6 +8,8 @@
 // The three targets / six (target, channel) pairs are concatenated along the GEMM's column axis,
 // so each stage is ONE launch for the whole batch.
 #include "gemm_ring.h"
+#include "ratio.h"
+#include "../../include/gccnmf_hip.h"
 
 
 // One-shot GEMMs of a launch that cannot fill the chip with 512 x 64 tiles (one mixture alone: 60 of them) take the small-tile ring
@@ -357,9 +359,16 @@ long gccnmf_reconstruct_workspace_floats(int T, int K, int S, int batch) {
 int gccnmf_reconstruct(const float* W, const float* H, const unsigned char* argmax, const float* masks, const float* X,
                        const float* V, int F, int T, int K, int S, int batch, float* workspace, float* spec, void* stream) {
     GCCNMF_ENTER();
-    if (!W || !H || (!argmax && !masks) || !X || !V || !workspace || !spec || F < 2 || T < 1 || K < 1 || S < 1 || batch < 1)
+    // the mode rides above the low byte of S (GCCNMF_RECONSTRUCT_RATIO); every check comes before the first HIP call
+    const int mode = S & ~0xff;
+    S &= 0xff;
+    if (mode & ~GCCNMF_RECONSTRUCT_RATIO) return GCCNMF_ERR_ARG;
+    const bool ratio = mode == GCCNMF_RECONSTRUCT_RATIO;      // needs neither V nor the masked-H workspace
+    if (!W || !H || (!argmax && !masks) || !X || (!ratio && (!V || !workspace)) || !spec || F < 2 || T < 1 || K < 1 || S < 1 || batch < 1)
         return GCCNMF_ERR_ARG;
+    if (ratio && S > GCCNMF_RATIO_MAX_TARGETS) return GCCNMF_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
+    if (ratio) return gccnmf_launch_ratio(W, H, argmax, masks, X, F, T, K, S, batch, spec, s);
     GccNmfPitches p = gccnmf_make_pitches(F, T, K);
     const int ncol = 2 * S * p.Tp;
     float* Hm = workspace;

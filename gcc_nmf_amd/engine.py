@@ -51,6 +51,18 @@ def klnmf_initial_factors(F, N, K, epsilon=1e-16, seedValue=0):
 
 
 GCCNMF_FLAG_FIXED_W = 1 << 16          # include/gccnmf_hip.h
+GCCNMF_RECONSTRUCT_RATIO = 0x100       # include/gccnmf_hip.h: the ratio-mask mode of gccnmf_reconstruct, above the low byte of S
+RECONSTRUCTIONS = ('direct', 'ratio')
+RATIO_MAX_TARGETS = 8                  # csrc/ratio.h
+
+
+def check_reconstruction(reconstruction, numTargets):
+    """The ``reconstruction`` keyword of the engines and of getTargetSpectrogramEstimates; ValueError before any device work."""
+    if reconstruction not in RECONSTRUCTIONS:
+        raise ValueError("reconstruction must be 'direct' or 'ratio', got %r" % (reconstruction,))
+    if reconstruction == 'ratio' and not 1 <= int(numTargets) <= RATIO_MAX_TARGETS:
+        raise ValueError("reconstruction='ratio' takes 1 to %d targets, got %d" % (RATIO_MAX_TARGETS, int(numTargets)))
+    return reconstruction
 GCCNMF_FLAG_H_ONES = 1 << 17
 
 
@@ -147,7 +159,11 @@ class GCCNMFEngine(object):
 
     ``dictionaryW``: a pre-trained (n_fft/2+1, K) dictionary (e.g. pretraining.loadPretrainedW): KL-NMF then infers only the coefficients
     against it (gccnmf_klnmf with GCCNMF_FLAG_FIXED_W, every iteration in one launch) and K is the dictionary's.  ``initialH``: 'random'
-    (the H0 performKLNMF draws) or 'ones'."""
+    (the H0 performKLNMF draws) or 'ones'.
+
+    ``reconstruction``: 'direct' = the reference's target spectrograms, W.(H_c o M_i) with the mixture phase (gccNMFFunctions.py:145-151);
+    'ratio' = the Wiener-like ratio mask X_c * W.(H_c o M_i) / sum_j W.(H_c o M_j), whose targets add up to the mixture (one fused launch,
+    csrc/ratio.hip; at most 8 targets).  Everything up to the coefficient masks is the same in both modes."""
 
     def __new__(cls, n_samples=None, *args, **kwargs):
         if cls is GCCNMFEngine and kwargs.get('lengths') is not None:
@@ -158,10 +174,11 @@ class GCCNMFEngine(object):
     def __init__(self, n_samples, sampleRate=16000, windowSize=1024, hopSize=256, numTDOAs=128,
                  microphoneSeparationInMetres=1.0, numTargets=3, dictionarySize=None, numIterations=100,
                  sparsityAlpha=0, epsilon=1e-16, seedValue=0, batch=1, windowFunction=np.hanning,
-                 device='cuda:0', klnmf_flags=0, nmf_groups=None, dictionaryW=None, initialH='random'):
+                 device='cuda:0', klnmf_flags=0, nmf_groups=None, dictionaryW=None, initialH='random', reconstruction='direct'):
         if initialH not in ('random', 'ones'):
             raise ValueError("initialH must be 'random' or 'ones'")
         self.initialH = initialH
+        self.reconstruction = check_reconstruction(reconstruction, numTargets)
         self.dictionaryW = None
         if dictionaryW is not None:
             self.dictionaryW = check_dictionary(dictionaryW, int(windowSize) // 2 + 1)
@@ -250,7 +267,7 @@ class GCCNMFEngine(object):
             self.ws_scores = z(self.lib.gccnmf_scores_workspace_floats(F, T, g.S, B))
             self.scores = z(B, g.Kp, g.S * g.Tp)
             self.argmax = torch.zeros((B, g.Kp, g.Tp), dtype=torch.uint8, device=dev)
-            self.ws_rec = z(self.lib.gccnmf_reconstruct_workspace_floats(T, g.K, g.S, B))
+            self.ws_rec = None if self.reconstruction == 'ratio' else z(self.lib.gccnmf_reconstruct_workspace_floats(T, g.K, g.S, B))
             self.spec = z(B, 2 * g.S, g.Fp, g.Tp, 2)
             # windowed time frames [B][2S][T][n_fft]: only the two-kernel iSTFT needs them (allocated on first use); the default is the
             # fused inverse-transform + overlap-add pass, available while n_fft + 3 * hop <= 2048
@@ -339,6 +356,11 @@ class GCCNMFEngine(object):
     @_on_device
     def reconstruct(self):
         g = self.g
+        if self.reconstruction == 'ratio':      # one fused launch: no masked-H workspace, |X| not read
+            _hip.check(self.lib.gccnmf_reconstruct(_ptr(self.W), _ptr(self.H), _ptr(self.argmax), 0, _ptr(self.X), 0, g.F, g.T, g.K,
+                                                   g.S | GCCNMF_RECONSTRUCT_RATIO, self.batch, 0, _ptr(self.spec), _stream()),
+                       'gccnmf_reconstruct')
+            return
         _hip.check(self.lib.gccnmf_reconstruct(_ptr(self.W), _ptr(self.H), _ptr(self.argmax), 0, _ptr(self.X), _ptr(self.V), g.F,
                                                g.T, g.K, g.S, self.batch, _ptr(self.ws_rec), _ptr(self.spec), _stream()),
                    'gccnmf_reconstruct')
@@ -610,7 +632,8 @@ class RaggedGCCNMFEngine(object):
 
     def __init__(self, lengths, sampleRate=16000, windowSize=1024, hopSize=256, numTDOAs=128, microphoneSeparationInMetres=1.0,
                  numTargets=3, dictionarySize=None, numIterations=100, sparsityAlpha=0, epsilon=1e-16, seedValue=0,
-                 windowFunction=np.hanning, device='cuda:0', klnmf_flags=0, dictionaryW=None, initialH='random'):
+                 windowFunction=np.hanning, device='cuda:0', klnmf_flags=0, dictionaryW=None, initialH='random', reconstruction='direct'):
+        self.reconstruction = check_reconstruction(reconstruction, numTargets)
         if not torch.cuda.is_available():
             raise _hip.HipLibraryError('no ROCm device visible: the GCC-NMF HIP path has no CPU fallback')
         self.lib = _hip.lib()
@@ -624,7 +647,8 @@ class RaggedGCCNMFEngine(object):
         kw = dict(sampleRate=sampleRate, windowSize=windowSize, hopSize=hopSize, numTDOAs=numTDOAs,
                   microphoneSeparationInMetres=microphoneSeparationInMetres, numTargets=numTargets, dictionarySize=dictionarySize,
                   numIterations=numIterations, sparsityAlpha=sparsityAlpha, epsilon=epsilon, seedValue=seedValue,
-                  windowFunction=windowFunction, device=device, klnmf_flags=klnmf_flags, dictionaryW=dictionaryW, initialH=initialH)
+                  windowFunction=windowFunction, device=device, klnmf_flags=klnmf_flags, dictionaryW=dictionaryW, initialH=initialH,
+                  reconstruction=reconstruction)
         # one ordinary engine per distinct length: its files (caller's indexes, ascending) are its batch
         self.files_of = {}
         for i, n in enumerate(self.lengths):

@@ -25,7 +25,7 @@ from numpy.random import random, seed
 from scipy.signal import argrelmax
 
 from . import _hip, _staging
-from .engine import Geometry, padded, fft_twiddles, steering_tables, _ptr, _stream
+from .engine import Geometry, padded, fft_twiddles, steering_tables, _ptr, _stream, check_reconstruction, GCCNMF_RECONSTRUCT_RATIO
 from .librosaSTFT import stft, istft, ParameterError, _window_vector, _istft_device
 from .wavfile import wavread, wavwrite
 
@@ -274,11 +274,16 @@ def getTargetCoefficientMasks(targetTDOAGCCNMFs, numTargets):
     return masks
 
 
-def getTargetSpectrogramEstimates(targetCoefficientMasks, complexMixtureSpectrogram, W, stereoH):
-    """gccNMF/gccNMFFunctions.py:145-151.  Returns (numTargets, 2, F, T) complex64."""
+def getTargetSpectrogramEstimates(targetCoefficientMasks, complexMixtureSpectrogram, W, stereoH, reconstruction='direct'):
+    """gccNMF/gccNMFFunctions.py:145-151.  Returns (numTargets, 2, F, T) complex64.
+
+    ``reconstruction='ratio'`` (not in the reference): the Wiener-like ratio mask X_c * W.(H_c o M_i) / den instead of W.(H_c o M_i) with
+    the mixture phase.  Masks that came from getTargetCoefficientMasks take the one-hot form (den = the sum of the targets' numerators:
+    the targets add up to the mixture); any other mask array takes the soft form (den = W.H_c).  At most 8 targets."""
     M = np.asarray(targetCoefficientMasks)
     X = np.asarray(complexMixtureSpectrogram)
     S, K, T = M.shape
+    ratio = check_reconstruction(reconstruction, S) == 'ratio'
     C, F, _ = X.shape
     if C != 2:
         raise ValueError('stereo spectrogram expected')
@@ -302,10 +307,11 @@ def getTargetSpectrogramEstimates(targetCoefficientMasks, complexMixtureSpectrog
         dW = _device_W(sc, W, g, dev)
         dH = sc.dev('H', (g.Kp, g.Np), corner=(K, g.N))
         dH[:K, :g.N].unflatten(1, (2, T)).copy_(sc.upload(np.asarray(stereoH), 'stereoH', float32).permute(1, 0, 2))   # (K, [L | R])
-        ws = sc.dev('ws_rec', (lib.gccnmf_reconstruct_workspace_floats(T, K, S, 1),))
+        ws = None if ratio else sc.dev('ws_rec', (lib.gccnmf_reconstruct_workspace_floats(T, K, S, 1),))
         spec = sc.dev('spec', (2 * S, g.Fp, g.Tp, 2))
-        _hip.check(lib.gccnmf_reconstruct(_ptr(dW), _ptr(dH), _ptr(dA), _ptr(dM), _ptr(dX), _ptr(dV), F, T, K, S, 1, _ptr(ws),
-                                          _ptr(spec), _stream()), 'gccnmf_reconstruct')
+        _hip.check(lib.gccnmf_reconstruct(_ptr(dW), _ptr(dH), _ptr(dA), _ptr(dM), _ptr(dX), _ptr(dV), F, T, K,
+                                          S | GCCNMF_RECONSTRUCT_RATIO if ratio else S, 1, _ptr(ws), _ptr(spec), _stream()),
+                   'gccnmf_reconstruct')
         out = sc.download(torch.view_as_complex(spec)[:, :F, :T], shape=(S, 2, F, T))
         sc.remember(out, 'S', dict(spec=spec), dict(nsig=2 * S, F=F, T=T))
     return out

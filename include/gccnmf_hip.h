@@ -276,7 +276,19 @@ int gccnmf_magnitude(const float* X, int F, int T, int batch, float* V, void* st
  * getTargetSpectrogramEstimates (gccNMFFunctions.py:145-151).
  *   the mask is either `argmax` [batch][Kp][Tp] uint8 (one-hot masks, the device pipeline) or, when
  *   `masks` != NULL, arbitrary float masks [batch][S][Kp][Tp] (the reference signature accepts any array)
- *   spec [batch][S*2][Fp][Tp] complex out (index i*2+c); workspace: gccnmf_reconstruct_workspace_floats */
+ *   spec [batch][S*2][Fp][Tp] complex out (index i*2+c); workspace: gccnmf_reconstruct_workspace_floats
+ * Ratio-mask (Wiener-like) mode: pass S | GCCNMF_RECONSTRUCT_RATIO (the mode rides above the low byte of S, which the score stage
+ * limits to 255 anyway; any other bit above the low byte: GCCNMF_ERR_ARG).  One fused launch (csrc/ratio.hip), 1 <= S <= 8, else
+ * GCCNMF_ERR_UNSUPPORTED; with H_c = H[:, c*T:(c+1)*T]:
+ *   num_i[f,t]  = sum_k W[f,k] H_c[k,t] M_i[k,t]                   (f32 fma chain in k order)
+ *   den[f,t]    = num_0 + num_1 + ... + num_{S-1}                  one-hot form (`masks` == NULL, M_i = [argmax == i])
+ *               = sum_k W[f,k] H_c[k,t]                            soft form (`masks` != NULL)
+ *   S[i,c][f,t] = X_c[f,t] * (num_i / den)  if den > 0, else 0 for every i        (IEEE quotient; NaN / Inf in W or H propagate)
+ * -- the numerator is the magnitude model of gccNMFFunctions.py:150, the mixture phase of :147-151 comes with X_c itself, and in the
+ * one-hot form the targets add up to the mixture, sum_i S[i,c] = X_c, to a few ulp.  In this mode `V` and `workspace` are not read and
+ * may be NULL, and every element of spec [batch][S*2][Fp][Tp] is written (rows >= F and frames >= T as zeros).  A file's spec does not
+ * depend on the batch it is in.  gccnmf_reconstruct_workspace_floats keeps its meaning (the direct mode's need). */
+#define GCCNMF_RECONSTRUCT_RATIO 0x100
 long gccnmf_reconstruct_workspace_floats(int T, int K, int S, int batch);
 int gccnmf_reconstruct(const float* W, const float* H, const unsigned char* argmax, const float* masks,
                        const float* X, const float* V, int F, int T, int K, int S, int batch, float* workspace,
