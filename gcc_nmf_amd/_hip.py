@@ -112,6 +112,31 @@ class HipLibraryError(RuntimeError):
     pass
 
 
+def check_gcc_phat_nl(gccPHATNLEnabled, gccPHATNLAlpha):
+    """The reference's two GCC-NONLIN settings (gccNMF/realtime/config.py:42-43) as the engines, the named functions and the real-time
+    processor take them; no device needed.  Returns (enabled, alpha): alpha a finite number > 0 that is a normal float32, ValueError
+    otherwise (checked whether or not the setting is enabled, so a bad value cannot wait for the switch)."""
+    import math
+    import numbers
+    a = gccPHATNLAlpha
+    if isinstance(a, bool) or not isinstance(a, numbers.Real) or not math.isfinite(a) or not a > 0:
+        raise ValueError('gccPHATNLAlpha must be a finite number > 0, got %r' % (a,))
+    a32 = ctypes.c_float(float(a)).value
+    if not 1.17549435e-38 <= a32 < float('inf'):
+        raise ValueError('gccPHATNLAlpha=%r is not a normal float32' % (a,))
+    return bool(gccPHATNLEnabled), float(a32)
+
+
+def angular_nl_words(D, batch, alpha):
+    """(D, batch) arguments of gccnmf_angular_spectrogram with GCC-NONLIN on: the float32 bits of alpha in their upper halves
+    (GCCNMF_ANGULAR_NL_D / GCCNMF_ANGULAR_NL_BATCH of include/gccnmf_hip.h), as signed 32-bit values."""
+    if not (0 < int(D) < 65536 and 0 < int(batch) < 65536):
+        raise ValueError('GCC-NONLIN takes D and batch below 65536, got %r, %r' % (D, batch))
+    bits = ctypes.c_uint32.from_buffer_copy(ctypes.c_float(alpha)).value
+    signed = lambda v: ctypes.c_int32(v & 0xffffffff).value
+    return signed(int(D) | (bits & 0xffff0000)), signed(int(batch) | ((bits & 0xffff) << 16))
+
+
 _lib = None
 
 

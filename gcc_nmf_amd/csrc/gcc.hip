@@ -9,6 +9,7 @@
 // so each stage is ONE launch for the whole batch.
 #include "gemm_ring.h"
 #include "ratio.h"
+#include "angular_nl.h"
 #include "../../include/gccnmf_hip.h"
 
 
@@ -241,10 +242,29 @@ extern "C" {
 int gccnmf_angular_spectrogram(const float* CC, const float* trig, int F, int T, int D, int batch, float* ang,
                                double* mean_ang, void* stream) {
     GCCNMF_ENTER();
+    // GCC-NONLIN rides in the upper halves of D and batch (GCCNMF_ANGULAR_NL_D / _BATCH: the float32 bits of alpha, no new entry point);
+    // both zero = PHAT, every call as it was.  Every check comes before the first HIP call.
+    const unsigned alpha_bits = ((unsigned)D & 0xffff0000u) | ((unsigned)batch >> 16);
+    float nl_alpha = 0.f;
+    if (alpha_bits) {
+        __builtin_memcpy(&nl_alpha, &alpha_bits, sizeof(float));
+        if (!gccnmf_nl_alpha_ok(nl_alpha)) return GCCNMF_ERR_ARG;        // alpha <= 0, NaN, Inf, subnormal -- and any negative D or batch
+        D &= 0xffff;
+        batch &= 0xffff;
+    }
     if (!CC || !trig || !ang || F < 2 || T < 1 || D < 1 || batch < 1) return GCCNMF_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     GccNmfPitches p = gccnmf_make_pitches(F, T, 1);
     const int Dp = gccnmf_round_up(D, 64);
+    if (alpha_bits) {
+        const int rc = gccnmf_launch_angular_nl(CC, trig, F, T, D, batch, nl_alpha, ang, s);
+        if (rc) return rc;
+        if (mean_ang) {
+            hipLaunchKernelGGL(ang_mean_kernel, dim3(batch * D), dim3(256), 0, s, ang, T, D, Dp, p.Tp, mean_ang);
+            GCCNMF_CHECK_LAUNCH();
+        }
+        return GCCNMF_OK;
+    }
     GemmArgs a = {};
     a.A = trig; a.sA = 0; a.lda = Dp; a.a_clamp = Dp - 4;
     a.B = CC; a.sB = 2L * p.Fp * p.Tp; a.ldb = p.Tp; a.b_clamp = p.Tp - 4;

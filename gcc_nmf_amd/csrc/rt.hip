@@ -27,10 +27,11 @@
 // gccPHAT peaks tracked.  Its kernels are new kernels or the `true` / 16-word instantiations of templates whose other instantiation is
 // the single-target kernel unchanged (LABBOOK R7.3).
 #include "fft_core.h"
+#include "angular_nl.h"
 
 typedef float rt_f32x16 __attribute__((ext_vector_type(16)));
 
-#define RT_ROW 8                                           // bank layout: target row {index, eps, beta, noiseFloor, sep, loc, 0, 0}
+#define RT_ROW 8                                           // bank layout: target row {index, eps, beta, noiseFloor, sep, loc, nlAlpha, 0}
 #define RT_ROW_MULTI 16                                    // multi-target layout (frames_mode bit 20): the 8 words above + tau_0 .. tau_7
 #define RT_MAX_TARGETS 8
 
@@ -542,6 +543,8 @@ __global__ __launch_bounds__(256) void rt_synth_dft_kernel(const float2* __restr
 // ---- rt_localize: one workgroup of 1024 threads per stream = Dq TDOAs x 1024/Dq frequency phases ---------------------------
 // hist is a [D][Lh] float ring with write position hist_pos[0]; target[0] is updated for the NEXT block (:216-222).  In the bank layout
 // a stream whose row word 5 is 0 fills its history and leaves its target index alone.
+// GCC-NONLIN (gccPHATNLEnabled): a stream whose row word 6 holds alpha > 0 accumulates phi(term) = 1 - tanh(alpha sqrt(max(0, 1 - term)))
+// instead of the term (angular_nl.h), NaN terms skipped as before; the ring, the window mean and the arg-max / peak rule do not change.
 // MULTI: the window mean then goes through the offline peak rule (gcc.hip pick_peaks_kernel): strict local maxima, edges excluded, NaN
 // never a peak; the `ntargets` largest, the larger index kept among equal heights, written in ascending order to words 8.. of the row.
 // With fewer peaks than targets the indexes stay as they are.
@@ -550,7 +553,7 @@ __global__ __launch_bounds__(1024) void rt_localize_kernel(const float2* __restr
                                                            const float* __restrict__ sinT, int F, int D, int Dp, int Dq, int Tc,
                                                            float* __restrict__ hist, int Lh, int* __restrict__ hist_pos,
                                                            int loc_enabled, int loc_window, float* __restrict__ target,
-                                                           float* __restrict__ gccphat_out, int bank, int ntargets) {
+                                                           float* __restrict__ gccphat_out, int bank, int ntargets, int nl_row) {
     __shared__ float s_sum[1024];
     __shared__ int s_cnt[1024];
     const long sid = blockIdx.z;
@@ -560,12 +563,27 @@ __global__ __launch_bounds__(1024) void rt_localize_kernel(const float2* __restr
     target += sid * (MULTI ? RT_ROW_MULTI : RT_ROW);
     if (gccphat_out) gccphat_out += sid * D * Tc;
     if (bank && target[5] == 0.f) loc_enabled = 0;
+    // word 6 of the stream's row: gccPHATNLAlpha, 0 = plain PHAT (a value that is not positive and finite is read as 0).  nl_row = 0: the
+    // 4-word row of the single-stream call without frames_mode bit 24, which has no word 6.
+    const float nl_alpha = nl_row ? target[6] : 0.f;
+    const float nl_k2 = gccnmf_nl_alpha_ok(nl_alpha) ? gccnmf_nl_k2(nl_alpha) : 0.f;
     const int tau = threadIdx.x % Dq, g = threadIdx.x / Dq, G = 1024 / Dq;
     int pos = hist_pos[0];
     for (int t = 0; t < Tc; ++t) {
         float s = 0.f;
         int cnt = 0;
-        if (tau < D)
+        if (nl_k2 != 0.f) {                               // workgroup-uniform: the PHAT loop below is the code it was
+            if (tau < D)
+                for (int f = g; f < F; f += G) {
+                    const float2 c = C[(long)f * Tc + t];
+                    const float v = c.x * cosT[(long)f * Dp + tau] + c.y * sinT[(long)f * Dp + tau];
+                    if (v == v) {                         // a zero-magnitude bin (NaN coherence) is skipped, not counted
+                        s += gccnmf_nl_half_phi(v, nl_k2);
+                        ++cnt;
+                    }
+                }
+            s *= 2.f;                                     // phi = 2 * half_phi: exact on the partial sum
+        } else if (tau < D)
             for (int f = g; f < F; f += G) {
                 const float2 c = C[(long)f * Tc + t];
                 const float v = c.x * cosT[(long)f * Dp + tau] + c.y * sinT[(long)f * Dp + tau];
@@ -879,14 +897,19 @@ int gccnmf_rt_process_block_ll(const float* block_in, float* block_out, float* i
     // frames_mode_bits: 1 = frames mode (above); 2 = leave the localisation kernel out of this call; 4 = ONLY the localisation kernel
     // (2 then 4 = the same work in two calls, so that a host can fetch block_out before the tracking update has run); 8 = bank layout
     // of S = bits 8..19 + 1 streams (streaming only); 1 << 20 = multi-target layout of NT = bits 21..23 + 1 targets (target_mode 1 only);
-    // any bit above 23, S bits without the bank layout, or target bits without the multi-target layout is an error
+    // 1 << 24 = 8-word single-stream target row (below); any bit above 24, S bits without the bank layout, or target bits without the
+    // multi-target layout is an error
     const int frames_mode = frames_mode_bits & 1;
     const bool skip_localize = frames_mode_bits & 2, only_localize = frames_mode_bits & 4;
     const int bank = (frames_mode_bits >> 3) & 1;
     const int S = ((frames_mode_bits >> 8) & 0xfff) + 1;
     const bool multi = (frames_mode_bits >> 20) & 1;
     const int NT = ((frames_mode_bits >> 21) & 7) + 1;
-    if ((frames_mode_bits & ~0xffffff) || (bank && frames_mode) || (!bank && S > 1)) return GCCNMF_ERR_ARG;
+    // 1 << 24: the single-stream target row has 8 words and word 6 is gccPHATNLAlpha (GCC-NONLIN localisation); the bank and multi-target
+    // rows always have that word, so the bit is an error there
+    const bool row8 = (frames_mode_bits >> 24) & 1;
+    if ((frames_mode_bits & ~0x1ffffff) || (bank && frames_mode) || (!bank && S > 1) || (row8 && (bank || multi))) return GCCNMF_ERR_ARG;
+    const int nl_row = (bank || multi || row8) ? 1 : 0;
     if ((multi && target_mode != 1) || (!multi && NT > 1)) return GCCNMF_ERR_ARG;
     const float* rows = bank ? target : nullptr;          // the per-stream switches the mask and synthesis kernels read
     // powers of two from 64 up: the radix-2 LDS transform (twiddle = N/2 values of exp(-2 pi j k / N)); every other even size: the direct
@@ -912,10 +935,10 @@ int gccnmf_rt_process_block_ll(const float* block_in, float* block_out, float* i
     auto localize = [&]() {
         if (multi)
             hipLaunchKernelGGL(rt_localize_kernel<true>, dim3(1, 1, S), dim3(1024), 0, s, (const float2*)C, cosT, sinT, F, D, Dp, Dq, Tc, hist,
-                               numTDOAHistory, hist_pos, localization_enabled, localization_window, target, gccphat, bank, NT);
+                               numTDOAHistory, hist_pos, localization_enabled, localization_window, target, gccphat, bank, NT, 1);
         else
             hipLaunchKernelGGL(rt_localize_kernel<false>, dim3(1, 1, S), dim3(1024), 0, s, (const float2*)C, cosT, sinT, F, D, Dp, Dq, Tc, hist,
-                               numTDOAHistory, hist_pos, localization_enabled, localization_window, target, gccphat, bank, 1);
+                               numTDOAHistory, hist_pos, localization_enabled, localization_window, target, gccphat, bank, 1, nl_row);
     };
     if (only_localize) {
         localize();

@@ -64,6 +64,7 @@ def check_reconstruction(reconstruction, numTargets):
         raise ValueError("reconstruction='ratio' takes 1 to %d targets, got %d" % (RATIO_MAX_TARGETS, int(numTargets)))
     return reconstruction
 GCCNMF_FLAG_H_ONES = 1 << 17
+check_gcc_phat_nl = _hip.check_gcc_phat_nl        # the gccPHATNLEnabled / gccPHATNLAlpha keywords; ValueError before any device work
 
 
 def check_dictionary(W, F):
@@ -163,7 +164,12 @@ class GCCNMFEngine(object):
 
     ``reconstruction``: 'direct' = the reference's target spectrograms, W.(H_c o M_i) with the mixture phase (gccNMFFunctions.py:145-151);
     'ratio' = the Wiener-like ratio mask X_c * W.(H_c o M_i) / sum_j W.(H_c o M_j), whose targets add up to the mixture (one fused launch,
-    csrc/ratio.hip; at most 8 targets).  Everything up to the coefficient masks is the same in both modes."""
+    csrc/ratio.hip; at most 8 targets).  Everything up to the coefficient masks is the same in both modes.
+
+    ``gccPHATNLEnabled`` / ``gccPHATNLAlpha`` (the reference's settings, gccNMF/realtime/config.py:42-43): localise on the GCC-NONLIN
+    angular spectrum sum_f 1 - tanh(alpha sqrt(max(0, 1 - Re(C e^{-j 2 pi f tau})))) of Blandin, Ozerov & Vincent (2012) instead of
+    GCC-PHAT (csrc/angular_nl.hip).  The BSS-Locate toolbox writes sqrt(2 - 2 re): that is this function with alpha * sqrt(2).  Only the
+    TDOA indexes change; the GCC-NMF atom scores stay PHAT."""
 
     def __new__(cls, n_samples=None, *args, **kwargs):
         if cls is GCCNMFEngine and kwargs.get('lengths') is not None:
@@ -174,11 +180,13 @@ class GCCNMFEngine(object):
     def __init__(self, n_samples, sampleRate=16000, windowSize=1024, hopSize=256, numTDOAs=128,
                  microphoneSeparationInMetres=1.0, numTargets=3, dictionarySize=None, numIterations=100,
                  sparsityAlpha=0, epsilon=1e-16, seedValue=0, batch=1, windowFunction=np.hanning,
-                 device='cuda:0', klnmf_flags=0, nmf_groups=None, dictionaryW=None, initialH='random', reconstruction='direct'):
+                 device='cuda:0', klnmf_flags=0, nmf_groups=None, dictionaryW=None, initialH='random', reconstruction='direct',
+                 gccPHATNLEnabled=False, gccPHATNLAlpha=2.0):
         if initialH not in ('random', 'ones'):
             raise ValueError("initialH must be 'random' or 'ones'")
         self.initialH = initialH
         self.reconstruction = check_reconstruction(reconstruction, numTargets)
+        self.gccPHATNLEnabled, self.gccPHATNLAlpha = check_gcc_phat_nl(gccPHATNLEnabled, gccPHATNLAlpha)
         self.dictionaryW = None
         if dictionaryW is not None:
             self.dictionaryW = check_dictionary(dictionaryW, int(windowSize) // 2 + 1)
@@ -341,7 +349,9 @@ class GCCNMFEngine(object):
     @_on_device
     def localize(self):
         g = self.g
-        _hip.check(self.lib.gccnmf_angular_spectrogram(_ptr(self.CC), _ptr(self.trig), g.F, g.T, g.D, self.batch, _ptr(self.ang),
+        # GCC-NONLIN: the same call with alpha in the upper halves of D and batch (include/gccnmf_hip.h); only the localisation changes
+        D, B = _hip.angular_nl_words(g.D, self.batch, self.gccPHATNLAlpha) if self.gccPHATNLEnabled else (g.D, self.batch)
+        _hip.check(self.lib.gccnmf_angular_spectrogram(_ptr(self.CC), _ptr(self.trig), g.F, g.T, D, B, _ptr(self.ang),
                                                        _ptr(self.mean_ang), _stream()), 'gccnmf_angular_spectrogram')
         _hip.check(self.lib.gccnmf_pick_tdoa_peaks(_ptr(self.mean_ang), g.D, g.Dp, g.S, self.batch, _ptr(self.tdoa_idx),
                                                    _ptr(self.status), _stream()), 'gccnmf_pick_tdoa_peaks')
@@ -632,8 +642,10 @@ class RaggedGCCNMFEngine(object):
 
     def __init__(self, lengths, sampleRate=16000, windowSize=1024, hopSize=256, numTDOAs=128, microphoneSeparationInMetres=1.0,
                  numTargets=3, dictionarySize=None, numIterations=100, sparsityAlpha=0, epsilon=1e-16, seedValue=0,
-                 windowFunction=np.hanning, device='cuda:0', klnmf_flags=0, dictionaryW=None, initialH='random', reconstruction='direct'):
+                 windowFunction=np.hanning, device='cuda:0', klnmf_flags=0, dictionaryW=None, initialH='random', reconstruction='direct',
+                 gccPHATNLEnabled=False, gccPHATNLAlpha=2.0):
         self.reconstruction = check_reconstruction(reconstruction, numTargets)
+        self.gccPHATNLEnabled, self.gccPHATNLAlpha = check_gcc_phat_nl(gccPHATNLEnabled, gccPHATNLAlpha)
         if not torch.cuda.is_available():
             raise _hip.HipLibraryError('no ROCm device visible: the GCC-NMF HIP path has no CPU fallback')
         self.lib = _hip.lib()
@@ -648,7 +660,7 @@ class RaggedGCCNMFEngine(object):
                   microphoneSeparationInMetres=microphoneSeparationInMetres, numTargets=numTargets, dictionarySize=dictionarySize,
                   numIterations=numIterations, sparsityAlpha=sparsityAlpha, epsilon=epsilon, seedValue=seedValue,
                   windowFunction=windowFunction, device=device, klnmf_flags=klnmf_flags, dictionaryW=dictionaryW, initialH=initialH,
-                  reconstruction=reconstruction)
+                  reconstruction=reconstruction, gccPHATNLEnabled=gccPHATNLEnabled, gccPHATNLAlpha=gccPHATNLAlpha)
         # one ordinary engine per distinct length: its files (caller's indexes, ascending) are its batch
         self.files_of = {}
         for i, n in enumerate(self.lengths):

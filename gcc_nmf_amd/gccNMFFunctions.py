@@ -180,18 +180,25 @@ def _device_W(sc, W, g, dev):
     return dW
 
 
-def getAngularSpectrogram(spectralCoherenceV, frequenciesInHz, microphoneSeparationInMetres, numTDOAs):
+def getAngularSpectrogram(spectralCoherenceV, frequenciesInHz, microphoneSeparationInMetres, numTDOAs, gccPHATNLEnabled=False,
+                          gccPHATNLAlpha=2.0):
     """gccNMF/gccNMFFunctions.py:85-92.  Returns (numTDOAs, T) float64 like the reference; the
-    contraction itself is an f32 MFMA GEMM [cos;sin]^T.[Re C;Im C]."""
+    contraction itself is an f32 MFMA GEMM [cos;sin]^T.[Re C;Im C].
+
+    ``gccPHATNLEnabled`` / ``gccPHATNLAlpha`` (trailing keywords, the reference's setting names, realtime/config.py:42-43): the
+    GCC-NONLIN spectrum sum_f 1 - tanh(alpha sqrt(max(0, 1 - Re(C e^{-j 2 pi f tau})))) of Blandin, Ozerov & Vincent (2012) instead,
+    a VALU kernel (csrc/angular_nl.hip).  BSS-Locate's sqrt(2 - 2 re) form is this one with alpha * sqrt(2)."""
+    nl, alpha = _hip.check_gcc_phat_nl(gccPHATNLEnabled, gccPHATNLAlpha)
     C = np.asarray(spectralCoherenceV)
     F, T = C.shape
     lib, dev = _hip.lib(), _device()
     g = Geometry(F, T, 1, int(numTDOAs))
+    Dw, Bw = _hip.angular_nl_words(g.D, 1, alpha) if nl else (g.D, 1)
     trig = _trig_table(frequenciesInHz, microphoneSeparationInMetres, numTDOAs, g, dev)
     with _staging.Scope(dev) as sc:
         dC = _upload_coherence(sc, C, g)
         ang = sc.dev('ang', (g.Dp, g.Tp))
-        _hip.check(lib.gccnmf_angular_spectrogram(_ptr(dC), _ptr(trig), F, T, g.D, 1, _ptr(ang), 0, _stream()),
+        _hip.check(lib.gccnmf_angular_spectrogram(_ptr(dC), _ptr(trig), F, T, Dw, Bw, _ptr(ang), 0, _stream()),
                    'gccnmf_angular_spectrogram')
         out = sc.download(ang[:g.D, :T], dtype=np.float64)
     return out
@@ -339,10 +346,13 @@ def saveTargetSignalEstimates(targetSignalEstimates, sampleRate, mixtureFileName
 
 
 # ---- named by BASELINE.json's north_star; not in the reference -----------------
-def getTargetTDOAEstimates(complexMixtureSpectrogram, sampleRate, microphoneSeparationInMetres, numTDOAs, numSources):
+def getTargetTDOAEstimates(complexMixtureSpectrogram, sampleRate, microphoneSeparationInMetres, numTDOAs, numSources,
+                           gccPHATNLEnabled=False, gccPHATNLAlpha=2.0):
     """Convenience wrapper over the reference's three-step TDOA estimation
     (runGCCNMF.py:44-47): coherence -> getAngularSpectrogram -> time mean ->
-    estimateTargetTDOAIndexesFromAngularSpectrum.  Returns (targetTDOAIndexes, meanAngularSpectrum)."""
+    estimateTargetTDOAIndexesFromAngularSpectrum.  Returns (targetTDOAIndexes, meanAngularSpectrum).
+    ``gccPHATNLEnabled`` / ``gccPHATNLAlpha``: as for getAngularSpectrogram (the peaks of the GCC-NONLIN spectrum)."""
+    nl, alpha = _hip.check_gcc_phat_nl(gccPHATNLEnabled, gccPHATNLAlpha)
     X = np.asarray(complexMixtureSpectrogram).astype(complex64)
     C, F, T = X.shape
     lib, dev = _hip.lib(), _device()
@@ -357,7 +367,8 @@ def getTargetTDOAEstimates(complexMixtureSpectrogram, sampleRate, microphoneSepa
     idx = torch.zeros((g.S,), dtype=torch.int32, device=dev)
     status = torch.zeros((1,), dtype=torch.int32, device=dev)
     _hip.check(lib.gccnmf_coherence(_ptr(dX), F, T, 1, _ptr(dC), _stream()), 'gccnmf_coherence')
-    _hip.check(lib.gccnmf_angular_spectrogram(_ptr(dC), _ptr(trig), F, T, g.D, 1, _ptr(ang), _ptr(meanA), _stream()),
+    Dw, Bw = _hip.angular_nl_words(g.D, 1, alpha) if nl else (g.D, 1)
+    _hip.check(lib.gccnmf_angular_spectrogram(_ptr(dC), _ptr(trig), F, T, Dw, Bw, _ptr(ang), _ptr(meanA), _stream()),
                'gccnmf_angular_spectrogram')
     _hip.check(lib.gccnmf_pick_tdoa_peaks(_ptr(meanA), g.D, g.Dp, g.S, 1, _ptr(idx), _ptr(status), _stream()),
                'gccnmf_pick_tdoa_peaks')

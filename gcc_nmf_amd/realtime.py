@@ -23,6 +23,7 @@ TARGET_MODE_MULTIPLE = 1
 TARGET_MODE_WINDOW_FUNCTION = 2
 MAX_SOURCES = 8                          # frames_mode bits 21..23 (csrc/rt.hip)
 _MULTI_LAYOUT = 1 << 20
+_ROW8_LAYOUT = 1 << 24                   # single-stream call: the target row has 8 words, word 6 = gccPHATNLAlpha (csrc/rt.hip)
 
 
 def asymmetricWindows(windowSize, synthesisSize):
@@ -58,17 +59,27 @@ class GCCNMFProcessor(object):
     synthesis and output, and the online localisation keeps the ``numSources`` largest peaks of the gccPHAT window mean as the next
     block's targets, in ascending order -- target identity is left-to-right order, so two talkers that cross swap outputs.  The host
     mirrors ``gccPHATHistory`` and ``inputSpectrogramHistory`` are filled as in the other modes and ``tdoaHistory`` receives the N
-    indexes as an (N, 1) column; ``outputSpectrogramHistory`` and ``coefficientMaskHistories`` are not filled in this mode."""
+    indexes as an (N, 1) column; ``outputSpectrogramHistory`` and ``coefficientMaskHistories`` are not filled in this mode.
+
+    ``gccPHATNLEnabled`` (default False) / ``gccPHATNLAlpha`` (default 2.0): the reference's GCC-NONLIN settings (config.py:42-43,
+    a processor parameter that needs ``reset()``, gccNMFProcessor.py:131-132; parity unpinned: the reference has no code for them).
+    Attributes and constructor keywords; a new value takes effect with ``reset()``.  When enabled, gccPHAT is
+    nanmean_f 1 - tanh(alpha sqrt(max(0, 1 - Re(C e^{-j w tau})))) (Blandin, Ozerov & Vincent 2012; BSS-Locate's sqrt(2 - 2 re) form
+    is this one with alpha * sqrt(2)) in all three target modes; the history, window mean and arg-max / peak rule are unchanged and the
+    GCC-NMF scores stay PHAT."""
 
     def __init__(self, sampleRate, windowSize, numTimePerChunk, dictionariesW, dictionaryType, dictionarySize, numHUpdates,
                  microphoneSeparationInMetres, localizationEnabled, localizationWindowSize, gccPHATHistory=None, tdoaHistory=None,
                  inputSpectrogramHistory=None, outputSpectrogramHistory=None, coefficientMaskHistories=None, numTDOAs=64,
-                 numTDOAHistory=128, analysisWindow=None, synthesisWindow=None, numSources=2):
+                 numTDOAHistory=128, analysisWindow=None, synthesisWindow=None, numSources=2, gccPHATNLEnabled=False,
+                 gccPHATNLAlpha=2.0):
         # any even size like the reference (numpy.fft.rfft / irfft, gccNMFProcessor.py:202,:231): powers of two from 64 up take the
         # radix-2 LDS transform, every other even size the direct-sum kernels of csrc/rt.hip
         if int(windowSize) != windowSize or int(windowSize) < 4 or int(windowSize) > 4096 or int(windowSize) % 2:
             raise ValueError('windowSize=%r is not supported by the HIP frame processor: an even size from 4 to 4096' % (windowSize,))
         _check_num_sources(numSources)
+        self.gccPHATNLEnabled, self.gccPHATNLAlpha = gccPHATNLEnabled, gccPHATNLAlpha
+        self._gcc_phat_nl()               # ValueError before the constructor looks for a device
         self.lib = _hip.lib()
         self.device = _device()
         self.sampleRate, self.windowSize, self.numTimePerChunk = sampleRate, int(windowSize), int(numTimePerChunk)
@@ -100,6 +111,11 @@ class GCCNMFProcessor(object):
         self.numSources = numSources
         self.reset()
 
+    def _gcc_phat_nl(self):
+        """Word 6 of the target row for the current attributes: gccPHATNLAlpha when GCC-NONLIN is enabled, 0.0 (PHAT) when not."""
+        enabled, alpha = _hip.check_gcc_phat_nl(self.gccPHATNLEnabled, self.gccPHATNLAlpha)
+        return np.float32(alpha if enabled else 0.0)
+
     # ---- reference API ------------------------------------------------------------------------------------------
     @_on_device
     def reset(self):
@@ -112,6 +128,7 @@ class GCCNMFProcessor(object):
             raise ValueError('dictionary has %d rows, window size %d needs %d' % (self.numFrequencies, self.windowSize, self.windowSize // 2 + 1))
         F, K, D, Tc = self.numFrequencies, self.numAtom, self.numTDOAs, self.numTimePerChunk
         NS = _check_num_sources(self.numSources)
+        nl_word = self._gcc_phat_nl()
         self.Kp, self.Dp = -(-K // 64) * 64, -(-D // 32) * 32
         self.frequenciesInHz = np.linspace(0, self.sampleRate / 2, F).astype(np.float32)                 # :245
         self.maxTDOA = self.microphoneSeparationInMetres / SPEED_OF_SOUND_IN_METRES_PER_SECOND
@@ -132,7 +149,7 @@ class GCCNMFProcessor(object):
             ang = 2.0 * np.pi * np.arange(N, dtype=np.float64) / N
             self.dTwiddle = torch.from_numpy(np.ascontiguousarray(np.stack([np.cos(ang), np.sin(ang)], axis=1).astype(np.float32)).reshape(-1)).to(dev)
         # what the host mirrors are computed from lives in ONE block, so that they cost one download per call: X | Y | HMask | gccPHAT | target
-        # (the target row is 16 words: {index, epsilon, beta, noiseFloor, -, -, -, -, tau_0 .. tau_7}; words 8.. are multiple mode's)
+        # (the target row is 16 words: {index, epsilon, beta, noiseFloor, -, -, nlAlpha, -, tau_0 .. tau_7}; words 8.. are multiple mode's)
         sizes = [2 * F * Tc * 2, 2 * F * Tc * 2, self.Kp * Tc, D * Tc, 16]
         offs = np.concatenate([[0], np.cumsum([-(-n // 4) * 4 for n in sizes])])
         self.dMirror = z(int(offs[-1]))
@@ -143,6 +160,8 @@ class GCCNMFProcessor(object):
         self.dHist, self.dHistPos = z(D, self.numTDOAHistory), z(1, dtype=torch.int32)
         self.dTarget = part(4, 16)
         self.dTarget[:4].copy_(torch.from_numpy(self._target_host))
+        self._nl_word = nl_word                           # GCC-NONLIN as this reset() saw it: alpha, or 0 = PHAT
+        self.dTarget[6] = float(nl_word)
         self._mirror_offs, self._mirror_sizes, self._mirror_host = offs, sizes, None
         # _target_dirty: a device call ran with the online localisation on since the value was last known on the host
         self._calls, self._target_dirty, self._target_value, self._target_pin = 0, False, float(self._target_host[0]), None
@@ -219,6 +238,8 @@ class GCCNMFProcessor(object):
                 self._target_dirty = True
         if multi:
             frames_mode |= _MULTI_LAYOUT | ((self._sources - 1) << 21)
+        elif self._nl_word > 0:             # the multi-target row always has word 6; the single-target call is told that its row does
+            frames_mode |= _ROW8_LAYOUT
         Y, HMask, tfMask = (self.dYm, self.dHMaskm, self.dTfMaskm) if multi else (self.dY, self.dHMask, self.dTfMask)
         _hip.check(self.lib.gccnmf_rt_process_block_ll(
             _ptr(block_in), _ptr(block_out), _ptr(in_ring), _ptr(out_ring), _ptr(self.dX), _ptr(Y), _ptr(self.dC), _ptr(HMask),
@@ -482,8 +503,8 @@ class StreamingGCCNMFBank(object):
     ``processor`` is the shared configuration: its dictionary, TDOA grid, windows, twiddles, ``targetMode``, ``numHUpdates`` and
     ``localizationWindowSize``, and its ``separationEnabled`` / ``localizationEnabled`` as master switches.  The bank allocates its
     own per-stream state (rings, spectra, masks, history ring, target row) and never touches the processor's.  Each stream has a
-    target row {index, epsilon, beta, noiseFloor, separation, localisation}: a stream separates (localises) when the processor's
-    switch and its own are both on.  After ``processor.reset()`` the next call re-allocates all per-stream state.
+    target row {index, epsilon, beta, noiseFloor, separation, localisation, nlAlpha}: a stream separates (localises) when the processor's
+    switch and its own are both on, and localises on GCC-NONLIN when its nlAlpha word is > 0 (``setGCCPHATNL``).  After ``processor.reset()`` the next call re-allocates all per-stream state.
 
     The GUI's host mirrors (``GCCNMFProcessor.fill_histories``) are not produced for a bank.
 
@@ -505,7 +526,7 @@ class StreamingGCCNMFBank(object):
 
     # ---- per-stream state ----------------------------------------------------------------------------------------------
     def _initial_row(self):
-        row = np.concatenate([self.p._target_host, np.array([1, 1, 0, 0], np.float32)]).astype(np.float32)
+        row = np.concatenate([self.p._target_host, np.array([1, 1, self.p._nl_word, 0], np.float32)]).astype(np.float32)
         if self._multi:                    # + the processor's target indexes (words 8..)
             tau = np.zeros(8, np.float32)
             tau[:self._sources] = self.p.targetTDOAIndexes
@@ -575,6 +596,16 @@ class StreamingGCCNMFBank(object):
         s = self._stream_index(s)
         self._ensure_state()
         self.dTarget[s, 5] = float(bool(on))
+
+    @_on_device
+    def setGCCPHATNL(self, s, enabled, alpha=2.0):
+        """Word 6 of stream s's row: GCC-NONLIN localisation for this stream alone (``gccPHATNLEnabled`` / ``gccPHATNLAlpha``; initially
+        the processor's, as of its last ``reset()``).  Takes effect with the next block; the stream's gccPHAT history is kept, so reset
+        the stream as well where PHAT and NONLIN columns must not share a window mean."""
+        s = self._stream_index(s)
+        on, a = _hip.check_gcc_phat_nl(enabled, alpha)
+        self._ensure_state()
+        self.dTarget[s, 6] = a if on else 0.0
 
     @_on_device
     def setTargetTDOAIndexes(self, s, indexes):

@@ -238,7 +238,21 @@ gccnmf_allreduce_fn gccnmf_rccl_allreduce_hook(void);
  * [cos;sin]^T . [Re C; Im C], plus its time mean.  Replaces getAngularSpectrogram
  * (gccNMFFunctions.py:85-92) and mean(.., axis=-1) (runGCCNMF.py:46).
  *   trig   [2][Fp][Dp] float32: cos(2 pi f tau) / sin(2 pi f tau), Dp = round_up(D,64), zero padded
- *   ang    [batch][Dp][Tp] float32 out,  mean_ang [batch][Dp] float64 out (may be NULL) */
+ *   ang    [batch][Dp][Tp] float32 out,  mean_ang [batch][Dp] float64 out (may be NULL)
+ *
+ * GCC-NONLIN (the reference's settings gccPHATNLEnabled / gccPHATNLAlpha, gccNMF/realtime/config.py:42-43,53-54, handed on in
+ * runRealtimeGCCNMF.py:101 and gccNMFInterface.py:64-65 and never evaluated there; Blandin, Ozerov & Vincent 2012):
+ *     A[tau][t] = sum_f 1 - tanh(alpha sqrt(max(0, 1 - Re(C[f,t] exp(-2j pi f tau)))))
+ * is a mode of this call, not an entry point of its own (the header does not grow; gccnmf_reconstruct carries its mode the same
+ * way): the float32 bits of alpha ride in the upper halves of D and batch,
+ *     gccnmf_angular_spectrogram(CC, trig, F, T, GCCNMF_ANGULAR_NL_D(D, bits), GCCNMF_ANGULAR_NL_BATCH(batch, bits), ang, mean_ang, stream)
+ * with D and batch below 65536.  Both halves zero = PHAT: every call that existed before computes what it computed.  Same buffers,
+ * pitches and padding rules (only tau < D, t < T is written), same mean_ang; the nonlinearity sits inside the sum, so this is a
+ * register-tiled VALU kernel (csrc/angular_nl.hip), every output summed in an order that depends on F alone (a file alone and in a
+ * batch agree bit for bit).  A zero coherence bin adds 1 - tanh(alpha) to every tau.  GCCNMF_ERR_ARG: alpha <= 0, NaN, Inf or
+ * subnormal, and whatever the PHAT form rejects. */
+#define GCCNMF_ANGULAR_NL_D(D, alpha_bits) ((int)((unsigned)(D) | ((unsigned)(alpha_bits) & 0xffff0000u)))
+#define GCCNMF_ANGULAR_NL_BATCH(batch, alpha_bits) ((int)((unsigned)(batch) | ((unsigned)(alpha_bits) << 16)))
 int gccnmf_angular_spectrogram(const float* CC, const float* trig, int F, int T, int D, int batch, float* ang,
                                double* mean_ang, void* stream);
 
@@ -355,11 +369,11 @@ int gccnmf_rt_process_block(const float* block_in, float* block_out, float* in_r
  *                                  together in the same launches (S <= 4096).  Every per-stream buffer holds S consecutive
  *                                  single-stream images (block_in / block_out, in_ring / out_ring, X, Y, C, HMask, argmaxTDOA,
  *                                  tfMask as [S][2][F][Tc] whatever numHUpdates, gccphat, hist, Hcoef, Rv); hist_pos is [S];
- *                                  target is [S][8] = {index, epsilon, beta, noiseFloor, separation, localisation, 0, 0}.  A
+ *                                  target is [S][8] = {index, epsilon, beta, noiseFloor, separation, localisation, nlAlpha, 0}.  A
  *                                  stream separates (localises) when separation_enabled (localization_enabled) AND its row word
  *                                  4 (5) are non-zero; with separation_enabled = 0 no mask kernel is launched.  Stream s computes
  *                                  bit for bit what a single-stream call on its images computes.  Bits 2 and 4 work as above.
- *                                  GCCNMF_ERR_ARG: 8 together with 1 (frames mode), bits 8..19 without 8, any bit above 23.
+ *                                  GCCNMF_ERR_ARG: 8 together with 1 (frames mode), bits 8..19 without 8, any bit above 24.
  *                                  1 << 20 = multi-target layout (separation of N = (bits 21..23) + 1 talkers, N <= 8; needs
  *                                  target_mode 1 = TARGET_MODE_MULTIPLE).  The target row is 16 floats per stream (single-stream
  *                                  call and bank): words 0..7 as above (0..3 unused), words 8..8+N-1 = target TDOA indexes
@@ -371,6 +385,15 @@ int gccnmf_rt_process_block(const float* block_in, float* block_out, float* in_r
  *                                  every other buffer as above.  With separation off every output is the unmasked mixture.
  *                                  GCCNMF_ERR_ARG: 1 << 20 with target_mode != 1, bits 21..23 without 1 << 20.  Without bit 20 a
  *                                  call computes what it computed before the layout existed (target_mode 1 = window function).
+ *                                  GCC-NONLIN localisation (gccPHATNLEnabled / gccPHATNLAlpha, config.py:42-43): word 6 of a stream's
+ *                                  target row is alpha, 0 = plain PHAT (a value that is not a positive normal float is read as 0).
+ *                                  With alpha > 0 the localisation kernel accumulates 1 - tanh(alpha sqrt(max(0, 1 - term))) instead
+ *                                  of each term of gccphat = nanmean_f Re(C e^{-jwt}); NaN terms are skipped as before, and the
+ *                                  history ring, window mean and arg-max / peak rule are unchanged.  The GCC-NMF scores stay PHAT.
+ *                                  The row word was chosen over a new entry point or argument: it gives per-stream control in the
+ *                                  bank and leaves both signatures alone.  The bank and multi-target rows always have word 6; the
+ *                                  single-stream row is 4 words unless 1 << 24 says it has 8 (words 4, 5, 7 unused there).
+ *                                  GCCNMF_ERR_ARG: 1 << 24 together with 8 or 1 << 20, any bit above 24.
  *   out_delay_blocks               which finished block is handed out: 2 = the reference (utils.py:116); 1 is complete when
  *                                  the synthesis window spans at most two hops */
 int gccnmf_rt_process_block_ll(const float* block_in, float* block_out, float* in_ring, float* out_ring, float* X, float* Y, float* C,
