@@ -137,6 +137,38 @@ def angular_nl_words(D, batch, alpha):
     return signed(int(D) | (bits & 0xffff0000)), signed(int(batch) | ((bits & 0xffff) << 16))
 
 
+GCCNMF_SCORES_TRACKS = 0x100            # include/gccnmf_hip.h: per-(target, frame) indexes in gccnmf_target_scores_masks
+TRACKS_MAX_FRAMES = (1 << 21) - 1
+
+
+def check_tdoa_tracking(tdoaTracking, localizationWindowSize, numSources):
+    """The ``tdoaTracking`` / ``localizationWindowSize`` keywords of the engines and the window argument of
+    estimateTargetTDOATracksFromAngularSpectrogram; no device needed.  The window is a number of frames: an integer >= 1 (checked
+    whether or not tracking is on, so a bad value cannot wait for the switch), required when tracking is on; tracking also needs
+    the number of sources (the peak rule keeps that many peaks per frame, 1 to 255).  Returns (tracking, window or None)."""
+    import numbers
+    L = localizationWindowSize
+    if L is not None:
+        if isinstance(L, bool) or not isinstance(L, numbers.Integral) or L < 1:
+            raise ValueError('localizationWindowSize must be a whole number of frames >= 1, got %r' % (L,))
+        L = int(L)
+    if tdoaTracking:
+        if L is None:
+            raise ValueError('tdoaTracking needs localizationWindowSize (frames)')
+        S = numSources
+        if S is None or isinstance(S, bool) or not isinstance(S, numbers.Integral) or not 1 <= S <= 255:
+            raise ValueError('tdoaTracking needs the number of sources (1 to 255), got %r' % (S,))
+    return bool(tdoaTracking), L
+
+
+def peaks_tracks_word(S, L, T):
+    """The S argument of gccnmf_pick_tdoa_peaks in its tracks mode: GCCNMF_PEAKS_TRACKS(S, L) of include/gccnmf_hip.h.  A window of
+    2T - 1 frames or more is the whole file for every frame, so L is passed as min(L, 2T - 1)."""
+    if not (1 <= int(S) <= 255 and 1 <= int(T) <= TRACKS_MAX_FRAMES and int(L) >= 1):
+        raise ValueError('tracks take 1 <= S <= 255, 1 <= T < 2^21 and L >= 1, got %r, %r, %r' % (S, T, L))
+    return int(S) | 0x100 | (min(int(L), 2 * int(T) - 1) << 9)
+
+
 _lib = None
 
 

@@ -43,21 +43,17 @@ __global__ __launch_bounds__(256) void ang_mean_kernel(const float* __restrict__
 // Strict local maxima (scipy.signal.argrelmax, order 1: edges never qualify, NaN never compares greater),
 // keep the S largest, ascending index order.  Among peaks of equal height the LARGER index is kept: the reference keeps
 // peakIndexes[argsort(values)[-S:]], and a stable ascending sort puts the larger of two equal values last.
-// One 64-thread block per file; D <= 4096.
-__global__ __launch_bounds__(64) void pick_peaks_kernel(const double* __restrict__ mean_ang, int D, int Dp, int S,
-                                                        int* __restrict__ tdoa_idx, int* __restrict__ status) {
-    __shared__ double v[4096];
-    __shared__ unsigned char is_peak[4096];
-    const int b = blockIdx.x;
-    const double* m = mean_ang + (long)b * Dp;
-    for (int i = threadIdx.x; i < D; i += 64) v[i] = m[i];
+// THE peak rule, on one row v[0..D) that the calling 64-thread block has put into LDS (D <= 4096): the whole-file estimate runs it on
+// the time mean, the time-varying tracks on every frame's windowed mean.  out[n * out_stride], n < S, receives the chosen indexes
+// (-1 beyond the peaks found); returns whether S peaks were found (valid in thread 0).
+__device__ __forceinline__ bool pick_peaks_row(const double* v, unsigned char* is_peak, int* s_found, int D, int S, int* out,
+                                               long out_stride) {
     __syncthreads();
     for (int i = threadIdx.x; i < D; i += 64) is_peak[i] = (i > 0 && i < D - 1 && v[i] > v[i - 1] && v[i] > v[i + 1]) ? 1 : 0;
     __syncthreads();
     // top-S peaks: S rounds of a 64-lane arg-max over the peaks still standing (largest value, largest index on ties; a serial scan
     // cost 33 us of a single-mixture run)
-    __shared__ int s_found;
-    if (threadIdx.x == 0) s_found = 0;
+    if (threadIdx.x == 0) *s_found = 0;
     __syncthreads();
     for (int s = 0; s < S; ++s) {
         double bv = 0.0;
@@ -79,23 +75,131 @@ __global__ __launch_bounds__(64) void pick_peaks_kernel(const double* __restrict
         if (bi < 0) break;                     // wave-uniform after the butterfly
         if (threadIdx.x == 0) {
             is_peak[bi] = 2;
-            ++s_found;
+            ++*s_found;
         }
         __syncthreads();
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        int* out = tdoa_idx + (long)b * S;
-        int n = 0;
-        for (int i = 1; i < D - 1 && n < S; ++i)
-            if (is_peak[i] == 2) out[n++] = i;
-        for (; n < S; ++n) out[n] = -1;
-        status[b] = (s_found == S) ? 0 : 1;
+    if (threadIdx.x != 0) return false;
+    int n = 0;
+    for (int i = 1; i < D - 1 && n < S; ++i)
+        if (is_peak[i] == 2) out[(n++) * out_stride] = i;
+    for (; n < S; ++n) out[n * out_stride] = -1;
+    return *s_found == S;
+}
+
+// One 64-thread block per file; D <= 4096.
+__global__ __launch_bounds__(64) void pick_peaks_kernel(const double* __restrict__ mean_ang, int D, int Dp, int S,
+                                                        int* __restrict__ tdoa_idx, int* __restrict__ status) {
+    __shared__ double v[4096];
+    __shared__ unsigned char is_peak[4096];
+    __shared__ int s_found;
+    const int b = blockIdx.x;
+    const double* m = mean_ang + (long)b * Dp;
+    for (int i = threadIdx.x; i < D; i += 64) v[i] = m[i];
+    const bool all = pick_peaks_row(v, is_peak, &s_found, D, S, tdoa_idx + (long)b * S, 1);
+    if (threadIdx.x == 0) status[b] = all ? 0 : 1;
+}
+
+// Time-varying TDOA tracks, stage 1 of 2: for frame t of file b the mean of ang over the centred window
+// [lo, hi) = [max(0, t - L/2), min(T, t - L/2 + L)) -- a float64 sum in ascending frame order over its own length, so a value depends on
+// (t, L, T) and the file alone, never on the batch -- and the peak rule above on that column.  One 64-thread block per (frame, file):
+// a lane owns the TDOAs d = lane, lane + 64, ... and walks its rows in aligned 16-byte groups (the groups that straddle lo or hi are
+// masked: Tp is a multiple of 64, so they stay inside the row).  Dynamic LDS: 8 D + 16 + round_up(D, 16) bytes.  tracks [batch][S][Tp], status [batch][Tp]: 0 = S peaks, 1 = fewer
+// (stage 2 replaces the set).  Frames t >= T are not written.  grid = (T, batch)
+__global__ __launch_bounds__(64) void track_peaks_kernel(const float* __restrict__ ang, int T, int Tp, int D, int Dp, int S, int L,
+                                                         int* __restrict__ tracks, int* __restrict__ status) {
+    extern __shared__ double track_lds[];                        // v [D] | s_found (16 bytes) | is_peak [D]: sized by D, not by the
+    double* v = track_lds;                                       // 4096-TDOA limit (36 KB a block would leave one wave per SIMD)
+    int* s_found = (int*)(track_lds + D);
+    unsigned char* is_peak = (unsigned char*)(track_lds + D + 2);
+    const int t = blockIdx.x, b = blockIdx.y;
+    const int first = t - L / 2;
+    const int lo = first < 0 ? 0 : first, hi = first + L < T ? first + L : T;       // lo <= t < hi
+    const double len = (double)(hi - lo);
+    for (int d = threadIdx.x; d < D; d += 64) {
+        const float* row = ang + ((long)b * Dp + d) * Tp;
+        double s = 0.0;
+        for (int g = lo & ~3; g < hi; g += 4) {
+            const float4 a = *(const float4*)(row + g);
+            if (g >= lo) s += (double)a.x;
+            if (g + 1 >= lo && g + 1 < hi) s += (double)a.y;
+            if (g + 2 >= lo && g + 2 < hi) s += (double)a.z;
+            if (g + 3 >= lo && g + 3 < hi) s += (double)a.w;
+        }
+        v[d] = s / len;
     }
+    const bool all = pick_peaks_row(v, is_peak, s_found, D, S, tracks + (long)b * S * Tp + t, Tp);
+    if (threadIdx.x == 0) status[(long)b * Tp + t] = all ? 0 : 1;
+}
+
+// Stage 2: a frame with fewer than S peaks takes the set of the last complete frame before it, the frames in front of the first
+// complete one take that one's; status 1 marks both, 3 (= 1 | 2) every frame of a file without any complete frame (tracks -1).
+// Pass 1 leaves in status[t] the last complete frame <= t (-1: none yet) -- a running maximum, 256 frames per step -- and pass 2
+// copies: a complete frame is never written, and a thread reads back only the words it wrote itself.  One 256-thread block per file.
+__global__ __launch_bounds__(256) void track_carry_kernel(int T, int Tp, int S, int* __restrict__ tracks, int* __restrict__ status) {
+    __shared__ int scan[256];
+    __shared__ int s_carry, s_first;
+    const int tid = threadIdx.x;
+    int* st = status + (long)blockIdx.x * Tp;
+    int* tr = tracks + (long)blockIdx.x * S * Tp;
+    if (tid == 0) {
+        s_carry = -1;
+        s_first = T;
+    }
+    __syncthreads();
+    for (int c = 0; c < T; c += 256) {
+        const int t = c + tid;
+        const bool complete = t < T && st[t] == 0;
+        if (complete) atomicMin(&s_first, t);
+        scan[tid] = complete ? t : -1;
+        __syncthreads();
+        for (int o = 1; o < 256; o <<= 1) {
+            const int left = tid >= o ? scan[tid - o] : -1;
+            __syncthreads();
+            if (left > scan[tid]) scan[tid] = left;
+            __syncthreads();
+        }
+        const int src = scan[tid] > s_carry ? scan[tid] : s_carry;
+        if (t < T) st[t] = src;
+        __syncthreads();
+        if (tid == 255) s_carry = src;
+        __syncthreads();
+    }
+    const int first = s_first;
+    for (int t = tid; t < T; t += 256) {
+        int src = st[t];
+        if (src == t) {
+            st[t] = 0;
+            continue;
+        }
+        if (src < 0) src = first;
+        for (int i = 0; i < S; ++i) tr[(long)i * Tp + t] = first < T ? tr[(long)i * Tp + src] : -1;
+        st[t] = first < T ? 1 : 3;
+    }
+}
+
+// The steering product Re(C e^{-j w tau}) = Cr cos + Ci sin of a thread's four frames, with its roundings written out: frames 0, 2 and 3
+// fma(Cr, cos, Ci * sin), frame 1 the two rounded products added.  That is what the compiler made of `cr * c + ci * sn` while the
+// fixed-index kernel was the only form (its packed-math pairing decides which sums it contracts), and the results of every existing
+// call rest on it; stated explicitly, with contraction off, the fixed-index and the per-frame form share it and give the same bits
+// for the same (cos, sin) whatever a later compiler would have paired.
+__device__ __forceinline__ float4 gcc_steer4(float4 cr, float4 ci, float4 c, float4 sn) {
+#pragma clang fp contract(off)
+    float4 out;
+    out.x = fmaf(cr.x, c.x, ci.x * sn.x);
+    out.y = cr.y * c.y + ci.y * sn.y;
+    out.z = fmaf(cr.z, c.z, ci.z * sn.z);
+    out.w = fmaf(cr.w, c.w, ci.w * sn.w);
+    return out;
 }
 
 // P[f][i*Tp + t] = Re(C[f,t] * exp(-j 2 pi f tau_i)) = Cr*cos + Ci*sin, zero in every padded position.
 // One thread = four consecutive frames (16-byte loads of Cr / Ci, one 16-byte store).  grid = (ceil(S*Tp/1024), Fp, batch)
+// TRACKS: tdoa_idx is [batch][S][Tp], one index per (target, frame) -- the four frames' indexes are one 16-byte load, their table
+// entries four lookups in row f of the steering table (512 bytes at D = 128: they hit the vector cache); the same products in the
+// same order (gcc_steer4), so constant tracks give the bits of the fixed-index form.
+template <bool TRACKS>
 __global__ __launch_bounds__(256) void gcc_steer_kernel(const float* __restrict__ CC, const float* __restrict__ trig,
                                                         const int* __restrict__ tdoa_idx, int F, int Fp, int T, int Tp, int D,
                                                         int Dp, int S, float* __restrict__ P) {
@@ -105,16 +209,23 @@ __global__ __launch_bounds__(256) void gcc_steer_kernel(const float* __restrict_
     const int i = col / Tp, t = col - i * Tp;                   // Tp is a multiple of 64: the four frames share the target
     float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
     if (f < F && t < T) {
-        int tau = tdoa_idx[(long)b * S + i];
-        tau = tau < 0 ? 0 : (tau >= D ? D - 1 : tau);
         const long plane = (long)Fp * Tp;
         const float4 cr = *(const float4*)(CC + (long)b * 2 * plane + (long)f * Tp + t);
         const float4 ci = *(const float4*)(CC + (long)b * 2 * plane + plane + (long)f * Tp + t);
-        const float c = trig[(long)f * Dp + tau], sn = trig[((long)Fp + f) * Dp + tau];
-        out.x = cr.x * c + ci.x * sn;
-        if (t + 1 < T) out.y = cr.y * c + ci.y * sn;
-        if (t + 2 < T) out.z = cr.z * c + ci.z * sn;
-        if (t + 3 < T) out.w = cr.w * c + ci.w * sn;
+        const float* cos_row = trig + (long)f * Dp;
+        const float* sin_row = trig + ((long)Fp + f) * Dp;
+        int4 tau;
+        if (TRACKS) tau = *(const int4*)(tdoa_idx + ((long)b * S + i) * Tp + t);
+        else tau.x = tau.y = tau.z = tau.w = tdoa_idx[(long)b * S + i];
+        tau.x = tau.x < 0 ? 0 : (tau.x >= D ? D - 1 : tau.x);
+        tau.y = tau.y < 0 ? 0 : (tau.y >= D ? D - 1 : tau.y);
+        tau.z = tau.z < 0 ? 0 : (tau.z >= D ? D - 1 : tau.z);
+        tau.w = tau.w < 0 ? 0 : (tau.w >= D ? D - 1 : tau.w);
+        out = gcc_steer4(cr, ci, make_float4(cos_row[tau.x], cos_row[tau.y], cos_row[tau.z], cos_row[tau.w]),
+                         make_float4(sin_row[tau.x], sin_row[tau.y], sin_row[tau.z], sin_row[tau.w]));
+        if (t + 1 >= T) out.y = 0.f;
+        if (t + 2 >= T) out.z = 0.f;
+        if (t + 3 >= T) out.w = 0.f;
     }
     *(float4*)(P + ((long)b * Fp + f) * ((long)S * Tp) + col) = out;
 }
@@ -286,6 +397,22 @@ int gccnmf_angular_spectrogram(const float* CC, const float* trig, int F, int T,
 int gccnmf_pick_tdoa_peaks(const double* mean_ang, int D, int Dp, int S, int batch, int* tdoa_idx, int* status,
                            void* stream) {
     GCCNMF_ENTER();
+    // time-varying tracks ride above the low byte of S (GCCNMF_PEAKS_TRACKS: bit 8, the window length L in bits 9-30); nothing above
+    // the low byte = the whole-file estimate, every call as it was.  Every check comes before the first HIP call.
+    if (S & ~0xff) {
+        const int L = (S >> 9) & 0x3fffff, T = Dp;              // ang's pitches follow from D and T: the Dp argument carries T
+        if (S < 0 || !(S & GCCNMF_PEAKS_TRACKS_BIT) || L < 1) return GCCNMF_ERR_ARG;
+        S &= 0xff;
+        if (!mean_ang || !tdoa_idx || !status || D < 3 || D > 4096 || T < 1 || T >= (1 << 21) || S < 1 || batch < 1 || batch > 65535)
+            return GCCNMF_ERR_ARG;
+        const int Tp = gccnmf_round_up(T, 64);
+        hipLaunchKernelGGL(track_peaks_kernel, dim3(T, batch), dim3(64), 8 * D + 16 + gccnmf_round_up(D, 16), (hipStream_t)stream, (const float*)mean_ang, T, Tp, D,
+                           gccnmf_round_up(D, 64), S, L, tdoa_idx, status);
+        GCCNMF_CHECK_LAUNCH();
+        hipLaunchKernelGGL(track_carry_kernel, dim3(batch), dim3(256), 0, (hipStream_t)stream, T, Tp, S, tdoa_idx, status);
+        GCCNMF_CHECK_LAUNCH();
+        return GCCNMF_OK;
+    }
     if (!mean_ang || !tdoa_idx || !status || D < 3 || D > 4096 || Dp < D || S < 1 || batch < 1) return GCCNMF_ERR_ARG;
     hipLaunchKernelGGL(pick_peaks_kernel, dim3(batch), dim3(64), 0, (hipStream_t)stream, mean_ang, D, Dp, S, tdoa_idx, status);
     GCCNMF_CHECK_LAUNCH();
@@ -303,16 +430,24 @@ int gccnmf_target_scores_masks(const float* CC, const float* trig, const int* td
                                int K, int D, int S, int batch, float* workspace, float* scores, unsigned char* argmax,
                                void* stream) {
     GCCNMF_ENTER();
-    if (!CC || !trig || !tdoa_idx || !W || !workspace || !scores || F < 2 || T < 1 || K < 1 || D < 1 || S < 1 || S > 255 ||
-        batch < 1)
+    // per-(target, frame) indexes ride above the low byte of S (GCCNMF_SCORES_TRACKS); every check comes before the first HIP call
+    const int mode = S & ~0xff;
+    if (S < 0 || (mode & ~GCCNMF_SCORES_TRACKS)) return GCCNMF_ERR_ARG;
+    S &= 0xff;
+    const bool tracks = mode == GCCNMF_SCORES_TRACKS;
+    if (!CC || !trig || !tdoa_idx || !W || !workspace || !scores || F < 2 || T < 1 || K < 1 || D < 1 || S < 1 || batch < 1)
         return GCCNMF_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     GccNmfPitches p = gccnmf_make_pitches(F, T, K);
     const int Dp = gccnmf_round_up(D, 64);
     const int ncol = S * p.Tp;
     float* P = workspace;
-    hipLaunchKernelGGL(gcc_steer_kernel, dim3(gccnmf_ceil_div(ncol, 1024), p.Fp, batch), dim3(256), 0, s, CC, trig, tdoa_idx, F,
-                       p.Fp, T, p.Tp, D, Dp, S, P);
+    if (tracks)
+        hipLaunchKernelGGL(gcc_steer_kernel<true>, dim3(gccnmf_ceil_div(ncol, 1024), p.Fp, batch), dim3(256), 0, s, CC, trig, tdoa_idx,
+                           F, p.Fp, T, p.Tp, D, Dp, S, P);
+    else
+        hipLaunchKernelGGL(gcc_steer_kernel<false>, dim3(gccnmf_ceil_div(ncol, 1024), p.Fp, batch), dim3(256), 0, s, CC, trig, tdoa_idx,
+                           F, p.Fp, T, p.Tp, D, Dp, S, P);
     GCCNMF_CHECK_LAUNCH();
     GemmArgs a = {};
     a.A = W; a.sA = (long)p.Fp * p.Kp; a.lda = p.Kp; a.a_clamp = p.Kp - 4;

@@ -65,6 +65,7 @@ def check_reconstruction(reconstruction, numTargets):
     return reconstruction
 GCCNMF_FLAG_H_ONES = 1 << 17
 check_gcc_phat_nl = _hip.check_gcc_phat_nl        # the gccPHATNLEnabled / gccPHATNLAlpha keywords; ValueError before any device work
+check_tdoa_tracking = _hip.check_tdoa_tracking    # the tdoaTracking / localizationWindowSize keywords; ValueError before any device work
 
 
 def check_dictionary(W, F):
@@ -169,7 +170,14 @@ class GCCNMFEngine(object):
     ``gccPHATNLEnabled`` / ``gccPHATNLAlpha`` (the reference's settings, gccNMF/realtime/config.py:42-43): localise on the GCC-NONLIN
     angular spectrum sum_f 1 - tanh(alpha sqrt(max(0, 1 - Re(C e^{-j 2 pi f tau})))) of Blandin, Ozerov & Vincent (2012) instead of
     GCC-PHAT (csrc/angular_nl.hip).  The BSS-Locate toolbox writes sqrt(2 - 2 re): that is this function with alpha * sqrt(2).  Only the
-    TDOA indexes change; the GCC-NMF atom scores stay PHAT."""
+    TDOA indexes change; the GCC-NMF atom scores stay PHAT.
+
+    ``tdoaTracking`` / ``localizationWindowSize`` (talkers who move): instead of one TDOA per target for the whole
+    file, ``localize()`` also picks the ``numTargets`` peaks of every frame's windowed mean of the angular spectrogram (a centred window
+    of ``localizationWindowSize`` frames, truncated at the ends of the file) and ``masks()`` scores every atom and frame against that
+    frame's directions: ``get_tdoa_tracks()`` (batch, S, T), ``get_track_status()`` (batch, T; 1 = the frame had fewer peaks and took
+    the previous frame's set).  Target i of a frame is its i-th peak from the left: talkers whose directions cross swap outputs.
+    ``get_tdoa_indexes()`` stays the whole-file estimate.  A window of 2T - 1 frames or more gives the static path bit for bit."""
 
     def __new__(cls, n_samples=None, *args, **kwargs):
         if cls is GCCNMFEngine and kwargs.get('lengths') is not None:
@@ -181,10 +189,11 @@ class GCCNMFEngine(object):
                  microphoneSeparationInMetres=1.0, numTargets=3, dictionarySize=None, numIterations=100,
                  sparsityAlpha=0, epsilon=1e-16, seedValue=0, batch=1, windowFunction=np.hanning,
                  device='cuda:0', klnmf_flags=0, nmf_groups=None, dictionaryW=None, initialH='random', reconstruction='direct',
-                 gccPHATNLEnabled=False, gccPHATNLAlpha=2.0):
+                 gccPHATNLEnabled=False, gccPHATNLAlpha=2.0, tdoaTracking=False, localizationWindowSize=None):
         if initialH not in ('random', 'ones'):
             raise ValueError("initialH must be 'random' or 'ones'")
         self.initialH = initialH
+        self.tdoaTracking, self.localizationWindowSize = check_tdoa_tracking(tdoaTracking, localizationWindowSize, numTargets)
         self.reconstruction = check_reconstruction(reconstruction, numTargets)
         self.gccPHATNLEnabled, self.gccPHATNLAlpha = check_gcc_phat_nl(gccPHATNLEnabled, gccPHATNLAlpha)
         self.dictionaryW = None
@@ -272,6 +281,11 @@ class GCCNMFEngine(object):
             self.mean_ang = torch.zeros((B, g.Dp), dtype=torch.float64, device=dev)
             self.tdoa_idx = torch.zeros((B, g.S), dtype=torch.int32, device=dev)
             self.status = torch.zeros((B,), dtype=torch.int32, device=dev)
+            if self.tdoaTracking:
+                if T > _hip.TRACKS_MAX_FRAMES:
+                    raise ValueError('tdoaTracking takes files of fewer than 2^21 frames, got %d' % T)
+                self.tracks = torch.zeros((B, g.S, g.Tp), dtype=torch.int32, device=dev)
+                self.track_status = torch.zeros((B, g.Tp), dtype=torch.int32, device=dev)
             self.ws_scores = z(self.lib.gccnmf_scores_workspace_floats(F, T, g.S, B))
             self.scores = z(B, g.Kp, g.S * g.Tp)
             self.argmax = torch.zeros((B, g.Kp, g.Tp), dtype=torch.uint8, device=dev)
@@ -355,12 +369,18 @@ class GCCNMFEngine(object):
                                                        _ptr(self.mean_ang), _stream()), 'gccnmf_angular_spectrogram')
         _hip.check(self.lib.gccnmf_pick_tdoa_peaks(_ptr(self.mean_ang), g.D, g.Dp, g.S, self.batch, _ptr(self.tdoa_idx),
                                                    _ptr(self.status), _stream()), 'gccnmf_pick_tdoa_peaks')
+        if self.tdoaTracking:
+            # the same call in its tracks mode: reads ang itself (the Dp argument carries T), writes one index per (target, frame)
+            _hip.check(self.lib.gccnmf_pick_tdoa_peaks(_ptr(self.ang), g.D, g.T, _hip.peaks_tracks_word(g.S, self.localizationWindowSize, g.T),
+                                                       self.batch, _ptr(self.tracks), _ptr(self.track_status), _stream()),
+                       'gccnmf_pick_tdoa_peaks (tracks)')
 
     @_on_device
     def masks(self):
         g = self.g
-        _hip.check(self.lib.gccnmf_target_scores_masks(_ptr(self.CC), _ptr(self.trig), _ptr(self.tdoa_idx), _ptr(self.W), g.F, g.T,
-                                                       g.K, g.D, g.S, self.batch, _ptr(self.ws_scores), _ptr(self.scores),
+        idx, S = (self.tracks, g.S | _hip.GCCNMF_SCORES_TRACKS) if self.tdoaTracking else (self.tdoa_idx, g.S)
+        _hip.check(self.lib.gccnmf_target_scores_masks(_ptr(self.CC), _ptr(self.trig), _ptr(idx), _ptr(self.W), g.F, g.T,
+                                                       g.K, g.D, S, self.batch, _ptr(self.ws_scores), _ptr(self.scores),
                                                        _ptr(self.argmax), _stream()), 'gccnmf_target_scores_masks')
 
     @_on_device
@@ -525,7 +545,7 @@ class GCCNMFEngine(object):
                         ev_stft.record(compute)
                         download(ev_stft)
                     self.run(stft=False)
-                    self._pipe['ds'][slot].copy_(self.status)            # per-slot snapshot ON the compute stream: batch i+1's
+                    self._pipe['ds'][slot].copy_(self.file_status())     # per-slot snapshot ON the compute stream: batch i+1's
                     ev_done[slot].record(compute)                        # localize() rewrites self.status before s_out has copied it
 
                     # The download is a shader copy on this runtime (rocprofv3: __amd_rocclr_copyBuffer, 4.6 ms for 244 MB at PCIe
@@ -555,10 +575,15 @@ class GCCNMFEngine(object):
         if bad.any():
             raise ValueError('non-finite samples in the separated waveforms of file(s) %s' % np.nonzero(bad.any(axis=1))[0].tolist())
 
+    def file_status(self):
+        """int32 [batch] on the device, non-zero = the file cannot be separated: too few peaks in its mean angular spectrum -- with
+        tdoaTracking, in every frame's windowed mean (bit 1 of any frame's track status; the whole-file estimate is then only reported)."""
+        return (self.track_status[:, 0] & 2) if self.tdoaTracking else self.status
+
     @_on_device
     def check_status(self):
         self.check_chain_status()
-        st = self.status.cpu().numpy()
+        st = self.file_status().cpu().numpy()
         if st.any():
             raise ValueError('fewer than %d angular-spectrum peaks in file(s) %s' % (self.g.S, np.nonzero(st)[0].tolist()))
 
@@ -615,6 +640,18 @@ class GCCNMFEngine(object):
     def get_tdoa_indexes(self):
         return self.tdoa_idx.cpu().numpy()
 
+    def get_tdoa_tracks(self):
+        """(batch, S, T) int32: the TDOA index of target i in frame t (tdoaTracking only)."""
+        if not self.tdoaTracking:
+            raise ValueError('get_tdoa_tracks needs tdoaTracking=True')
+        return self.tracks[:, :, :self.g.T].cpu().numpy()
+
+    def get_track_status(self):
+        """(batch, T) int32: 0 = the frame had numTargets peaks, 1 = it took another frame's set, 3 = no frame of the file had enough."""
+        if not self.tdoaTracking:
+            raise ValueError('get_track_status needs tdoaTracking=True')
+        return self.track_status[:, :self.g.T].cpu().numpy()
+
     def get_scores(self):
         g = self.g
         s = self.scores.view(self.batch, g.Kp, g.S, g.Tp)[:, :g.K, :, :g.T]
@@ -643,9 +680,10 @@ class RaggedGCCNMFEngine(object):
     def __init__(self, lengths, sampleRate=16000, windowSize=1024, hopSize=256, numTDOAs=128, microphoneSeparationInMetres=1.0,
                  numTargets=3, dictionarySize=None, numIterations=100, sparsityAlpha=0, epsilon=1e-16, seedValue=0,
                  windowFunction=np.hanning, device='cuda:0', klnmf_flags=0, dictionaryW=None, initialH='random', reconstruction='direct',
-                 gccPHATNLEnabled=False, gccPHATNLAlpha=2.0):
+                 gccPHATNLEnabled=False, gccPHATNLAlpha=2.0, tdoaTracking=False, localizationWindowSize=None):
         self.reconstruction = check_reconstruction(reconstruction, numTargets)
         self.gccPHATNLEnabled, self.gccPHATNLAlpha = check_gcc_phat_nl(gccPHATNLEnabled, gccPHATNLAlpha)
+        self.tdoaTracking, self.localizationWindowSize = check_tdoa_tracking(tdoaTracking, localizationWindowSize, numTargets)
         if not torch.cuda.is_available():
             raise _hip.HipLibraryError('no ROCm device visible: the GCC-NMF HIP path has no CPU fallback')
         self.lib = _hip.lib()
@@ -660,7 +698,8 @@ class RaggedGCCNMFEngine(object):
                   microphoneSeparationInMetres=microphoneSeparationInMetres, numTargets=numTargets, dictionarySize=dictionarySize,
                   numIterations=numIterations, sparsityAlpha=sparsityAlpha, epsilon=epsilon, seedValue=seedValue,
                   windowFunction=windowFunction, device=device, klnmf_flags=klnmf_flags, dictionaryW=dictionaryW, initialH=initialH,
-                  reconstruction=reconstruction, gccPHATNLEnabled=gccPHATNLEnabled, gccPHATNLAlpha=gccPHATNLAlpha)
+                  reconstruction=reconstruction, gccPHATNLEnabled=gccPHATNLEnabled, gccPHATNLAlpha=gccPHATNLAlpha,
+                  tdoaTracking=tdoaTracking, localizationWindowSize=localizationWindowSize)     # (each file's windows end at its own T)
         # one ordinary engine per distinct length: its files (caller's indexes, ascending) are its batch
         self.files_of = {}
         for i, n in enumerate(self.lengths):
@@ -745,6 +784,16 @@ class RaggedGCCNMFEngine(object):
             for k, i in enumerate(self.files_of[n]):
                 out[i] = y[k]
         return out
+
+    def get_tdoa_tracks(self):
+        """One (S, T_i) int32 array per file, in the caller's order (tdoaTracking only)."""
+        tracks = dict((n, e.get_tdoa_tracks()) for n, e in self.sub.items())
+        return [tracks[n][self.files_of[n].index(i)] for i, n in enumerate(self.lengths)]
+
+    def get_track_status(self):
+        """One (T_i,) int32 array per file, in the caller's order (tdoaTracking only)."""
+        status = dict((n, e.get_track_status()) for n, e in self.sub.items())
+        return [status[n][self.files_of[n].index(i)] for i, n in enumerate(self.lengths)]
 
     def file(self, i):
         """(engine of file i's length, its index in that engine's batch): ``e, k = eng.file(i); e.get_WH()[0][k]``."""

@@ -228,11 +228,64 @@ def estimateTargetTDOAIndexesFromAngularSpectrum(angularSpectrum, microphoneSepa
     return sourcePeakIndexes
 
 
+def check_target_tdoa_indexes(targetTDOAIndexes, numTime):
+    """The ``targetTDOAIndexes`` argument of getTargetTDOAGCCNMFs, no device needed: the reference's 1-D list (one index per target) or
+    a 2-D (numTargets, T) array of per-frame indexes (estimateTargetTDOATracksFromAngularSpectrogram).  Returns (int32 array, tracks?)."""
+    idx = np.asarray(targetTDOAIndexes)
+    if idx.ndim not in (1, 2) or idx.size == 0 or not 1 <= idx.shape[0] <= 255:
+        raise ValueError('targetTDOAIndexes must be a list of 1 to 255 indexes or a (numTargets, T) array, got shape %s' % (idx.shape,))
+    if idx.dtype.kind not in 'iu':
+        if idx.dtype.kind != 'f' or not np.array_equal(idx, np.round(idx)):
+            raise ValueError('targetTDOAIndexes must be whole numbers')
+    if idx.ndim == 2 and idx.shape[1] != int(numTime):
+        raise ValueError('per-frame targetTDOAIndexes must have one column per frame: expected (numTargets, %d), got %s' % (numTime, idx.shape))
+    return np.ascontiguousarray(idx, dtype=np.int32), idx.ndim == 2
+
+
+def check_angular_spectrogram_for_tracks(angularSpectrogram, numTDOAs, numSources, localizationWindowSize):
+    """Arguments of estimateTargetTDOATracksFromAngularSpectrogram, no device needed.  Returns (float32 (D, T) array, S, L)."""
+    _, L = _hip.check_tdoa_tracking(True, localizationWindowSize, numSources)
+    A = np.asarray(angularSpectrogram)
+    if A.ndim != 2 or A.dtype.kind not in 'fiu' or not 3 <= A.shape[0] <= 4096 or not 1 <= A.shape[1] <= _hip.TRACKS_MAX_FRAMES:
+        raise ValueError('angularSpectrogram must be a real (numTDOAs, T) array with 3 <= numTDOAs <= 4096, got %s %s' % (A.dtype, A.shape))
+    if numTDOAs is not None and int(numTDOAs) != A.shape[0]:
+        raise ValueError('angularSpectrogram has %d rows, numTDOAs is %r' % (A.shape[0], numTDOAs))
+    return np.ascontiguousarray(A, dtype=np.float32), int(numSources), L
+
+
+def estimateTargetTDOATracksFromAngularSpectrogram(angularSpectrogram, microphoneSeparationInMetres, numTDOAs, numSources,
+                                                   localizationWindowSize):
+    """Time-varying twin of estimateTargetTDOAIndexesFromAngularSpectrum (not in the reference): for every frame t
+    the ``numSources`` largest strict local maxima of mean(angularSpectrogram[:, lo:hi], axis=-1) over the centred window lo = max(0, t -
+    L // 2), hi = min(T, t - L // 2 + L), L = ``localizationWindowSize`` frames, ascending.  A frame with fewer peaks takes the previous
+    frame's set (the frames in front of the first complete one take that one's); no complete frame at all raises ValueError.  Target i is
+    a frame's i-th peak from the left: talkers whose directions cross swap rows.  The spectrogram is taken as float32 (what
+    getAngularSpectrogram computes); the window sums are float64.  Returns an int64 (numSources, T) array -- pass it to
+    getTargetTDOAGCCNMFs as ``targetTDOAIndexes``."""
+    A, S, L = check_angular_spectrogram_for_tracks(angularSpectrogram, numTDOAs, numSources, localizationWindowSize)
+    D, T = A.shape
+    lib, dev = _hip.lib(), _device()
+    g = Geometry(2, T, 1, D, S)
+    with _staging.Scope(dev) as sc:
+        ang = sc.dev('ang', (g.Dp, g.Tp), corner=(D, T))
+        ang[:D, :T].copy_(sc.upload(A, 'A', float32))
+        res = sc.dev('tracks', (S + 1, g.Tp), torch.int32)              # rows [0..S): tracks, row S: per-frame status
+        _hip.check(lib.gccnmf_pick_tdoa_peaks(_ptr(ang), D, T, _hip.peaks_tracks_word(S, L, T), 1, res.data_ptr(),
+                                              res.data_ptr() + 4 * S * g.Tp, _stream()), 'gccnmf_pick_tdoa_peaks (tracks)')
+        out = sc.download(res[:, :T])
+    if (out[S] & 2).any():
+        raise ValueError("didn't find enough peaks in any frame in estimateTargetTDOATracksFromAngularSpectrogram")
+    return out[:S].astype(np.int64)
+
+
 def getTargetTDOAGCCNMFs(coherenceV, microphoneSeparationInMetres, numTDOAs, frequenciesInHz, targetTDOAIndexes, W, stereoH):
-    """gccNMF/gccNMFFunctions.py:118-135.  Returns (numTargets, K, T) float32."""
-    numTargets = len(targetTDOAIndexes)
+    """gccNMF/gccNMFFunctions.py:118-135.  Returns (numTargets, K, T) float32.  ``targetTDOAIndexes``: the reference's list of one
+    index per target, or a 2-D (numTargets, T) array of per-frame indexes (estimateTargetTDOATracksFromAngularSpectrogram): atom k of
+    frame t is then scored against tau[i, t]."""
     C = np.asarray(coherenceV)
     F, T = C.shape
+    targetTDOAIndexes, tracks = check_target_tdoa_indexes(targetTDOAIndexes, T)
+    numTargets = targetTDOAIndexes.shape[0]
     numChannels, K, numTime = stereoH.shape
     lib, dev = _hip.lib(), _device()
     g = Geometry(F, T, K, int(numTDOAs), numTargets)
@@ -240,10 +293,15 @@ def getTargetTDOAGCCNMFs(coherenceV, microphoneSeparationInMetres, numTDOAs, fre
     with _staging.Scope(dev) as sc:
         dC = _upload_coherence(sc, C, g)
         dW = _device_W(sc, W, g, dev)
-        dIdx = sc.upload(np.asarray([int(i) for i in targetTDOAIndexes], dtype=np.int32), 'idx')
+        if tracks:
+            dIdx = sc.dev('idx_tracks', (numTargets, g.Tp), torch.int32, corner=(numTargets, T))
+            dIdx[:, :T].copy_(sc.upload(targetTDOAIndexes, 'idx', np.int32))
+        else:
+            dIdx = sc.upload(targetTDOAIndexes, 'idx')
         ws = sc.dev('ws_scores', (lib.gccnmf_scores_workspace_floats(F, T, numTargets, 1),))
         scores = sc.dev('scores', (g.Kp, numTargets, g.Tp))
-        _hip.check(lib.gccnmf_target_scores_masks(_ptr(dC), _ptr(trig), _ptr(dIdx), _ptr(dW), F, T, K, g.D, numTargets, 1,
+        _hip.check(lib.gccnmf_target_scores_masks(_ptr(dC), _ptr(trig), _ptr(dIdx), _ptr(dW), F, T, K, g.D,
+                                                  numTargets | _hip.GCCNMF_SCORES_TRACKS if tracks else numTargets, 1,
                                                   _ptr(ws), _ptr(scores), 0, _stream()), 'gccnmf_target_scores_masks')
         out = sc.download(scores[:K, :, :T].permute(1, 0, 2), shape=(numTargets, K, T))
         sc.remember(out, 'G', dict(scores=scores), dict(S=numTargets, K=K, T=T))

@@ -32,3 +32,37 @@ def synthetic_mixture(fileIndex, numSamples=160000, sampleRate=16000, delays=(-2
 
 def synthetic_batch(firstIndex, count, numSamples=160000, sampleRate=16000):
     return np.stack([synthetic_mixture(firstIndex + i, numSamples, sampleRate) for i in range(count)])
+
+
+def moving_source_mixture(seed, numSamples=96000, sampleRate=16000, staticDelay=-25, movingDelays=(5, 30), bandHz=250.0,
+                          lowHz=250.0, highHz=6000.0, returnSources=False):
+    """A talker who changes seat: two slowly amplitude-modulated noise sources in interleaved ``bandHz``-wide bands between ``lowHz``
+    and ``highHz`` (counted from ``lowHz``, source 1 takes the even bands and source 0 the odd ones).  Source 0 stays put -- the right channel holds roll(s0,
+    staticDelay) -- and source 1 jumps at the midpoint: roll(s1, movingDelays[0]) in the first half of the file, roll(s1,
+    movingDelays[1]) in the second.  At 16 kHz, 1 m and 128 TDOAs the defaults put source 0 at index 97 and source 1 at 56 / 57, then
+    23.  Sensor noise and int16-representable float32 samples as in synthetic_mixture.  ``returnSources``: also the two sources' left-
+    channel images (2, numSamples), float64, on the mixture's scale -- what a separated left channel is scored against."""
+    rng = np.random.default_rng(20261017 + seed)
+    t = np.arange(numSamples) / float(sampleRate)
+    freqs = np.fft.rfftfreq(numSamples, 1.0 / sampleRate)
+    band = np.floor((freqs - lowHz) / bandHz).astype(int)
+    inside = (freqs >= lowHz) & (freqs < highHz)
+    half = numSamples // 2
+    sources, right = [], np.zeros(numSamples)
+    for j in range(2):
+        spectrum = np.fft.rfft(rng.standard_normal(numSamples)) * (inside & (band % 2 == 1 - j))
+        s = np.fft.irfft(spectrum, numSamples)
+        phi = rng.uniform(0, 2 * np.pi)
+        s = s * 0.5 * (1 + np.sin(2 * np.pi * (0.7 + 0.3 * j) * t + phi))
+        sources.append(s)
+        if j == 0:
+            right += np.roll(s, staticDelay)
+        else:
+            right[:half] += np.roll(s, movingDelays[0])[:half]
+            right[half:] += np.roll(s, movingDelays[1])[half:]
+    sigma = 1e-2 * np.std(sources[0] + sources[1])
+    x = np.stack([sources[0] + sources[1] + rng.normal(0, sigma, numSamples), right + rng.normal(0, sigma, numSamples)])
+    scale = 0.1 / np.max(np.abs(x))
+    pcm = np.round(x * scale * 32768).astype(np.int16)
+    x = (pcm.astype('float32') / 32768).astype(np.float32)
+    return (x, np.stack(sources) * scale) if returnSources else x

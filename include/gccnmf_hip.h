@@ -259,7 +259,26 @@ int gccnmf_angular_spectrogram(const float* CC, const float* trig, int F, int T,
 /* Peak picking on the mean angular spectrum: strict local maxima (edges excluded), keep the
  * S largest (the larger index among equal heights), ascending order.  Replaces estimateTargetTDOAIndexesFromAngularSpectrum
  * (gccNMFFunctions.py:94-116) for numSources > 0.
- *   tdoa_idx [batch][S] int32 out; status [batch] int32 out (0 ok, 1 = fewer than S peaks) */
+ *   tdoa_idx [batch][S] int32 out; status [batch] int32 out (0 ok, 1 = fewer than S peaks)
+ *
+ * Time-varying TDOA tracks (talkers who move; the offline twin of the streaming multi-target localisation) are a mode of this call, not
+ * an entry point of its own: pass GCCNMF_PEAKS_TRACKS(S, L) as S -- bit 8 and the window length L (frames, 1 <= L < 2^22) above the low
+ * byte of S -- and the call reads the angular SPECTROGRAM instead of its time mean:
+ *     gccnmf_pick_tdoa_peaks((const double*)ang, D, T, GCCNMF_PEAKS_TRACKS(S, L), batch, tracks, status, stream)
+ *   ang    [batch][round_up(D,64)][round_up(T,64)] float32, as gccnmf_angular_spectrogram wrote it (either form); the pitches follow
+ *          from D and T, so the Dp argument carries T (1 <= T < 2^21) in this mode
+ *   tracks [batch][S][Tp] int32 out, 16-byte aligned: the peak rule above applied, per frame t, to the mean of ang over the centred
+ *          window [max(0, t - L/2), min(T, t - L/2 + L)) -- float64, frames added in ascending order, divided by the window's own
+ *          length: a value depends on (t, L, T) and the file only, a file alone and in any batch give the same tracks bit for bit
+ *   status [batch][Tp] int32 out: 0 = the frame had S peaks; 1 = it had fewer and holds the set of the last complete frame before it
+ *          (frames in front of the first complete frame: that frame's set); 3 = no frame of the file had S peaks (every frame of
+ *          the file; tracks -1) -- the condition the whole-file form reports as status 1
+ *   Target i of a frame is its i-th peak from the left, as in the whole-file form: two talkers whose directions cross swap outputs.
+ *   L >= 2T - 1 makes every window the whole file (constant tracks).  Frames >= T are not written.  1 <= S <= 255, batch <= 65535.
+ * Nothing above the low byte of S = the whole-file form: every call that existed before computes what it computed (S <= 255, the
+ * score stage's limit).  GCCNMF_ERR_ARG: bits above the low byte without bit 8, L = 0, a negative S, and what the plain form rejects. */
+#define GCCNMF_PEAKS_TRACKS_BIT 0x100
+#define GCCNMF_PEAKS_TRACKS(S, L) ((S) | GCCNMF_PEAKS_TRACKS_BIT | ((L) << 9))
 int gccnmf_pick_tdoa_peaks(const double* mean_ang, int D, int Dp, int S, int batch, int* tdoa_idx, int* status,
                            void* stream);
 
@@ -268,7 +287,12 @@ int gccnmf_pick_tdoa_peaks(const double* mean_ang, int D, int Dp, int S, int bat
  * getTargetTDOAGCCNMFs (gccNMFFunctions.py:118-135) + getTargetCoefficientMasks (:137-143).
  *   tdoa_idx [batch][S] device int32 (from gccnmf_pick_tdoa_peaks or uploaded)
  *   scores   [batch][Kp][S*Tp] float32 out (target i occupies columns i*Tp .. i*Tp+T-1)
- *   argmax   [batch][Kp][Tp] uint8 out;  workspace: gccnmf_scores_workspace_floats floats */
+ *   argmax   [batch][Kp][Tp] uint8 out;  workspace: gccnmf_scores_workspace_floats floats
+ * Per-frame target directions: pass S | GCCNMF_SCORES_TRACKS (the mode rides above the low byte of S, like GCCNMF_RECONSTRUCT_RATIO;
+ * any other bit there: GCCNMF_ERR_ARG) and tdoa_idx is [batch][S][Tp] int32, 16-byte aligned -- one index per (target, frame), as the
+ * tracks mode of gccnmf_pick_tdoa_peaks writes them: G_i[k,t] = Re sum_f W[f,k] C[f,t] exp(-2j pi f tau_{i,t}).  Only the steering
+ * table lookup in front of the GEMM changes (indexes are clamped to [0, D) as before); constant tracks give the bits of the plain form. */
+#define GCCNMF_SCORES_TRACKS 0x100
 long gccnmf_scores_workspace_floats(int F, int T, int S, int batch);
 int gccnmf_target_scores_masks(const float* CC, const float* trig, const int* tdoa_idx, const float* W, int F,
                                int T, int K, int D, int S, int batch, float* workspace, float* scores,
