@@ -137,6 +137,29 @@ def angular_nl_words(D, batch, alpha):
     return signed(int(D) | (bits & 0xffff0000)), signed(int(batch) | ((bits & 0xffff) << 16))
 
 
+def check_convergence(tolerance, checkEvery, numIterations):
+    """The ``tolerance`` / ``checkEvery`` keywords of the engines, inferKLNMFCoefficients and performKLNMFUntilConverged, and the
+    iteration count they cap; no device needed.  ``tolerance``: None (a fixed number of iterations) or a finite float with
+    0 < tolerance < 1, the relative decrease of the KL divergence per check below which a file stops.  ``checkEvery``: iterations between
+    two checks, an integer >= 1 (checked whether or not a tolerance is given, so a bad value cannot wait for the switch).
+    ``numIterations``: with a tolerance the maximum, an integer >= 0; without one it is the fixed count and is taken as
+    ``int(numIterations)``, as it always was.  Returns (tolerance or None, checkEvery, numIterations)."""
+    import math
+    import numbers
+    if tolerance is not None:
+        if isinstance(tolerance, bool) or not isinstance(tolerance, numbers.Real) or not math.isfinite(tolerance) or not 0 < tolerance < 1:
+            raise ValueError('tolerance must be None or a finite number with 0 < tolerance < 1, got %r' % (tolerance,))
+        tolerance = float(tolerance)
+    if isinstance(checkEvery, bool) or not isinstance(checkEvery, numbers.Integral) or checkEvery < 1:
+        raise ValueError('checkEvery must be a whole number of iterations >= 1, got %r' % (checkEvery,))
+    if tolerance is None:
+        return None, int(checkEvery), int(numIterations)
+    if isinstance(numIterations, bool) or not isinstance(numIterations, numbers.Integral) or numIterations < 0:
+        raise ValueError('the number of iterations must be a whole number >= 0, got %r' % (numIterations,))
+    return tolerance, int(checkEvery), int(numIterations)
+
+
+GCCNMF_STAGE_DIVERGENCE = 7             # include/gccnmf_hip.h: gccnmf_klnmf_stage, "KL divergence of the current factors"
 GCCNMF_SCORES_TRACKS = 0x100            # include/gccnmf_hip.h: per-(target, frame) indexes in gccnmf_target_scores_masks
 TRACKS_MAX_FRAMES = (1 << 21) - 1
 

@@ -1,0 +1,38 @@
+// Generalised KL divergence of the current factors, D(V || W.H) per file: stage 7 of gccnmf_klnmf_stage (divergence.hip).
+#pragma once
+#include "common.h"
+
+// One term of D = sum V log(V / R) - V + R, from V and R = (W.H)[f][n], evaluated in float32 without the cancellation of the textbook
+// form near V = R.  With x = (V - R) / R the term is R * g(x), g(x) = (1 + x) log1p(x) - x = x^2/2 - x^3/6 + x^4/12 - ...:
+//   |x| < 1/8   the alternating series sum_{n=2..9} (-1)^n x^n / (n (n - 1)) (Horner); the first dropped term is x^10 / 90, below
+//               2^-24 of the sum -- nothing is subtracted, so a term of size R x^2 / 2 keeps its full relative precision
+//   otherwise   (1 + x) log1p(x) - x directly: g >= 0.007 there and the two parts are of size |x|, a few bits at the worst
+// V = 0 contributes R alone (the limit: no logarithm, no 0 / 0).  NaN in V or R propagates.  V > 0 with R == 0 (an underflowed
+// product; not reachable from positive factors) gives fma(inf, inf, -inf) = NaN where float64 arithmetic gives +inf: non-finite either
+// way, and a non-finite D stops nothing.
+__device__ __forceinline__ float gccnmf_kl_term(float v, float r) {
+    if (v == 0.f) return r;
+    const float x = (v - r) / r;
+    float g;
+    if (fabsf(x) < 0.125f) {
+        float p = -1.f / 72.f;
+        p = fmaf(p, x, 1.f / 56.f);
+        p = fmaf(p, x, -1.f / 42.f);
+        p = fmaf(p, x, 1.f / 30.f);
+        p = fmaf(p, x, -1.f / 20.f);
+        p = fmaf(p, x, 1.f / 12.f);
+        p = fmaf(p, x, -1.f / 6.f);
+        p = fmaf(p, x, 0.5f);
+        g = (x * x) * p;
+    } else {
+        g = fmaf(1.f + x, log1pf(x), -x);
+    }
+    return r * g;
+}
+
+// out[b] = D(V_b || W_b . H_b) for b < batch, float64.  V [batch][Fp][Np], H [batch][Kp][Np], W [batch][Fp][Kp] (sW = Fp * Kp) or one
+// shared dictionary (sW = 0).  partials: scratch, gccnmf_kl_divergence_tiles(F, N) doubles per file, s_partials doubles apart.
+// Reads only f < F, n < N, k < K of the operands' valid extent (padding may hold anything); writes partials and out only.
+int gccnmf_kl_divergence_tiles(int F, int N);
+int gccnmf_kl_divergence_launch(const float* V, const float* W, long sW, const float* H, int F, int N, int K, int Fp, int Kp, int Np,
+                                int batch, double* partials, long s_partials, double* out, hipStream_t stream);

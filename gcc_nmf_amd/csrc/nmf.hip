@@ -14,6 +14,7 @@
 #include "gemm_ring.h"
 #include "direct.h"
 #include "update_w.h"
+#include "divergence.h"
 #ifdef GCCNMF_EXPERIMENTS
 int gccnmf_launch_gemm_stream(GemmArgs a, hipStream_t stream);       // the LDS-free throughput tile (direct.hip)
 #endif
@@ -1018,7 +1019,7 @@ long gccnmf_klnmf_workspace_floats(int F, int N, int K, int batch) {
 }
 
 // One launch group of the iteration, addressable on its own so that tests and the benchmark can time /
-// check each kernel in isolation.  stage: 0 prepare | 1 K1 | 2 K2 | 3 K3 | 4 K4a | 5 K4b | 6 final H rescale
+// check each kernel in isolation.  stage: 0 prepare | 1 K1 | 2 K2 | 3 K3 | 4 K4a | 5 K4b | 6 final H rescale | 7 KL divergence of the current factors
 static int klnmf_stage(int stage, const float* V, float* W, float* H, float* workspace, const NmfGeom& g, int batch,
                        float alpha, float eps, int flags, hipStream_t s) {
     float* R = workspace;
@@ -1029,6 +1030,13 @@ static int klnmf_stage(int stage, const float* V, float* W, float* H, float* wor
     float* parts = hscale + (long)batch * g.Kp;                                   // batch == 1 only
     float* rowsum_parts = parts + GCCNMF_SPLITS * (g.sV > g.sU ? g.sV : g.sU);
     float* direct_base = batch == 1 ? rowsum_parts + GCCNMF_SPLITS * (long)g.Kp : parts;
+    if (stage == 7) {
+        // D(V || W.H) of the current (materialised) factors, divergence.hip: tile partials (float64) in each file's R block, the batch
+        // results (float64) at the start of the U region; one launch form whatever the batch or the tuning.  V, W, H are read only.
+        if (((uintptr_t)workspace & 7) != 0) return GCCNMF_ERR_ARG;          // float64 partials and results (both offsets are multiples of 4096 bytes)
+        return gccnmf_kl_divergence_launch(V, W, (flags & GCCNMF_FLAG_FIXED_W) ? 0 : g.sW, H, g.F, g.N, g.K, g.Fp, g.Kp, g.Np, batch, (double*)R, g.sV / 2,
+                                           (double*)U, s);
+    }
     const bool fused12 = fused_wh_updh(g, batch, flags);
     const int head34 = fused_whdiv_rht_files(g, batch, flags), rest34 = batch - head34;      // files on the slab launch | behind it on the two launches
     const bool fused34 = head34 > 0;
@@ -1133,7 +1141,9 @@ int gccnmf_klnmf_plan(int F, int N, int K, int batch, int flags) {
 int gccnmf_klnmf_stage(const float* V, float* W, float* H, float* workspace, int F, int N, int K, int batch,
                        float sparsity_alpha, float epsilon, int flags, int stage, void* stream) {
     GCCNMF_ENTER();
-    if (!V || !W || !H || !workspace || F < 2 || N < 1 || K < 1 || batch < 1 || (flags & GCCNMF_FIXED_BITS)) return GCCNMF_ERR_ARG;
+    // (a fixed dictionary -- one W for every file -- exists for stage 7 alone: the divergence against it; the iteration stages have no such form)
+    if (!V || !W || !H || !workspace || F < 2 || N < 1 || K < 1 || batch < 1 || ((flags & GCCNMF_FIXED_BITS) && !(stage == 7 && flags == GCCNMF_FLAG_FIXED_W)))
+        return GCCNMF_ERR_ARG;
     return klnmf_stage(stage, V, W, H, workspace, make_geom(F, N, K), batch, sparsity_alpha, epsilon, flags, (hipStream_t)stream);
 }
 

@@ -50,6 +50,75 @@ def klnmf_initial_factors(F, N, K, epsilon=1e-16, seedValue=0):
     return W.astype(np.float32), H.astype(np.float32)
 
 
+class ChainHandOverError(RuntimeError):
+    """A chained KL-NMF launch of a chunk did not hand over cleanly (gccnmf_klnmf_chain_status): the run is repeated on plain launches."""
+
+
+def klnmf_divergence(lib, V, W, H, ws, F, N, K, batch, fixed=False):
+    """One stage-7 launch of gccnmf_klnmf_stage: D(V || W.H) of every file of a padded batch.  Returns the (batch,) float64 DEVICE
+    view of the result inside the workspace `ws` (valid until the workspace is used again); asynchronous.  fixed: W is one shared
+    [Fp][Kp] dictionary."""
+    Fp, Np = -(-F // 16) * 16, -(-N // 64) * 64
+    _hip.check(lib.gccnmf_klnmf_stage(_ptr(V), _ptr(W), _ptr(H), _ptr(ws), F, N, K, batch, 0.0, 0.0, GCCNMF_FLAG_FIXED_W if fixed else 0,
+                                      _hip.GCCNMF_STAGE_DIVERGENCE, _stream()), 'gccnmf_klnmf_stage (divergence)')
+    at = batch * Fp * Np
+    return ws[at:at + 2 * batch].view(torch.float64)
+
+
+def converge_klnmf(launch, divergence, factors, maxIterations, tolerance, checkEvery, failed=None):
+    """KL-NMF in chunks of ``checkEvery`` iterations until every file has converged or ``maxIterations`` is reached (plumbing: the
+    iterations and the divergence are library calls).
+
+    launch(n, first) runs n more iterations on the factors in place (repeated gccnmf_klnmf calls continue where the last one stopped);
+    divergence() returns the (batch,) float64 host array of D(V || W.H) (one synchronisation per check); factors: the device tensors,
+    batch first, that hold each file's result; failed(): the chain status after a chunk (non-zero raises ChainHandOverError).
+
+    After a chunk, file b has converged when D_prev - D_cur < tolerance * D_prev or D_cur <= 0, D_prev of the first check being the
+    divergence of the initial factors.  A RISE of D therefore stops a file too: intended for sparsityAlpha > 0, where the updates
+    minimise D + alpha * sum(H) and D alone may go up.  A non-finite D stops nothing (it surfaces through the status checks).  A
+    converged file's factors are copied aside at that check and put back at the end, while the batch goes on: its result and its
+    iteration count depend on that file alone.  Chunked and single-call runs agree to round-off only (H is materialised, H *= atom
+    norms, between chunks).  Returns (iterations (batch,) int64, trace (checks + 1, batch) float64; a converged file's column
+    keeps the value it stopped at)."""
+    D_prev = np.array(divergence(), dtype=np.float64)
+    batch = D_prev.shape[0]
+    trace = [D_prev.copy()]
+    iterations = np.zeros(batch, np.int64)
+    active = np.ones(batch, bool)
+    snapshots, frozen, done = None, [], 0
+    while done < maxIterations and active.any():
+        n = min(checkEvery, maxIterations - done)
+        launch(n, done == 0)
+        done += n
+        if failed is not None and failed():
+            raise ChainHandOverError('a chained KL-NMF launch did not hand over cleanly')
+        D = np.array(divergence(), dtype=np.float64)
+        with np.errstate(invalid='ignore', over='ignore'):
+            converged = active & ((D_prev - D < tolerance * D_prev) | (D <= 0))
+        trace.append(np.where(active, D, trace[-1]))
+        iterations[converged] = done
+        active &= ~converged
+        D_prev = np.where(active, D, D_prev)
+        if converged.any() and active.any() and done < maxIterations:          # the batch goes on: keep what these files have now
+            idx = torch.as_tensor(np.nonzero(converged)[0], device=factors[0].device)
+            if snapshots is None:
+                snapshots = [torch.empty_like(t) for t in factors]
+            for snap, t in zip(snapshots, factors):
+                snap.index_copy_(0, idx, t.index_select(0, idx))
+            frozen.extend(np.nonzero(converged)[0].tolist())
+    iterations[active] = done
+    if frozen:
+        idx = torch.as_tensor(frozen, device=factors[0].device)
+        for snap, t in zip(snapshots, factors):
+            t.index_copy_(0, idx, snap.index_select(0, idx))
+    return iterations, np.stack(trace)
+
+
+def check_iterations(trace, checkEvery, maxIterations):
+    """The iteration count behind every row of a converge_klnmf trace: 0, checkEvery, 2 checkEvery, ... capped at maxIterations."""
+    return [c * checkEvery if c * checkEvery < maxIterations else maxIterations for c in range(len(trace))]
+
+
 GCCNMF_FLAG_FIXED_W = 1 << 16          # include/gccnmf_hip.h
 GCCNMF_RECONSTRUCT_RATIO = 0x100       # include/gccnmf_hip.h: the ratio-mask mode of gccnmf_reconstruct, above the low byte of S
 RECONSTRUCTIONS = ('direct', 'ratio')
@@ -79,10 +148,15 @@ def check_dictionary(W, F):
     return W
 
 
-def inferKLNMFCoefficients(V, W, numIterations, sparsityAlpha=0, epsilon=1e-16, seedValue=0, initialH='random', device='cuda:0'):
+def inferKLNMFCoefficients(V, W, numIterations, sparsityAlpha=0, epsilon=1e-16, seedValue=0, initialH='random', device='cuda:0',
+                           tolerance=None, checkEvery=10):
     """H of KL-NMF against the fixed dictionary W -- performKLNMF's H update (gccNMF/gccNMFFunctions.py:76) with W never updated, on
     the device (gccnmf_klnmf with GCCNMF_FLAG_FIXED_W).  V: (F, N) or (batch, F, N); W: (F, K).  initialH: 'random' = the H0 that
-    performKLNMF draws (klnmf_initial_factors(...)[1]), 'ones' = all ones.  Returns float32 H of shape (K, N) or (batch, K, N)."""
+    performKLNMF draws (klnmf_initial_factors(...)[1]), 'ones' = all ones.  Returns float32 H of shape (K, N) or (batch, K, N).
+
+    ``tolerance`` (None = exactly ``numIterations`` iterations): stop each file once its KL divergence has stopped falling, checked
+    every ``checkEvery`` iterations with ``numIterations`` as the maximum (converge_klnmf states the rule).  Returns (H, info) then,
+    info = {'iterations': per file (an int for a single V), 'divergences': [(iteration, D), ...] from (0, D of the initial H)}."""
     V = np.asarray(V, dtype=np.float32)
     single = V.ndim == 2
     if single:
@@ -94,6 +168,7 @@ def inferKLNMFCoefficients(V, W, numIterations, sparsityAlpha=0, epsilon=1e-16, 
     K = W.shape[1]
     if initialH not in ('random', 'ones'):
         raise ValueError("initialH must be 'random' or 'ones'")
+    tolerance, checkEvery, numIterations = _hip.check_convergence(tolerance, checkEvery, numIterations)
     lib = _hip.lib()
     dev = torch.device(device)
     g = Geometry(F, -(-N // 2), K)
@@ -109,10 +184,23 @@ def inferKLNMFCoefficients(V, W, numIterations, sparsityAlpha=0, epsilon=1e-16, 
         else:
             Hd[:, :K, :N] = torch.from_numpy(klnmf_initial_factors(F, N, K, epsilon, seedValue)[1]).to(dev)
         ws = torch.zeros(lib.gccnmf_klnmf_workspace_floats(F, N, K, B), dtype=torch.float32, device=dev)
-        _hip.check(lib.gccnmf_klnmf(_ptr(Vd), _ptr(Wd), _ptr(Hd), _ptr(ws), F, N, K, B, int(numIterations), float(sparsityAlpha),
-                                    float(epsilon), flags, _stream()), 'gccnmf_klnmf')
+
+        def launch(n, first):            # (the all-ones start is a flag of the first call only: later chunks continue from H)
+            _hip.check(lib.gccnmf_klnmf(_ptr(Vd), _ptr(Wd), _ptr(Hd), _ptr(ws), F, N, K, B, n, float(sparsityAlpha), float(epsilon),
+                                        flags if first else GCCNMF_FLAG_FIXED_W, _stream()), 'gccnmf_klnmf')
+        if tolerance is None:
+            launch(numIterations, True)
+            H = Hd[:, :K, :N].cpu().numpy()
+            return H[0] if single else H
+        if initialH == 'ones':
+            Hd[:, :K, :N] = 1            # the divergence of the initial factors reads H
+        iterations, trace = converge_klnmf(launch, lambda: klnmf_divergence(lib, Vd, Wd, Hd, ws, F, N, K, B, fixed=True).cpu().numpy(),
+                                           [Hd], numIterations, tolerance, checkEvery)
         H = Hd[:, :K, :N].cpu().numpy()
-    return H[0] if single else H
+    checks = check_iterations(trace, checkEvery, numIterations)
+    if single:
+        return H[0], dict(iterations=int(iterations[0]), divergences=[(it, float(d[0])) for it, d in zip(checks, trace)])
+    return H, dict(iterations=iterations, divergences=[(it, d.copy()) for it, d in zip(checks, trace)])
 
 
 def fft_twiddles(n_fft):
@@ -177,7 +265,14 @@ class GCCNMFEngine(object):
     of ``localizationWindowSize`` frames, truncated at the ends of the file) and ``masks()`` scores every atom and frame against that
     frame's directions: ``get_tdoa_tracks()`` (batch, S, T), ``get_track_status()`` (batch, T; 1 = the frame had fewer peaks and took
     the previous frame's set).  Target i of a frame is its i-th peak from the left: talkers whose directions cross swap outputs.
-    ``get_tdoa_indexes()`` stays the whole-file estimate.  A window of 2T - 1 frames or more gives the static path bit for bit."""
+    ``get_tdoa_indexes()`` stays the whole-file estimate.  A window of 2T - 1 frames or more gives the static path bit for bit.
+
+    ``tolerance`` / ``checkEvery``: with a tolerance, ``numIterations`` is the MAXIMUM -- ``klnmf()`` runs the
+    library in chunks of ``checkEvery`` iterations and stops each file once its KL divergence D(V || W.H) has stopped falling
+    (converge_klnmf states the rule; a rise stops a file too, which is intended for sparsityAlpha > 0).  ``get_iterations()`` (batch,),
+    ``get_divergence_trace()`` (checks + 1, batch).  A file's factors and count depend on that file alone; they agree with a
+    single call of the same count to round-off, not to the bit.  ``tolerance=None`` is the single call, bit for bit.
+    ``get_divergence()`` (batch,) float64 works after ``klnmf()`` either way: one launch (gccnmf_klnmf_stage, stage 7)."""
 
     def __new__(cls, n_samples=None, *args, **kwargs):
         if cls is GCCNMFEngine and kwargs.get('lengths') is not None:
@@ -189,10 +284,12 @@ class GCCNMFEngine(object):
                  microphoneSeparationInMetres=1.0, numTargets=3, dictionarySize=None, numIterations=100,
                  sparsityAlpha=0, epsilon=1e-16, seedValue=0, batch=1, windowFunction=np.hanning,
                  device='cuda:0', klnmf_flags=0, nmf_groups=None, dictionaryW=None, initialH='random', reconstruction='direct',
-                 gccPHATNLEnabled=False, gccPHATNLAlpha=2.0, tdoaTracking=False, localizationWindowSize=None):
+                 gccPHATNLEnabled=False, gccPHATNLAlpha=2.0, tdoaTracking=False, localizationWindowSize=None, tolerance=None, checkEvery=10):
         if initialH not in ('random', 'ones'):
             raise ValueError("initialH must be 'random' or 'ones'")
         self.initialH = initialH
+        self.tolerance, self.checkEvery, numIterations = _hip.check_convergence(tolerance, checkEvery, numIterations)
+        self.iterations_used = self.divergence_trace = None
         self.tdoaTracking, self.localizationWindowSize = check_tdoa_tracking(tdoaTracking, localizationWindowSize, numTargets)
         self.reconstruction = check_reconstruction(reconstruction, numTargets)
         self.gccPHATNLEnabled, self.gccPHATNLAlpha = check_gcc_phat_nl(gccPHATNLEnabled, gccPHATNLAlpha)
@@ -326,21 +423,80 @@ class GCCNMFEngine(object):
 
     @_on_device
     def klnmf(self):
-        g = self.g
+        """KL-NMF of the batch from the initial factors: ``numIterations`` iterations in one call, or -- with a tolerance -- in chunks
+        of ``checkEvery`` until every file has converged (at most ``numIterations``)."""
+        if self.tolerance is None:
+            self._klnmf_start()
+            self._klnmf_iterate(self.iters, True)
+            return
+        for attempt in range(2):
+            self._klnmf_start()
+            if self.dictionaryW is not None and self.initialH == 'ones':
+                self.H[:, :self.g.K, :self.g.N] = 1                 # the divergence of the initial factors reads H
+            try:
+                self.iterations_used, self.divergence_trace = converge_klnmf(
+                    self._klnmf_iterate, lambda: self._divergence().cpu().numpy(), [self.H] if self.dictionaryW is not None else [self.W, self.H],
+                    self.iters, self.tolerance, self.checkEvery, failed=self.chain_failed)
+                return
+            except ChainHandOverError:
+                if attempt:
+                    raise
+                import warnings
+                warnings.warn('gcc_nmf_amd: a chained KL-NMF launch did not hand over cleanly; this process falls back to the plain launches '
+                              '(gccnmf_set_tuning(21, 0)) and repeats the batch', RuntimeWarning)
+                _hip.check(self.lib.gccnmf_set_tuning(21, 0), 'gccnmf_set_tuning')
+
+    def _klnmf_start(self):
+        """The initial factors into W and H (a fixed dictionary with the all-ones start needs none: H is then output only)."""
         if self.dictionaryW is not None:
-            flags = GCCNMF_FLAG_FIXED_W
-            if self.initialH == 'ones':
-                flags |= GCCNMF_FLAG_H_ONES                         # H is output only: no H0 broadcast
-            else:
+            if self.initialH != 'ones':
                 self.H.copy_(self.H0.unsqueeze(0).expand_as(self.H))
-            _hip.check(self.lib.gccnmf_klnmf(_ptr(self.V), _ptr(self.W0), _ptr(self.H), _ptr(self.ws_nmf), g.F, g.N, g.K, self.batch,
-                                             self.iters, self.alpha, self.eps, flags, _stream()), 'gccnmf_klnmf')
             return
         self.W.copy_(self.W0.unsqueeze(0).expand_as(self.W))
         self.H.copy_(self.H0.unsqueeze(0).expand_as(self.H))
+
+    def _divergence(self):
+        """(batch,) float64 on the device: stage 7 per file group, each in its own workspace (a group's status words sit at the end of
+        its own slice)."""
+        g = self.g
+        per = self.batch // self.nmf_groups
+        ws_per = self.ws_nmf.numel() // self.nmf_groups
+        fixed = self.dictionaryW is not None
+        out = [klnmf_divergence(self.lib, self.V[i * per], self.W0 if fixed else self.W[i * per], self.H[i * per], self.ws_nmf[i * ws_per:],
+                                g.F, g.N, g.K, per, fixed) for i in range(self.nmf_groups)]
+        return out[0] if len(out) == 1 else torch.cat(out)
+
+    @_on_device
+    def get_divergence(self):
+        """(batch,) float64: D(V || W.H) of the factors as they are now (after klnmf()); one launch and a download."""
+        return self._divergence().cpu().numpy()
+
+    def get_iterations(self):
+        """(batch,) int64: the iterations each file ran (the check at which it converged, else numIterations).  Needs a tolerance."""
+        if self.tolerance is None or self.iterations_used is None:
+            raise ValueError('get_iterations needs tolerance= and a klnmf() run')
+        return self.iterations_used.copy()
+
+    def get_divergence_trace(self):
+        """(checks + 1, batch) float64: each file's divergence at iteration 0 and at every check; a converged file's column keeps the
+        value it stopped at.  Needs a tolerance."""
+        if self.tolerance is None or self.divergence_trace is None:
+            raise ValueError('get_divergence_trace needs tolerance= and a klnmf() run')
+        return self.divergence_trace.copy()
+
+    def _klnmf_iterate(self, iters, first):
+        """``iters`` more iterations on W and H in place, as the library chooses to launch them (first: the first call of a run)."""
+        g = self.g
+        if self.dictionaryW is not None:
+            flags = GCCNMF_FLAG_FIXED_W
+            if self.initialH == 'ones' and first:
+                flags |= GCCNMF_FLAG_H_ONES                         # H is output only: no H0 broadcast
+            _hip.check(self.lib.gccnmf_klnmf(_ptr(self.V), _ptr(self.W0), _ptr(self.H), _ptr(self.ws_nmf), g.F, g.N, g.K, self.batch,
+                                             iters, self.alpha, self.eps, flags, _stream()), 'gccnmf_klnmf')
+            return
         if self.nmf_groups == 1:
             _hip.check(self.lib.gccnmf_klnmf(_ptr(self.V), _ptr(self.W), _ptr(self.H), _ptr(self.ws_nmf), g.F, g.N, g.K, self.batch,
-                                             self.iters, self.alpha, self.eps, self.klnmf_flags, _stream()), 'gccnmf_klnmf')
+                                             iters, self.alpha, self.eps, self.klnmf_flags, _stream()), 'gccnmf_klnmf')
             return
         main = torch.cuda.current_stream(self.device)
         ready = torch.cuda.Event()
@@ -355,7 +511,7 @@ class GCCNMFEngine(object):
             # partial last round overlaps the other group's kernels (all-half-height tiles, which win for a 32-file launch ALONE,
             # lose here: 152.4 k vs 155.4 k frames/s)
             _hip.check(self.lib.gccnmf_klnmf(_ptr(self.V[b0]), _ptr(self.W[b0]), _ptr(self.H[b0]), _ptr(self.ws_nmf[i * ws_per:]), g.F, g.N,
-                                             g.K, per, self.iters, self.alpha, self.eps, self.klnmf_flags | 4 | (self.nmf_groups << 8), st.cuda_stream), 'gccnmf_klnmf')
+                                             g.K, per, iters, self.alpha, self.eps, self.klnmf_flags | 4 | (self.nmf_groups << 8), st.cuda_stream), 'gccnmf_klnmf')
             done = torch.cuda.Event()
             done.record(st)
             main.wait_event(done)
@@ -680,7 +836,8 @@ class RaggedGCCNMFEngine(object):
     def __init__(self, lengths, sampleRate=16000, windowSize=1024, hopSize=256, numTDOAs=128, microphoneSeparationInMetres=1.0,
                  numTargets=3, dictionarySize=None, numIterations=100, sparsityAlpha=0, epsilon=1e-16, seedValue=0,
                  windowFunction=np.hanning, device='cuda:0', klnmf_flags=0, dictionaryW=None, initialH='random', reconstruction='direct',
-                 gccPHATNLEnabled=False, gccPHATNLAlpha=2.0, tdoaTracking=False, localizationWindowSize=None):
+                 gccPHATNLEnabled=False, gccPHATNLAlpha=2.0, tdoaTracking=False, localizationWindowSize=None, tolerance=None, checkEvery=10):
+        self.tolerance, self.checkEvery, numIterations = _hip.check_convergence(tolerance, checkEvery, numIterations)
         self.reconstruction = check_reconstruction(reconstruction, numTargets)
         self.gccPHATNLEnabled, self.gccPHATNLAlpha = check_gcc_phat_nl(gccPHATNLEnabled, gccPHATNLAlpha)
         self.tdoaTracking, self.localizationWindowSize = check_tdoa_tracking(tdoaTracking, localizationWindowSize, numTargets)
@@ -699,7 +856,8 @@ class RaggedGCCNMFEngine(object):
                   numIterations=numIterations, sparsityAlpha=sparsityAlpha, epsilon=epsilon, seedValue=seedValue,
                   windowFunction=windowFunction, device=device, klnmf_flags=klnmf_flags, dictionaryW=dictionaryW, initialH=initialH,
                   reconstruction=reconstruction, gccPHATNLEnabled=gccPHATNLEnabled, gccPHATNLAlpha=gccPHATNLAlpha,
-                  tdoaTracking=tdoaTracking, localizationWindowSize=localizationWindowSize)     # (each file's windows end at its own T)
+                  tdoaTracking=tdoaTracking, localizationWindowSize=localizationWindowSize,     # (each file's windows end at its own T)
+                  tolerance=tolerance, checkEvery=checkEvery)
         # one ordinary engine per distinct length: its files (caller's indexes, ascending) are its batch
         self.files_of = {}
         for i, n in enumerate(self.lengths):
@@ -712,7 +870,8 @@ class RaggedGCCNMFEngine(object):
         with torch.cuda.device(self.device):
             z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=self.device)
             self.ragged = None
-            if len(self.sub) > 1 and dictionaryW is None:       # a fixed dictionary: each length's engine runs its own one-launch call
+            # a fixed dictionary: each length's engine runs its own one-launch call; a tolerance: each length's files converge as a batch of their own
+            if len(self.sub) > 1 and dictionaryW is None and self.tolerance is None:
                 import ctypes
                 ws = self.lib.gccnmf_klnmf_ragged_workspace_floats(g.F, g.N, g.K, self.batch)
                 if ws > 0:
@@ -784,6 +943,22 @@ class RaggedGCCNMFEngine(object):
             for k, i in enumerate(self.files_of[n]):
                 out[i] = y[k]
         return out
+
+    def _per_file(self, values):
+        return [values[n][self.files_of[n].index(i)] for i, n in enumerate(self.lengths)]
+
+    def get_divergence(self):
+        """(batch,) float64 in the caller's order: D(V || W.H) of every file's factors (after klnmf())."""
+        return np.array(self._per_file(dict((n, e.get_divergence()) for n, e in self.sub.items())), dtype=np.float64)
+
+    def get_iterations(self):
+        """(batch,) int64 in the caller's order: the iterations each file ran.  Needs a tolerance."""
+        return np.array(self._per_file(dict((n, e.get_iterations()) for n, e in self.sub.items())), dtype=np.int64)
+
+    def get_divergence_trace(self):
+        """One (checks_i + 1,) float64 array per file, in the caller's order (the files of each length run, and are checked, as a batch
+        of their own).  Needs a tolerance."""
+        return self._per_file(dict((n, e.get_divergence_trace().T) for n, e in self.sub.items()))
 
     def get_tdoa_tracks(self):
         """One (S, T_i) int32 array per file, in the caller's order (tdoaTracking only)."""

@@ -100,8 +100,19 @@ def performKLNMF(V, dictionarySize, numIterations, sparsityAlpha, epsilon=1e-16,
     lib, dev = _hip.lib(), _device()
     if N > LARGE_N_COLUMNS:
         return _performKLNMF_column_blocks(V, K, int(numIterations), float(sparsityAlpha), float(epsilon), seedValue, dev)
-    g = Geometry(F, 1, K)
-    Np = -(-N // 64) * 64
+    init = _klnmf_initial_factors(F, N, K, epsilon, seedValue, dev)
+    with _staging.Scope(dev) as sc:
+        dV, dW, dH, ws = _klnmf_buffers(sc, lib, V, K, init)
+        _hip.check(lib.gccnmf_klnmf(_ptr(dV), _ptr(dW), _ptr(dH), _ptr(ws), F, N, K, 1, int(numIterations),
+                                    float(sparsityAlpha), float(epsilon), 0, _stream()), 'gccnmf_klnmf')
+        W = sc.remember(sc.download(dW[:F, :K]), 'W', dict(W=dW), dict(F=F, K=K))
+        H = sc.download(dH[:K, :N])
+    return W, H
+
+
+def _klnmf_initial_factors(F, N, K, epsilon, seedValue, dev):
+    """Device images of performKLNMF's initial W and H (gccNMF/gccNMFFunctions.py:70-73), with the reference's side effect on the
+    GLOBAL generator."""
     # The initial factors depend on (seedValue, F, K, N, epsilon) only, and so does the state the reference leaves the GLOBAL generator
     # in (seeded, advanced by F*K + K*N draws).  Drawn once per shape: later calls copy the device images and put the generator into
     # that same state (1.8 M MT19937 draws and 7 MB of upload are 5 ms of a 15 ms call at K = 1024).
@@ -118,20 +129,84 @@ def performKLNMF(V, dictionarySize, numIterations, sparsityAlpha, epsilon=1e-16,
             _KLNMF_INIT[init_key] = init
     else:
         np.random.set_state(init['state'])
+    return init
+
+
+def _klnmf_buffers(sc, lib, V, K, init):
+    """The padded device buffers of one batch-1 KL-NMF call, loaded with V and the initial factors: (dV, dW, dH, workspace)."""
+    F, N = V.shape
+    g = Geometry(F, 1, K)
+    Np = -(-N // 64) * 64
+    # pooled padded buffers: the padding is zero and stays zero (uploads write the corner, the kernels never write beyond it)
+    dV = sc.dev('V', (g.Fp, Np), corner=(F, N))
+    dW = sc.dev('W', (g.Fp, g.Kp), corner=(F, K))
+    dH = sc.dev('H', (g.Kp, Np), corner=(K, N))
+    ws = sc.dev('ws_klnmf', (lib.gccnmf_klnmf_workspace_floats(F, N, K, 1),))
+    dV[:F, :N].copy_(sc.upload(V, 'V', float32))
+    dW[:F, :K].copy_(init['W'])
+    dH[:K, :N].copy_(init['H'])
+    return dV, dW, dH, ws
+
+
+def performKLNMFUntilConverged(V, dictionarySize, maxIterations, sparsityAlpha, tolerance=1e-4, checkEvery=10, epsilon=1e-16, seedValue=0):
+    """performKLNMF with a stopping rule (not in the reference, which runs a fixed count and never evaluates its objective; DESIGN
+    section 2a): the same initial W and H (and the same side effect on the global generator), the same updates, run in chunks of
+    ``checkEvery`` iterations -- the last one shorter where ``maxIterations`` cuts it -- with the KL divergence
+    D(V || W.H) = sum V log(V / WH) - V + WH (a zero of V contributes WH alone) evaluated on the GPU after each.  The run stops at the
+    first check with D_prev - D < tolerance * D_prev or D <= 0, D_prev of the first check being the divergence of the initial factors.
+    A RISE of D stops the run too: that is intended for sparsityAlpha > 0, where the updates minimise D + alpha * sum(H) and D alone
+    may go up.  A non-finite D stops nothing.  Returns (W, H, info), info = {'iterations': n, 'divergences': [(iteration, D), ...]}
+    starting with (0, D of the initial factors).  W and H agree with performKLNMF(V, dictionarySize, n, ...) to round-off, not to the
+    bit (H is rescaled by the atom norms in place between chunks instead of lazily).  One call's worth of columns only: V of more
+    than LARGE_N_COLUMNS columns raises NotImplementedError."""
+    tolerance, checkEvery, maxIterations = _hip.check_convergence(tolerance, checkEvery, maxIterations)
+    if tolerance is None:
+        raise ValueError('performKLNMFUntilConverged needs a tolerance; performKLNMF runs a fixed number of iterations')
+    from .engine import check_iterations, converge_klnmf, klnmf_divergence
+    V = np.asarray(V)
+    F, N = V.shape
+    K = int(dictionarySize)
+    if N > LARGE_N_COLUMNS:
+        raise NotImplementedError('performKLNMFUntilConverged runs V as one call: at most %d columns, got %d (performKLNMF takes such a V '
+                                  'as column blocks, without a stopping rule)' % (LARGE_N_COLUMNS, N))
+    lib, dev = _hip.lib(), _device()
+    init = _klnmf_initial_factors(F, N, K, epsilon, seedValue, dev)
     with _staging.Scope(dev) as sc:
-        # pooled padded buffers: the padding is zero and stays zero (uploads write the corner, the kernels never write beyond it)
+        dV, dW, dH, ws = _klnmf_buffers(sc, lib, V, K, init)
+
+        def launch(n, first):
+            _hip.check(lib.gccnmf_klnmf(_ptr(dV), _ptr(dW), _ptr(dH), _ptr(ws), F, N, K, 1, n, float(sparsityAlpha), float(epsilon), 0,
+                                        _stream()), 'gccnmf_klnmf')
+        iterations, trace = converge_klnmf(launch, lambda: klnmf_divergence(lib, dV, dW, dH, ws, F, N, K, 1).cpu().numpy(),
+                                           [dW.unsqueeze(0), dH.unsqueeze(0)], maxIterations, tolerance, checkEvery)
+        W = sc.remember(sc.download(dW[:F, :K]), 'W', dict(W=dW), dict(F=F, K=K))
+        H = sc.download(dH[:K, :N])
+    checks = check_iterations(trace, checkEvery, maxIterations)      # (this module's min / max are NumPy's: the reference's star import)
+    return W, H, dict(iterations=int(iterations[0]), divergences=[(it, float(d[0])) for it, d in zip(checks, trace)])
+
+
+def getKLDivergence(V, W, H):
+    """The objective of performKLNMF, which the reference never evaluates: D(V || W.H) = sum V log(V / WH) - V + WH over every element
+    (a zero of V contributes WH alone), as a float64 scalar.  W.H runs in float32 on the matrix cores and is never stored; the terms
+    are summed in float64 (gccnmf_klnmf_stage, stage 7: csrc/divergence.hip).  V (F, N), W (F, K), H (K, N)."""
+    V, H = np.asarray(V), np.asarray(H)
+    if V.ndim != 2 or np.ndim(W) != 2 or H.ndim != 2 or np.shape(W) != (V.shape[0], H.shape[0]) or H.shape[1] != V.shape[1]:
+        raise ValueError('getKLDivergence takes V (F, N), W (F, K) and H (K, N), got %s, %s, %s' % (V.shape, np.shape(W), H.shape))
+    from .engine import klnmf_divergence
+    F, N = V.shape
+    K = H.shape[0]
+    lib, dev = _hip.lib(), _device()
+    g = Geometry(F, 1, K)
+    Np = -(-N // 64) * 64
+    with _staging.Scope(dev) as sc:
         dV = sc.dev('V', (g.Fp, Np), corner=(F, N))
-        dW = sc.dev('W', (g.Fp, g.Kp), corner=(F, K))
         dH = sc.dev('H', (g.Kp, Np), corner=(K, N))
         ws = sc.dev('ws_klnmf', (lib.gccnmf_klnmf_workspace_floats(F, N, K, 1),))
         dV[:F, :N].copy_(sc.upload(V, 'V', float32))
-        dW[:F, :K].copy_(init['W'])
-        dH[:K, :N].copy_(init['H'])
-        _hip.check(lib.gccnmf_klnmf(_ptr(dV), _ptr(dW), _ptr(dH), _ptr(ws), F, N, K, 1, int(numIterations),
-                                    float(sparsityAlpha), float(epsilon), 0, _stream()), 'gccnmf_klnmf')
-        W = sc.remember(sc.download(dW[:F, :K]), 'W', dict(W=dW), dict(F=F, K=K))
-        H = sc.download(dH[:K, :N])
-    return W, H
+        dH[:K, :N].copy_(sc.upload(H, 'H', float32))
+        dW = _device_W(sc, W, g, dev)                      # the image behind W if performKLNMF returned it (resident mode)
+        out = sc.download(klnmf_divergence(lib, dV, dW, dH, ws, F, N, K, 1))
+    return np.float64(out[0])
 
 
 _KLNMF_INIT = {}             # (F, N, K, seed, epsilon, device) -> device images of the initial factors + the generator state, a few shapes

@@ -48,7 +48,7 @@ extern "C" {
                                           * the result on exit (h <- h o W^T(v / Wh) / (colsum W + alpha + eps), every iteration of the call in one
                                           * launch, csrc/nmf_fixed.hip).  V, workspace, sparsity_alpha and epsilon as for the blind call; the
                                           * chain-status words are left cleared.  F <= 2049 and K <= 1024, else GCCNMF_ERR_UNSUPPORTED.  Not
-                                          * combinable with bits 0-15 (GCCNMF_ERR_ARG); gccnmf_klnmf_stage / gccnmf_klnmf_ragged reject it */
+                                          * combinable with bits 0-15 (GCCNMF_ERR_ARG); gccnmf_klnmf_stage (but for its stage 7) / gccnmf_klnmf_ragged reject it */
 #define GCCNMF_FLAG_H_ONES (1 << 17)    /* with GCCNMF_FLAG_FIXED_W only (else GCCNMF_ERR_ARG): the initial H is all ones (the streaming
                                           * processor's h0 = 1); H is output only and is not read */
 
@@ -168,7 +168,22 @@ int gccnmf_klnmf_plan(int F, int N, int K, int batch, int flags);
 
 /* One launch group of the iteration on its own (per-kernel tests and per-kernel timing in bench.py).
  * stage: 0 prepare (zero R, colsum W, scale = 1) | 1 R=V/(W.(s*H)) | 2 H update | 3 R=V/(W.H) |
- *        4 U=R.H^T + rowsum H | 5 W update + atom normalisation | 6 materialise H *= s */
+ *        4 U=R.H^T + rowsum H | 5 W update + atom normalisation | 6 materialise H *= s |
+ *        7 KL divergence of the current factors (csrc/divergence.hip), per file b
+ *              D_b = sum_{f < F, n < N} V log(V / R) - V + R,   R = W.H in f32 on the matrix cores (never stored),
+ *          a V = 0 element contributing R alone; each term is formed in float32 as R g((V - R) / R), g(x) = (1 + x) log1p(x) - x (its
+ *          series for |x| < 1/8: no cancellation near V = R), and summed in float64 from the tile on, in an order fixed by (F, N): no
+ *          atomics, D_b is bit for bit the same for a file alone, in any batch, and from run to run.  Valid whenever W and H are
+ *          materialised -- before a gccnmf_klnmf call or after a complete one, not between stages 1-6; V, W and H are read only, and only
+ *          inside f < F, n < N, k < K (their padding is not read into the result).  The result is `batch` float64 values at
+ *              (const double*)(workspace + (size_t)batch * Fp * Np)          -- the start of the U region: a multiple of 4096 bytes from
+ *          `workspace`, hence 16-byte aligned whenever the workspace is (it must be 8-byte aligned, else GCCNMF_ERR_ARG); the tile partials, ceil(F / 128) * ceil(N / 64) float64 per
+ *          file, go to the head of each file's [Fp][Np] block of the R region (workspace + b * Fp * Np).  Both are scratch of the
+ *          iteration, far below the chain counters and status words at the workspace's end, which stage 7 neither reads nor writes;
+ *          because R's zero padding is overwritten, stage 0 (every gccnmf_klnmf call starts with it) must run before further stages
+ *          1-6.  sparsity_alpha, epsilon and bits 0-15 of flags are ignored.  flags = GCCNMF_FLAG_FIXED_W (exactly) is accepted by
+ *          this stage alone: W is then ONE [Fp][Kp] dictionary shared by every file, as in the fixed-dictionary call.
+ * Any other stage number: GCCNMF_ERR_ARG. */
 int gccnmf_klnmf_stage(const float* V, float* W, float* H, float* workspace, int F, int N, int K, int batch,
                        float sparsity_alpha, float epsilon, int flags, int stage, void* stream);
 
