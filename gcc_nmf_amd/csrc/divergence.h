@@ -7,12 +7,18 @@
 //   |x| < 1/8   the alternating series sum_{n=2..9} (-1)^n x^n / (n (n - 1)) (Horner); the first dropped term is x^10 / 90, below
 //               2^-24 of the sum -- nothing is subtracted, so a term of size R x^2 / 2 keeps its full relative precision
 //   otherwise   (1 + x) log1p(x) - x directly: g >= 0.007 there and the two parts are of size |x|, a few bits at the worst
-// V = 0 contributes R alone (the limit: no logarithm, no 0 / 0).  NaN in V or R propagates.  V > 0 with R == 0 (an underflowed
+// V = 0 contributes R alone (the limit: no logarithm, no 0 / 0).  0 < V < R * 2^-24 or so (a silent bin under the random initial factors):
+// V - R rounds to -R, x to -1 exactly, and (1 + x) log1p(x) would be 0 * -inf = NaN; the term is then R + V (log(V / R) - 1) -- R alone once
+// V / R is below the smallest normal number (the rest is below 2^-119 of R).  NaN in V or R propagates.  V > 0 with R == 0 (an underflowed
 // product; not reachable from positive factors) gives fma(inf, inf, -inf) = NaN where float64 arithmetic gives +inf: non-finite either
 // way, and a non-finite D stops nothing.
 __device__ __forceinline__ float gccnmf_kl_term(float v, float r) {
     if (v == 0.f) return r;
     const float x = (v - r) / r;
+    if (x <= -1.f) {
+        const float q = v / r;
+        return q >= 1.17549435e-38f ? fmaf(v, logf(q) - 1.f, r) : r;
+    }
     float g;
     if (fabsf(x) < 0.125f) {
         float p = -1.f / 72.f;

@@ -306,8 +306,9 @@ __global__ __launch_bounds__(256) void nmf_update_w_onepass_kernel(float* __rest
 
 static int launch_update_w(float* W, const float* U, const float* rowsumH, float* colsumW, float* hscale, int F, int Fp, int K,
                            int Kp, long sW, long sU, long sVec, long sRowsum, int batch, hipStream_t s, int nsplit = 1,
-                           long sSplitU = 0, long sSplitR = 0, float* Wt = nullptr, long sWt = 0, int ldwt = 0) {
-    if ((long)batch * (Kp / 64) < 256 && gccnmf_tune_ring && F <= 64 * 9 && (nsplit == 1 || nsplit == 2 || nsplit == 4)) {
+                           long sSplitU = 0, long sSplitR = 0, float* Wt = nullptr, long sWt = 0, int ldwt = 0, int groups = 1) {
+    const long sized = (long)batch * groups;           // files of every group that runs this launch side by side: the kernel is chosen for all of them
+    if (sized * (Kp / 64) < 256 && gccnmf_tune_ring && F <= 64 * 9 && (nsplit == 1 || nsplit == 2 || nsplit == 4)) {
         // 16 atoms per workgroup (64-byte row segments); 8 (twice the workgroups, 32-byte segments) measured slower: 13.0 vs 11.4 us for one
         // file at K = 1024 -- kept selectable for experiments (tuning key 1 = 64)
 #define GCCNMF_ONEPASS(AT_, NS_) hipLaunchKernelGGL((nmf_update_w_onepass_kernel<AT_, NS_>), dim3(batch * (Kp / AT_)), dim3(256), 0, s, W, U, rowsumH, \
@@ -316,7 +317,7 @@ static int launch_update_w(float* W, const float* U, const float* rowsumH, float
         // short dictionaries at batch scale (64 files, K = 128: the launch between the two fused GEMM launches): 32 atoms per workgroup =
         // whole 128-byte lines per row and workgroup -- with 16 atoms every line of W and U is fetched by two workgroups (17 us for 51 MB).
         // Only for K <= 128, where the launch forms follow the batch size anyway (a file's bits are batch-independent for K > 128).
-        const bool wide = !narrow && nsplit == 1 && !Wt && K <= 128 && (long)batch * (Kp / 32) >= 256 && gccnmf_tune_wide_update_w;
+        const bool wide = !narrow && nsplit == 1 && !Wt && K <= 128 && sized * (Kp / 32) >= 256 && gccnmf_tune_wide_update_w;
         if (wide) {
             GCCNMF_ONEPASS(32, 1);
         } else if (narrow) {
@@ -332,7 +333,7 @@ static int launch_update_w(float* W, const float* U, const float* rowsumH, float
         GCCNMF_CHECK_LAUNCH();
         return GCCNMF_OK;
     }
-    if ((long)batch * (Kp / 64) >= 256) {
+    if (sized * (Kp / 64) >= 256) {
         hipLaunchKernelGGL(nmf_update_w_kernel<64>, dim3(batch * (Kp / 64)), dim3(256), 0, s, W, U, rowsumH, colsumW, hscale, F, Fp, K,
                            Kp, sW, sU, sVec, sRowsum, nsplit, sSplitU, sSplitR);
     } else {
@@ -387,7 +388,8 @@ __global__ __launch_bounds__(256) void nmf_reduce_files_kernel(const float* __re
 static bool small_batch_tile(const GemmArgs& a) {
     if (a.M <= 128 || gccnmf_tune_tile_policy == 1) return false;
     if (gccnmf_tune_tile_policy == 2) return true;
-    const long tall_tiles = (long)a.batch * gccnmf_ceil_div(a.M, 512) * gccnmf_ceil_div(a.N, 64);
+    // (file groups that run side by side -- a.concurrent of them -- are sized together: a file's tile does not depend on how the batch was split)
+    const long tall_tiles = (long)a.batch * (a.concurrent > 1 ? a.concurrent : 1) * gccnmf_ceil_div(a.M, 512) * gccnmf_ceil_div(a.N, 64);
     return tall_tiles < 256;
 }
 
@@ -451,7 +453,7 @@ static int launch_wh_div(const NmfGeom& g, const float* V, const float* W, long 
     a.A = W; a.sA = sW; a.lda = g.Kp; a.a_clamp = g.Fp - 1;
     a.B = H; a.sB = g.sH; a.ldb = g.ld; a.b_clamp = g.Np - 4;
     a.M = g.Fm; a.N = g.N; a.Kd = g.K;
-    a.batch = batch; a.xcd_affine = xcd & 1; a.concurrent = (xcd >> 1) & 1;
+    a.batch = batch; a.xcd_affine = xcd & 1; a.concurrent = xcd >> 1;
     a.bscale = hscale; a.s_bscale = sScale;
     a.tail_row = g.F - 1;
     a.C = R; a.sC = g.sV; a.ldc = g.ld;
@@ -472,7 +474,7 @@ static int launch_update_h(const NmfGeom& g, const float* W, long sW, const floa
         a.ktailA = W + (long)(g.F - 1) * g.Kp; a.s_ktailA = sW;
         a.ktailB = R + (long)(g.F - 1) * g.ld; a.s_ktailB = g.sV;
     }
-    a.batch = batch; a.xcd_affine = xcd & 1; a.concurrent = (xcd >> 1) & 1;
+    a.batch = batch; a.xcd_affine = xcd & 1; a.concurrent = xcd >> 1;
     a.C = H; a.sC = g.sH; a.ldc = g.ld;
     a.E1 = hscale; a.sE1 = sScale;
     a.E2 = colsumW; a.sE2 = sVec;
@@ -487,7 +489,7 @@ static int launch_rht(const NmfGeom& g, const float* R, const float* H, float* U
     a.A = R; a.sA = g.sV; a.lda = g.ld; a.a_clamp = g.Fp - 1;
     a.B = H; a.sB = g.sH; a.ldb = g.ld; a.b_clamp = g.Kp - 1;
     a.M = g.Fm; a.N = g.K; a.Kd = g.N;
-    a.batch = batch; a.xcd_affine = xcd & 1; a.concurrent = (xcd >> 1) & 1;
+    a.batch = batch; a.xcd_affine = xcd & 1; a.concurrent = xcd >> 1;
     a.tail_row = g.F - 1;
     a.rowsumB = rowsumH; a.s_rowsumB = g.Kp;
     a.C = U; a.sC = g.sU; a.ldc = g.Kp;
@@ -495,10 +497,10 @@ static int launch_rht(const NmfGeom& g, const float* R, const float* H, float* U
 }
 
 // W = normalise(W * (R.H^T) / rowsumH), colsumW, hscale -- K4a and K4b in one launch (tall tile, all F rows in one workgroup)
-static bool can_fuse_w_update(const NmfGeom& g, int batch) {
+static bool can_fuse_w_update(const NmfGeom& g, int batch, int groups = 1) {
     // the fused epilogue needs the tall tile; tiny launches prefer the small-batch tile and the two-launch form
     if (g.Fm <= 128 || g.Fm > 512 || gccnmf_tune_tile_policy == 2) return false;
-    return gccnmf_tune_tile_policy == 1 || (long)batch * gccnmf_ceil_div(g.K, 64) >= 256;
+    return gccnmf_tune_tile_policy == 1 || (long)batch * groups * gccnmf_ceil_div(g.K, 64) >= 256;
 }
 
 static int launch_rht_update_w(const NmfGeom& g, const float* R, const float* H, float* W, float* colsumW, float* hscale, int batch,
@@ -507,7 +509,7 @@ static int launch_rht_update_w(const NmfGeom& g, const float* R, const float* H,
     a.A = R; a.sA = g.sV; a.lda = g.ld; a.a_clamp = g.Fp - 1;
     a.B = H; a.sB = g.sH; a.ldb = g.ld; a.b_clamp = g.Kp - 1;
     a.M = g.Fm; a.N = g.K; a.Kd = g.N;
-    a.batch = batch; a.xcd_affine = xcd & 1; a.concurrent = (xcd >> 1) & 1;
+    a.batch = batch; a.xcd_affine = xcd & 1; a.concurrent = xcd >> 1;
     a.tail_row = g.F - 1;
     a.C = W; a.sC = g.sW; a.ldc = g.Kp;
     a.out_colsum = colsumW; a.out_norm = hscale; a.s_out = g.Kp;
@@ -627,8 +629,8 @@ struct DirectBufs {
     int ldwt, ldht, ldrt;
 };
 static long direct_floats(const NmfGeom& g, int batch) { return batch <= GCCNMF_DIRECT_MAX_BATCH ? (long)batch * (g.sU + g.sH + g.sV) : 0; }
-static bool direct_path(const NmfGeom& g, int batch) {
-    return gccnmf_tune_direct && gccnmf_tune_tile_policy == 0 && batch <= gccnmf_tune_direct_batch && batch <= GCCNMF_DIRECT_MAX_BATCH;
+static bool direct_path(const NmfGeom& g, int batch, int groups = 1) {
+    return gccnmf_tune_direct && gccnmf_tune_tile_policy == 0 && (long)batch * groups <= gccnmf_tune_direct_batch && batch <= GCCNMF_DIRECT_MAX_BATCH;
 }
 static DirectBufs direct_bufs(const NmfGeom& g, float* base, int batch) {
     DirectBufs d;
@@ -704,7 +706,7 @@ static int concurrent_groups(int flags) {
     return (flags & 4) ? (n >= 2 ? n : 2) : 1;
 }
 static bool fused_wh_updh(const NmfGeom& g, int batch, int flags) {
-    if (!gccnmf_tune_fused_k12 || gccnmf_tune_tile_policy != 0 || direct_path(g, batch) || batch < 2 || !g.tail || g.Fm < 64 || g.Fm > 512 ||
+    if (!gccnmf_tune_fused_k12 || gccnmf_tune_tile_policy != 0 || direct_path(g, batch, concurrent_groups(flags)) || batch < 2 || !g.tail || g.Fm < 64 || g.Fm > 512 ||
         (g.Fm % 64) != 0 || g.K > 128)
         return false;
     if (gccnmf_tune_fused_k12 == 2) return true;
@@ -732,7 +734,7 @@ static int launch_wh_updh(const NmfGeom& g, const float* V, const float* W, floa
 // the two launches behind it (72 files: 64 + 8 -> 184 + 40 us against 268 for the two launches over all of them, 368 for two slab rounds).
 // (GCCNMF_FLAG_GROUPS: the file groups that run side by side share the rounds; they are not split.)
 static int fused_whdiv_rht_files(const NmfGeom& g, int batch, int flags) {
-    if (!gccnmf_tune_fused_k34 || gccnmf_tune_tile_policy != 0 || direct_path(g, batch) || batch < 2 || !g.tail || g.Fm < 64 || g.Fm > 512 ||
+    if (!gccnmf_tune_fused_k34 || gccnmf_tune_tile_policy != 0 || direct_path(g, batch, concurrent_groups(flags)) || batch < 2 || !g.tail || g.Fm < 64 || g.Fm > 512 ||
         (g.Fm % 64) != 0 || g.K > 128 || (g.Fm / 64) * 16 < 32 * gccnmf_ceil_div(g.K, 32))
         return 0;
     if (gccnmf_tune_fused_k34 == 2) return batch;
@@ -768,12 +770,21 @@ static int launch_whdiv_rht(const NmfGeom& g, const float* V, const float* W, co
 // Counters of one file group, behind everything else in the workspace: c12 [batch][tiles_n] (K1 -> K2, in 32-column blocks), c23
 // [batch][tiles_n] (K2 -> K3), c34 [batch] (K3 -> K4, items), c41 [batch] (K4 -> the next iteration's K1, items), error [1].  Zeroed once per gccnmf_klnmf call; iteration `it` waits for
 // (it + 1) x the per-iteration count, so nothing is reset between launches.
-static long chain_counter_floats(const NmfGeom& g, int batch) { return (long)batch * (2L * gccnmf_ceil_div(g.N, 64) + 2) + 32; }      // ... error [1], 7 unused, tickets [8], XCCs seen per list [8], 8 unused
+// The ready counters are rounded up to a 128-byte line (32 words), the 32 status words follow: error [1], 7 unused, tickets [8], XCCs seen per list [8],
+// 8 unused.  Every block in front of the counters is a multiple of 64 floats, so the workspace is one too (a ragged batch's, with its tables: of 4) --
+// workspaces carved back to back out of ONE allocation (the engine's file groups) all start 16-byte aligned when the first does, which the float4 /
+// LDS-DMA accesses to R, U, Wt, Ht, Rt rely on (the entry points reject a workspace that is not 16-byte aligned).  Everything that locates the
+// counters, the status words or what lies behind them (the ragged tables) goes through these helpers.
+static long chain_ready_counters(const NmfGeom& g, int batch) { return (long)batch * (2L * gccnmf_ceil_div(g.N, 64) + 2); }
+static long chain_counter_floats(const NmfGeom& g, int batch) { return (chain_ready_counters(g, batch) + 31) / 32 * 32 + 32; }
+static unsigned* chain_status_words(unsigned* counters, const NmfGeom& g, int batch) { return counters + chain_counter_floats(g, batch) - 32; }
+static bool workspace_aligned(const void* workspace) { return ((uintptr_t)workspace & 15) == 0; }
 static long klnmf_workspace_base_floats(const NmfGeom& g, int batch) {
     long n = (long)batch * (g.sV + g.sU + 3L * g.Kp);
     if (batch == 1) n += GCCNMF_SPLITS * ((g.sV > g.sU ? g.sV : g.sU) + (long)g.Kp);
     return n + direct_floats(g, batch);
 }
+static unsigned* chain_counters(const float* workspace, const NmfGeom& g, int batch) { return (unsigned*)(workspace + klnmf_workspace_base_floats(g, batch)); }
 // Which iterations can be chained: the four GEMMs all on full-height LDS-DMA throughput tiles with one XCD-affine list per XCD, every
 // file's tiles on ONE XCD in every stage (batch a multiple of 8: list x holds the files x, x + 8, ... in all four GEMMs).
 static bool chain_capable(const NmfGeom& g, int batch, int flags, bool any_size = false);
@@ -806,12 +817,12 @@ static int chain_stages(const NmfGeom& g, int batch, int flags) {
 // with one XCD-affine list per XCD
 static bool chain_capable(const NmfGeom& g, int batch, int flags, bool any_size) {
     if (!gccnmf_tune_dma || gccnmf_tune_tile_policy == 2 || gccnmf_tune_tail_split > 1) return false;
-    if (direct_path(g, batch) || (flags & 3) || batch < 8) return false;
+    if (direct_path(g, batch, concurrent_groups(flags)) || (flags & 3) || batch < 8) return false;
     // (K a multiple of 128: a K2 tile whose last wave is partly beyond M takes the generic epilogue h * (acc / den) for that wave, a plain
     // launch on half-height tiles the lean one (h * acc) * (s / den) for the same rows: a few ulp apart, so the forms would not be bitwise equal)
     if (g.K <= 128 || g.Fm <= 128 || g.Fm > 512 || (g.Fm & 127) || (g.K & 127) || (g.F % 16) != 1 || !g.tail) return false;
     // (a plain launch of a few files takes the two-launch W update -- other kernels, other summation order; a ragged batch has no plain form to agree with)
-    return any_size || can_fuse_w_update(g, batch);
+    return any_size || can_fuse_w_update(g, batch, concurrent_groups(flags));
 }
 static bool chain_rule(int batch, int flags) {
     // The rule (profiles/r06h_files_sweep_*.txt, one-stream iteration as a fraction of the f32 peak, plain launches -> whole-call chain):
@@ -902,7 +913,7 @@ static int launch_klnmf_chain(int stages, const NmfGeom& g, const float* V, floa
     unsigned* c23 = c12 + (long)batch * tn;
     unsigned* c34 = c23 + (long)batch * tn;
     unsigned* c41 = c34 + batch;
-    unsigned* err = c41 + batch;
+    unsigned* err = chain_status_words(counters, g, batch);      // (behind the padding of the ready counters)
     const bool wide = !rg && chain_list_mode(batch) == 2;          // a file's tiles spread over the XCDs: agent-scope hand-over, no XCC check
     for (int i = 0; i < 4; ++i) {
         ch.sync[i].error = err;
@@ -960,7 +971,7 @@ static int launch_klnmf_chain(int stages, const NmfGeom& g, const float* V, floa
 static int short_chain_group(const NmfGeom& g, int batch, int flags) {
     const int want = gccnmf_tune_chain;
     if (!want || want == 2 || want == 4 || !gccnmf_tune_fused_k12 || !gccnmf_tune_fused_k34 || gccnmf_tune_tile_policy != 0) return 0;
-    if (direct_path(g, batch) || (flags & 3) || batch < 8 || !g.tail || g.Fm < 64 || g.Fm > 512 || (g.Fm % 64) != 0 || g.K > 128) return 0;
+    if (direct_path(g, batch, concurrent_groups(flags)) || (flags & 3) || batch < 8 || !g.tail || g.Fm < 64 || g.Fm > 512 || (g.Fm % 64) != 0 || g.K > 128) return 0;
     if ((g.Fm / 64) * 16 < 32 * gccnmf_ceil_div(g.K, 32) || g.F > 64 * 9 || !gccnmf_tune_ring || (long)batch * (g.Kp / 64) >= 256) return 0;
     // by rule: only where the plain call runs the SAME three item programs for every file (both fused launches, no files left to the two-launch
     // form) -- the chained call is then bit for bit the plain one, and a file's bits keep following the batch size exactly as before
@@ -988,7 +999,7 @@ static int launch_short_chain(const NmfGeom& g, const float* V, float* W, float*
     c.aw.F = g.F; c.aw.K = g.K; c.aw.Kp = g.Kp; c.aw.sW = g.sW; c.aw.sU = g.sU; c.aw.sVec = g.Kp; c.aw.sRowsum = g.Kp;
     c.it0 = it0; c.iterations = iterations; c.atoms_per_group = group; c.solo = gccnmf_tune_chain_solo;
     c.counters = counters;
-    c.error = counters + chain_counter_floats(g, batch) - 32;
+    c.error = chain_status_words(counters, g, batch);
     c.xcc_seen = c.error + 16;
     c.timeout = gccnmf_tune_chain_fault ? 0 : GEMM_SYNC_TIMEOUT;
     return gccnmf_short_chain_launch(c, s);
@@ -1033,14 +1044,15 @@ static int klnmf_stage(int stage, const float* V, float* W, float* H, float* wor
     if (stage == 7) {
         // D(V || W.H) of the current (materialised) factors, divergence.hip: tile partials (float64) in each file's R block, the batch
         // results (float64) at the start of the U region; one launch form whatever the batch or the tuning.  V, W, H are read only.
-        if (((uintptr_t)workspace & 7) != 0) return GCCNMF_ERR_ARG;          // float64 partials and results (both offsets are multiples of 4096 bytes)
+        // (float64 partials and results: the workspace is 16-byte aligned -- the entry point checked -- and both offsets are multiples of 4096 bytes)
         return gccnmf_kl_divergence_launch(V, W, (flags & GCCNMF_FLAG_FIXED_W) ? 0 : g.sW, H, g.F, g.N, g.K, g.Fp, g.Kp, g.Np, batch, (double*)R, g.sV / 2,
                                            (double*)U, s);
     }
     const bool fused12 = fused_wh_updh(g, batch, flags);
     const int head34 = fused_whdiv_rht_files(g, batch, flags), rest34 = batch - head34;      // files on the slab launch | behind it on the two launches
     const bool fused34 = head34 > 0;
-    if (direct_path(g, batch)) {
+    const int groups = concurrent_groups(flags);      // launch forms that follow the launch size are chosen for all groups together (GCCNMF_FLAG_GROUPS)
+    if (direct_path(g, batch, groups)) {
         const DirectBufs d = direct_bufs(g, direct_base, batch);
         switch (stage) {
             case 0: {
@@ -1057,7 +1069,7 @@ static int klnmf_stage(int stage, const float* V, float* W, float* H, float* wor
             case 4: return direct_rht(g, d, R, U, rowsumH, batch, s);
             case 5:
                 return launch_update_w(W, U, rowsumH, colsumW, hscale, g.F, g.Fp, g.K, g.Kp, g.sW, g.sU, (long)g.Kp, (long)g.Kp, batch, s, 1, 0, 0,
-                                       d.Wt, d.sWt, d.ldwt);
+                                       d.Wt, d.sWt, d.ldwt, groups);
             case 6:
                 hipLaunchKernelGGL(nmf_scale_h_kernel, dim3(batch * g.K), dim3(256), 0, s, H, hscale, (long)g.Kp, g.K, g.sH, g.ld, g.Np);
                 GCCNMF_CHECK_LAUNCH();
@@ -1071,7 +1083,7 @@ static int klnmf_stage(int stage, const float* V, float* W, float* H, float* wor
 #else
     constexpr bool split_rht = false;              // the split-K path is compiled out of the product library
 #endif
-    const int xcd = ((flags & 1) ? 0 : 1) | ((flags & 4) ? 2 : 0);      // bit 1: another file group's launches run beside these
+    const int xcd = ((flags & 1) ? 0 : 1) | ((flags & 4) ? groups << 1 : 0);      // above bit 0: the file groups whose launches run side by side (0: this one alone)
     const int vec_grid = batch * (g.Kp / 16);
     switch (stage) {
         case 0:
@@ -1105,14 +1117,14 @@ static int klnmf_stage(int stage, const float* V, float* W, float* H, float* wor
 #ifdef GCCNMF_EXPERIMENTS
             if (split_rht) return launch_rht_split(g, R, H, parts, rowsum_parts, s);
 #endif
-            if (can_fuse_w_update(g, batch) && !(flags & 2)) return launch_rht_update_w(g, R, H, W, colsumW, hscale, batch, xcd, s);
+            if (can_fuse_w_update(g, batch, groups) && !(flags & 2)) return launch_rht_update_w(g, R, H, W, colsumW, hscale, batch, xcd, s);
             return launch_rht(g, R, H, U, rowsumH, batch, xcd, s);
         case 5:
             if (split_rht)
                 return launch_update_w(W, parts, rowsum_parts, colsumW, hscale, g.F, g.Fp, g.K, g.Kp, g.sW, g.sU, (long)g.Kp, (long)g.Kp, batch,
                                        s, gccnmf_tune_rht_splits, g.sU, (long)g.Kp);
-            if (can_fuse_w_update(g, batch) && !(flags & 2) && !fused34) return GCCNMF_OK;     // done by stage 4's epilogue
-            return launch_update_w(W, U, rowsumH, colsumW, hscale, g.F, g.Fp, g.K, g.Kp, g.sW, g.sU, (long)g.Kp, (long)g.Kp, batch, s);
+            if (can_fuse_w_update(g, batch, groups) && !(flags & 2) && !fused34) return GCCNMF_OK;     // done by stage 4's epilogue
+            return launch_update_w(W, U, rowsumH, colsumW, hscale, g.F, g.Fp, g.K, g.Kp, g.sW, g.sU, (long)g.Kp, (long)g.Kp, batch, s, 1, 0, 0, nullptr, 0, 0, groups);
         case 6:
             hipLaunchKernelGGL(nmf_scale_h_kernel, dim3(batch * g.K), dim3(256), 0, s, H, hscale, (long)g.Kp, g.K, g.sH, g.ld, g.Np);
             break;
@@ -1134,7 +1146,7 @@ int gccnmf_klnmf_plan(int F, int N, int K, int batch, int flags) {
     if (F < 2 || N < 1 || K < 1 || batch < 1) return -1;
     if (flags & GCCNMF_FIXED_BITS) return fixed_flags_ok(flags) && gccnmf_klnmf_fixed_supported(F, K) ? 16 : -1;
     const NmfGeom g = make_geom(F, N, K);
-    return (direct_path(g, batch) ? 1 : 0) | (fused_wh_updh(g, batch, flags) ? 2 : 0) | (fused_whdiv_rht_files(g, batch, flags) > 0 ? 4 : 0) |
+    return (direct_path(g, batch, concurrent_groups(flags)) ? 1 : 0) | (fused_wh_updh(g, batch, flags) ? 2 : 0) | (fused_whdiv_rht_files(g, batch, flags) > 0 ? 4 : 0) |
            ((chain_stages(g, batch, flags) || short_chain_group(g, batch, flags)) ? 8 : 0);
 }
 
@@ -1144,6 +1156,7 @@ int gccnmf_klnmf_stage(const float* V, float* W, float* H, float* workspace, int
     // (a fixed dictionary -- one W for every file -- exists for stage 7 alone: the divergence against it; the iteration stages have no such form)
     if (!V || !W || !H || !workspace || F < 2 || N < 1 || K < 1 || batch < 1 || ((flags & GCCNMF_FIXED_BITS) && !(stage == 7 && flags == GCCNMF_FLAG_FIXED_W)))
         return GCCNMF_ERR_ARG;
+    if (!workspace_aligned(workspace)) return GCCNMF_ERR_ARG;          // float4 / LDS-DMA accesses to its blocks; stage 7's float64 partials and results
     return klnmf_stage(stage, V, W, H, workspace, make_geom(F, N, K), batch, sparsity_alpha, epsilon, flags, (hipStream_t)stream);
 }
 
@@ -1151,6 +1164,7 @@ int gccnmf_klnmf(const float* V, float* W, float* H, float* workspace, int F, in
                  float sparsity_alpha, float epsilon, int flags, void* stream) {
     GCCNMF_ENTER();
     if (!V || !W || !H || !workspace || F < 2 || N < 1 || K < 1 || batch < 1 || iterations < 0) return GCCNMF_ERR_ARG;
+    if (!workspace_aligned(workspace)) return GCCNMF_ERR_ARG;          // R, U, Wt, Ht, Rt are read with float4 loads and LDS-DMA: 16 bytes
     hipStream_t s = (hipStream_t)stream;
     NmfGeom g = make_geom(F, N, K);
     if (flags & GCCNMF_FIXED_BITS) {
@@ -1159,7 +1173,7 @@ int gccnmf_klnmf(const float* V, float* W, float* H, float* workspace, int F, in
         if (!fixed_flags_ok(flags)) return GCCNMF_ERR_ARG;
         if (!gccnmf_klnmf_fixed_supported(F, K) || gccnmf_klnmf_fixed_workspace_floats(F, K) > klnmf_workspace_base_floats(g, batch))
             return GCCNMF_ERR_UNSUPPORTED;
-        unsigned* status = (unsigned*)(workspace + klnmf_workspace_base_floats(g, batch)) + chain_counter_floats(g, batch) - 32;
+        unsigned* status = chain_status_words(chain_counters(workspace, g, batch), g, batch);
         if (hipMemsetAsync(status, 0, 32 * sizeof(unsigned), s) != hipSuccess) return GCCNMF_ERR_LAUNCH;
         return gccnmf_klnmf_fixed_launch(V, W, H, workspace, F, N, K, batch, iterations, sparsity_alpha, epsilon,
                                          (flags & GCCNMF_FLAG_H_ONES) != 0, s);
@@ -1167,10 +1181,10 @@ int gccnmf_klnmf(const float* V, float* W, float* H, float* workspace, int F, in
     int rc;
     if ((rc = klnmf_stage(0, V, W, H, workspace, g, batch, sparsity_alpha, epsilon, flags, s))) return rc;
     const int chained = chain_stages(g, batch, flags);          // 0 | 2: K1 | K2 in one launch | 4: the whole iteration | 8: the whole call
-    unsigned* counters = (unsigned*)(workspace + klnmf_workspace_base_floats(g, batch));
+    unsigned* counters = chain_counters(workspace, g, batch);
     const int short_group = chained ? 0 : short_chain_group(g, batch, flags);      // K <= 128: the three launches of every iteration as one chained launch
     // the status words describe THIS call (gccnmf_klnmf_chain_status): a call that does not chain clears what an earlier, chained one may have left
-    if (!chained && !short_group && hipMemsetAsync(counters + chain_counter_floats(g, batch) - 32, 0, 32 * sizeof(unsigned), s) != hipSuccess) return GCCNMF_ERR_LAUNCH;
+    if (!chained && !short_group && hipMemsetAsync(chain_status_words(counters, g, batch), 0, 32 * sizeof(unsigned), s) != hipSuccess) return GCCNMF_ERR_LAUNCH;
     if (short_group && iterations > 0) {
         if (hipMemsetAsync(counters, 0, sizeof(unsigned) * chain_counter_floats(g, batch), s) != hipSuccess) return GCCNMF_ERR_LAUNCH;
         float* R0 = workspace;
@@ -1182,7 +1196,7 @@ int gccnmf_klnmf(const float* V, float* W, float* H, float* workspace, int F, in
             if ((rc = launch_short_chain(g, V, W, H, U0, colsum0, rowsum0, hscale0, sparsity_alpha, epsilon, batch, short_group, counters, it0,
                                          std::min(GCCNMF_CHAIN_MAX_ITERATIONS, iterations - it0), s)))
                 return rc;
-        hipLaunchKernelGGL(nmf_chain_poison_kernel, dim3(64), dim3(256), 0, s, counters + chain_counter_floats(g, batch) - 32, W, H, (long)batch * g.sW, (long)batch * g.sH);
+        hipLaunchKernelGGL(nmf_chain_poison_kernel, dim3(64), dim3(256), 0, s, chain_status_words(counters, g, batch), W, H, (long)batch * g.sW, (long)batch * g.sH);
         GCCNMF_CHECK_LAUNCH();
         return klnmf_stage(6, V, W, H, workspace, g, batch, sparsity_alpha, epsilon, flags, s);
     }
@@ -1203,7 +1217,7 @@ int gccnmf_klnmf(const float* V, float* W, float* H, float* workspace, int F, in
         }
     }
     if (chained && iterations > 0) {
-        hipLaunchKernelGGL(nmf_chain_poison_kernel, dim3(64), dim3(256), 0, s, counters + chain_counter_floats(g, batch) - 32, W, H, (long)batch * g.sW, (long)batch * g.sH);
+        hipLaunchKernelGGL(nmf_chain_poison_kernel, dim3(64), dim3(256), 0, s, chain_status_words(counters, g, batch), W, H, (long)batch * g.sW, (long)batch * g.sH);
         GCCNMF_CHECK_LAUNCH();
     }
     return klnmf_stage(6, V, W, H, workspace, g, batch, sparsity_alpha, epsilon, flags, s);
@@ -1217,7 +1231,7 @@ int gccnmf_klnmf_chain_status(const float* workspace, int F, int N, int K, int b
     GCCNMF_ENTER();
     if (!workspace || !status || F < 2 || N < 1 || K < 1 || batch < 1) return GCCNMF_ERR_ARG;
     NmfGeom g = make_geom(F, N, K);
-    const unsigned* words = (const unsigned*)(workspace + klnmf_workspace_base_floats(g, batch)) + chain_counter_floats(g, batch) - 32;
+    const unsigned* words = chain_status_words(chain_counters(workspace, g, batch), g, batch);
     unsigned host[32];
     if (hipMemcpy(host, words, sizeof(host), hipMemcpyDeviceToHost) != hipSuccess) return GCCNMF_ERR_LAUNCH;
     int st = host[0] ? 1 : 0;
@@ -1248,6 +1262,7 @@ int gccnmf_klnmf_ragged(const float* V, float* W, float* H, float* workspace, in
     GCCNMF_ENTER();
     if (!V || !W || !H || !workspace || !N || F < 2 || Nmax < 1 || K < 1 || batch < 1 || iterations < 0 || (flags & GCCNMF_FIXED_BITS))
         return GCCNMF_ERR_ARG;
+    if (!workspace_aligned(workspace)) return GCCNMF_ERR_ARG;
     if (batch > GCCNMF_RAGGED_MAX_BATCH) return GCCNMF_ERR_UNSUPPORTED;
     long tiles = 0;
     for (int f = 0; f < batch; ++f) {
@@ -1276,7 +1291,7 @@ int gccnmf_klnmf_ragged(const float* V, float* W, float* H, float* workspace, in
         load[best] += gccnmf_ceil_div(N[f], 64);
     }
     for (int l = 0; l < 8; ++l) std::sort(rg.lists[l] + 1, rg.lists[l] + 1 + rg.lists[l][0]);      // a list serves its files in ascending order
-    unsigned* counters = (unsigned*)(workspace + klnmf_workspace_base_floats(g, batch));
+    unsigned* counters = chain_counters(workspace, g, batch);
     int* tables = (int*)(counters + chain_counter_floats(g, batch));
     RaggedTables t = {};
     for (int f = 0; f < batch; ++f) t.v[f] = N[f];
@@ -1297,7 +1312,7 @@ int gccnmf_klnmf_ragged(const float* V, float* W, float* H, float* workspace, in
             if ((rc = launch_klnmf_chain(4, g, V, W, H, R, colsumW, hscale, sparsity_alpha, epsilon, batch, flags & ~4, counters, it0,
                                          std::min(GCCNMF_CHAIN_MAX_ITERATIONS, iterations - it0), s, &rg)))
                 return rc;
-        hipLaunchKernelGGL(nmf_chain_poison_kernel, dim3(64), dim3(256), 0, s, counters + chain_counter_floats(g, batch) - 32, W, H, (long)batch * g.sW, (long)batch * g.sH);
+        hipLaunchKernelGGL(nmf_chain_poison_kernel, dim3(64), dim3(256), 0, s, chain_status_words(counters, g, batch), W, H, (long)batch * g.sW, (long)batch * g.sH);
         GCCNMF_CHECK_LAUNCH();
     }
     return klnmf_stage(6, V, W, H, workspace, g, batch, sparsity_alpha, epsilon, flags, s);

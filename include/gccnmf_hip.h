@@ -41,8 +41,9 @@ extern "C" {
 #define GCCNMF_FLAG_CONCURRENT_GROUPS 4  /* another file group runs the same call on another stream: keep the throughput tile (a launch
                                           * that has the chip to itself may run its partial last round, or all of it, on half-height tiles) */
 #define GCCNMF_FLAG_GROUPS(n) (GCCNMF_FLAG_CONCURRENT_GROUPS | ((n) << 8))   /* ... n equal groups in all (bits 8-15; 0 = two): launch forms that
-                                          * are chosen by the size of a launch (tuning keys 16 / 17) are chosen for the groups together, so a
-                                          * file's result does not depend on how the batch was split */
+                                          * are chosen by the size of a launch (tuning keys 16 / 17, the direct latency kernels of a handful of
+                                          * files, the GEMM tile, the W-update kernel) are chosen for the n x batch files of all groups together,
+                                          * so a file's result does not depend on how the batch was split */
 #define GCCNMF_FLAG_FIXED_W (1 << 16)   /* a pre-trained dictionary: W is ONE [Fp][Kp] zero-padded dictionary shared by every file of the call,
                                           * read only (bit-identical after the call); H [batch][Kp][Np] holds the initial coefficients on entry and
                                           * the result on exit (h <- h o W^T(v / Wh) / (colsum W + alpha + eps), every iteration of the call in one
@@ -134,7 +135,11 @@ int gccnmf_pack_pcm16(const float* y, int groups, int L, unsigned int* peak_scra
  *   V [batch][Fp][Np], W [batch][Fp][Kp], H [batch][Kp][Np] with Np = round_up(N,64); N = 2T on the
  *   GCC-NMF path but any N >= 1 is accepted (performKLNMF is also called on arbitrary V).
  *   workspace: gccnmf_klnmf_workspace_floats(...) floats of scratch (R, R.H^T, K-vectors; for batch == 1 also the partial
- *   products of the split-K latency path).  Always size it with the batch of the call it is used with.
+ *   products of the split-K latency path, and at its end the counters and status words of the chained launches).  Always size it with the
+ *   batch of the call it is used with.  The size is a multiple of 4 floats for every valid argument tuple (so is every other
+ *   *_workspace_floats of this header), and `workspace` must be 16-byte aligned, else GCCNMF_ERR_ARG before anything is launched -- here, in
+ *   gccnmf_klnmf_ragged and in gccnmf_klnmf_stage: its blocks are read with 16-byte vector loads and LDS-DMA.  Workspaces carved back to back
+ *   out of one aligned allocation, each of the size this function returns, therefore all qualify.
  *   batch >= 2: a file's result is bit-identical whatever batch it rides in (for equal launch-size decisions); batch == 1
  *   cuts the two long reductions in four parts added in a fixed order (deterministic, summation-order accuracy). */
 long gccnmf_klnmf_workspace_floats(int F, int N, int K, int batch);
@@ -148,7 +153,7 @@ int gccnmf_klnmf(const float* V, float* W, float* H, float* workspace, int F, in
  * XCDs by length; a file's factors are bit for bit those of gccnmf_klnmf on a batch of files of its length.  GCCNMF_ERR_UNSUPPORTED where
  * the chained form does not exist (K <= 128 or not a multiple of 128, fewer than 8 files or 256 column tiles, more than 248 files,
  * F - 1 not a multiple of 128 up to 512): run the files of each length as a batch of their own then.
- * workspace: gccnmf_klnmf_ragged_workspace_floats(F, Nmax, K, batch). */
+ * workspace: gccnmf_klnmf_ragged_workspace_floats(F, Nmax, K, batch) floats (a multiple of 4), 16-byte aligned. */
 long gccnmf_klnmf_ragged_workspace_floats(int F, int Nmax, int K, int batch);
 int gccnmf_klnmf_ragged(const float* V, float* W, float* H, float* workspace, int F, const int* N, int Nmax, int K, int batch,
                         int iterations, float sparsity_alpha, float epsilon, int flags, void* stream);
@@ -177,7 +182,7 @@ int gccnmf_klnmf_plan(int F, int N, int K, int batch, int flags);
  *          materialised -- before a gccnmf_klnmf call or after a complete one, not between stages 1-6; V, W and H are read only, and only
  *          inside f < F, n < N, k < K (their padding is not read into the result).  The result is `batch` float64 values at
  *              (const double*)(workspace + (size_t)batch * Fp * Np)          -- the start of the U region: a multiple of 4096 bytes from
- *          `workspace`, hence 16-byte aligned whenever the workspace is (it must be 8-byte aligned, else GCCNMF_ERR_ARG); the tile partials, ceil(F / 128) * ceil(N / 64) float64 per
+ *          `workspace`, hence 16-byte aligned like the workspace itself (which must be 16-byte aligned for every stage, else GCCNMF_ERR_ARG); the tile partials, ceil(F / 128) * ceil(N / 64) float64 per
  *          file, go to the head of each file's [Fp][Np] block of the R region (workspace + b * Fp * Np).  Both are scratch of the
  *          iteration, far below the chain counters and status words at the workspace's end, which stage 7 neither reads nor writes;
  *          because R's zero padding is overwritten, stage 0 (every gccnmf_klnmf call starts with it) must run before further stages

@@ -58,7 +58,8 @@ def test_pitches_and_workspace_sizes():
     assert lib.gccnmf_pitches(1, 622, 128, *[ctypes.byref(x) for x in v]) == 1           # GCCNMF_ERR_ARG
     base = 528 * 1280 + 528 * 1024 + 3 * 1024                      # R, U, three K-vectors per file
     direct = 1024 * 528 + 1280 * 1024 + 1280 * 528                 # Wt, Ht, Rt: the transposed copies of the direct path, per file
-    chain = lambda batch: batch * (2 * 20 + 2) + 32                # ready counters of the chained launches (K1 -> K2, K2 -> K3 per column tile; K3 -> K4, K4 -> K1 per file) + error flag
+    # ready counters of the chained launches (K1 -> K2, K2 -> K3 per column tile; K3 -> K4, K4 -> K1 per file), rounded up to a 128-byte line, + 32 status words
+    chain = lambda batch: -(-(batch * (2 * 20 + 2)) // 32) * 32 + 32
     assert lib.gccnmf_klnmf_workspace_floats(513, 1244, 1024, 2) == 2 * (base + direct) + chain(2)
     assert lib.gccnmf_klnmf_workspace_floats(513, 1244, 1024, 64) == 64 * base + chain(64)               # (a handful of files at most)
     assert lib.gccnmf_klnmf_workspace_floats(513, 1244, 1024, 1) == base + 4 * (528 * 1280 + 1024) + direct + chain(1)      # + the split-K partials of one file alone
@@ -68,6 +69,73 @@ def test_pitches_and_workspace_sizes():
     assert lib.gccnmf_klnmf(0, 0, 0, 0, 513, 1244, 1024, 1, 1, 0.0, 1e-16, 0, 0) == 1
     assert lib.gccnmf_stft_stereo(0, 0, 0, 1000, 256, 1, 1, 0, 0, 0, 0, 0, 0) == 1
     assert lib.gccnmf_istft_ola(0, 3, 1024, 256, 4, 1, 0, 0, 1.0, 1, 0, 0, 0) == 1
+
+
+SWEEP_F, SWEEP_N = (129, 200, 257, 513), (1, 63, 64, 65, 127, 128, 129, 244, 1244)
+SWEEP_K, SWEEP_BATCH = (1, 16, 25, 100, 128, 1000, 1024), (1, 2, 3, 5, 7, 8, 9, 17, 25, 33, 51)
+
+
+def _workspace_sizes(lib, F, N, K, batch):
+    """name -> floats of every workspace size function the header declares, for one (F, N, K, batch); N is the column count of the KL-NMF
+    calls and the frame count T of the others, batch the signal count of the any-n_fft transform (n_fft = 2 (F - 1), and the odd F itself)."""
+    out = {'klnmf': lib.gccnmf_klnmf_workspace_floats(F, N, K, batch),
+           'klnmf_ragged': lib.gccnmf_klnmf_ragged_workspace_floats(F, N, K, batch),
+           'klnmf_shared': lib.gccnmf_klnmf_shared_workspace_floats(F, N, K, batch),
+           'klnmf_shared_shard': lib.gccnmf_klnmf_shared_shard_workspace_floats(F, N, K, batch, 0)}
+    if N % 64 == 0 or batch == 1:                                  # column blocks of one matrix: whole tiles per block unless there is one block
+        out['klnmf_shared_shard ld'] = lib.gccnmf_klnmf_shared_shard_workspace_floats(F, N, K, batch, -(-batch * N // 64) * 64 + 64)
+    for S in (1, 2, 3):
+        out['scores S=%d' % S] = lib.gccnmf_scores_workspace_floats(F, N, S, batch)
+        out['reconstruct S=%d' % S] = lib.gccnmf_reconstruct_workspace_floats(N, K, S, batch)
+    for n_fft in (2 * (F - 1), F):
+        out['dft n_fft=%d' % n_fft] = lib.gccnmf_dft_workspace_floats(n_fft, N, batch)
+    return out
+
+
+def test_every_workspace_size_is_a_multiple_of_four_floats():
+    """Workspaces are carved back to back out of one allocation (the engine's file groups: group i gets ws[i * size:]) and their blocks are
+    read with 16-byte vector loads and LDS-DMA, so every *_workspace_floats of the header returns a multiple of 4 floats for every valid
+    argument tuple.  The counters of the chained launches at the end of the KL-NMF workspace, batch * (2 * ceil(N / 64) + 2) + 32 words,
+    were not one for an odd batch and an even number of column tiles: 25 files of the benchmark shape (1082 words, the workspace ended 8
+    bytes past a 16-byte boundary) and 3 files of a two-second one are named; the block is now rounded up to a 128-byte line."""
+    from gcc_nmf_amd import _hip
+    lib = _hip.lib()
+    for named in [(513, 1244, 1000, 25), (513, 244, 128, 3)]:
+        F, N, K, batch = named
+        assert batch % 2 == 1 and -(-N // 64) % 2 == 0 and (batch * (2 * -(-N // 64) + 2) + 32) % 4 == 2        # the old counter block
+        assert lib.gccnmf_klnmf_workspace_floats(*named) > 0 and lib.gccnmf_klnmf_workspace_floats(*named) % 4 == 0, named
+        assert lib.gccnmf_klnmf_ragged_workspace_floats(*named) > 0 and lib.gccnmf_klnmf_ragged_workspace_floats(*named) % 4 == 0, named
+    bad, valid = [], dict()
+    for F in SWEEP_F:
+        for N in SWEEP_N:
+            for K in SWEEP_K:
+                for batch in SWEEP_BATCH:
+                    for name, n in _workspace_sizes(lib, F, N, K, batch).items():
+                        if n == -1:
+                            continue                                  # not a valid tuple for this function
+                        valid[name.split()[0]] = valid.get(name.split()[0], 0) + 1
+                        if n <= 0 or n % 4:
+                            bad.append((name, F, N, K, batch, n))
+    assert not bad, '%d sizes are not multiples of 4 floats, e.g. %s' % (len(bad), bad[:6])
+    tuples = len(SWEEP_F) * len(SWEEP_N) * len(SWEEP_K) * len(SWEEP_BATCH)
+    assert valid['klnmf'] == valid['klnmf_ragged'] == tuples and valid['scores'] == valid['reconstruct'] == 3 * tuples and valid['dft'] == 2 * tuples
+    assert valid['klnmf_shared'] > tuples // 4 and valid['klnmf_shared_shard'] > tuples // 4        # (a batch of shared-dictionary files needs whole column tiles)
+
+
+def test_klnmf_entry_points_reject_a_workspace_that_is_not_16_byte_aligned():
+    """gccnmf_klnmf, gccnmf_klnmf_ragged and every stage of gccnmf_klnmf_stage: a workspace address = 8 (mod 16) -- what the second file
+    group's carve used to be for an odd batch -- with otherwise valid arguments is GCCNMF_ERR_ARG, decided before any HIP call."""
+    from gcc_nmf_amd import _hip
+    lib, P = _hip.lib(), 4096
+    F, N, K, batch = 513, 244, 256, 9
+    lengths = (ctypes.c_int * batch)(*([N, 100, 200] * 3))
+    for ws in (P + 8, P + 4, P + 12, P + 1):
+        assert lib.gccnmf_klnmf(P, P, P, ws, F, N, K, batch, 1, 0.0, 1e-16, 0, None) == 1
+        assert lib.gccnmf_klnmf(P, P, P, ws, F, N, K, batch, 1, 0.0, 1e-16, 4 | (2 << 8), None) == 1
+        assert lib.gccnmf_klnmf(P, P, P, ws, F, N, K, batch, 1, 0.0, 1e-16, 1 << 16, None) == 1          # the fixed-dictionary form too
+        assert lib.gccnmf_klnmf_ragged(P, P, P, ws, F, lengths, N, K, batch, 1, 0.0, 1e-16, 0, None) == 1
+        for stage in range(8):
+            assert lib.gccnmf_klnmf_stage(P, P, P, ws, F, N, K, batch, 0.0, 1e-16, 0, stage, None) == 1, stage
 
 
 def test_shared_run_argument_checks_and_workspace_sizes():
@@ -221,6 +289,10 @@ def test_klnmf_plan_is_a_pure_function_of_shape_batch_and_tuning():
     groups = lambda n: 4 | (n << 8)
     assert plan(513, 1244, 128, 32, groups(2)) == 6 and plan(513, 1244, 128, 16, groups(4)) == 6 and plan(513, 1244, 128, 32, 0) == 2
     assert plan(513, 0, 128, 64, 0) == -1
+    # a handful of files take the direct latency kernels -- unless they are one of several groups that together are more than a handful: the
+    # launch forms that follow the launch size are chosen for the files of all groups together, so a file's bits do not depend on the split
+    assert plan(513, 244, 128, 3, 0) & 1 and plan(513, 244, 128, 6, 0) & 1 == 0 and plan(513, 244, 128, 3, groups(2)) == plan(513, 244, 128, 6, 0)
+    assert plan(513, 244, 300, 2, groups(2)) & 1 and plan(513, 244, 300, 1, groups(4)) & 1 and plan(513, 244, 300, 1, groups(5)) & 1 == 0
     try:
         assert lib.gccnmf_set_tuning(16, 0) == 0 and lib.gccnmf_set_tuning(17, 2) == 0
         assert plan(513, 1244, 128, 26, 0) == 4 and plan(513, 1244, 64, 5, 0) == 4
