@@ -162,6 +162,20 @@ def check_convergence(tolerance, checkEvery, numIterations):
 GCCNMF_STAGE_DIVERGENCE = 7             # include/gccnmf_hip.h: gccnmf_klnmf_stage, "KL divergence of the current factors"
 GCCNMF_SCORES_TRACKS = 0x100            # include/gccnmf_hip.h: per-(target, frame) indexes in gccnmf_target_scores_masks
 TRACKS_MAX_FRAMES = (1 << 21) - 1
+GCCNMF_RECONSTRUCT_SPATIAL_BIT = 1 << 16  # include/gccnmf_hip.h: the spatial filter behind the ratio stage, in the upper half of gccnmf_reconstruct's batch
+GCCNMF_SPATIAL_LOADING = 1e-3           # include/gccnmf_hip.h: the diagonal loading of the spatial covariances
+
+
+def reconstruct_spatial_batch(batch):
+    """The batch argument of gccnmf_reconstruct in its spatial mode: GCCNMF_RECONSTRUCT_SPATIAL_BATCH(batch) of include/gccnmf_hip.h."""
+    if not 1 <= int(batch) <= 65535:
+        raise ValueError('the spatial reconstruction takes 1 to 65535 files per call, got %r' % (batch,))
+    return int(batch) | GCCNMF_RECONSTRUCT_SPATIAL_BIT
+
+
+def reconstruct_spatial_workspace_floats(batch, S, Fp):
+    """Floats of the covariance workspace of that mode: GCCNMF_RECONSTRUCT_SPATIAL_WORKSPACE_FLOATS(batch, S, Fp), Fp = round_up(F, 16)."""
+    return 4 * int(batch) * int(S) * int(Fp)
 
 
 def check_tdoa_tracking(tdoaTracking, localizationWindowSize, numSources):

@@ -9,6 +9,7 @@
 // so each stage is ONE launch for the whole batch.
 #include "gemm_ring.h"
 #include "ratio.h"
+#include "spatial.h"
 #include "angular_nl.h"
 #include "../../include/gccnmf_hip.h"
 
@@ -514,16 +515,26 @@ long gccnmf_reconstruct_workspace_floats(int T, int K, int S, int batch) {
 int gccnmf_reconstruct(const float* W, const float* H, const unsigned char* argmax, const float* masks, const float* X,
                        const float* V, int F, int T, int K, int S, int batch, float* workspace, float* spec, void* stream) {
     GCCNMF_ENTER();
-    // the mode rides above the low byte of S (GCCNMF_RECONSTRUCT_RATIO); every check comes before the first HIP call
+    // the modes ride above the low byte of S (GCCNMF_RECONSTRUCT_RATIO) and in the upper half of batch (GCCNMF_RECONSTRUCT_SPATIAL_BATCH);
+    // every check comes before the first HIP call
     const int mode = S & ~0xff;
     S &= 0xff;
     if (mode & ~GCCNMF_RECONSTRUCT_RATIO) return GCCNMF_ERR_ARG;
     const bool ratio = mode == GCCNMF_RECONSTRUCT_RATIO;      // needs neither V nor the masked-H workspace
+    if (batch < 1 || (batch & ~(0xffff | GCCNMF_RECONSTRUCT_SPATIAL_BIT))) return GCCNMF_ERR_ARG;
+    const bool spatial = (batch & GCCNMF_RECONSTRUCT_SPATIAL_BIT) != 0;     // the spatial filter behind the ratio stage: covariances in workspace
+    batch &= 0xffff;
+    if (spatial && !ratio) return GCCNMF_ERR_ARG;
     if (!W || !H || (!argmax && !masks) || !X || (!ratio && (!V || !workspace)) || !spec || F < 2 || T < 1 || K < 1 || S < 1 || batch < 1)
         return GCCNMF_ERR_ARG;
+    if (spatial && (!workspace || ((uintptr_t)workspace & 15))) return GCCNMF_ERR_ARG;
     if (ratio && S > GCCNMF_RATIO_MAX_TARGETS) return GCCNMF_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
-    if (ratio) return gccnmf_launch_ratio(W, H, argmax, masks, X, F, T, K, S, batch, spec, s);
+    if (ratio) {
+        const int rc = gccnmf_launch_ratio(W, H, argmax, masks, X, F, T, K, S, batch, spec, s);
+        if (rc != GCCNMF_OK || !spatial) return rc;
+        return gccnmf_launch_spatial(X, F, T, S, batch, workspace, spec, s);
+    }
     GccNmfPitches p = gccnmf_make_pitches(F, T, K);
     const int ncol = 2 * S * p.Tp;
     float* Hm = workspace;

@@ -121,16 +121,16 @@ def check_iterations(trace, checkEvery, maxIterations):
 
 GCCNMF_FLAG_FIXED_W = 1 << 16          # include/gccnmf_hip.h
 GCCNMF_RECONSTRUCT_RATIO = 0x100       # include/gccnmf_hip.h: the ratio-mask mode of gccnmf_reconstruct, above the low byte of S
-RECONSTRUCTIONS = ('direct', 'ratio')
-RATIO_MAX_TARGETS = 8                  # csrc/ratio.h
+RECONSTRUCTIONS = ('direct', 'ratio', 'spatial')
+RATIO_MAX_TARGETS = 8                  # csrc/ratio.h, csrc/spatial.h
 
 
 def check_reconstruction(reconstruction, numTargets):
     """The ``reconstruction`` keyword of the engines and of getTargetSpectrogramEstimates; ValueError before any device work."""
     if reconstruction not in RECONSTRUCTIONS:
-        raise ValueError("reconstruction must be 'direct' or 'ratio', got %r" % (reconstruction,))
-    if reconstruction == 'ratio' and not 1 <= int(numTargets) <= RATIO_MAX_TARGETS:
-        raise ValueError("reconstruction='ratio' takes 1 to %d targets, got %d" % (RATIO_MAX_TARGETS, int(numTargets)))
+        raise ValueError("reconstruction must be 'direct', 'ratio' or 'spatial', got %r" % (reconstruction,))
+    if reconstruction != 'direct' and not 1 <= int(numTargets) <= RATIO_MAX_TARGETS:
+        raise ValueError("reconstruction=%r takes 1 to %d targets, got %d" % (reconstruction, RATIO_MAX_TARGETS, int(numTargets)))
     return reconstruction
 GCCNMF_FLAG_H_ONES = 1 << 17
 check_gcc_phat_nl = _hip.check_gcc_phat_nl        # the gccPHATNLEnabled / gccPHATNLAlpha keywords; ValueError before any device work
@@ -253,7 +253,10 @@ class GCCNMFEngine(object):
 
     ``reconstruction``: 'direct' = the reference's target spectrograms, W.(H_c o M_i) with the mixture phase (gccNMFFunctions.py:145-151);
     'ratio' = the Wiener-like ratio mask X_c * W.(H_c o M_i) / sum_j W.(H_c o M_j), whose targets add up to the mixture (one fused launch,
-    csrc/ratio.hip; at most 8 targets).  Everything up to the coefficient masks is the same in both modes.
+    csrc/ratio.hip; at most 8 targets); 'spatial' = the ratio mask followed by a multichannel Wiener filter (csrc/spatial.hip; DESIGN
+    section 4c): one 2 x 2 spatial covariance per target and bin from the masked estimates, then the stereo mixture vector filtered with
+    v_i R_i (sum_j v_j R_j)^-1 per (bin, frame) -- the targets still add up to the mixture, and the inter-channel phase is used.
+    Everything up to the coefficient masks is the same in all modes.
 
     ``gccPHATNLEnabled`` / ``gccPHATNLAlpha`` (the reference's settings, gccNMF/realtime/config.py:42-43): localise on the GCC-NONLIN
     angular spectrum sum_f 1 - tanh(alpha sqrt(max(0, 1 - Re(C e^{-j 2 pi f tau})))) of Blandin, Ozerov & Vincent (2012) instead of
@@ -292,6 +295,8 @@ class GCCNMFEngine(object):
         self.iterations_used = self.divergence_trace = None
         self.tdoaTracking, self.localizationWindowSize = check_tdoa_tracking(tdoaTracking, localizationWindowSize, numTargets)
         self.reconstruction = check_reconstruction(reconstruction, numTargets)
+        if self.reconstruction == 'spatial':
+            _hip.reconstruct_spatial_batch(batch)          # at most 65535 files per call: ValueError here, not at the first reconstruct()
         self.gccPHATNLEnabled, self.gccPHATNLAlpha = check_gcc_phat_nl(gccPHATNLEnabled, gccPHATNLAlpha)
         self.dictionaryW = None
         if dictionaryW is not None:
@@ -386,7 +391,9 @@ class GCCNMFEngine(object):
             self.ws_scores = z(self.lib.gccnmf_scores_workspace_floats(F, T, g.S, B))
             self.scores = z(B, g.Kp, g.S * g.Tp)
             self.argmax = torch.zeros((B, g.Kp, g.Tp), dtype=torch.uint8, device=dev)
-            self.ws_rec = None if self.reconstruction == 'ratio' else z(self.lib.gccnmf_reconstruct_workspace_floats(T, g.K, g.S, B))
+            self.ws_rec = None if self.reconstruction != 'direct' else z(self.lib.gccnmf_reconstruct_workspace_floats(T, g.K, g.S, B))
+            # the spatial mode's covariances [B][S][Fp][4]; an engine switched to 'spatial' later allocates them at its first reconstruct()
+            self.ws_cov = z(_hip.reconstruct_spatial_workspace_floats(B, g.S, g.Fp)) if self.reconstruction == 'spatial' else None
             self.spec = z(B, 2 * g.S, g.Fp, g.Tp, 2)
             # windowed time frames [B][2S][T][n_fft]: only the two-kernel iSTFT needs them (allocated on first use); the default is the
             # fused inverse-transform + overlap-add pass, available while n_fft + 3 * hop <= 2048
@@ -542,6 +549,13 @@ class GCCNMFEngine(object):
     @_on_device
     def reconstruct(self):
         g = self.g
+        if self.reconstruction == 'spatial':    # the ratio launch, then the covariance reduction and the 2 x 2 filter over spec in place
+            if self.ws_cov is None:
+                self.ws_cov = torch.zeros(_hip.reconstruct_spatial_workspace_floats(self.batch, g.S, g.Fp), dtype=torch.float32, device=self.device)
+            _hip.check(self.lib.gccnmf_reconstruct(_ptr(self.W), _ptr(self.H), _ptr(self.argmax), 0, _ptr(self.X), 0, g.F, g.T, g.K,
+                                                   g.S | GCCNMF_RECONSTRUCT_RATIO, _hip.reconstruct_spatial_batch(self.batch),
+                                                   _ptr(self.ws_cov), _ptr(self.spec), _stream()), 'gccnmf_reconstruct')
+            return
         if self.reconstruction == 'ratio':      # one fused launch: no masked-H workspace, |X| not read
             _hip.check(self.lib.gccnmf_reconstruct(_ptr(self.W), _ptr(self.H), _ptr(self.argmax), 0, _ptr(self.X), 0, g.F, g.T, g.K,
                                                    g.S | GCCNMF_RECONSTRUCT_RATIO, self.batch, 0, _ptr(self.spec), _stream()),

@@ -419,11 +419,15 @@ def getTargetSpectrogramEstimates(targetCoefficientMasks, complexMixtureSpectrog
 
     ``reconstruction='ratio'`` (not in the reference): the Wiener-like ratio mask X_c * W.(H_c o M_i) / den instead of W.(H_c o M_i) with
     the mixture phase.  Masks that came from getTargetCoefficientMasks take the one-hot form (den = the sum of the targets' numerators:
-    the targets add up to the mixture); any other mask array takes the soft form (den = W.H_c).  At most 8 targets."""
+    the targets add up to the mixture); any other mask array takes the soft form (den = W.H_c).  At most 8 targets.
+
+    ``reconstruction='spatial'``: either form of the ratio mask followed by the multichannel Wiener filter of csrc/spatial.hip (one 2 x 2
+    spatial covariance per target and bin from the masked estimates, then v_i R_i (sum_j v_j R_j)^-1 applied to the stereo mixture)."""
     M = np.asarray(targetCoefficientMasks)
     X = np.asarray(complexMixtureSpectrogram)
     S, K, T = M.shape
-    ratio = check_reconstruction(reconstruction, S) == 'ratio'
+    spatial = check_reconstruction(reconstruction, S) == 'spatial'
+    ratio = spatial or reconstruction == 'ratio'
     C, F, _ = X.shape
     if C != 2:
         raise ValueError('stereo spectrogram expected')
@@ -447,10 +451,14 @@ def getTargetSpectrogramEstimates(targetCoefficientMasks, complexMixtureSpectrog
         dW = _device_W(sc, W, g, dev)
         dH = sc.dev('H', (g.Kp, g.Np), corner=(K, g.N))
         dH[:K, :g.N].unflatten(1, (2, T)).copy_(sc.upload(np.asarray(stereoH), 'stereoH', float32).permute(1, 0, 2))   # (K, [L | R])
-        ws = None if ratio else sc.dev('ws_rec', (lib.gccnmf_reconstruct_workspace_floats(T, K, S, 1),))
+        if spatial:
+            ws = sc.dev('ws_cov', (_hip.reconstruct_spatial_workspace_floats(1, S, g.Fp),))
+        else:
+            ws = None if ratio else sc.dev('ws_rec', (lib.gccnmf_reconstruct_workspace_floats(T, K, S, 1),))
         spec = sc.dev('spec', (2 * S, g.Fp, g.Tp, 2))
         _hip.check(lib.gccnmf_reconstruct(_ptr(dW), _ptr(dH), _ptr(dA), _ptr(dM), _ptr(dX), _ptr(dV), F, T, K,
-                                          S | GCCNMF_RECONSTRUCT_RATIO if ratio else S, 1, _ptr(ws), _ptr(spec), _stream()),
+                                          S | GCCNMF_RECONSTRUCT_RATIO if ratio else S, _hip.reconstruct_spatial_batch(1) if spatial else 1,
+                                          _ptr(ws), _ptr(spec), _stream()),
                    'gccnmf_reconstruct')
         out = sc.download(torch.view_as_complex(spec)[:, :F, :T], shape=(S, 2, F, T))
         sc.remember(out, 'S', dict(spec=spec), dict(nsig=2 * S, F=F, T=T))

@@ -66,3 +66,33 @@ def moving_source_mixture(seed, numSamples=96000, sampleRate=16000, staticDelay=
     pcm = np.round(x * scale * 32768).astype(np.int16)
     x = (pcm.astype('float32') / 32768).astype(np.float32)
     return (x, np.stack(sources) * scale) if returnSources else x
+
+
+def reverberant_mixture(seed, numSamples=96000, sampleRate=16000, delays=(-20, 3, 27), responseMs=3.0, reverbGain=0.4,
+                        returnSources=False):
+    """Three talkers in a (slightly) reverberant room: low-passed noise sources with syllable-rate on/off envelopes, each convolved per
+    channel with its own short seeded decaying impulse response (a unit direct path followed by ``responseMs`` of exponentially decaying
+    noise, ``reverbGain`` at its start) on top of the integer delay of its right channel.  The two channels of a source are therefore
+    not delayed copies of each other: its spatial covariance has full rank in every bin, which is what the spatial reconstruction
+    models and a per-channel mask cannot use.  No sensor noise: the int16 rounding is the noise floor.  int16-representable float32
+    samples as in synthetic_mixture.  ``returnSources``: also the sources' stereo images (3, 2, numSamples), float64, on the mixture's
+    scale; they add up to the mixture before it is rounded to int16."""
+    from scipy.signal import butter, lfilter
+    rng = np.random.default_rng(20261018 + seed)
+    t = np.arange(numSamples) / float(sampleRate)
+    b, a = butter(4, 4000.0 / (sampleRate / 2.0))
+    taps = max(2, int(round(responseMs * 1e-3 * sampleRate)))
+    decay = np.exp(-np.arange(1, taps) / (taps / 4.0))
+    images = []
+    for j, d in enumerate(delays):
+        s = lfilter(b, a, rng.standard_normal(numSamples))
+        phi = rng.uniform(0, 2 * np.pi)
+        s = s * (0.5 * (1 + np.sin(2 * np.pi * (2.0 + 0.7 * j) * t + phi))) ** 4
+        h = [np.concatenate([[1.0], reverbGain * decay * rng.standard_normal(taps - 1)]) for _ in range(2)]
+        images.append(np.stack([np.convolve(s, h[0])[:numSamples], np.roll(np.convolve(s, h[1])[:numSamples], d)]))
+    images = np.stack(images)
+    x = images.sum(axis=0)
+    scale = 0.1 / np.max(np.abs(x))
+    pcm = np.round(x * scale * 32768).astype(np.int16)
+    x = (pcm.astype('float32') / 32768).astype(np.float32)
+    return (x, images * scale) if returnSources else x

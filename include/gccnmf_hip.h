@@ -345,8 +345,32 @@ int gccnmf_magnitude(const float* X, int F, int T, int batch, float* V, void* st
  * -- the numerator is the magnitude model of gccNMFFunctions.py:150, the mixture phase of :147-151 comes with X_c itself, and in the
  * one-hot form the targets add up to the mixture, sum_i S[i,c] = X_c, to a few ulp.  In this mode `V` and `workspace` are not read and
  * may be NULL, and every element of spec [batch][S*2][Fp][Tp] is written (rows >= F and frames >= T as zeros).  A file's spec does not
- * depend on the batch it is in.  gccnmf_reconstruct_workspace_floats keeps its meaning (the direct mode's need). */
+ * depend on the batch it is in.  gccnmf_reconstruct_workspace_floats keeps its meaning (the direct mode's need).
+ *
+ * Spatial (multichannel Wiener) mode: pass S | GCCNMF_RECONSTRUCT_RATIO and GCCNMF_RECONSTRUCT_SPATIAL_BATCH(batch) as batch (the mode
+ * rides in the upper half of batch, like GCCNMF_ANGULAR_NL_BATCH; batch <= 65535).  The ratio-mask stage runs exactly as above -- spec
+ * holds its bits -- and a spatial filter (csrc/spatial.hip, two launches) then replaces the estimates in place.  Per file, with
+ * S_i,c[f,t] the ratio-mode estimate of target i, channel c, and X[f,t] = (X_0, X_1)^T:
+ *   v_i[f,t] = 1/2 (|S_i,0|^2 + |S_i,1|^2)
+ *   p_c = sum_t |S_i,c|^2,  q = sum_t S_i,0 conj(S_i,1),  n = (p_0 + p_1) / 2        (frames t < T, float64, an order fixed by T alone)
+ *   R_i[f]   = [[p_0, q], [conj q, p_1]] / n  (trace 2);  R_i[f] = I when n = 0
+ *   R~_i[f]  = R_i[f] + GCCNMF_SPATIAL_LOADING * I, rounded to float32 once
+ *   Sigma[f,t] = sum_j v_j[f,t] R~_j[f]  (ascending j),  y = Sigma^-1 X  (closed 2 x 2 Hermitian inverse),  S'_i[f,t] = v_i[f,t] R~_i[f] y
+ *   every target is 0 where sum_j v_j[f,t] = 0 (as for den = 0 above); NaN / Inf in the inputs propagate; rows >= F and frames >= T
+ *   are written as zeros.  Sigma, y and S'_i are float32, each product and sum rounded on its own, evaluated on w_j = v_j 2^-e with e
+ *   the binary exponent of sum_j v_j: S'_i = w_i R~_i (sum_j w_j R~_j)^-1 X is the same quantity, has the same roundings while every
+ *   intermediate of the unscaled form is a normal float32 number, and stays accurate where that form's determinant would underflow (a
+ *   nearly silent frame).
+ * The targets still add up to the mixture (sum_i S'_i = Sigma y = X up to rounding), one target returns it, and swapping the input
+ * channels swaps the output channels.  `workspace` holds the covariances, [batch][S][Fp][4] float32 = (R~00, R~11, Re R~01, Im R~01):
+ * GCCNMF_RECONSTRUCT_SPATIAL_WORKSPACE_FLOATS(batch, S, Fp) floats, Fp = round_up(F, 16); it must be non-NULL and 16-byte aligned, else
+ * GCCNMF_ERR_ARG.  `V` is not read.  A file's spec does not depend on the batch it is in or on its place there.  GCCNMF_ERR_ARG: the
+ * spatial bit without GCCNMF_RECONSTRUCT_RATIO, any other bit above the low half of batch (so: a batch above 65535 in any mode). */
 #define GCCNMF_RECONSTRUCT_RATIO 0x100
+#define GCCNMF_RECONSTRUCT_SPATIAL_BIT (1 << 16)
+#define GCCNMF_RECONSTRUCT_SPATIAL_BATCH(batch) ((batch) | GCCNMF_RECONSTRUCT_SPATIAL_BIT)
+#define GCCNMF_RECONSTRUCT_SPATIAL_WORKSPACE_FLOATS(batch, S, Fp) (4L * (batch) * (S) * (Fp))
+#define GCCNMF_SPATIAL_LOADING 1e-3
 long gccnmf_reconstruct_workspace_floats(int T, int K, int S, int batch);
 int gccnmf_reconstruct(const float* W, const float* H, const unsigned char* argmax, const float* masks,
                        const float* X, const float* V, int F, int T, int K, int S, int batch, float* workspace,
