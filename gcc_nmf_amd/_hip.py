@@ -3,9 +3,17 @@
 The library is the product: there is NO CPU fallback.  If the shared object is
 missing (or its symbols do not match the header) importing this module's
 ``lib()`` raises ``HipLibraryError`` -- loudly, on every call path.
+
+Below ``lib()`` is the stage layer: one plain function per product stage, the ONLY place in the package that builds the mode words
+of the C ABI (modes are keywords here; pointers are tensors, None or raw addresses; the stream defaults to torch's current one).
 """
 import ctypes
+import math
+import numbers
 import os
+import warnings
+
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GCCNMF_HIP_LIB') or os.path.join(_HERE, 'libgccnmf_hip.so')     # override: A/B builds only
@@ -116,8 +124,6 @@ def check_gcc_phat_nl(gccPHATNLEnabled, gccPHATNLAlpha):
     """The reference's two GCC-NONLIN settings (gccNMF/realtime/config.py:42-43) as the engines, the named functions and the real-time
     processor take them; no device needed.  Returns (enabled, alpha): alpha a finite number > 0 that is a normal float32, ValueError
     otherwise (checked whether or not the setting is enabled, so a bad value cannot wait for the switch)."""
-    import math
-    import numbers
     a = gccPHATNLAlpha
     if isinstance(a, bool) or not isinstance(a, numbers.Real) or not math.isfinite(a) or not a > 0:
         raise ValueError('gccPHATNLAlpha must be a finite number > 0, got %r' % (a,))
@@ -127,16 +133,6 @@ def check_gcc_phat_nl(gccPHATNLEnabled, gccPHATNLAlpha):
     return bool(gccPHATNLEnabled), float(a32)
 
 
-def angular_nl_words(D, batch, alpha):
-    """(D, batch) arguments of gccnmf_angular_spectrogram with GCC-NONLIN on: the float32 bits of alpha in their upper halves
-    (GCCNMF_ANGULAR_NL_D / GCCNMF_ANGULAR_NL_BATCH of include/gccnmf_hip.h), as signed 32-bit values."""
-    if not (0 < int(D) < 65536 and 0 < int(batch) < 65536):
-        raise ValueError('GCC-NONLIN takes D and batch below 65536, got %r, %r' % (D, batch))
-    bits = ctypes.c_uint32.from_buffer_copy(ctypes.c_float(alpha)).value
-    signed = lambda v: ctypes.c_int32(v & 0xffffffff).value
-    return signed(int(D) | (bits & 0xffff0000)), signed(int(batch) | ((bits & 0xffff) << 16))
-
-
 def check_convergence(tolerance, checkEvery, numIterations):
     """The ``tolerance`` / ``checkEvery`` keywords of the engines, inferKLNMFCoefficients and performKLNMFUntilConverged, and the
     iteration count they cap; no device needed.  ``tolerance``: None (a fixed number of iterations) or a finite float with
@@ -144,8 +140,6 @@ def check_convergence(tolerance, checkEvery, numIterations):
     two checks, an integer >= 1 (checked whether or not a tolerance is given, so a bad value cannot wait for the switch).
     ``numIterations``: with a tolerance the maximum, an integer >= 0; without one it is the fixed count and is taken as
     ``int(numIterations)``, as it always was.  Returns (tolerance or None, checkEvery, numIterations)."""
-    import math
-    import numbers
     if tolerance is not None:
         if isinstance(tolerance, bool) or not isinstance(tolerance, numbers.Real) or not math.isfinite(tolerance) or not 0 < tolerance < 1:
             raise ValueError('tolerance must be None or a finite number with 0 < tolerance < 1, got %r' % (tolerance,))
@@ -159,31 +153,11 @@ def check_convergence(tolerance, checkEvery, numIterations):
     return tolerance, int(checkEvery), int(numIterations)
 
 
-GCCNMF_STAGE_DIVERGENCE = 7             # include/gccnmf_hip.h: gccnmf_klnmf_stage, "KL divergence of the current factors"
-GCCNMF_SCORES_TRACKS = 0x100            # include/gccnmf_hip.h: per-(target, frame) indexes in gccnmf_target_scores_masks
-TRACKS_MAX_FRAMES = (1 << 21) - 1
-GCCNMF_RECONSTRUCT_SPATIAL_BIT = 1 << 16  # include/gccnmf_hip.h: the spatial filter behind the ratio stage, in the upper half of gccnmf_reconstruct's batch
-GCCNMF_SPATIAL_LOADING = 1e-3           # include/gccnmf_hip.h: the diagonal loading of the spatial covariances
-
-
-def reconstruct_spatial_batch(batch):
-    """The batch argument of gccnmf_reconstruct in its spatial mode: GCCNMF_RECONSTRUCT_SPATIAL_BATCH(batch) of include/gccnmf_hip.h."""
-    if not 1 <= int(batch) <= 65535:
-        raise ValueError('the spatial reconstruction takes 1 to 65535 files per call, got %r' % (batch,))
-    return int(batch) | GCCNMF_RECONSTRUCT_SPATIAL_BIT
-
-
-def reconstruct_spatial_workspace_floats(batch, S, Fp):
-    """Floats of the covariance workspace of that mode: GCCNMF_RECONSTRUCT_SPATIAL_WORKSPACE_FLOATS(batch, S, Fp), Fp = round_up(F, 16)."""
-    return 4 * int(batch) * int(S) * int(Fp)
-
-
 def check_tdoa_tracking(tdoaTracking, localizationWindowSize, numSources):
     """The ``tdoaTracking`` / ``localizationWindowSize`` keywords of the engines and the window argument of
     estimateTargetTDOATracksFromAngularSpectrogram; no device needed.  The window is a number of frames: an integer >= 1 (checked
     whether or not tracking is on, so a bad value cannot wait for the switch), required when tracking is on; tracking also needs
     the number of sources (the peak rule keeps that many peaks per frame, 1 to 255).  Returns (tracking, window or None)."""
-    import numbers
     L = localizationWindowSize
     if L is not None:
         if isinstance(L, bool) or not isinstance(L, numbers.Integral) or L < 1:
@@ -196,14 +170,6 @@ def check_tdoa_tracking(tdoaTracking, localizationWindowSize, numSources):
         if S is None or isinstance(S, bool) or not isinstance(S, numbers.Integral) or not 1 <= S <= 255:
             raise ValueError('tdoaTracking needs the number of sources (1 to 255), got %r' % (S,))
     return bool(tdoaTracking), L
-
-
-def peaks_tracks_word(S, L, T):
-    """The S argument of gccnmf_pick_tdoa_peaks in its tracks mode: GCCNMF_PEAKS_TRACKS(S, L) of include/gccnmf_hip.h.  A window of
-    2T - 1 frames or more is the whole file for every frame, so L is passed as min(L, 2T - 1)."""
-    if not (1 <= int(S) <= 255 and 1 <= int(T) <= TRACKS_MAX_FRAMES and int(L) >= 1):
-        raise ValueError('tracks take 1 <= S <= 255, 1 <= T < 2^21 and L >= 1, got %r, %r, %r' % (S, T, L))
-    return int(S) | 0x100 | (min(int(L), 2 * int(T) - 1) << 9)
 
 
 _lib = None
@@ -245,7 +211,6 @@ def lib():
             msg = 'GCCNMF_TUNE: gccnmf_set_tuning(%d, %d) was rejected by %s' % (key, value, LIB_PATH)
             if os.environ.get('GCCNMF_TUNE_LENIENT', '') in ('', '0'):
                 raise HipLibraryError(msg)
-            import warnings
             warnings.warn(msg + ' -- running with that key at its default')
     _lib = handle
     return _lib
@@ -254,3 +219,182 @@ def lib():
 def check(status, what):
     if status != 0:
         raise HipLibraryError('%s failed: %s' % (what, STATUS.get(status, 'status %d' % status)))
+
+
+# ---- the stage layer ---------------------------------------------------------------------------------------------------------
+def _ptr(t):
+    """A pointer argument of the ABI: a tensor's address, a raw integer address as it is, None = null."""
+    return 0 if t is None else t if isinstance(t, int) else t.data_ptr()
+
+
+def _stream(device=None):
+    """Raw hipStream_t of torch's current stream on `device` (default: the current device)."""
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def _stage(name, *args, stream=None, what=None):
+    """One stage call: the arguments in the header's order (pointers, by the prototype, through ``_ptr``), the stream last, the
+    status checked under the entry point's name (or ``what``)."""
+    args = [_ptr(a) if t is c_void_p else a for a, t in zip(args, SIGNATURES[name][1])]
+    check(getattr(lib(), name)(*args, _stream() if stream is None else stream), what or name)
+
+
+def stft_stereo(x, n, n_fft, hop, T, batch, window, twiddle, X, V, CC, pcm16=False, stream=None):
+    """x: [batch][2][n] float32 samples, or with pcm16 [batch][n][2] int16 interleaved frames (contiguous files either way)."""
+    name, stride = ('gccnmf_stft_stereo_pcm16', n) if pcm16 else ('gccnmf_stft_stereo', 2 * n)
+    _stage(name, x, stride, n, n_fft, hop, T, batch, window, twiddle, X, V, CC, stream=stream)
+
+
+def istft_ola(spec, nsig, n_fft, hop, T, batch, window, twiddle, gain, center, frames, y, stream=None):
+    """frames: None = the fused inverse transform + overlap-add where the library has one, else the scratch of the two-kernel form."""
+    _stage('gccnmf_istft_ola', spec, nsig, n_fft, hop, T, batch, window, twiddle, gain, 1 if center else 0, frames, y, stream=stream)
+
+
+def ola_frames_halo(previous, halo, frames, nsig, n_fft, hop, T, first, L, gain, y, stream=None):
+    _stage('gccnmf_ola_frames_halo', previous, halo, frames, nsig, n_fft, hop, T, first, L, gain, y, stream=stream)
+
+
+def pack_pcm16(y, nsig, L, peak, out, stream=None):
+    _stage('gccnmf_pack_pcm16', y, nsig, L, peak, out, stream=stream)
+
+
+def coherence(X, F, T, batch, CC, stream=None):
+    _stage('gccnmf_coherence', X, F, T, batch, CC, stream=stream)
+
+
+def magnitude(X, F, T, batch, V, stream=None):
+    _stage('gccnmf_magnitude', X, F, T, batch, V, stream=stream)
+
+
+GCCNMF_FLAG_FIXED_W = 1 << 16           # include/gccnmf_hip.h: W is one shared [Fp][Kp] dictionary and is never updated
+GCCNMF_FLAG_H_ONES = 1 << 17            # include/gccnmf_hip.h: H starts as all ones (output only)
+GCCNMF_STAGE_DIVERGENCE = 7             # include/gccnmf_hip.h: gccnmf_klnmf_stage, "KL divergence of the current factors"
+
+
+def klnmf(V, W, H, ws, F, N, K, batch, iterations, alpha, eps, fixed_w=False, h_ones=False, groups=1, flags=0, stream=None):
+    """``iterations`` KL-NMF iterations on W and H in place.  groups > 1: this call is one of that many concurrent ones
+    (GCCNMF_FLAG_GROUPS(n) = 4 | n << 8: launch forms are chosen for all groups together); flags: further low flag bits."""
+    flags |= (GCCNMF_FLAG_FIXED_W if fixed_w else 0) | (GCCNMF_FLAG_H_ONES if h_ones else 0) | (4 | groups << 8 if groups > 1 else 0)
+    _stage('gccnmf_klnmf', V, W, H, ws, F, N, K, batch, iterations, alpha, eps, flags, stream=stream)
+
+
+def klnmf_divergence(V, W, H, ws, F, N, K, batch, fixed=False, stream=None):
+    """One stage-7 launch of gccnmf_klnmf_stage: D(V || W.H) of every file of a padded batch.  Returns the (batch,) float64 DEVICE
+    view of the result inside the workspace `ws` (valid until the workspace is used again); asynchronous.  fixed: W is one shared
+    [Fp][Kp] dictionary."""
+    Fp, Np = -(-F // 16) * 16, -(-N // 64) * 64
+    _stage('gccnmf_klnmf_stage', V, W, H, ws, F, N, K, batch, 0.0, 0.0, GCCNMF_FLAG_FIXED_W if fixed else 0, GCCNMF_STAGE_DIVERGENCE,
+           stream=stream, what='gccnmf_klnmf_stage (divergence)')
+    at = batch * Fp * Np
+    return ws[at:at + 2 * batch].view(torch.float64)
+
+
+def klnmf_chain_status(ws, F, N, K, batch):
+    """Status word of the last chained KL-NMF launch in the workspace `ws` (0 = clean or not chained); the caller has synchronised."""
+    st = c_int(0)
+    check(lib().gccnmf_klnmf_chain_status(_ptr(ws), F, N, K, batch, ctypes.byref(st)), 'gccnmf_klnmf_chain_status')
+    return st.value
+
+
+def angular_nl_words(D, batch, alpha):
+    """(D, batch) arguments of gccnmf_angular_spectrogram with GCC-NONLIN on: the float32 bits of alpha in their upper halves
+    (GCCNMF_ANGULAR_NL_D / GCCNMF_ANGULAR_NL_BATCH of include/gccnmf_hip.h), as signed 32-bit values."""
+    if not (0 < int(D) < 65536 and 0 < int(batch) < 65536):
+        raise ValueError('GCC-NONLIN takes D and batch below 65536, got %r, %r' % (D, batch))
+    bits = ctypes.c_uint32.from_buffer_copy(ctypes.c_float(alpha)).value
+    signed = lambda v: ctypes.c_int32(v & 0xffffffff).value
+    return signed(int(D) | (bits & 0xffff0000)), signed(int(batch) | ((bits & 0xffff) << 16))
+
+
+def angular_spectrogram(CC, trig, F, T, D, batch, ang, mean_ang, nl_alpha=None, stream=None):
+    """nl_alpha: None = GCC-PHAT, else the GCC-NONLIN spectrum with that alpha (only the localisation changes)."""
+    if nl_alpha is not None:
+        D, batch = angular_nl_words(D, batch, nl_alpha)
+    _stage('gccnmf_angular_spectrogram', CC, trig, F, T, D, batch, ang, mean_ang, stream=stream)
+
+
+def pick_tdoa_peaks(mean_ang, D, Dp, S, batch, idx, status, stream=None):
+    """The S largest peaks of each file's mean angular spectrum [batch][Dp] -> idx [batch][S], status [batch]."""
+    _stage('gccnmf_pick_tdoa_peaks', mean_ang, D, Dp, S, batch, idx, status, stream=stream)
+
+
+TRACKS_MAX_FRAMES = (1 << 21) - 1
+
+
+def peaks_tracks_word(S, L, T):
+    """The S argument of gccnmf_pick_tdoa_peaks in its tracks mode: GCCNMF_PEAKS_TRACKS(S, L) of include/gccnmf_hip.h.  A window of
+    2T - 1 frames or more is the whole file for every frame, so L is passed as min(L, 2T - 1)."""
+    if not (1 <= int(S) <= 255 and 1 <= int(T) <= TRACKS_MAX_FRAMES and int(L) >= 1):
+        raise ValueError('tracks take 1 <= S <= 255, 1 <= T < 2^21 and L >= 1, got %r, %r, %r' % (S, T, L))
+    return int(S) | 0x100 | (min(int(L), 2 * int(T) - 1) << 9)
+
+
+def pick_tdoa_tracks(ang, D, T, S, window, batch, tracks, status, stream=None):
+    """The same entry point in its tracks mode: reads the angular spectrogram itself (the Dp argument carries T) and writes the peaks
+    of every frame's windowed mean -> tracks [batch][S][Tp], status [batch][Tp]."""
+    _stage('gccnmf_pick_tdoa_peaks', ang, D, T, peaks_tracks_word(S, window, T), batch, tracks, status, stream=stream,
+           what='gccnmf_pick_tdoa_peaks (tracks)')
+
+
+GCCNMF_SCORES_TRACKS = 0x100            # include/gccnmf_hip.h: per-(target, frame) indexes in gccnmf_target_scores_masks
+
+
+def target_scores_masks(CC, trig, idx, W, F, T, K, D, S, batch, ws, scores, argmax, tracks=False, stream=None):
+    """idx: one TDOA index per (file, target), or with tracks one per (file, target, frame) [batch][S][Tp]."""
+    _stage('gccnmf_target_scores_masks', CC, trig, idx, W, F, T, K, D, S | GCCNMF_SCORES_TRACKS if tracks else S, batch, ws, scores,
+           argmax, stream=stream)
+
+
+def argmax_targets(scores, K, T, S, batch, argmax, stream=None):
+    _stage('gccnmf_argmax_targets', scores, K, T, S, batch, argmax, stream=stream)
+
+
+RECONSTRUCTIONS = ('direct', 'ratio', 'spatial')
+GCCNMF_RECONSTRUCT_RATIO = 0x100        # include/gccnmf_hip.h: the ratio-mask mode of gccnmf_reconstruct, above the low byte of S
+RATIO_MAX_TARGETS = 8                   # csrc/ratio.h, csrc/spatial.h
+GCCNMF_RECONSTRUCT_SPATIAL_BIT = 1 << 16  # include/gccnmf_hip.h: the spatial filter behind the ratio stage, in the upper half of gccnmf_reconstruct's batch
+GCCNMF_SPATIAL_LOADING = 1e-3           # include/gccnmf_hip.h: the diagonal loading of the spatial covariances
+
+
+def check_reconstruction(reconstruction, numTargets):
+    """The ``reconstruction`` keyword of the engines and of getTargetSpectrogramEstimates; ValueError before any device work."""
+    if reconstruction not in RECONSTRUCTIONS:
+        raise ValueError("reconstruction must be 'direct', 'ratio' or 'spatial', got %r" % (reconstruction,))
+    if reconstruction != 'direct' and not 1 <= int(numTargets) <= RATIO_MAX_TARGETS:
+        raise ValueError("reconstruction=%r takes 1 to %d targets, got %d" % (reconstruction, RATIO_MAX_TARGETS, int(numTargets)))
+    return reconstruction
+
+
+def reconstruct_spatial_batch(batch):
+    """The batch argument of gccnmf_reconstruct in its spatial mode: GCCNMF_RECONSTRUCT_SPATIAL_BATCH(batch) of include/gccnmf_hip.h."""
+    if not 1 <= int(batch) <= 65535:
+        raise ValueError('the spatial reconstruction takes 1 to 65535 files per call, got %r' % (batch,))
+    return int(batch) | GCCNMF_RECONSTRUCT_SPATIAL_BIT
+
+
+def reconstruct_spatial_workspace_floats(batch, S, Fp):
+    """Floats of the covariance workspace of that mode: GCCNMF_RECONSTRUCT_SPATIAL_WORKSPACE_FLOATS(batch, S, Fp), Fp = round_up(F, 16)."""
+    return 4 * int(batch) * int(S) * int(Fp)
+
+
+def reconstruct_workspace_floats(mode, T, K, S, batch, Fp):
+    """Floats of the workspace ``reconstruct`` takes in that mode: the masked H of 'direct', nothing for 'ratio' (one fused launch),
+    the covariances [batch][S][Fp][4] of 'spatial'."""
+    if mode == 'direct':
+        return lib().gccnmf_reconstruct_workspace_floats(T, K, S, batch)
+    return reconstruct_spatial_workspace_floats(batch, S, Fp) if mode == 'spatial' else 0
+
+
+def reconstruct(W, H, argmax, masks, X, V, F, T, K, S, batch, spec, mode='direct', workspace=None, stream=None):
+    """Target spectrograms from the arg-max image or the masks (either may be None).  'ratio' reads neither V nor a workspace;
+    'spatial' is the ratio launch, then the covariance reduction and the 2 x 2 filter over spec in place, with the covariances in
+    ``workspace`` (a missing 'direct' workspace is the library's GCCNMF_ERR_ARG, as a missing V is)."""
+    if mode not in RECONSTRUCTIONS:
+        raise ValueError('unknown reconstruction mode %r' % (mode,))
+    if mode == 'spatial':
+        if workspace is None:
+            raise ValueError("reconstruction='spatial' needs its covariance workspace (reconstruct_workspace_floats)")
+        batch = reconstruct_spatial_batch(batch)
+    if mode != 'direct':
+        S |= GCCNMF_RECONSTRUCT_RATIO
+    _stage('gccnmf_reconstruct', W, H, argmax, masks, X, V, F, T, K, S, batch, None if mode == 'ratio' else workspace, spec, stream=stream)

@@ -591,16 +591,14 @@ class HipTimeShard(object):
     @_on_device
     def angular_sum(self):
         e, g = self.e, self.e.g
-        _hip.check(e.lib.gccnmf_angular_spectrogram(_ptr(e.CC), _ptr(e.trig), g.F, g.T, g.D, 1, _ptr(e.ang), _ptr(e.mean_ang), _stream()),
-                   'gccnmf_angular_spectrogram')
+        _hip.angular_spectrogram(e.CC, e.trig, g.F, g.T, g.D, 1, e.ang, e.mean_ang)
         return e.mean_ang[0, :g.D] * float(g.T)                  # float64: mean over own frames * own frames
 
     @_on_device
     def set_angular_mean(self, mean):
         e, g = self.e, self.e.g
         e.mean_ang[0, :g.D].copy_(mean.to(e.mean_ang.device))
-        _hip.check(e.lib.gccnmf_pick_tdoa_peaks(_ptr(e.mean_ang), g.D, g.Dp, g.S, 1, _ptr(e.tdoa_idx), _ptr(e.status), _stream()),
-                   'gccnmf_pick_tdoa_peaks')
+        _hip.pick_tdoa_peaks(e.mean_ang, g.D, g.Dp, g.S, 1, e.tdoa_idx, e.status)
         e.check_status()
 
     @_on_device
@@ -629,8 +627,7 @@ class HipTimeShard(object):
         # frames = the previous rank's last `halo` frames, then the own ones, in ascending order -- read from where they are
         halo = self.halo if previous is not None else 0
         first = self.halo * self.hop - (self.halo - halo) * self.hop                      # rank 0 has no predecessor: its stream starts at its own frame 0
-        _hip.check(e.lib.gccnmf_ola_frames_halo(_ptr(previous), halo, _ptr(e.frames[0]), nsig, self.n_fft, self.hop, g.T, first, L, gain,
-                                                _ptr(self._y), _stream()), 'gccnmf_ola_frames_halo')
+        _hip.ola_frames_halo(previous, halo, e.frames[0], nsig, self.n_fft, self.hop, g.T, first, L, gain, self._y)
         self._y_host.copy_(self._y, non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()
         return self._y_host.numpy().reshape(g.S, 2, L), self.t0 * self.hop - self.n_fft // 2    # centre trim (librosaSTFT.py:283-284)

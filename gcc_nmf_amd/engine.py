@@ -9,27 +9,22 @@ host (gccNMF/gccNMFFunctions.py:53-59, :70-73, :87-89).
 
 Stage order = gccNMF/runGCCNMF.py:36-52.
 """
+import ctypes
+import functools
+import warnings
+
 import numpy as np
 import torch
 
 from . import _hip
+from ._hip import (_ptr, _stream, klnmf_divergence, check_gcc_phat_nl, check_tdoa_tracking, check_reconstruction,       # noqa: F401
+                   GCCNMF_FLAG_FIXED_W, GCCNMF_FLAG_H_ONES, GCCNMF_RECONSTRUCT_RATIO, RECONSTRUCTIONS, RATIO_MAX_TARGETS)
 
 SPEED_OF_SOUND_IN_METRES_PER_SECOND = 340.29          # gccNMF/gccNMFFunctions.py:38
 
 
-def _ptr(t):
-    return 0 if t is None else t.data_ptr()
-
-
-def _stream(device=None):
-    """Raw hipStream_t of torch's current stream on `device` (default: the current device)."""
-    return torch.cuda.current_stream(device).cuda_stream
-
-
 def _on_device(method):
     """The C library launches on the CURRENT HIP device: make the object's device current for the duration of the call."""
-    import functools
-
     @functools.wraps(method)
     def wrapper(self, *args, **kwargs):
         with torch.cuda.device(self.device):
@@ -52,17 +47,6 @@ def klnmf_initial_factors(F, N, K, epsilon=1e-16, seedValue=0):
 
 class ChainHandOverError(RuntimeError):
     """A chained KL-NMF launch of a chunk did not hand over cleanly (gccnmf_klnmf_chain_status): the run is repeated on plain launches."""
-
-
-def klnmf_divergence(lib, V, W, H, ws, F, N, K, batch, fixed=False):
-    """One stage-7 launch of gccnmf_klnmf_stage: D(V || W.H) of every file of a padded batch.  Returns the (batch,) float64 DEVICE
-    view of the result inside the workspace `ws` (valid until the workspace is used again); asynchronous.  fixed: W is one shared
-    [Fp][Kp] dictionary."""
-    Fp, Np = -(-F // 16) * 16, -(-N // 64) * 64
-    _hip.check(lib.gccnmf_klnmf_stage(_ptr(V), _ptr(W), _ptr(H), _ptr(ws), F, N, K, batch, 0.0, 0.0, GCCNMF_FLAG_FIXED_W if fixed else 0,
-                                      _hip.GCCNMF_STAGE_DIVERGENCE, _stream()), 'gccnmf_klnmf_stage (divergence)')
-    at = batch * Fp * Np
-    return ws[at:at + 2 * batch].view(torch.float64)
 
 
 def converge_klnmf(launch, divergence, factors, maxIterations, tolerance, checkEvery, failed=None):
@@ -119,24 +103,6 @@ def check_iterations(trace, checkEvery, maxIterations):
     return [c * checkEvery if c * checkEvery < maxIterations else maxIterations for c in range(len(trace))]
 
 
-GCCNMF_FLAG_FIXED_W = 1 << 16          # include/gccnmf_hip.h
-GCCNMF_RECONSTRUCT_RATIO = 0x100       # include/gccnmf_hip.h: the ratio-mask mode of gccnmf_reconstruct, above the low byte of S
-RECONSTRUCTIONS = ('direct', 'ratio', 'spatial')
-RATIO_MAX_TARGETS = 8                  # csrc/ratio.h, csrc/spatial.h
-
-
-def check_reconstruction(reconstruction, numTargets):
-    """The ``reconstruction`` keyword of the engines and of getTargetSpectrogramEstimates; ValueError before any device work."""
-    if reconstruction not in RECONSTRUCTIONS:
-        raise ValueError("reconstruction must be 'direct', 'ratio' or 'spatial', got %r" % (reconstruction,))
-    if reconstruction != 'direct' and not 1 <= int(numTargets) <= RATIO_MAX_TARGETS:
-        raise ValueError("reconstruction=%r takes 1 to %d targets, got %d" % (reconstruction, RATIO_MAX_TARGETS, int(numTargets)))
-    return reconstruction
-GCCNMF_FLAG_H_ONES = 1 << 17
-check_gcc_phat_nl = _hip.check_gcc_phat_nl        # the gccPHATNLEnabled / gccPHATNLAlpha keywords; ValueError before any device work
-check_tdoa_tracking = _hip.check_tdoa_tracking    # the tdoaTracking / localizationWindowSize keywords; ValueError before any device work
-
-
 def check_dictionary(W, F):
     """A pre-trained dictionary as the fixed-dictionary call takes it: finite, non-negative float32 (F, K) with 1 <= K <= 1024."""
     W = np.asarray(W)
@@ -178,23 +144,19 @@ def inferKLNMFCoefficients(V, W, numIterations, sparsityAlpha=0, epsilon=1e-16, 
         Vd[:, :F, :N] = torch.from_numpy(np.ascontiguousarray(V)).to(dev)
         Wd = padded(W, (g.Fp, g.Kp), dev)
         Hd = torch.zeros((B, g.Kp, Np), dtype=torch.float32, device=dev)
-        flags = GCCNMF_FLAG_FIXED_W
-        if initialH == 'ones':
-            flags |= GCCNMF_FLAG_H_ONES
-        else:
+        if initialH != 'ones':
             Hd[:, :K, :N] = torch.from_numpy(klnmf_initial_factors(F, N, K, epsilon, seedValue)[1]).to(dev)
         ws = torch.zeros(lib.gccnmf_klnmf_workspace_floats(F, N, K, B), dtype=torch.float32, device=dev)
 
         def launch(n, first):            # (the all-ones start is a flag of the first call only: later chunks continue from H)
-            _hip.check(lib.gccnmf_klnmf(_ptr(Vd), _ptr(Wd), _ptr(Hd), _ptr(ws), F, N, K, B, n, float(sparsityAlpha), float(epsilon),
-                                        flags if first else GCCNMF_FLAG_FIXED_W, _stream()), 'gccnmf_klnmf')
+            _hip.klnmf(Vd, Wd, Hd, ws, F, N, K, B, n, float(sparsityAlpha), float(epsilon), fixed_w=True, h_ones=first and initialH == 'ones')
         if tolerance is None:
             launch(numIterations, True)
             H = Hd[:, :K, :N].cpu().numpy()
             return H[0] if single else H
         if initialH == 'ones':
             Hd[:, :K, :N] = 1            # the divergence of the initial factors reads H
-        iterations, trace = converge_klnmf(launch, lambda: klnmf_divergence(lib, Vd, Wd, Hd, ws, F, N, K, B, fixed=True).cpu().numpy(),
+        iterations, trace = converge_klnmf(launch, lambda: klnmf_divergence(Vd, Wd, Hd, ws, F, N, K, B, fixed=True).cpu().numpy(),
                                            [Hd], numIterations, tolerance, checkEvery)
         H = Hd[:, :K, :N].cpu().numpy()
     checks = check_iterations(trace, checkEvery, numIterations)
@@ -224,7 +186,6 @@ class Geometry(object):
     """Padded storage geometry; the pitches come from the library so host and kernels cannot disagree."""
 
     def __init__(self, F, T, K, D=1, S=1):
-        import ctypes
         vals = [ctypes.c_int() for _ in range(4)]
         _hip.check(_hip.lib().gccnmf_pitches(F, T, K, *[ctypes.byref(v) for v in vals]), 'gccnmf_pitches')
         self.F, self.T, self.K, self.D, self.S = F, T, K, D, S
@@ -391,9 +352,9 @@ class GCCNMFEngine(object):
             self.ws_scores = z(self.lib.gccnmf_scores_workspace_floats(F, T, g.S, B))
             self.scores = z(B, g.Kp, g.S * g.Tp)
             self.argmax = torch.zeros((B, g.Kp, g.Tp), dtype=torch.uint8, device=dev)
-            self.ws_rec = None if self.reconstruction != 'direct' else z(self.lib.gccnmf_reconstruct_workspace_floats(T, g.K, g.S, B))
+            self.ws_rec = z(self._reconstruct_workspace_floats()) if self.reconstruction == 'direct' else None
             # the spatial mode's covariances [B][S][Fp][4]; an engine switched to 'spatial' later allocates them at its first reconstruct()
-            self.ws_cov = z(_hip.reconstruct_spatial_workspace_floats(B, g.S, g.Fp)) if self.reconstruction == 'spatial' else None
+            self.ws_cov = z(self._reconstruct_workspace_floats()) if self.reconstruction == 'spatial' else None
             self.spec = z(B, 2 * g.S, g.Fp, g.Tp, 2)
             # windowed time frames [B][2S][T][n_fft]: only the two-kernel iSTFT needs them (allocated on first use); the default is the
             # fused inverse-transform + overlap-add pass, available while n_fft + 3 * hop <= 2048
@@ -408,15 +369,9 @@ class GCCNMFEngine(object):
     # ---- stages (each asynchronous on the current torch stream) ---------------------------------
     @_on_device
     def stft(self):
-        g = self.g
-        if self.pcm_in is not None:       # int16 interleaved frames straight from the wav data chunk
-            _hip.check(self.lib.gccnmf_stft_stereo_pcm16(_ptr(self.pcm_in), self.n_samples, self.n_samples, self.n_fft, self.hop, g.T,
-                                                         self.batch, _ptr(self.window), _ptr(self.twiddle), _ptr(self.X), _ptr(self.V),
-                                                         _ptr(self.CC), _stream()), 'gccnmf_stft_stereo_pcm16')
-            return
-        _hip.check(self.lib.gccnmf_stft_stereo(_ptr(self.x), 2 * self.n_samples, self.n_samples, self.n_fft, self.hop, g.T,
-                                               self.batch, _ptr(self.window), _ptr(self.twiddle), _ptr(self.X), _ptr(self.V),
-                                               _ptr(self.CC), _stream()), 'gccnmf_stft_stereo')
+        pcm = self.pcm_in is not None     # int16 interleaved frames straight from the wav data chunk
+        _hip.stft_stereo(self.pcm_in if pcm else self.x, self.n_samples, self.n_fft, self.hop, self.g.T, self.batch, self.window, self.twiddle,
+                         self.X, self.V, self.CC, pcm16=pcm)
 
     @_on_device
     def pack_pcm16(self):
@@ -425,8 +380,7 @@ class GCCNMFEngine(object):
         if self.pcm_out is None:
             self.pcm_out = torch.zeros((self.batch, g.S, self.L, 2), dtype=torch.int16, device=self.device)
             self.pcm_peak = torch.zeros((self.batch * g.S,), dtype=torch.int32, device=self.device)
-        _hip.check(self.lib.gccnmf_pack_pcm16(_ptr(self.y), self.batch * g.S, self.L, _ptr(self.pcm_peak), _ptr(self.pcm_out), _stream()),
-                   'gccnmf_pack_pcm16')
+        _hip.pack_pcm16(self.y, self.batch * g.S, self.L, self.pcm_peak, self.pcm_out)
 
     @_on_device
     def klnmf(self):
@@ -448,10 +402,12 @@ class GCCNMFEngine(object):
             except ChainHandOverError:
                 if attempt:
                     raise
-                import warnings
-                warnings.warn('gcc_nmf_amd: a chained KL-NMF launch did not hand over cleanly; this process falls back to the plain launches '
-                              '(gccnmf_set_tuning(21, 0)) and repeats the batch', RuntimeWarning)
-                _hip.check(self.lib.gccnmf_set_tuning(21, 0), 'gccnmf_set_tuning')
+                self._fall_back_to_plain_launches()
+
+    def _fall_back_to_plain_launches(self):
+        warnings.warn('gcc_nmf_amd: a chained KL-NMF launch did not hand over cleanly; this process falls back to the plain launches '
+                      '(gccnmf_set_tuning(21, 0)) and repeats the batch', RuntimeWarning)
+        _hip.check(self.lib.gccnmf_set_tuning(21, 0), 'gccnmf_set_tuning')
 
     def _klnmf_start(self):
         """The initial factors into W and H (a fixed dictionary with the all-ones start needs none: H is then output only)."""
@@ -462,15 +418,19 @@ class GCCNMFEngine(object):
         self.W.copy_(self.W0.unsqueeze(0).expand_as(self.W))
         self.H.copy_(self.H0.unsqueeze(0).expand_as(self.H))
 
+    def _groups(self):
+        """(first file, files, workspace, stream or None) of every KL-NMF file group: equal shares of the batch and of ws_nmf (a group's
+        status words sit at the end of its own share); a single group is the whole batch on the current stream."""
+        per, ws_per = self.batch // self.nmf_groups, self.ws_nmf.numel() // self.nmf_groups
+        for i in range(self.nmf_groups):
+            yield i * per, per, self.ws_nmf[i * ws_per:], self.nmf_streams[i] if self.nmf_streams else None
+
     def _divergence(self):
-        """(batch,) float64 on the device: stage 7 per file group, each in its own workspace (a group's status words sit at the end of
-        its own slice)."""
+        """(batch,) float64 on the device: stage 7 per file group, each in its own workspace."""
         g = self.g
-        per = self.batch // self.nmf_groups
-        ws_per = self.ws_nmf.numel() // self.nmf_groups
         fixed = self.dictionaryW is not None
-        out = [klnmf_divergence(self.lib, self.V[i * per], self.W0 if fixed else self.W[i * per], self.H[i * per], self.ws_nmf[i * ws_per:],
-                                g.F, g.N, g.K, per, fixed) for i in range(self.nmf_groups)]
+        out = [klnmf_divergence(self.V[b0], self.W0 if fixed else self.W[b0], self.H[b0], ws, g.F, g.N, g.K, per, fixed)
+               for b0, per, ws, _ in self._groups()]
         return out[0] if len(out) == 1 else torch.cat(out)
 
     @_on_device
@@ -494,76 +454,51 @@ class GCCNMFEngine(object):
     def _klnmf_iterate(self, iters, first):
         """``iters`` more iterations on W and H in place, as the library chooses to launch them (first: the first call of a run)."""
         g = self.g
-        if self.dictionaryW is not None:
-            flags = GCCNMF_FLAG_FIXED_W
-            if self.initialH == 'ones' and first:
-                flags |= GCCNMF_FLAG_H_ONES                         # H is output only: no H0 broadcast
-            _hip.check(self.lib.gccnmf_klnmf(_ptr(self.V), _ptr(self.W0), _ptr(self.H), _ptr(self.ws_nmf), g.F, g.N, g.K, self.batch,
-                                             iters, self.alpha, self.eps, flags, _stream()), 'gccnmf_klnmf')
-            return
-        if self.nmf_groups == 1:
-            _hip.check(self.lib.gccnmf_klnmf(_ptr(self.V), _ptr(self.W), _ptr(self.H), _ptr(self.ws_nmf), g.F, g.N, g.K, self.batch,
-                                             iters, self.alpha, self.eps, self.klnmf_flags, _stream()), 'gccnmf_klnmf')
-            return
-        main = torch.cuda.current_stream(self.device)
-        ready = torch.cuda.Event()
-        ready.record(main)
-        per = self.batch // self.nmf_groups
-        ws_per = self.ws_nmf.numel() // self.nmf_groups
-        for i, st in enumerate(self.nmf_streams):
-            st.wait_event(ready)
-            b0 = i * per
-            # GCCNMF_FLAG_GROUPS(n) = 4 | n << 8: the groups' launches share the chip, so launch forms are chosen for all groups together (a
-            # file's bits do not depend on the split) and each keeps the throughput tile -- its
-            # partial last round overlaps the other group's kernels (all-half-height tiles, which win for a 32-file launch ALONE,
-            # lose here: 152.4 k vs 155.4 k frames/s)
-            _hip.check(self.lib.gccnmf_klnmf(_ptr(self.V[b0]), _ptr(self.W[b0]), _ptr(self.H[b0]), _ptr(self.ws_nmf[i * ws_per:]), g.F, g.N,
-                                             g.K, per, iters, self.alpha, self.eps, self.klnmf_flags | 4 | (self.nmf_groups << 8), st.cuda_stream), 'gccnmf_klnmf')
-            done = torch.cuda.Event()
-            done.record(st)
-            main.wait_event(done)
+        fixed = self.dictionaryW is not None        # (one group then; with the all-ones start H is output only: no H0 broadcast)
+        if self.nmf_groups > 1:
+            main = torch.cuda.current_stream(self.device)
+            ready = torch.cuda.Event()
+            ready.record(main)
+        for b0, per, ws, st in self._groups():
+            if st is not None:
+                st.wait_event(ready)
+            # groups: the groups' launches share the chip, so launch forms are chosen for all groups together (a file's bits do not
+            # depend on the split) and each keeps the throughput tile -- its partial last round overlaps the other group's kernels
+            # (all-half-height tiles, which win for a 32-file launch ALONE, lose here: 152.4 k vs 155.4 k frames/s)
+            _hip.klnmf(self.V[b0], self.W0 if fixed else self.W[b0], self.H[b0], ws, g.F, g.N, g.K, per, iters, self.alpha, self.eps,
+                       fixed_w=fixed, h_ones=fixed and first and self.initialH == 'ones', groups=self.nmf_groups,
+                       flags=0 if fixed else self.klnmf_flags, stream=None if st is None else st.cuda_stream)
+            if st is not None:
+                done = torch.cuda.Event()
+                done.record(st)
+                main.wait_event(done)
 
     @_on_device
     def localize(self):
         g = self.g
-        # GCC-NONLIN: the same call with alpha in the upper halves of D and batch (include/gccnmf_hip.h); only the localisation changes
-        D, B = _hip.angular_nl_words(g.D, self.batch, self.gccPHATNLAlpha) if self.gccPHATNLEnabled else (g.D, self.batch)
-        _hip.check(self.lib.gccnmf_angular_spectrogram(_ptr(self.CC), _ptr(self.trig), g.F, g.T, D, B, _ptr(self.ang),
-                                                       _ptr(self.mean_ang), _stream()), 'gccnmf_angular_spectrogram')
-        _hip.check(self.lib.gccnmf_pick_tdoa_peaks(_ptr(self.mean_ang), g.D, g.Dp, g.S, self.batch, _ptr(self.tdoa_idx),
-                                                   _ptr(self.status), _stream()), 'gccnmf_pick_tdoa_peaks')
+        _hip.angular_spectrogram(self.CC, self.trig, g.F, g.T, g.D, self.batch, self.ang, self.mean_ang,
+                                 nl_alpha=self.gccPHATNLAlpha if self.gccPHATNLEnabled else None)
+        _hip.pick_tdoa_peaks(self.mean_ang, g.D, g.Dp, g.S, self.batch, self.tdoa_idx, self.status)
         if self.tdoaTracking:
-            # the same call in its tracks mode: reads ang itself (the Dp argument carries T), writes one index per (target, frame)
-            _hip.check(self.lib.gccnmf_pick_tdoa_peaks(_ptr(self.ang), g.D, g.T, _hip.peaks_tracks_word(g.S, self.localizationWindowSize, g.T),
-                                                       self.batch, _ptr(self.tracks), _ptr(self.track_status), _stream()),
-                       'gccnmf_pick_tdoa_peaks (tracks)')
+            _hip.pick_tdoa_tracks(self.ang, g.D, g.T, g.S, self.localizationWindowSize, self.batch, self.tracks, self.track_status)
 
     @_on_device
     def masks(self):
         g = self.g
-        idx, S = (self.tracks, g.S | _hip.GCCNMF_SCORES_TRACKS) if self.tdoaTracking else (self.tdoa_idx, g.S)
-        _hip.check(self.lib.gccnmf_target_scores_masks(_ptr(self.CC), _ptr(self.trig), _ptr(idx), _ptr(self.W), g.F, g.T,
-                                                       g.K, g.D, S, self.batch, _ptr(self.ws_scores), _ptr(self.scores),
-                                                       _ptr(self.argmax), _stream()), 'gccnmf_target_scores_masks')
+        _hip.target_scores_masks(self.CC, self.trig, self.tracks if self.tdoaTracking else self.tdoa_idx, self.W, g.F, g.T, g.K, g.D, g.S,
+                                 self.batch, self.ws_scores, self.scores, self.argmax, tracks=self.tdoaTracking)
+
+    def _reconstruct_workspace_floats(self):
+        g = self.g
+        return _hip.reconstruct_workspace_floats(self.reconstruction, g.T, g.K, g.S, self.batch, g.Fp)
 
     @_on_device
     def reconstruct(self):
         g = self.g
-        if self.reconstruction == 'spatial':    # the ratio launch, then the covariance reduction and the 2 x 2 filter over spec in place
-            if self.ws_cov is None:
-                self.ws_cov = torch.zeros(_hip.reconstruct_spatial_workspace_floats(self.batch, g.S, g.Fp), dtype=torch.float32, device=self.device)
-            _hip.check(self.lib.gccnmf_reconstruct(_ptr(self.W), _ptr(self.H), _ptr(self.argmax), 0, _ptr(self.X), 0, g.F, g.T, g.K,
-                                                   g.S | GCCNMF_RECONSTRUCT_RATIO, _hip.reconstruct_spatial_batch(self.batch),
-                                                   _ptr(self.ws_cov), _ptr(self.spec), _stream()), 'gccnmf_reconstruct')
-            return
-        if self.reconstruction == 'ratio':      # one fused launch: no masked-H workspace, |X| not read
-            _hip.check(self.lib.gccnmf_reconstruct(_ptr(self.W), _ptr(self.H), _ptr(self.argmax), 0, _ptr(self.X), 0, g.F, g.T, g.K,
-                                                   g.S | GCCNMF_RECONSTRUCT_RATIO, self.batch, 0, _ptr(self.spec), _stream()),
-                       'gccnmf_reconstruct')
-            return
-        _hip.check(self.lib.gccnmf_reconstruct(_ptr(self.W), _ptr(self.H), _ptr(self.argmax), 0, _ptr(self.X), _ptr(self.V), g.F,
-                                               g.T, g.K, g.S, self.batch, _ptr(self.ws_rec), _ptr(self.spec), _stream()),
-                   'gccnmf_reconstruct')
+        if self.reconstruction == 'spatial' and self.ws_cov is None:
+            self.ws_cov = torch.zeros(self._reconstruct_workspace_floats(), dtype=torch.float32, device=self.device)
+        _hip.reconstruct(self.W, self.H, self.argmax, None, self.X, self.V, g.F, g.T, g.K, g.S, self.batch, self.spec, mode=self.reconstruction,
+                         workspace=self.ws_cov if self.reconstruction == 'spatial' else self.ws_rec)
 
     @_on_device
     def istft(self, keep_frames=False):
@@ -575,9 +510,7 @@ class GCCNMFEngine(object):
             if self.frames is None:
                 self.frames = torch.zeros((self.batch, 2 * g.S, g.T, self.n_fft), dtype=torch.float32, device=self.device)
             frames = self.frames
-        _hip.check(self.lib.gccnmf_istft_ola(_ptr(self.spec), 2 * g.S, self.n_fft, self.hop, g.T, self.batch, _ptr(self.window),
-                                             _ptr(self.twiddle), gain, 1, _ptr(frames), _ptr(self.y), _stream()),
-                   'gccnmf_istft_ola')
+        _hip.istft_ola(self.spec, 2 * g.S, self.n_fft, self.hop, g.T, self.batch, self.window, self.twiddle, gain, True, frames, self.y)
 
     @_on_device
     def run(self, stft=True):
@@ -591,15 +524,20 @@ class GCCNMFEngine(object):
         self.istft()
 
     # ---- host <-> device -------------------------------------------------------------------------
-    @_on_device
-    def upload(self, stereoSamples):
+    def _checked_samples(self, stereoSamples, one_file=True):
+        """Host samples as float32 (batch, 2, n), ValueError otherwise; one_file: a single (2, n) mixture is a batch of one."""
         x = np.asarray(stereoSamples, dtype=np.float32)
-        if x.ndim == 2:
+        if one_file and x.ndim == 2:
             x = x[None]
-        if x.shape != (self.batch, 2, self.n_samples):
-            raise ValueError('expected samples of shape %s, got %s' % ((self.batch, 2, self.n_samples), x.shape))
+        if x.shape != tuple(self.x.shape):
+            raise ValueError('expected samples of shape %s, got %s' % (tuple(self.x.shape), x.shape))
         if not np.isfinite(x).all():
             raise ValueError('Audio buffer is not finite everywhere')      # librosaSTFT.py:488-489
+        return x
+
+    @_on_device
+    def upload(self, stereoSamples):
+        x = self._checked_samples(stereoSamples)
         self.pcm_in = None
         self.x.copy_(torch.from_numpy(np.ascontiguousarray(x)))
 
@@ -630,13 +568,7 @@ class GCCNMFEngine(object):
     @_on_device
     def separate(self, stereoSamples):
         """(batch, 2, n) float32 host samples -> (batch, S, 2, hop*(T-1)) float32 host waveforms."""
-        x = np.asarray(stereoSamples, dtype=np.float32)
-        if x.ndim == 2:
-            x = x[None]
-        if x.shape != tuple(self.x.shape):
-            raise ValueError('expected samples of shape %s, got %s' % (tuple(self.x.shape), x.shape))
-        if not np.isfinite(x).all():
-            raise ValueError('Audio buffer is not finite everywhere')      # librosaSTFT.py:488-489
+        x = self._checked_samples(stereoSamples)
         # one page-locked staging pair (allocated on first use: 82 MB + 244 MB of host memory for a 64-file batch, nothing extra on the
         # device): both copies move at PCIe speed instead of through pageable bounce buffers (313 -> 285 ms host to host for one
         # batch).  The double-buffered pipeline -- a second x / y pair in HBM, two more pinned pairs -- belongs to separate_batches.
@@ -650,10 +582,7 @@ class GCCNMFEngine(object):
         if self.chain_failed():
             # The chained KL-NMF launch did not hand over cleanly (a consumer timed out / a work list ran on more than one XCC): its factors are
             # NaN by construction.  Do not fail the batch: switch this process to the plain launches and run the stages behind the STFT again.
-            import warnings
-            warnings.warn('gcc_nmf_amd: a chained KL-NMF launch did not hand over cleanly; this process falls back to the plain launches '
-                          '(gccnmf_set_tuning(21, 0)) and repeats the batch', RuntimeWarning)
-            _hip.check(self.lib.gccnmf_set_tuning(21, 0), 'gccnmf_set_tuning')
+            self._fall_back_to_plain_launches()
             self.run(stft=False)
         hy.copy_(self.y, non_blocking=True)
         torch.cuda.current_stream(self.device).synchronize()
@@ -697,11 +626,7 @@ class GCCNMFEngine(object):
                     slot = i & 1
                     if len(pending) == 2:                                # this slot's previous occupant must be handed out first
                         yield collect(pending.pop(0))
-                    x = np.asarray(batch, dtype=np.float32)
-                    if x.shape != tuple(self.x.shape):
-                        raise ValueError('expected samples of shape %s, got %s' % (tuple(self.x.shape), x.shape))
-                    if not np.isfinite(x).all():
-                        raise ValueError('Audio buffer is not finite everywhere')      # librosaSTFT.py:488-489
+                    x = self._checked_samples(batch, one_file=False)
                     hx[slot].copy_(torch.from_numpy(np.ascontiguousarray(x)))    # host memcpy into the pinned buffer
                     with torch.cuda.stream(s_in):
                         s_in.wait_event(ev_done[slot])                   # batch i-2 no longer reads this x buffer
@@ -758,32 +683,24 @@ class GCCNMFEngine(object):
             raise ValueError('fewer than %d angular-spectrum peaks in file(s) %s' % (self.g.S, np.nonzero(st)[0].tolist()))
 
     @_on_device
-    def chain_failed(self):
+    def _chain_status(self):
         """Status word of the last chained KL-NMF launch(es) of this engine (0 = clean or not chained); synchronises the stream."""
-        import ctypes
-        g, st, worst = self.g, ctypes.c_int(0), 0
-        per = self.batch // self.nmf_groups
-        ws_per = self.ws_nmf.numel() // self.nmf_groups
+        g = self.g
         torch.cuda.current_stream(self.device).synchronize()
-        for i in range(self.nmf_groups):
-            _hip.check(self.lib.gccnmf_klnmf_chain_status(_ptr(self.ws_nmf[i * ws_per:]), g.F, g.N, g.K, per, ctypes.byref(st)), 'gccnmf_klnmf_chain_status')
-            worst |= st.value
+        worst = 0
+        for _, per, ws, _ in self._groups():
+            worst |= _hip.klnmf_chain_status(ws, g.F, g.N, g.K, per)
         return worst
 
-    @_on_device
+    chain_failed = _chain_status
+
     def check_chain_status(self):
         """A chained KL-NMF launch whose hand-over failed has turned W and H into NaN; say so instead of letting NaN travel on."""
-        import ctypes
-        g, st = self.g, ctypes.c_int(0)
-        per = self.batch // self.nmf_groups
-        ws_per = self.ws_nmf.numel() // self.nmf_groups
-        torch.cuda.current_stream(self.device).synchronize()
-        for i in range(self.nmf_groups):
-            _hip.check(self.lib.gccnmf_klnmf_chain_status(_ptr(self.ws_nmf[i * ws_per:]), g.F, g.N, g.K, per, ctypes.byref(st)), 'gccnmf_klnmf_chain_status')
-            if st.value:
-                raise _hip.HipLibraryError('the chained KL-NMF launch did not hand over cleanly (status %d: %s): W and H of this batch are NaN.  '
-                                           'GCCNMF_TUNE="21=0" runs the plain launches.'
-                                           % (st.value, 'a consumer timed out' if st.value & 1 else 'a work list ran on more than one XCC'))
+        st = self._chain_status()
+        if st:
+            raise _hip.HipLibraryError('the chained KL-NMF launch did not hand over cleanly (status %d: %s): W and H of this batch are NaN.  '
+                                       'GCCNMF_TUNE="21=0" runs the plain launches.'
+                                       % (st, 'a consumer timed out' if st & 1 else 'a work list ran on more than one XCC'))
 
     # ---- views of device results in the reference's shapes ------------------------------------------
     def get_X(self):
@@ -886,7 +803,6 @@ class RaggedGCCNMFEngine(object):
             self.ragged = None
             # a fixed dictionary: each length's engine runs its own one-launch call; a tolerance: each length's files converge as a batch of their own
             if len(self.sub) > 1 and dictionaryW is None and self.tolerance is None:
-                import ctypes
                 ws = self.lib.gccnmf_klnmf_ragged_workspace_floats(g.F, g.N, g.K, self.batch)
                 if ws > 0:
                     self.ragged = dict(V=z(self.batch, g.Fp, g.Np), W=z(self.batch, g.Fp, g.Kp), H=z(self.batch, g.Kp, g.Np), ws=z(ws),
@@ -944,13 +860,10 @@ class RaggedGCCNMFEngine(object):
         self.run()
         out = [None] * self.batch
         if self.ragged_klnmf_used:
-            import ctypes
-            st = ctypes.c_int(0)
             torch.cuda.current_stream(self.device).synchronize()
-            _hip.check(self.lib.gccnmf_klnmf_chain_status(_ptr(self.ragged['ws']), self.g.F, self.g.N, self.g.K, self.batch, ctypes.byref(st)),
-                       'gccnmf_klnmf_chain_status')
-            if st.value:
-                raise _hip.HipLibraryError('the ragged chained KL-NMF launch did not hand over cleanly (status %d): W and H are NaN' % st.value)
+            st = _hip.klnmf_chain_status(self.ragged['ws'], self.g.F, self.g.N, self.g.K, self.batch)
+            if st:
+                raise _hip.HipLibraryError('the ragged chained KL-NMF launch did not hand over cleanly (status %d): W and H are NaN' % st)
         for n, e in self.sub.items():
             y = e.y.cpu().numpy()
             e.check_status()
@@ -976,13 +889,11 @@ class RaggedGCCNMFEngine(object):
 
     def get_tdoa_tracks(self):
         """One (S, T_i) int32 array per file, in the caller's order (tdoaTracking only)."""
-        tracks = dict((n, e.get_tdoa_tracks()) for n, e in self.sub.items())
-        return [tracks[n][self.files_of[n].index(i)] for i, n in enumerate(self.lengths)]
+        return self._per_file(dict((n, e.get_tdoa_tracks()) for n, e in self.sub.items()))
 
     def get_track_status(self):
         """One (T_i,) int32 array per file, in the caller's order (tdoaTracking only)."""
-        status = dict((n, e.get_track_status()) for n, e in self.sub.items())
-        return [status[n][self.files_of[n].index(i)] for i, n in enumerate(self.lengths)]
+        return self._per_file(dict((n, e.get_track_status()) for n, e in self.sub.items()))
 
     def file(self, i):
         """(engine of file i's length, its index in that engine's batch): ``e, k = eng.file(i); e.get_WH()[0][k]``."""

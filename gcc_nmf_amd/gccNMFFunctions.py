@@ -25,8 +25,9 @@ from numpy.random import random, seed
 from scipy.signal import argrelmax
 
 from . import _hip, _staging
-from .engine import Geometry, padded, fft_twiddles, steering_tables, _ptr, _stream, check_reconstruction, GCCNMF_RECONSTRUCT_RATIO
-from .librosaSTFT import stft, istft, ParameterError, _window_vector, _istft_device
+from .engine import (Geometry, padded, fft_twiddles, steering_tables, check_reconstruction, check_iterations, converge_klnmf,
+                     klnmf_divergence)
+from .librosaSTFT import stft, istft, ParameterError, _window_vector, _istft_device, _stft_device
 from .wavfile import wavread, wavwrite
 
 SPEED_OF_SOUND_IN_METRES_PER_SECOND = 340.29
@@ -85,7 +86,6 @@ def computeComplexMixtureSpectrogram(stereoSamples, windowSize, hopSize, windowF
     window length.  Returns (2, F, T) complex64.  Both channels share one packed complex FFT."""
     if fftSize is None:
         fftSize = windowSize
-    from .librosaSTFT import _stft_device
     chans = [np.ascontiguousarray(np.squeeze(stereoSamples[c])) for c in range(2)]       # (:64 copies each channel too)
     return _stft_device(chans[0], chans[1], windowSize, hopSize, fftSize, hanning, center=False, remember=True)
 
@@ -103,8 +103,7 @@ def performKLNMF(V, dictionarySize, numIterations, sparsityAlpha, epsilon=1e-16,
     init = _klnmf_initial_factors(F, N, K, epsilon, seedValue, dev)
     with _staging.Scope(dev) as sc:
         dV, dW, dH, ws = _klnmf_buffers(sc, lib, V, K, init)
-        _hip.check(lib.gccnmf_klnmf(_ptr(dV), _ptr(dW), _ptr(dH), _ptr(ws), F, N, K, 1, int(numIterations),
-                                    float(sparsityAlpha), float(epsilon), 0, _stream()), 'gccnmf_klnmf')
+        _hip.klnmf(dV, dW, dH, ws, F, N, K, 1, int(numIterations), float(sparsityAlpha), float(epsilon))
         W = sc.remember(sc.download(dW[:F, :K]), 'W', dict(W=dW), dict(F=F, K=K))
         H = sc.download(dH[:K, :N])
     return W, H
@@ -162,7 +161,6 @@ def performKLNMFUntilConverged(V, dictionarySize, maxIterations, sparsityAlpha, 
     tolerance, checkEvery, maxIterations = _hip.check_convergence(tolerance, checkEvery, maxIterations)
     if tolerance is None:
         raise ValueError('performKLNMFUntilConverged needs a tolerance; performKLNMF runs a fixed number of iterations')
-    from .engine import check_iterations, converge_klnmf, klnmf_divergence
     V = np.asarray(V)
     F, N = V.shape
     K = int(dictionarySize)
@@ -175,9 +173,8 @@ def performKLNMFUntilConverged(V, dictionarySize, maxIterations, sparsityAlpha, 
         dV, dW, dH, ws = _klnmf_buffers(sc, lib, V, K, init)
 
         def launch(n, first):
-            _hip.check(lib.gccnmf_klnmf(_ptr(dV), _ptr(dW), _ptr(dH), _ptr(ws), F, N, K, 1, n, float(sparsityAlpha), float(epsilon), 0,
-                                        _stream()), 'gccnmf_klnmf')
-        iterations, trace = converge_klnmf(launch, lambda: klnmf_divergence(lib, dV, dW, dH, ws, F, N, K, 1).cpu().numpy(),
+            _hip.klnmf(dV, dW, dH, ws, F, N, K, 1, n, float(sparsityAlpha), float(epsilon))
+        iterations, trace = converge_klnmf(launch, lambda: klnmf_divergence(dV, dW, dH, ws, F, N, K, 1).cpu().numpy(),
                                            [dW.unsqueeze(0), dH.unsqueeze(0)], maxIterations, tolerance, checkEvery)
         W = sc.remember(sc.download(dW[:F, :K]), 'W', dict(W=dW), dict(F=F, K=K))
         H = sc.download(dH[:K, :N])
@@ -192,7 +189,6 @@ def getKLDivergence(V, W, H):
     V, H = np.asarray(V), np.asarray(H)
     if V.ndim != 2 or np.ndim(W) != 2 or H.ndim != 2 or np.shape(W) != (V.shape[0], H.shape[0]) or H.shape[1] != V.shape[1]:
         raise ValueError('getKLDivergence takes V (F, N), W (F, K) and H (K, N), got %s, %s, %s' % (V.shape, np.shape(W), H.shape))
-    from .engine import klnmf_divergence
     F, N = V.shape
     K = H.shape[0]
     lib, dev = _hip.lib(), _device()
@@ -205,7 +201,7 @@ def getKLDivergence(V, W, H):
         dV[:F, :N].copy_(sc.upload(V, 'V', float32))
         dH[:K, :N].copy_(sc.upload(H, 'H', float32))
         dW = _device_W(sc, W, g, dev)                      # the image behind W if performKLNMF returned it (resident mode)
-        out = sc.download(klnmf_divergence(lib, dV, dW, dH, ws, F, N, K, 1))
+        out = sc.download(klnmf_divergence(dV, dW, dH, ws, F, N, K, 1))
     return np.float64(out[0])
 
 
@@ -266,15 +262,13 @@ def getAngularSpectrogram(spectralCoherenceV, frequenciesInHz, microphoneSeparat
     nl, alpha = _hip.check_gcc_phat_nl(gccPHATNLEnabled, gccPHATNLAlpha)
     C = np.asarray(spectralCoherenceV)
     F, T = C.shape
-    lib, dev = _hip.lib(), _device()
+    _, dev = _hip.lib(), _device()
     g = Geometry(F, T, 1, int(numTDOAs))
-    Dw, Bw = _hip.angular_nl_words(g.D, 1, alpha) if nl else (g.D, 1)
     trig = _trig_table(frequenciesInHz, microphoneSeparationInMetres, numTDOAs, g, dev)
     with _staging.Scope(dev) as sc:
         dC = _upload_coherence(sc, C, g)
         ang = sc.dev('ang', (g.Dp, g.Tp))
-        _hip.check(lib.gccnmf_angular_spectrogram(_ptr(dC), _ptr(trig), F, T, Dw, Bw, _ptr(ang), 0, _stream()),
-                   'gccnmf_angular_spectrogram')
+        _hip.angular_spectrogram(dC, trig, F, T, g.D, 1, ang, None, nl_alpha=alpha if nl else None)
         out = sc.download(ang[:g.D, :T], dtype=np.float64)
     return out
 
@@ -288,13 +282,12 @@ def estimateTargetTDOAIndexesFromAngularSpectrum(angularSpectrum, microphoneSepa
     spectrum = np.ascontiguousarray(angularSpectrum, dtype=np.float64)
     D = spectrum.shape[0]
     S = int(numSources)
-    lib, dev = _hip.lib(), _device()
+    _, dev = _hip.lib(), _device()
     logging.info('numSources provided, taking first %d peaks' % numSources)
     with _staging.Scope(dev) as sc:
         dM = sc.upload(spectrum, 'meanA')
         res = sc.dev('peaks', (S + 1,), torch.int32)                  # [0..S): indexes, [S]: status
-        _hip.check(lib.gccnmf_pick_tdoa_peaks(_ptr(dM), D, D, S, 1, res.data_ptr(), res.data_ptr() + 4 * S, _stream()),
-                   'gccnmf_pick_tdoa_peaks')
+        _hip.pick_tdoa_peaks(dM, D, D, S, 1, res, res.data_ptr() + 4 * S)
         out = sc.download(res)
     if int(out[S]) != 0:
         raise ValueError("didn't find enough peaks in estimateTargetTDOAIndexesFromAngularSpectrum")
@@ -339,14 +332,13 @@ def estimateTargetTDOATracksFromAngularSpectrogram(angularSpectrogram, microphon
     getTargetTDOAGCCNMFs as ``targetTDOAIndexes``."""
     A, S, L = check_angular_spectrogram_for_tracks(angularSpectrogram, numTDOAs, numSources, localizationWindowSize)
     D, T = A.shape
-    lib, dev = _hip.lib(), _device()
+    _, dev = _hip.lib(), _device()
     g = Geometry(2, T, 1, D, S)
     with _staging.Scope(dev) as sc:
         ang = sc.dev('ang', (g.Dp, g.Tp), corner=(D, T))
         ang[:D, :T].copy_(sc.upload(A, 'A', float32))
         res = sc.dev('tracks', (S + 1, g.Tp), torch.int32)              # rows [0..S): tracks, row S: per-frame status
-        _hip.check(lib.gccnmf_pick_tdoa_peaks(_ptr(ang), D, T, _hip.peaks_tracks_word(S, L, T), 1, res.data_ptr(),
-                                              res.data_ptr() + 4 * S * g.Tp, _stream()), 'gccnmf_pick_tdoa_peaks (tracks)')
+        _hip.pick_tdoa_tracks(ang, D, T, S, L, 1, res, res.data_ptr() + 4 * S * g.Tp)
         out = sc.download(res[:, :T])
     if (out[S] & 2).any():
         raise ValueError("didn't find enough peaks in any frame in estimateTargetTDOATracksFromAngularSpectrogram")
@@ -375,9 +367,7 @@ def getTargetTDOAGCCNMFs(coherenceV, microphoneSeparationInMetres, numTDOAs, fre
             dIdx = sc.upload(targetTDOAIndexes, 'idx')
         ws = sc.dev('ws_scores', (lib.gccnmf_scores_workspace_floats(F, T, numTargets, 1),))
         scores = sc.dev('scores', (g.Kp, numTargets, g.Tp))
-        _hip.check(lib.gccnmf_target_scores_masks(_ptr(dC), _ptr(trig), _ptr(dIdx), _ptr(dW), F, T, K, g.D,
-                                                  numTargets | _hip.GCCNMF_SCORES_TRACKS if tracks else numTargets, 1,
-                                                  _ptr(ws), _ptr(scores), 0, _stream()), 'gccnmf_target_scores_masks')
+        _hip.target_scores_masks(dC, trig, dIdx, dW, F, T, K, g.D, numTargets, 1, ws, scores, None, tracks=tracks)
         out = sc.download(scores[:K, :, :T].permute(1, 0, 2), shape=(numTargets, K, T))
         sc.remember(out, 'G', dict(scores=scores), dict(S=numTargets, K=K, T=T))
     return out
@@ -388,7 +378,7 @@ def getTargetCoefficientMasks(targetTDOAGCCNMFs, numTargets):
     only the first ``numTargets`` masks are filled, as in the reference loop."""
     G = np.asarray(targetTDOAGCCNMFs)
     S, K, T = G.shape
-    lib, dev = _hip.lib(), _device()
+    _, dev = _hip.lib(), _device()
     g = Geometry(2, T, K, 1, S)
     with _staging.Scope(dev) as sc:
         rec = _staging.lookup(G, 'G', dev)
@@ -398,7 +388,7 @@ def getTargetCoefficientMasks(targetTDOAGCCNMFs, numTargets):
             scores = sc.dev('scores', (g.Kp, S, g.Tp), corner=(K, S, T))
             scores[:K, :, :T].copy_(sc.upload(G, 'G', float32).permute(1, 0, 2))
         am = sc.dev('argmax', (g.Kp, g.Tp), torch.uint8)
-        _hip.check(lib.gccnmf_argmax_targets(_ptr(scores), K, T, S, 1, _ptr(am), _stream()), 'gccnmf_argmax_targets')
+        _hip.argmax_targets(scores, K, T, S, 1, am)
         # numpy.nanargmax raises on a slice that is NaN for every target (:138); argument validation, checked where the data is
         allnan = torch.isnan(scores[:K, :, :T]).all(dim=1).any()
         # the reference's loop (:140-142): masks[i][argmax == i] = 1 for i < numTargets -- an exact 0 / 1 format expansion of the arg-max image
@@ -426,12 +416,11 @@ def getTargetSpectrogramEstimates(targetCoefficientMasks, complexMixtureSpectrog
     M = np.asarray(targetCoefficientMasks)
     X = np.asarray(complexMixtureSpectrogram)
     S, K, T = M.shape
-    spatial = check_reconstruction(reconstruction, S) == 'spatial'
-    ratio = spatial or reconstruction == 'ratio'
+    check_reconstruction(reconstruction, S)
     C, F, _ = X.shape
     if C != 2:
         raise ValueError('stereo spectrogram expected')
-    lib, dev = _hip.lib(), _device()
+    _, dev = _hip.lib(), _device()
     g = Geometry(F, T, K, 1, S)
     with _staging.Scope(dev) as sc:
         recM = _staging.lookup(M, 'M', dev)
@@ -447,19 +436,15 @@ def getTargetSpectrogramEstimates(targetCoefficientMasks, complexMixtureSpectrog
             dX = sc.dev('X', (2, g.Fp, g.Tp, 2), corner=(F, T))
             torch.view_as_complex(dX)[:, :F, :T].copy_(sc.upload(X, 'X', complex64))
             dV = sc.dev('V', (g.Fp, g.Np), corner=(F, g.N))
-            _hip.check(lib.gccnmf_magnitude(_ptr(dX), F, T, 1, _ptr(dV), _stream()), 'gccnmf_magnitude')
+            _hip.magnitude(dX, F, T, 1, dV)
         dW = _device_W(sc, W, g, dev)
         dH = sc.dev('H', (g.Kp, g.Np), corner=(K, g.N))
         dH[:K, :g.N].unflatten(1, (2, T)).copy_(sc.upload(np.asarray(stereoH), 'stereoH', float32).permute(1, 0, 2))   # (K, [L | R])
-        if spatial:
-            ws = sc.dev('ws_cov', (_hip.reconstruct_spatial_workspace_floats(1, S, g.Fp),))
-        else:
-            ws = None if ratio else sc.dev('ws_rec', (lib.gccnmf_reconstruct_workspace_floats(T, K, S, 1),))
+        ws = None
+        if reconstruction != 'ratio':
+            ws = sc.dev('ws_cov' if reconstruction == 'spatial' else 'ws_rec', (_hip.reconstruct_workspace_floats(reconstruction, T, K, S, 1, g.Fp),))
         spec = sc.dev('spec', (2 * S, g.Fp, g.Tp, 2))
-        _hip.check(lib.gccnmf_reconstruct(_ptr(dW), _ptr(dH), _ptr(dA), _ptr(dM), _ptr(dX), _ptr(dV), F, T, K,
-                                          S | GCCNMF_RECONSTRUCT_RATIO if ratio else S, _hip.reconstruct_spatial_batch(1) if spatial else 1,
-                                          _ptr(ws), _ptr(spec), _stream()),
-                   'gccnmf_reconstruct')
+        _hip.reconstruct(dW, dH, dA, dM, dX, dV, F, T, K, S, 1, spec, mode=reconstruction, workspace=ws)
         out = sc.download(torch.view_as_complex(spec)[:, :F, :T], shape=(S, 2, F, T))
         sc.remember(out, 'S', dict(spec=spec), dict(nsig=2 * S, F=F, T=T))
     return out
@@ -496,7 +481,7 @@ def getTargetTDOAEstimates(complexMixtureSpectrogram, sampleRate, microphoneSepa
     nl, alpha = _hip.check_gcc_phat_nl(gccPHATNLEnabled, gccPHATNLAlpha)
     X = np.asarray(complexMixtureSpectrogram).astype(complex64)
     C, F, T = X.shape
-    lib, dev = _hip.lib(), _device()
+    _, dev = _hip.lib(), _device()
     g = Geometry(F, T, 1, int(numTDOAs), int(numSources))
     frequenciesInHz = linspace(0, sampleRate / 2.0, F)
     trig = torch.from_numpy(steering_tables(frequenciesInHz, getTDOAsInSeconds(microphoneSeparationInMetres, numTDOAs),
@@ -507,12 +492,9 @@ def getTargetTDOAEstimates(complexMixtureSpectrogram, sampleRate, microphoneSepa
     meanA = torch.zeros((g.Dp,), dtype=torch.float64, device=dev)
     idx = torch.zeros((g.S,), dtype=torch.int32, device=dev)
     status = torch.zeros((1,), dtype=torch.int32, device=dev)
-    _hip.check(lib.gccnmf_coherence(_ptr(dX), F, T, 1, _ptr(dC), _stream()), 'gccnmf_coherence')
-    Dw, Bw = _hip.angular_nl_words(g.D, 1, alpha) if nl else (g.D, 1)
-    _hip.check(lib.gccnmf_angular_spectrogram(_ptr(dC), _ptr(trig), F, T, Dw, Bw, _ptr(ang), _ptr(meanA), _stream()),
-               'gccnmf_angular_spectrogram')
-    _hip.check(lib.gccnmf_pick_tdoa_peaks(_ptr(meanA), g.D, g.Dp, g.S, 1, _ptr(idx), _ptr(status), _stream()),
-               'gccnmf_pick_tdoa_peaks')
+    _hip.coherence(dX, F, T, 1, dC)
+    _hip.angular_spectrogram(dC, trig, F, T, g.D, 1, ang, meanA, nl_alpha=alpha if nl else None)
+    _hip.pick_tdoa_peaks(meanA, g.D, g.Dp, g.S, 1, idx, status)
     if int(status.cpu()[0]) != 0:
         raise ValueError("didn't find enough peaks in getTargetTDOAEstimates")
     return sorted(np.int64(i) for i in idx.cpu().numpy()), meanA[:g.D].cpu().numpy()

@@ -178,8 +178,7 @@ def _stft_device(y0, y1, n_fft, hop_length, win_length, window, center, remember
             x[c].copy_(sc.upload(y, 'x%d' % c, np.float32))
         X = sc.dev('X', (2, g.Fp, g.Tp, 2), corner=(F, T))
         V = sc.dev('V', (g.Fp, g.Np), corner=(F, g.N)) if remember and _staging.resident_mode() else None
-        _hip.check(lib.gccnmf_stft_stereo(_ptr(x), 2 * n, n, n_fft, hop_length, T, 1, _ptr(dwin), _ptr(dtw), _ptr(X), _ptr(V), 0,
-                                          _stream()), 'gccnmf_stft_stereo')
+        _hip.stft_stereo(x, n, n_fft, hop_length, T, 1, dwin, dtw, X, V, None)
         nsig = 2 if y1 is not None else 1
         out = sc.download(torch.view_as_complex(X)[:nsig, :F, :T])
         if V is not None and nsig == 2:
@@ -230,8 +229,7 @@ def _istft_device(specs, hop_length, win_length, window, center, gain=1.0, devic
             torch.view_as_complex(dS)[:nsig, :F, :T].copy_(sc.upload(specs, 'spec', np.complex64))
         frames = sc.dev('frames', (npad, T, n_fft))                      # scratch of the two-kernel form: every frame t < T is written
         y = sc.dev('y', (npad, L))
-        _hip.check(lib.gccnmf_istft_ola(_ptr(dS), npad, n_fft, hop_length, T, 1, _ptr(dwin), _ptr(dtw), np.float32(gain),
-                                        1 if center else 0, _ptr(frames), _ptr(y), _stream()), 'gccnmf_istft_ola')
+        _hip.istft_ola(dS, npad, n_fft, hop_length, T, 1, dwin, dtw, np.float32(gain), center, frames, y)
         out = sc.download(y[:nsig])
     return out
 
