@@ -188,7 +188,25 @@ int gccnmf_klnmf_plan(int F, int N, int K, int batch, int flags);
  *          because R's zero padding is overwritten, stage 0 (every gccnmf_klnmf call starts with it) must run before further stages
  *          1-6.  sparsity_alpha, epsilon and bits 0-15 of flags are ignored.  flags = GCCNMF_FLAG_FIXED_W (exactly) is accepted by
  *          this stage alone: W is then ONE [Fp][Kp] dictionary shared by every file, as in the fixed-dictionary call.
- * Any other stage number: GCCNMF_ERR_ARG. */
+ * Any other stage number: GCCNMF_ERR_ARG.
+ * Where stages 0-6 keep their intermediates (tests read them by offset; floats from `workspace`, batch = the call's):
+ *     R        [batch][Fp][Np]      zero outside f < F, n < N from stage 0 on (a reduction operand of stages 2 and 4)
+ *     U        [batch][Fp][Kp]      R.H^T; its padding is nobody's operand and keeps whatever the workspace held
+ *     colsumW  [batch][Kp]
+ *     rowsumH  [batch][Kp]
+ *     hscale   [batch][Kp]          the lazy atom scale s: the H of the algorithm is s * H until stage 6
+ *     (batch == 1 only: 4 * (max(Fp * Np, Fp * Kp) + Kp) floats kept for the lab build's split reductions)
+ *     (batch <= 8) the direct kernels' transposed copies  Wt [batch][Kp][Fp] | Ht [batch][Np][Kp] | Rt [batch][Np][Fp]
+ *   followed by the counters and status words of the chained launches.  Stage 0 establishes R = 0, colsumW, hscale = 1 (and Wt = W^T,
+ *   Ht = Rt = 0 on the direct path); U and rowsumH are written before they are read.
+ * Which stage writes what depends on the launch form (gccnmf_klnmf_plan; a stage that has nothing left to do returns GCCNMF_OK and
+ * writes nothing):
+ *     four launches              1: R | 2: H | 3: R | 4: U, rowsumH | 5: W, hscale, colsumW | 6: H
+ *     plan bit 1 (K1 + K2)       1: H, R is not written | 2: nothing
+ *     plan bit 2 (K3 + K4a)      3: U, rowsumH, R is not written | 4: nothing (but for the files a partial slab launch left to the two launches)
+ *     W update in the epilogue of R.H^T (128 < Fm <= 512 on the throughput tile, neither GCCNMF_FLAG_UNFUSED_W_UPDATE nor plan bit 2; no
+ *       plan bit)                4: W, hscale, colsumW, U and rowsumH are not written | 5: nothing
+ *     plan bit 0 (direct)        0: also Wt | 2: H and Ht | 3: Rt and, of R, bin F - 1 alone (F = 16 n + 1) | 4: U, rowsumH from Rt and Ht | 5: W and Wt */
 int gccnmf_klnmf_stage(const float* V, float* W, float* H, float* workspace, int F, int N, int K, int batch,
                        float sparsity_alpha, float epsilon, int flags, int stage, void* stream);
 
