@@ -271,9 +271,46 @@ GCCNMF_FLAG_H_ONES = 1 << 17            # include/gccnmf_hip.h: H starts as all 
 GCCNMF_STAGE_DIVERGENCE = 7             # include/gccnmf_hip.h: gccnmf_klnmf_stage, "KL divergence of the current factors"
 
 
-def klnmf(V, W, H, ws, F, N, K, batch, iterations, alpha, eps, fixed_w=False, h_ones=False, groups=1, flags=0, stream=None):
+FREE_ATOMS_MAX = 128                    # include/gccnmf_hip.h: the most free atoms of a semi-supervised call
+SEMI_MAX_ATOMS, SEMI_MAX_BINS = 1024, 2049
+
+
+def GCCNMF_FLAG_FREE_ATOMS(n):
+    """include/gccnmf_hip.h: the last n atoms of every file's W are learned beside the dictionary in front of them (bits 18-25)."""
+    return int(n) << 18
+
+
+def check_free_atoms(numFreeAtoms, K_fixed, F=None):
+    """The argument rules of the semi-supervised call (GCCNMF_FLAG_FREE_ATOMS in include/gccnmf_hip.h) for ``numFreeAtoms`` free atoms
+    behind a dictionary of ``K_fixed`` atoms (and, if given, F bins); no device needed.  Returns the count as an int; 0 = not
+    semi-supervised.  ValueError otherwise: not a whole number in [0, 128], no dictionary in front of the free atoms, a dictionary whose
+    size is no multiple of 16 (the free block starts on an atom-group boundary), more than 1024 atoms in all, more than 2049 bins."""
+    n = numFreeAtoms
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or not 0 <= n <= FREE_ATOMS_MAX:
+        raise ValueError('numFreeAtoms must be a whole number from 0 to %d, got %r' % (FREE_ATOMS_MAX, n))
+    n = int(n)
+    if n == 0:
+        return 0
+    if isinstance(K_fixed, bool) or not isinstance(K_fixed, numbers.Integral) or K_fixed < 1:
+        raise ValueError('free atoms need a dictionary of at least one atom in front of them, got %r' % (K_fixed,))
+    if K_fixed % 16:
+        raise ValueError('free atoms take a dictionary whose size is a multiple of 16, got %d atoms' % K_fixed)
+    if K_fixed + n > SEMI_MAX_ATOMS:
+        raise ValueError('dictionary and free atoms together may have at most %d atoms, got %d + %d' % (SEMI_MAX_ATOMS, K_fixed, n))
+    if F is not None and not 2 <= F <= SEMI_MAX_BINS:
+        raise ValueError('the semi-supervised call takes 2 to %d bins, got %r' % (SEMI_MAX_BINS, F))
+    return n
+
+
+def klnmf(V, W, H, ws, F, N, K, batch, iterations, alpha, eps, fixed_w=False, h_ones=False, groups=1, flags=0, free_atoms=0, stream=None):
     """``iterations`` KL-NMF iterations on W and H in place.  groups > 1: this call is one of that many concurrent ones
-    (GCCNMF_FLAG_GROUPS(n) = 4 | n << 8: launch forms are chosen for all groups together); flags: further low flag bits."""
+    (GCCNMF_FLAG_GROUPS(n) = 4 | n << 8: launch forms are chosen for all groups together); flags: further low flag bits.
+    free_atoms = n > 0: semi-supervised -- columns [0, K - n) of every file's W are a dictionary that stays as it is, the last n atoms
+    and all of H are learned (GCCNMF_FLAG_FREE_ATOMS(n))."""
+    if free_atoms:
+        if fixed_w or h_ones or groups > 1 or flags & 6:
+            raise ValueError('free atoms cannot be combined with a fixed dictionary, the all-ones start, file groups or the unfused W update')
+        flags |= GCCNMF_FLAG_FREE_ATOMS(check_free_atoms(free_atoms, K - free_atoms, F))
     flags |= (GCCNMF_FLAG_FIXED_W if fixed_w else 0) | (GCCNMF_FLAG_H_ONES if h_ones else 0) | (4 | groups << 8 if groups > 1 else 0)
     _stage('gccnmf_klnmf', V, W, H, ws, F, N, K, batch, iterations, alpha, eps, flags, stream=stream)
 

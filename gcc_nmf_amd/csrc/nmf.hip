@@ -22,6 +22,11 @@ int gccnmf_klnmf_fixed_launch(const float* V, const float* W, float* H, float* w
                               float alpha, float eps, bool ones, hipStream_t s);      // fixed dictionary, every iteration in one launch (nmf_fixed.hip)
 bool gccnmf_klnmf_fixed_supported(int F, int K);
 long gccnmf_klnmf_fixed_workspace_floats(int F, int K);
+// semi-supervised KL-NMF (GCCNMF_FLAG_FREE_ATOMS): R.H^T and the W update of the free atoms alone (nmf_semi.hip)
+bool gccnmf_klnmf_semi_supported(int F, int K, int nfree);
+int gccnmf_klnmf_semi_rht_launch(const float* R, const float* H, float* U, float* rowsumH, int F, int N, int K, int nfree, int batch, hipStream_t s);
+int gccnmf_klnmf_semi_update_w_launch(float* W, const float* U, const float* rowsumH, float* colsumW, float* hscale, int F, int K, int nfree,
+                                      int batch, hipStream_t s);
 #include "../../include/gccnmf_hip.h"
 
 #include <atomic>
@@ -1029,6 +1034,16 @@ long gccnmf_klnmf_workspace_floats(int F, int N, int K, int batch) {
     return klnmf_workspace_base_floats(g, batch) + chain_counter_floats(g, batch);
 }
 
+// GCCNMF_FLAG_FREE_ATOMS(n): the last n atoms of every file's W are learned beside a dictionary in its first K - n columns (semi-supervised
+// KL-NMF).  The argument rules, decided before anything is launched: 0 = a valid call.
+#define GCCNMF_FREE_BITS (255 << 18)
+static int free_atoms(int flags) { return (flags >> 18) & 255; }
+static int semi_check(int F, int K, int flags) {
+    const int n = free_atoms(flags);
+    if ((flags & (GCCNMF_FLAG_FIXED_W | GCCNMF_FLAG_H_ONES | GCCNMF_FLAG_CONCURRENT_GROUPS | GCCNMF_FLAG_UNFUSED_W_UPDATE)) || n > 128 || n >= K) return GCCNMF_ERR_ARG;
+    return gccnmf_klnmf_semi_supported(F, K, n) ? GCCNMF_OK : GCCNMF_ERR_UNSUPPORTED;      // (K - n) % 16, K > 1024, F > 2049
+}
+
 // One launch group of the iteration, addressable on its own so that tests and the benchmark can time /
 // check each kernel in isolation.  stage: 0 prepare | 1 K1 | 2 K2 | 3 K3 | 4 K4a | 5 K4b | 6 final H rescale | 7 KL divergence of the current factors
 static int klnmf_stage(int stage, const float* V, float* W, float* H, float* workspace, const NmfGeom& g, int batch,
@@ -1048,11 +1063,16 @@ static int klnmf_stage(int stage, const float* V, float* W, float* H, float* wor
         return gccnmf_kl_divergence_launch(V, W, (flags & GCCNMF_FLAG_FIXED_W) ? 0 : g.sW, H, g.F, g.N, g.K, g.Fp, g.Kp, g.Np, batch, (double*)R, g.sV / 2,
                                            (double*)U, s);
     }
+    // Free atoms (semi-supervised): stage 4 reads a materialised R [batch][Fp][Np] with zero padding, so stages 1-3 take the forms that leave
+    // one in the workspace whatever the tuning keys say -- never the direct kernels (they keep Rt), never the K3 + K4a slab launch.  K1 + K2
+    // fused stays: stage 3 rewrites R.  Stages 4 and 5 are nmf_semi.hip's, on the free columns alone.
+    const int nfree = free_atoms(flags);
+    const bool semi = nfree > 0;
     const bool fused12 = fused_wh_updh(g, batch, flags);
-    const int head34 = fused_whdiv_rht_files(g, batch, flags), rest34 = batch - head34;      // files on the slab launch | behind it on the two launches
+    const int head34 = semi ? 0 : fused_whdiv_rht_files(g, batch, flags), rest34 = batch - head34;      // files on the slab launch | behind it on the two launches
     const bool fused34 = head34 > 0;
     const int groups = concurrent_groups(flags);      // launch forms that follow the launch size are chosen for all groups together (GCCNMF_FLAG_GROUPS)
-    if (direct_path(g, batch, groups)) {
+    if (!semi && direct_path(g, batch, groups)) {
         const DirectBufs d = direct_bufs(g, direct_base, batch);
         switch (stage) {
             case 0: {
@@ -1078,8 +1098,8 @@ static int klnmf_stage(int stage, const float* V, float* W, float* H, float* wor
         }
     }
 #ifdef GCCNMF_EXPERIMENTS
-    const bool split_wh = single_file_split(g, batch, g.Kp, gccnmf_tune_wh_splits);      // the round-3 latency path: one file's reductions as parts
-    const bool split_rht = single_file_split(g, batch, g.Np, gccnmf_tune_rht_splits);
+    const bool split_wh = !semi && single_file_split(g, batch, g.Kp, gccnmf_tune_wh_splits);      // the round-3 latency path: one file's reductions as parts
+    const bool split_rht = !semi && single_file_split(g, batch, g.Np, gccnmf_tune_rht_splits);
 #else
     constexpr bool split_rht = false;              // the split-K path is compiled out of the product library
 #endif
@@ -1111,6 +1131,7 @@ static int klnmf_stage(int stage, const float* V, float* W, float* H, float* wor
 #endif
             return launch_wh_div(g, V, W, g.sW, H, nullptr, 0, R, batch, xcd, s);
         case 4:
+            if (semi) return gccnmf_klnmf_semi_rht_launch(R, H, U, rowsumH, g.F, g.N, g.K, nfree, batch, s);           // U[:, K - n:], rowsumH[K - n:]
             if (fused34)                                                                                               // done by stage 3 ...
                 return rest34 ? launch_rht(g, R + head34 * g.sV, H + head34 * g.sH, U + head34 * g.sU, rowsumH + (long)head34 * g.Kp, rest34, xcd, s)
                               : GCCNMF_OK;                                                                             // ... but for the rest
@@ -1120,6 +1141,7 @@ static int klnmf_stage(int stage, const float* V, float* W, float* H, float* wor
             if (can_fuse_w_update(g, batch, groups) && !(flags & 2)) return launch_rht_update_w(g, R, H, W, colsumW, hscale, batch, xcd, s);
             return launch_rht(g, R, H, U, rowsumH, batch, xcd, s);
         case 5:
+            if (semi) return gccnmf_klnmf_semi_update_w_launch(W, U, rowsumH, colsumW, hscale, g.F, g.K, nfree, batch, s);
             if (split_rht)
                 return launch_update_w(W, parts, rowsum_parts, colsumW, hscale, g.F, g.Fp, g.K, g.Kp, g.sW, g.sU, (long)g.Kp, (long)g.Kp, batch,
                                        s, gccnmf_tune_rht_splits, g.sU, (long)g.Kp);
@@ -1145,6 +1167,7 @@ int gccnmf_klnmf_plan(int F, int N, int K, int batch, int flags) {
     GCCNMF_ENTER();
     if (F < 2 || N < 1 || K < 1 || batch < 1) return -1;
     if (flags & GCCNMF_FIXED_BITS) return fixed_flags_ok(flags) && gccnmf_klnmf_fixed_supported(F, K) ? 16 : -1;
+    if (flags & GCCNMF_FREE_BITS) return semi_check(F, K, flags) == GCCNMF_OK ? 32 : -1;      // bit 5: the semi-supervised iteration (then no other bit)
     const NmfGeom g = make_geom(F, N, K);
     return (direct_path(g, batch, concurrent_groups(flags)) ? 1 : 0) | (fused_wh_updh(g, batch, flags) ? 2 : 0) | (fused_whdiv_rht_files(g, batch, flags) > 0 ? 4 : 0) |
            ((chain_stages(g, batch, flags) || short_chain_group(g, batch, flags)) ? 8 : 0);
@@ -1157,6 +1180,8 @@ int gccnmf_klnmf_stage(const float* V, float* W, float* H, float* workspace, int
     if (!V || !W || !H || !workspace || F < 2 || N < 1 || K < 1 || batch < 1 || ((flags & GCCNMF_FIXED_BITS) && !(stage == 7 && flags == GCCNMF_FLAG_FIXED_W)))
         return GCCNMF_ERR_ARG;
     if (!workspace_aligned(workspace)) return GCCNMF_ERR_ARG;          // float4 / LDS-DMA accesses to its blocks; stage 7's float64 partials and results
+    if (flags & GCCNMF_FREE_BITS)
+        if (const int rc = semi_check(F, K, flags)) return rc;
     return klnmf_stage(stage, V, W, H, workspace, make_geom(F, N, K), batch, sparsity_alpha, epsilon, flags, (hipStream_t)stream);
 }
 
@@ -1167,6 +1192,18 @@ int gccnmf_klnmf(const float* V, float* W, float* H, float* workspace, int F, in
     if (!workspace_aligned(workspace)) return GCCNMF_ERR_ARG;          // R, U, Wt, Ht, Rt are read with float4 loads and LDS-DMA: 16 bytes
     hipStream_t s = (hipStream_t)stream;
     NmfGeom g = make_geom(F, N, K);
+    if ((flags & GCCNMF_FREE_BITS) && !(flags & GCCNMF_FIXED_BITS)) {
+        // semi-supervised: the dictionary in W[:, :K - n] of every file stays as it is, the n free atoms behind it and all of H are learned.
+        // Plain launches (klnmf_stage keeps R materialised); nothing chains: the status words are cleared for this call.
+        int rc;
+        if ((rc = semi_check(F, K, flags))) return rc;
+        if (hipMemsetAsync(chain_status_words(chain_counters(workspace, g, batch), g, batch), 0, 32 * sizeof(unsigned), s) != hipSuccess) return GCCNMF_ERR_LAUNCH;
+        if ((rc = klnmf_stage(0, V, W, H, workspace, g, batch, sparsity_alpha, epsilon, flags, s))) return rc;
+        for (int it = 0; it < iterations; ++it)
+            for (int stage = 1; stage <= 5; ++stage)
+                if ((rc = klnmf_stage(stage, V, W, H, workspace, g, batch, sparsity_alpha, epsilon, flags, s))) return rc;
+        return klnmf_stage(6, V, W, H, workspace, g, batch, sparsity_alpha, epsilon, flags, s);
+    }
     if (flags & GCCNMF_FIXED_BITS) {
         // fixed dictionary: W is read only, H holds the initial coefficients (or, with H_ONES, is output only); one launch runs every
         // iteration.  Nothing chains: the status words of gccnmf_klnmf_chain_status are cleared for this call.
@@ -1260,7 +1297,7 @@ long gccnmf_klnmf_ragged_workspace_floats(int F, int Nmax, int K, int batch) {
 int gccnmf_klnmf_ragged(const float* V, float* W, float* H, float* workspace, int F, const int* N, int Nmax, int K, int batch, int iterations,
                         float sparsity_alpha, float epsilon, int flags, void* stream) {
     GCCNMF_ENTER();
-    if (!V || !W || !H || !workspace || !N || F < 2 || Nmax < 1 || K < 1 || batch < 1 || iterations < 0 || (flags & GCCNMF_FIXED_BITS))
+    if (!V || !W || !H || !workspace || !N || F < 2 || Nmax < 1 || K < 1 || batch < 1 || iterations < 0 || (flags & (GCCNMF_FIXED_BITS | GCCNMF_FREE_BITS)))
         return GCCNMF_ERR_ARG;
     if (!workspace_aligned(workspace)) return GCCNMF_ERR_ARG;
     if (batch > GCCNMF_RAGGED_MAX_BATCH) return GCCNMF_ERR_UNSUPPORTED;

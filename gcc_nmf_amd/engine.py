@@ -45,6 +45,14 @@ def klnmf_initial_factors(F, N, K, epsilon=1e-16, seedValue=0):
     return W.astype(np.float32), H.astype(np.float32)
 
 
+def semi_supervised_initial_factors(dictionaryW, numFreeAtoms, N, epsilon=1e-16, seedValue=0):
+    """Initial (W, H) of semi-supervised KL-NMF: the dictionary's columns followed by columns [K_fixed, K) of the W0 that
+    klnmf_initial_factors(F, N, K, epsilon, seedValue) draws for K = K_fixed + numFreeAtoms; H is its H0.  float32 (F, K), (K, N)."""
+    F, Kf = dictionaryW.shape
+    W0, H0 = klnmf_initial_factors(F, N, Kf + int(numFreeAtoms), epsilon, seedValue)
+    return np.ascontiguousarray(np.concatenate([np.asarray(dictionaryW, np.float32), W0[:, Kf:]], axis=1)), H0
+
+
 class ChainHandOverError(RuntimeError):
     """A chained KL-NMF launch of a chunk did not hand over cleanly (gccnmf_klnmf_chain_status): the run is repeated on plain launches."""
 
@@ -212,6 +220,13 @@ class GCCNMFEngine(object):
     against it (gccnmf_klnmf with GCCNMF_FLAG_FIXED_W, every iteration in one launch) and K is the dictionary's.  ``initialH``: 'random'
     (the H0 performKLNMF draws) or 'ones'.
 
+    ``numFreeAtoms`` = n > 0 beside ``dictionaryW`` (semi-supervised KL-NMF): every file learns n free atoms of its
+    own beside the dictionary, with the coefficients of all K = K_fixed + n atoms (gccnmf_klnmf with GCCNMF_FLAG_FREE_ATOMS(n)) -- what
+    the dictionary was not trained on (an unseen noise, another room) goes to the free atoms instead of being forced onto speech atoms.
+    The dictionary's columns stay bit for bit; the free atoms start as columns [K_fixed, K) of the W0 that
+    klnmf_initial_factors(F, N, K, epsilon, seedValue) draws, H as its H0.  ``get_WH()`` returns each file's learned W.  K_fixed a
+    multiple of 16, n <= 128, K <= 1024; not with initialH='ones' or lengths=.
+
     ``reconstruction``: 'direct' = the reference's target spectrograms, W.(H_c o M_i) with the mixture phase (gccNMFFunctions.py:145-151);
     'ratio' = the Wiener-like ratio mask X_c * W.(H_c o M_i) / sum_j W.(H_c o M_j), whose targets add up to the mixture (one fused launch,
     csrc/ratio.hip; at most 8 targets); 'spatial' = the ratio mask followed by a multichannel Wiener filter (csrc/spatial.hip; DESIGN
@@ -241,6 +256,8 @@ class GCCNMFEngine(object):
     def __new__(cls, n_samples=None, *args, **kwargs):
         if cls is GCCNMFEngine and kwargs.get('lengths') is not None:
             kwargs = dict(kwargs)
+            if kwargs.pop('numFreeAtoms', 0):
+                raise ValueError('numFreeAtoms is not available with lengths= (the ragged engine has no semi-supervised form)')
             return RaggedGCCNMFEngine(kwargs.pop('lengths'), *args, **kwargs)
         return super(GCCNMFEngine, cls).__new__(cls)
 
@@ -248,10 +265,15 @@ class GCCNMFEngine(object):
                  microphoneSeparationInMetres=1.0, numTargets=3, dictionarySize=None, numIterations=100,
                  sparsityAlpha=0, epsilon=1e-16, seedValue=0, batch=1, windowFunction=np.hanning,
                  device='cuda:0', klnmf_flags=0, nmf_groups=None, dictionaryW=None, initialH='random', reconstruction='direct',
-                 gccPHATNLEnabled=False, gccPHATNLAlpha=2.0, tdoaTracking=False, localizationWindowSize=None, tolerance=None, checkEvery=10):
+                 gccPHATNLEnabled=False, gccPHATNLAlpha=2.0, tdoaTracking=False, localizationWindowSize=None, tolerance=None, checkEvery=10,
+                 numFreeAtoms=0):
         if initialH not in ('random', 'ones'):
             raise ValueError("initialH must be 'random' or 'ones'")
         self.initialH = initialH
+        if numFreeAtoms and dictionaryW is None:
+            raise ValueError('numFreeAtoms needs dictionaryW (without a dictionary every atom is free: dictionarySize)')
+        if numFreeAtoms and initialH == 'ones':
+            raise ValueError("numFreeAtoms cannot be combined with initialH='ones'")
         self.tolerance, self.checkEvery, numIterations = _hip.check_convergence(tolerance, checkEvery, numIterations)
         self.iterations_used = self.divergence_trace = None
         self.tdoaTracking, self.localizationWindowSize = check_tdoa_tracking(tdoaTracking, localizationWindowSize, numTargets)
@@ -259,12 +281,14 @@ class GCCNMFEngine(object):
         if self.reconstruction == 'spatial':
             _hip.reconstruct_spatial_batch(batch)          # at most 65535 files per call: ValueError here, not at the first reconstruct()
         self.gccPHATNLEnabled, self.gccPHATNLAlpha = check_gcc_phat_nl(gccPHATNLEnabled, gccPHATNLAlpha)
-        self.dictionaryW = None
+        self.dictionaryW, self.numFreeAtoms = None, 0
         if dictionaryW is not None:
             self.dictionaryW = check_dictionary(dictionaryW, int(windowSize) // 2 + 1)
-            K = self.dictionaryW.shape[1]
+            self.numFreeAtoms = _hip.check_free_atoms(numFreeAtoms, self.dictionaryW.shape[1], int(windowSize) // 2 + 1)
+            K = self.dictionaryW.shape[1] + self.numFreeAtoms
             if dictionarySize is not None and int(dictionarySize) != K:
-                raise ValueError('dictionarySize %d conflicts with the %d atoms of dictionaryW' % (dictionarySize, K))
+                raise ValueError('dictionarySize %d conflicts with the %d atoms of dictionaryW%s' % (
+                    dictionarySize, K, ' and the free atoms' if self.numFreeAtoms else ''))
             dictionarySize, nmf_groups = K, 1
         elif dictionarySize is None:
             dictionarySize = 128
@@ -328,7 +352,10 @@ class GCCNMFEngine(object):
             self.CC = z(B, 2, g.Fp, g.Tp)
             self.W = z(B, g.Fp, g.Kp)
             self.H = z(B, g.Kp, g.Np)
-            if self.dictionaryW is not None:
+            if self.numFreeAtoms:
+                # semi-supervised: every file starts from the dictionary followed by the drawn free atoms (refilled by _klnmf_start)
+                self.W0 = padded(semi_supervised_initial_factors(self.dictionaryW, self.numFreeAtoms, g.N, self.eps, seedValue)[0], (g.Fp, g.Kp), dev)
+            elif self.dictionaryW is not None:
                 # the dictionary never changes: the per-file W that the masks and the reconstruction read is filled once, here
                 self.W0 = padded(self.dictionaryW, (g.Fp, g.Kp), dev)
                 self.W.copy_(self.W0.unsqueeze(0).expand_as(self.W))
@@ -392,11 +419,11 @@ class GCCNMFEngine(object):
             return
         for attempt in range(2):
             self._klnmf_start()
-            if self.dictionaryW is not None and self.initialH == 'ones':
+            if self._fixed() and self.initialH == 'ones':
                 self.H[:, :self.g.K, :self.g.N] = 1                 # the divergence of the initial factors reads H
             try:
                 self.iterations_used, self.divergence_trace = converge_klnmf(
-                    self._klnmf_iterate, lambda: self._divergence().cpu().numpy(), [self.H] if self.dictionaryW is not None else [self.W, self.H],
+                    self._klnmf_iterate, lambda: self._divergence().cpu().numpy(), [self.H] if self._fixed() else [self.W, self.H],
                     self.iters, self.tolerance, self.checkEvery, failed=self.chain_failed)
                 return
             except ChainHandOverError:
@@ -409,9 +436,13 @@ class GCCNMFEngine(object):
                       '(gccnmf_set_tuning(21, 0)) and repeats the batch', RuntimeWarning)
         _hip.check(self.lib.gccnmf_set_tuning(21, 0), 'gccnmf_set_tuning')
 
+    def _fixed(self):
+        """A dictionary and no free atoms: the fixed-dictionary call (one shared W, never written)."""
+        return self.dictionaryW is not None and not self.numFreeAtoms
+
     def _klnmf_start(self):
         """The initial factors into W and H (a fixed dictionary with the all-ones start needs none: H is then output only)."""
-        if self.dictionaryW is not None:
+        if self._fixed():
             if self.initialH != 'ones':
                 self.H.copy_(self.H0.unsqueeze(0).expand_as(self.H))
             return
@@ -428,7 +459,7 @@ class GCCNMFEngine(object):
     def _divergence(self):
         """(batch,) float64 on the device: stage 7 per file group, each in its own workspace."""
         g = self.g
-        fixed = self.dictionaryW is not None
+        fixed = self._fixed()
         out = [klnmf_divergence(self.V[b0], self.W0 if fixed else self.W[b0], self.H[b0], ws, g.F, g.N, g.K, per, fixed)
                for b0, per, ws, _ in self._groups()]
         return out[0] if len(out) == 1 else torch.cat(out)
@@ -454,7 +485,7 @@ class GCCNMFEngine(object):
     def _klnmf_iterate(self, iters, first):
         """``iters`` more iterations on W and H in place, as the library chooses to launch them (first: the first call of a run)."""
         g = self.g
-        fixed = self.dictionaryW is not None        # (one group then; with the all-ones start H is output only: no H0 broadcast)
+        fixed = self._fixed()        # (one group then; with the all-ones start H is output only: no H0 broadcast)
         if self.nmf_groups > 1:
             main = torch.cuda.current_stream(self.device)
             ready = torch.cuda.Event()
@@ -467,7 +498,7 @@ class GCCNMFEngine(object):
             # (all-half-height tiles, which win for a 32-file launch ALONE, lose here: 152.4 k vs 155.4 k frames/s)
             _hip.klnmf(self.V[b0], self.W0 if fixed else self.W[b0], self.H[b0], ws, g.F, g.N, g.K, per, iters, self.alpha, self.eps,
                        fixed_w=fixed, h_ones=fixed and first and self.initialH == 'ones', groups=self.nmf_groups,
-                       flags=0 if fixed else self.klnmf_flags, stream=None if st is None else st.cuda_stream)
+                       flags=0 if fixed else self.klnmf_flags, free_atoms=self.numFreeAtoms, stream=None if st is None else st.cuda_stream)
             if st is not None:
                 done = torch.cuda.Event()
                 done.record(st)

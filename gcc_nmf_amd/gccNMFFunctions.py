@@ -26,7 +26,7 @@ from scipy.signal import argrelmax
 
 from . import _hip, _staging
 from .engine import (Geometry, padded, fft_twiddles, steering_tables, check_reconstruction, check_iterations, converge_klnmf,
-                     klnmf_divergence)
+                     klnmf_divergence, check_dictionary, semi_supervised_initial_factors)
 from .librosaSTFT import stft, istft, ParameterError, _window_vector, _istft_device, _stft_device
 from .wavfile import wavread, wavwrite
 
@@ -180,6 +180,36 @@ def performKLNMFUntilConverged(V, dictionarySize, maxIterations, sparsityAlpha, 
         H = sc.download(dH[:K, :N])
     checks = check_iterations(trace, checkEvery, maxIterations)      # (this module's min / max are NumPy's: the reference's star import)
     return W, H, dict(iterations=int(iterations[0]), divergences=[(it, float(d[0])) for it, d in zip(checks, trace)])
+
+
+def performSemiSupervisedKLNMF(V, dictionaryW, numFreeAtoms, numIterations, sparsityAlpha, epsilon=1e-16, seedValue=0):
+    """Semi-supervised KL-NMF (not in the reference): performKLNMF's iteration with the pre-trained ``dictionaryW``
+    (F, K_fixed) kept as it is -- bit for bit, not normalised -- in the first columns of W, and ``numFreeAtoms`` free atoms learned from
+    V beside it, with the coefficients of all K = K_fixed + numFreeAtoms atoms (gccnmf_klnmf with GCCNMF_FLAG_FREE_ATOMS).  The
+    initial factors are the engine's (GCCNMFEngine(dictionaryW=, numFreeAtoms=)): with W0, H0 = klnmf_initial_factors(F, N, K, epsilon,
+    seedValue), the free atoms start as W0[:, K_fixed:] and H as H0 (a generator of its own: no side effect on NumPy's global one).
+    Returns float32 (W, H) of shapes (F, K) and (K, N).  K_fixed a multiple of 16, numFreeAtoms in [1, 128], K <= 1024, F <= 2049, else
+    ValueError.  One call's worth of columns only: V of more than LARGE_N_COLUMNS columns raises NotImplementedError."""
+    V = np.asarray(V)
+    if V.ndim != 2:
+        raise ValueError('V must be (F, N)')
+    F, N = V.shape
+    Wfix = check_dictionary(dictionaryW, F)
+    n = _hip.check_free_atoms(numFreeAtoms, Wfix.shape[1], F)
+    if n == 0:
+        raise ValueError('performSemiSupervisedKLNMF needs at least one free atom (inferKLNMFCoefficients takes a dictionary alone)')
+    if N > LARGE_N_COLUMNS:
+        raise NotImplementedError('performSemiSupervisedKLNMF runs V as one call: at most %d columns, got %d' % (LARGE_N_COLUMNS, N))
+    K = Wfix.shape[1] + n
+    lib, dev = _hip.lib(), _device()
+    W0, H0 = semi_supervised_initial_factors(Wfix, n, N, epsilon, seedValue)
+    init = dict(W=torch.from_numpy(W0).to(dev), H=torch.from_numpy(H0).to(dev))
+    with _staging.Scope(dev) as sc:
+        dV, dW, dH, ws = _klnmf_buffers(sc, lib, V, K, init)
+        _hip.klnmf(dV, dW, dH, ws, F, N, K, 1, int(numIterations), float(sparsityAlpha), float(epsilon), free_atoms=n)
+        W = sc.remember(sc.download(dW[:F, :K]), 'W', dict(W=dW), dict(F=F, K=K))
+        H = sc.download(dH[:K, :N])
+    return W, H
 
 
 def getKLDivergence(V, W, H):

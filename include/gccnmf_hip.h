@@ -53,6 +53,27 @@ extern "C" {
 #define GCCNMF_FLAG_H_ONES (1 << 17)    /* with GCCNMF_FLAG_FIXED_W only (else GCCNMF_ERR_ARG): the initial H is all ones (the streaming
                                           * processor's h0 = 1); H is output only and is not read */
 
+#define GCCNMF_FLAG_FREE_ATOMS(n) ((n) << 18)     /* bits 18-25; 0 = not semi-supervised.  SEMI-SUPERVISED KL-NMF: per file W = [ W_fixed (F x (K - n)) |
+                                          * W_free (F x n) ] -- the caller has put a pre-trained dictionary into columns [0, K - n) of every file's W
+                                          * [batch][Fp][Kp] and the initial free atoms into the LAST n columns [K - n, K).  One iteration is performKLNMF's
+                                          * with its W half restricted to the free columns:
+                                          *     H      <- H o W^T(V / WH) / (colsum W + alpha + eps)      all K atoms             (gccNMFFunctions.py:76)
+                                          *     R       = V / (W H)                                       with the new H
+                                          *     W_free <- W_free o (R . H_free^T) / rowsum(H_free)        the n free columns only (:77)
+                                          *     s = sqrt(sum_f W_free^2);  W_free /= s;  H_free *= s      free atoms only         (:79-81)
+                                          * The fixed columns are never written (bit-identical after the call), are not normalised, and their rows of H are
+                                          * not rescaled -- as in the fixed-dictionary call; padding rows, atoms and columns stay exactly zero; a free atom
+                                          * whose row of H sums to 0 behaves as in the blind call.  V, W, H, the workspace and its size are exactly the blind
+                                          * call's.  Plain launches: three of the four GEMMs are the blind call's in the forms that materialise R, R.H^T and
+                                          * the W update run over the free atoms alone (csrc/nmf_semi.hip: one pass over R, every sum in an order fixed by
+                                          * (F, N, K, n) -- a file's factors are bit for bit the same alone and in any batch).  The chain-status words are
+                                          * cleared: nothing chains.  Decided before anything is launched -- GCCNMF_ERR_ARG: together with
+                                          * GCCNMF_FLAG_FIXED_W, GCCNMF_FLAG_H_ONES, GCCNMF_FLAG_CONCURRENT_GROUPS or GCCNMF_FLAG_UNFUSED_W_UPDATE; n > 128;
+                                          * n >= K.  GCCNMF_ERR_UNSUPPORTED: (K - n) % 16 != 0 (the free block starts on a float4 / atom-group boundary; the
+                                          * dictionaries the reference trains have 64 ... 1024 atoms), K > 1024, F > 2049.  gccnmf_klnmf_ragged rejects the
+                                          * bits (GCCNMF_ERR_ARG); gccnmf_klnmf_plan returns bit 5 alone, or -1 for a call these rules reject;
+                                          * gccnmf_klnmf_stage takes the same bits (see there) */
+
 int gccnmf_version(void);
 
 /* Tuning knobs: process-global atomics; every library call works on a snapshot taken at its entry.  Results stay valid (and, where a
@@ -166,8 +187,9 @@ int gccnmf_klnmf_chain_status(const float* workspace, int F, int N, int K, int b
 
 /* Which launches gccnmf_klnmf uses for this problem under the current tuning: bit 0 = the direct latency kernels (a handful of files),
  * bit 1 = K1 + K2 as one launch of column tiles (tuning key 16), bit 2 = K3 + K4a as one launch of 64-bin slabs (key 17), bit 3 = the whole
- * call as one chained launch (key 21), bit 4 = the fused fixed-dictionary launch (GCCNMF_FLAG_FIXED_W; then no other bit).  -1 on bad
- * arguments (a flag combination gccnmf_klnmf rejects, or a fixed-dictionary shape outside its envelope).
+ * call as one chained launch (key 21), bit 4 = the fused fixed-dictionary launch (GCCNMF_FLAG_FIXED_W; then no other bit), bit 5 = the semi-supervised
+ * iteration (GCCNMF_FLAG_FREE_ATOMS; then no other bit).  -1 on bad arguments (a flag combination gccnmf_klnmf rejects, or a fixed-dictionary
+ * or semi-supervised shape outside its envelope).
  * (Benchmarks and tests name the kernel they time by this; the result of gccnmf_klnmf does not depend on it beyond round-off.) */
 int gccnmf_klnmf_plan(int F, int N, int K, int batch, int flags);
 
@@ -206,7 +228,12 @@ int gccnmf_klnmf_plan(int F, int N, int K, int batch, int flags);
  *     plan bit 2 (K3 + K4a)      3: U, rowsumH, R is not written | 4: nothing (but for the files a partial slab launch left to the two launches)
  *     W update in the epilogue of R.H^T (128 < Fm <= 512 on the throughput tile, neither GCCNMF_FLAG_UNFUSED_W_UPDATE nor plan bit 2; no
  *       plan bit)                4: W, hscale, colsumW, U and rowsumH are not written | 5: nothing
- *     plan bit 0 (direct)        0: also Wt | 2: H and Ht | 3: Rt and, of R, bin F - 1 alone (F = 16 n + 1) | 4: U, rowsumH from Rt and Ht | 5: W and Wt */
+ *     plan bit 0 (direct)        0: also Wt | 2: H and Ht | 3: Rt and, of R, bin F - 1 alone (F = 16 n + 1) | 4: U, rowsumH from Rt and Ht | 5: W and Wt
+ * With GCCNMF_FLAG_FREE_ATOMS(n) in flags (same argument rules as gccnmf_klnmf, decided first): stages 0, 1, 2, 3, 6 and 7 mean what they mean
+ * without it, but stages 1-3 always take forms that leave R [batch][Fp][Np], zero padded, in the workspace (K1 + K2 fused included: stage 3
+ * rewrites R; never the direct kernels or the K3 + K4a slab launch); stage 4 writes U[:, K - n : K] and rowsumH[K - n : K] only, at their ordinary
+ * places, stage 5 updates W[:, K - n : K], hscale[K - n : K] and colsumW[K - n : K] only: what belongs to the fixed atoms is not written (hscale
+ * stays 1 and colsumW what stage 0 computed).  A call without the bits launches exactly what it launched before they existed. */
 int gccnmf_klnmf_stage(const float* V, float* W, float* H, float* workspace, int F, int N, int K, int batch,
                        float sparsity_alpha, float epsilon, int flags, int stage, void* stream);
 
