@@ -517,12 +517,15 @@ int gccnmf_istft_ola(const float* spec, int nsig, int n_fft, int hop, int T, int
     const int F = n_fft / 2 + 1;
     const int ps = fft_ps();
     GccNmfPitches p = gccnmf_make_pitches(F, T, 1);
+    const int trim = center ? n_fft / 2 : 0;
+    const int L = n_fft + hop * (T - 1) - 2 * trim;
+    if (L < 1) return GCCNMF_ERR_ARG;       // (both forms, before anything is launched)
     if (!frames) {      // fused form: no frame buffer, one pass
-        const int trim = center ? n_fft / 2 : 0;
-        const int L = n_fft + hop * (T - 1) - 2 * trim;
-        if (L < 1) return GCCNMF_ERR_ARG;
         const int span = n_fft + hop * (ISTFT_TB - 1);
         if (span > 8 * FFT_NT) return GCCNMF_ERR_UNSUPPORTED;          // hop > n_fft / 3 or so: use the two-kernel form
+        // hop > n_fft leaves hop - n_fft samples between consecutive frames that no frame touches: the sliding accumulator covers a
+        // sub-batch's span only, so the gap behind every ISTFT_TB-th frame would never be written (the two-kernel form writes 0 there)
+        if (hop > n_fft) return GCCNMF_ERR_UNSUPPORTED;
         const size_t lds = fft_rows_bytes(ISTFT_TB, n_fft, ps) + sizeof(float) * (2 * span + n_fft);
         if (lds > 64 * 1024) {
             if (hipFuncSetAttribute((const void*)istft_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
@@ -551,9 +554,6 @@ int gccnmf_istft_ola(const float* spec, int nsig, int n_fft, int hop, int T, int
         hipLaunchKernelGGL(istft_frames_kernel<FFT_TB>, dim3(batch * (nsig / 2) * groups), dim3(FFT_NT), lds, s, (const float2*)spec, nsig,
                            n_fft, logN, T, window, (const float2*)twiddle, frames, F, p.Fp, p.Tp, ps);
     GCCNMF_CHECK_LAUNCH();
-    const int trim = center ? n_fft / 2 : 0;
-    const int L = n_fft + hop * (T - 1) - 2 * trim;
-    if (L < 1) return GCCNMF_ERR_ARG;
     hipLaunchKernelGGL(istft_ola_kernel, dim3(gccnmf_ceil_div(L, 256), nsig, batch), dim3(256), 0, s, frames, n_fft, hop, T, L,
                        trim, gain, y);
     GCCNMF_CHECK_LAUNCH();

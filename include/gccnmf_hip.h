@@ -426,9 +426,12 @@ int gccnmf_reconstruct(const float* W, const float* H, const unsigned char* argm
  *   spec   [batch][nsig][Fp][Tp] complex (nsig must be even: signals are inverse-transformed in pairs)
  *   window [n_fft] synthesis window; twiddle as for the forward transform
  *   frames [batch][nsig][T][n_fft] float32 scratch, or NULL: inverse transform and overlap-add fused in one pass (same accumulation
- *          order, no frame buffer; needs n_fft + 3*hop <= 2048, else GCCNMF_ERR_UNSUPPORTED)
+ *          order, no frame buffer; needs n_fft + 3*hop <= 2048 and hop <= n_fft, else GCCNMF_ERR_UNSUPPORTED: with hop > n_fft there are
+ *          samples between consecutive frames that no frame touches, which only the two-kernel form writes -- as 0)
  *   center != 0 trims n_fft/2 samples at both ends (the reference path), 0 keeps all n_fft + hop*(T-1)
- *   y      [batch][nsig][L] float32 out, L = n_fft + hop*(T-1) - (center ? n_fft : 0) */
+ *   y      [batch][nsig][L] float32 out, L = n_fft + hop*(T-1) - (center ? n_fft : 0); every sample is written, and where both forms
+ *          accept a call they give the same bits.  L < 1 (T = 1 with center != 0): GCCNMF_ERR_ARG from both forms, like every other
+ *          argument error before anything is launched */
 int gccnmf_istft_ola(const float* spec, int nsig, int n_fft, int hop, int T, int batch, const float* window,
                      const float* twiddle, float gain, int center, float* frames, float* y, void* stream);
 

@@ -398,7 +398,8 @@ def test_pcm16_ingest_and_egress(dev1, tmp_path):
     for i in range(3):
         m = np.max(np.abs(yl[i]))
         expect = O.float2pcm((yl[i] / m * 0.99).astype(np.float32)) if m >= 1 else O.float2pcm(yl[i])
-        assert np.abs(loud[i].astype(int) - expect.astype(int)).max() <= 1
+        # exactly: fft.hip is built without fma contraction and the reference computes in float32 (tests/test_gpu_fft_stages.py shows it group by group)
+        assert np.array_equal(loud[i], expect)
 
 
 def test_nmf_file_groups_on_streams_are_bitwise_the_single_stream_result():
