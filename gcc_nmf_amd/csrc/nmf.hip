@@ -309,20 +309,22 @@ __global__ __launch_bounds__(256) void nmf_update_w_onepass_kernel(float* __rest
     nmf_update_w_onepass_item<AT, NSPLIT>(W, U, rowsumH, colsumW, hscale, F, K, Kp, sW, sU, sVec, sRowsum, sSplitU, sSplitR, Wt, sWt, ldwt, b, ch, smem, (int)threadIdx.x);
 }
 
-static int launch_update_w(float* W, const float* U, const float* rowsumH, float* colsumW, float* hscale, int F, int Fp, int K,
-                           int Kp, long sW, long sU, long sVec, long sRowsum, int batch, hipStream_t s, int nsplit = 1,
-                           long sSplitU = 0, long sSplitR = 0, float* Wt = nullptr, long sWt = 0, int ldwt = 0, int groups = 1) {
+// `a`: the factors and their strides (direct.h; update_w_args below fills it); what it does not hold: the files of this launch, the file groups that
+// run it side by side, split-K partials (nsplit > 1) and the transposed copy of W the direct path keeps (Wt, or nullptr)
+static int launch_update_w(const UpdateWArgs& a, int batch, int groups, hipStream_t s, int nsplit, long sSplitU, long sSplitR, float* Wt, long sWt,
+                           int ldwt) {
+    const int Kp = a.Kp;
     const long sized = (long)batch * groups;           // files of every group that runs this launch side by side: the kernel is chosen for all of them
-    if (sized * (Kp / 64) < 256 && gccnmf_tune_ring && F <= 64 * 9 && (nsplit == 1 || nsplit == 2 || nsplit == 4)) {
+    if (sized * (Kp / 64) < 256 && gccnmf_tune_ring && a.F <= 64 * 9 && (nsplit == 1 || nsplit == 2 || nsplit == 4)) {
         // 16 atoms per workgroup (64-byte row segments); 8 (twice the workgroups, 32-byte segments) measured slower: 13.0 vs 11.4 us for one
         // file at K = 1024 -- kept selectable for experiments (tuning key 1 = 64)
-#define GCCNMF_ONEPASS(AT_, NS_) hipLaunchKernelGGL((nmf_update_w_onepass_kernel<AT_, NS_>), dim3(batch * (Kp / AT_)), dim3(256), 0, s, W, U, rowsumH, \
-                                                    colsumW, hscale, F, K, Kp, sW, sU, sVec, sRowsum, sSplitU, sSplitR, Wt, sWt, ldwt)
+#define GCCNMF_ONEPASS(AT_, NS_) hipLaunchKernelGGL((nmf_update_w_onepass_kernel<AT_, NS_>), dim3(batch * (Kp / AT_)), dim3(256), 0, s, a.W, a.U, a.rowsumH, \
+                                                    a.colsumW, a.hscale, a.F, a.K, Kp, a.sW, a.sU, a.sVec, a.sRowsum, sSplitU, sSplitR, Wt, sWt, ldwt)
         const bool narrow = gccnmf_tune_ablate == 64;
         // short dictionaries at batch scale (64 files, K = 128: the launch between the two fused GEMM launches): 32 atoms per workgroup =
         // whole 128-byte lines per row and workgroup -- with 16 atoms every line of W and U is fetched by two workgroups (17 us for 51 MB).
         // Only for K <= 128, where the launch forms follow the batch size anyway (a file's bits are batch-independent for K > 128).
-        const bool wide = !narrow && nsplit == 1 && !Wt && K <= 128 && sized * (Kp / 32) >= 256 && gccnmf_tune_wide_update_w;
+        const bool wide = !narrow && nsplit == 1 && !Wt && a.K <= 128 && sized * (Kp / 32) >= 256 && gccnmf_tune_wide_update_w;
         if (wide) {
             GCCNMF_ONEPASS(32, 1);
         } else if (narrow) {
@@ -338,15 +340,16 @@ static int launch_update_w(float* W, const float* U, const float* rowsumH, float
         GCCNMF_CHECK_LAUNCH();
         return GCCNMF_OK;
     }
+    const int Fp = gccnmf_round_up(a.F, 16);
     if (sized * (Kp / 64) >= 256) {
-        hipLaunchKernelGGL(nmf_update_w_kernel<64>, dim3(batch * (Kp / 64)), dim3(256), 0, s, W, U, rowsumH, colsumW, hscale, F, Fp, K,
-                           Kp, sW, sU, sVec, sRowsum, nsplit, sSplitU, sSplitR);
+        hipLaunchKernelGGL(nmf_update_w_kernel<64>, dim3(batch * (Kp / 64)), dim3(256), 0, s, a.W, a.U, a.rowsumH, a.colsumW, a.hscale, a.F, Fp, a.K,
+                           Kp, a.sW, a.sU, a.sVec, a.sRowsum, nsplit, sSplitU, sSplitR);
     } else {
-        hipLaunchKernelGGL(nmf_update_w_kernel<16>, dim3(batch * (Kp / 16)), dim3(256), 0, s, W, U, rowsumH, colsumW, hscale, F, Fp, K,
-                           Kp, sW, sU, sVec, sRowsum, nsplit, sSplitU, sSplitR);
+        hipLaunchKernelGGL(nmf_update_w_kernel<16>, dim3(batch * (Kp / 16)), dim3(256), 0, s, a.W, a.U, a.rowsumH, a.colsumW, a.hscale, a.F, Fp, a.K,
+                           Kp, a.sW, a.sU, a.sVec, a.sRowsum, nsplit, sSplitU, sSplitR);
     }
     GCCNMF_CHECK_LAUNCH();
-    if (Wt) return gccnmf_transpose_launch(W, sW, Kp, Wt, sWt, ldwt, F, Kp, batch, s);      // (the one-pass kernel writes it itself)
+    if (Wt) return gccnmf_transpose_launch(a.W, a.sW, Kp, Wt, sWt, ldwt, a.F, Kp, batch, s);      // (the one-pass kernel writes it itself)
     return GCCNMF_OK;
 }
 
@@ -451,73 +454,110 @@ static NmfGeom make_geom(int F, int N, int K) {
     return g;
 }
 
-// R = V / (W . (bscale*H))
-static int launch_wh_div(const NmfGeom& g, const float* V, const float* W, long sW, const float* H, const float* hscale,
-                         long sScale, float* R, int batch, int xcd, hipStream_t s) {
+// What the `flags` word of gccnmf_klnmf / _stage / _plan / _ragged asks for, decoded ONCE at the entry point; everything below reads these fields.
+struct KlnmfMode {
+    bool xcd_affine;            // not GCCNMF_FLAG_NO_XCD_AFFINITY
+    bool unfused_w_update;      // GCCNMF_FLAG_UNFUSED_W_UPDATE
+    int groups;                 // GCCNMF_FLAG_GROUPS: file groups that run this call side by side on separate streams, launch forms sized for all (1 = alone)
+    bool fixed_w, h_ones;       // GCCNMF_FLAG_FIXED_W, GCCNMF_FLAG_H_ONES
+    int free_atoms;             // GCCNMF_FLAG_FREE_ATOMS(n): the last n atoms of every file's W are learned beside a dictionary (0 = not semi-supervised)
+};
+// ... with the argument rules of the flag combinations, decided before anything is launched: GCCNMF_OK = a valid word.
+//   fixed dictionary: GCCNMF_FLAG_FIXED_W alone or with GCCNMF_FLAG_H_ONES, nothing else (H_ONES without FIXED_W: GCCNMF_ERR_ARG)
+//   free atoms: not with the concurrent-groups or the unfused-W-update bit, n <= 128, n < K (GCCNMF_ERR_ARG); (K - n) % 16 == 0, K <= 1024,
+//   F <= 2049 (GCCNMF_ERR_UNSUPPORTED)
+static int decode_mode(int flags, int F, int K, KlnmfMode& m) {
+    const int n = (flags & (GCCNMF_FLAG_GROUPS(255) & ~GCCNMF_FLAG_CONCURRENT_GROUPS)) / (GCCNMF_FLAG_GROUPS(1) & ~GCCNMF_FLAG_CONCURRENT_GROUPS);
+    m.xcd_affine = !(flags & GCCNMF_FLAG_NO_XCD_AFFINITY);
+    m.unfused_w_update = (flags & GCCNMF_FLAG_UNFUSED_W_UPDATE) != 0;
+    m.groups = (flags & GCCNMF_FLAG_CONCURRENT_GROUPS) ? (n >= 2 ? n : 2) : 1;
+    m.fixed_w = (flags & GCCNMF_FLAG_FIXED_W) != 0;
+    m.h_ones = (flags & GCCNMF_FLAG_H_ONES) != 0;
+    m.free_atoms = (flags & GCCNMF_FLAG_FREE_ATOMS(255)) / GCCNMF_FLAG_FREE_ATOMS(1);
+    if (m.fixed_w || m.h_ones) return m.fixed_w && !(flags & ~(GCCNMF_FLAG_FIXED_W | GCCNMF_FLAG_H_ONES)) ? GCCNMF_OK : GCCNMF_ERR_ARG;
+    if (!m.free_atoms) return GCCNMF_OK;
+    if (m.groups > 1 || m.unfused_w_update || m.free_atoms > 128 || m.free_atoms >= K) return GCCNMF_ERR_ARG;
+    return gccnmf_klnmf_semi_supported(F, K, m.free_atoms) ? GCCNMF_OK : GCCNMF_ERR_UNSUPPORTED;
+}
+
+// The operands of the iteration's GEMMs, stated ONCE: the plain launches below and the chained launch (launch_klnmf_chain) both build them here, which
+// is what makes a chained call bit for bit the plain one.  sW, sScale, sVec: per-file strides of W and of the K-vectors (0 = one dictionary shared
+// by every file: the shared-dictionary callers).  xcd_affine / concurrent: GemmArgs' fields of those names (gemm_dma.h).
+// K1, K3: R = V / (W . (hscale*H))   (hscale = nullptr: K3, H carries its scale already)
+static GemmArgs wh_div_args(const NmfGeom& g, const float* V, const float* W, long sW, const float* H, const float* hscale, long sScale, float* R,
+                            int batch, int xcd_affine, int concurrent) {
     GemmArgs a = {};
     a.A = W; a.sA = sW; a.lda = g.Kp; a.a_clamp = g.Fp - 1;
     a.B = H; a.sB = g.sH; a.ldb = g.ld; a.b_clamp = g.Np - 4;
     a.M = g.Fm; a.N = g.N; a.Kd = g.K;
-    a.batch = batch; a.xcd_affine = xcd & 1; a.concurrent = xcd >> 1;
+    a.batch = batch; a.xcd_affine = xcd_affine; a.concurrent = concurrent;
     a.bscale = hscale; a.s_bscale = sScale;
     a.tail_row = g.F - 1;
     a.C = R; a.sC = g.sV; a.ldc = g.ld;
     a.E0 = V; a.sE0 = g.sV;
-    return dispatch_gemm<true, false, EPI_DIV>(a, g.tail, s);
+    return a;
 }
 
-// H = (hscale*H) * (W^T . R) / (colsumW + alpha + eps)
-static int launch_update_h(const NmfGeom& g, const float* W, long sW, const float* R, float* H, const float* hscale,
-                           long sScale, const float* colsumW, long sVec, float alpha, float eps, int batch, int xcd,
-                           hipStream_t s) {
+// K2: H = (hscale*H) * (W^T . R) / (colsumW + alpha + eps)
+static GemmArgs update_h_args(const NmfGeom& g, const float* W, long sW, const float* R, float* H, const float* hscale, long sScale,
+                              const float* colsumW, long sVec, float alpha, float eps, int batch, int xcd_affine, int concurrent) {
     GemmArgs a = {};
     a.A = W; a.sA = sW; a.lda = g.Kp; a.a_clamp = g.Kp - 4;
     a.B = R; a.sB = g.sV; a.ldb = g.ld; a.b_clamp = g.Np - 4;
     a.M = g.K; a.N = g.N; a.Kd = g.F;
     if ((g.F % 16) == 1) {   // F = 16*n + 1: bin F-1 leaves the matrix cores and becomes a rank-1 term of the epilogue
-        a.Kd = g.F - 1;
+        a.Kd = g.F - 1;      // (always so in a chained launch: chain_capable admits no other F)
         a.ktailA = W + (long)(g.F - 1) * g.Kp; a.s_ktailA = sW;
         a.ktailB = R + (long)(g.F - 1) * g.ld; a.s_ktailB = g.sV;
     }
-    a.batch = batch; a.xcd_affine = xcd & 1; a.concurrent = xcd >> 1;
+    a.batch = batch; a.xcd_affine = xcd_affine; a.concurrent = concurrent;
     a.C = H; a.sC = g.sH; a.ldc = g.ld;
     a.E1 = hscale; a.sE1 = sScale;
     a.E2 = colsumW; a.sE2 = sVec;
     a.alpha = alpha; a.eps = eps;
-    return dispatch_gemm<false, false, EPI_UPDH>(a, false, s);
+    return a;
 }
 
-// U = R . H^T, rowsumH = sum_n H
-static int launch_rht(const NmfGeom& g, const float* R, const float* H, float* U, float* rowsumH, int batch, int xcd,
-                      hipStream_t s) {
+// the product both forms of K4 share: R . H^T
+static GemmArgs rht_operands(const NmfGeom& g, const float* R, const float* H, int batch, int xcd_affine, int concurrent) {
     GemmArgs a = {};
     a.A = R; a.sA = g.sV; a.lda = g.ld; a.a_clamp = g.Fp - 1;
     a.B = H; a.sB = g.sH; a.ldb = g.ld; a.b_clamp = g.Kp - 1;
     a.M = g.Fm; a.N = g.K; a.Kd = g.N;
-    a.batch = batch; a.xcd_affine = xcd & 1; a.concurrent = xcd >> 1;
+    a.batch = batch; a.xcd_affine = xcd_affine; a.concurrent = concurrent;
     a.tail_row = g.F - 1;
-    a.rowsumB = rowsumH; a.s_rowsumB = g.Kp;
-    a.C = U; a.sC = g.sU; a.ldc = g.Kp;
-    return dispatch_gemm<true, true, EPI_STORE>(a, g.tail, s);
+    return a;
 }
 
+// K4a: U = R . H^T, rowsumH = sum_n H
+static GemmArgs rht_args(const NmfGeom& g, const float* R, const float* H, float* U, float* rowsumH, int batch, int xcd_affine, int concurrent) {
+    GemmArgs a = rht_operands(g, R, H, batch, xcd_affine, concurrent);
+    a.rowsumB = rowsumH; a.s_rowsumB = g.Kp;
+    a.C = U; a.sC = g.sU; a.ldc = g.Kp;
+    return a;
+}
+
+// K4a and K4b in one: W = normalise(W * (R.H^T) / rowsumH), colsumW, hscale
+static GemmArgs rht_update_w_args(const NmfGeom& g, const float* R, const float* H, float* W, float* colsumW, float* hscale, int batch,
+                                  int xcd_affine, int concurrent) {
+    GemmArgs a = rht_operands(g, R, H, batch, xcd_affine, concurrent);
+    a.C = W; a.sC = g.sW; a.ldc = g.Kp;
+    a.out_colsum = colsumW; a.out_norm = hscale; a.s_out = g.Kp;
+    return a;
+}
+
+static int launch_wh_div(const NmfGeom& g, const GemmArgs& a, hipStream_t s) { return dispatch_gemm<true, false, EPI_DIV>(a, g.tail, s); }
+static int launch_update_h(const GemmArgs& a, hipStream_t s) { return dispatch_gemm<false, false, EPI_UPDH>(a, false, s); }
+static int launch_rht(const NmfGeom& g, const GemmArgs& a, hipStream_t s) { return dispatch_gemm<true, true, EPI_STORE>(a, g.tail, s); }
+
 // W = normalise(W * (R.H^T) / rowsumH), colsumW, hscale -- K4a and K4b in one launch (tall tile, all F rows in one workgroup)
-static bool can_fuse_w_update(const NmfGeom& g, int batch, int groups = 1) {
+static bool can_fuse_w_update(const NmfGeom& g, int batch, int groups) {
     // the fused epilogue needs the tall tile; tiny launches prefer the small-batch tile and the two-launch form
     if (g.Fm <= 128 || g.Fm > 512 || gccnmf_tune_tile_policy == 2) return false;
     return gccnmf_tune_tile_policy == 1 || (long)batch * groups * gccnmf_ceil_div(g.K, 64) >= 256;
 }
 
-static int launch_rht_update_w(const NmfGeom& g, const float* R, const float* H, float* W, float* colsumW, float* hscale, int batch,
-                               int xcd, hipStream_t s) {
-    GemmArgs a = {};
-    a.A = R; a.sA = g.sV; a.lda = g.ld; a.a_clamp = g.Fp - 1;
-    a.B = H; a.sB = g.sH; a.ldb = g.ld; a.b_clamp = g.Kp - 1;
-    a.M = g.Fm; a.N = g.K; a.Kd = g.N;
-    a.batch = batch; a.xcd_affine = xcd & 1; a.concurrent = xcd >> 1;
-    a.tail_row = g.F - 1;
-    a.C = W; a.sC = g.sW; a.ldc = g.Kp;
-    a.out_colsum = colsumW; a.out_norm = hscale; a.s_out = g.Kp;
+static int launch_rht_update_w(const NmfGeom& g, const GemmArgs& a, hipStream_t s) {
     // the LDS-DMA kernel carries only the full-tile form of this epilogue (every wave entirely inside or outside M, no
     // ragged atom tile); anything else takes the register-staged kernel with the generic one
     if (gccnmf_tune_dma && (a.M & 127) == 0 && (a.N & 63) == 0)
@@ -634,7 +674,7 @@ struct DirectBufs {
     int ldwt, ldht, ldrt;
 };
 static long direct_floats(const NmfGeom& g, int batch) { return batch <= GCCNMF_DIRECT_MAX_BATCH ? (long)batch * (g.sU + g.sH + g.sV) : 0; }
-static bool direct_path(const NmfGeom& g, int batch, int groups = 1) {
+static bool direct_path(const NmfGeom& g, int batch, int groups) {
     return gccnmf_tune_direct && gccnmf_tune_tile_policy == 0 && (long)batch * groups <= gccnmf_tune_direct_batch && batch <= GCCNMF_DIRECT_MAX_BATCH;
 }
 static DirectBufs direct_bufs(const NmfGeom& g, float* base, int batch) {
@@ -705,22 +745,17 @@ static int direct_rht(const NmfGeom& g, const DirectBufs& d, const float* R, flo
 // 40: 153 / 186, 50: 160 / 189, 64: 208 / 240, 96: 312 / 333, 128: 379 / 431; K = 64, 64 files: 116 / 195.  A full round of 512 workgroups
 // (two per CU) takes 78 us, a last round of at most 256 (one per CU) 45, a larger one 76; the two launches 25 + 0.17 us per column tile.
 // Both scale alike with K, so the choice is made in those units.  (GCCNMF_FLAG_GROUPS: the file groups that run side by side are priced together.)
-// file groups that run this call side by side on separate streams (GCCNMF_FLAG_GROUPS): launch forms are chosen for all of them together
-static int concurrent_groups(int flags) {
-    const int n = (flags >> 8) & 255;
-    return (flags & 4) ? (n >= 2 ? n : 2) : 1;
-}
-static bool fused_wh_updh(const NmfGeom& g, int batch, int flags) {
-    if (!gccnmf_tune_fused_k12 || gccnmf_tune_tile_policy != 0 || direct_path(g, batch, concurrent_groups(flags)) || batch < 2 || !g.tail || g.Fm < 64 || g.Fm > 512 ||
+static bool fused_wh_updh(const NmfGeom& g, int batch, const KlnmfMode& m) {
+    if (!gccnmf_tune_fused_k12 || gccnmf_tune_tile_policy != 0 || direct_path(g, batch, m.groups) || batch < 2 || !g.tail || g.Fm < 64 || g.Fm > 512 ||
         (g.Fm % 64) != 0 || g.K > 128)
         return false;
     if (gccnmf_tune_fused_k12 == 2) return true;
-    const long wgs = (long)batch * gccnmf_ceil_div(g.N, 64) * concurrent_groups(flags), rem = wgs % 512;
+    const long wgs = (long)batch * gccnmf_ceil_div(g.N, 64) * m.groups, rem = wgs % 512;
     const long fused = 780 * (wgs / 512) + (rem == 0 ? 0 : rem <= 256 ? 450 : 760), two = 250 + 17 * wgs / 10;      // tenths of a microsecond
     return fused < two;
 }
-static int launch_wh_updh(const NmfGeom& g, const float* V, const float* W, float* H, const float* hscale, const float* colsumW, float alpha,
-                          float eps, int batch, hipStream_t s) {
+static WhUpdhArgs wh_updh_args(const NmfGeom& g, const float* V, const float* W, float* H, const float* hscale, const float* colsumW, float alpha,
+                               float eps, int batch) {
     WhUpdhArgs a = {};
     a.W = W; a.sW = g.sW; a.lda = g.Kp;
     a.H = H; a.sH = g.sH; a.ldb = g.ld;
@@ -728,7 +763,7 @@ static int launch_wh_updh(const NmfGeom& g, const float* V, const float* W, floa
     a.scale = hscale; a.colsum = colsumW; a.sVec = g.Kp;
     a.M = g.Fm; a.N = g.N; a.Kd = g.K; a.batch = batch;
     a.alpha = alpha; a.eps = eps;
-    return gccnmf_wh_updh_launch(a, s);
+    return a;
 }
 
 // K3 and K4a as ONE launch (gccnmf_whdiv_rht_kernel: 64-bin slabs with their W rows in registers), K <= 128.
@@ -738,12 +773,12 @@ static int launch_wh_updh(const NmfGeom& g, const float* V, const float* W, floa
 // files (from the front of the batch) that take the slab launch: all of them, none, or whole rounds' worth with the REST of the files on
 // the two launches behind it (72 files: 64 + 8 -> 184 + 40 us against 268 for the two launches over all of them, 368 for two slab rounds).
 // (GCCNMF_FLAG_GROUPS: the file groups that run side by side share the rounds; they are not split.)
-static int fused_whdiv_rht_files(const NmfGeom& g, int batch, int flags) {
-    if (!gccnmf_tune_fused_k34 || gccnmf_tune_tile_policy != 0 || direct_path(g, batch, concurrent_groups(flags)) || batch < 2 || !g.tail || g.Fm < 64 || g.Fm > 512 ||
+static int fused_whdiv_rht_files(const NmfGeom& g, int batch, const KlnmfMode& m) {
+    if (!gccnmf_tune_fused_k34 || gccnmf_tune_tile_policy != 0 || direct_path(g, batch, m.groups) || batch < 2 || !g.tail || g.Fm < 64 || g.Fm > 512 ||
         (g.Fm % 64) != 0 || g.K > 128 || (g.Fm / 64) * 16 < 32 * gccnmf_ceil_div(g.K, 32))
         return 0;
     if (gccnmf_tune_fused_k34 == 2) return batch;
-    const long slabs = g.Fm / 64, groups = concurrent_groups(flags), wgs = (long)batch * slabs * groups, rounds = (wgs + 511) / 512;
+    const long slabs = g.Fm / 64, groups = m.groups, wgs = (long)batch * slabs * groups, rounds = (wgs + 511) / 512;
     const long per_round = 512 / slabs;                          // files per round
     // in hundredths of a microsecond: 3.72 us x slabs / 8 per file on the two launches, 184 us per round, 10 us for the extra launch pair
     const long two = 372 * slabs / 8;
@@ -760,7 +795,7 @@ static int fused_whdiv_rht_files(const NmfGeom& g, int batch, int flags) {
     }
     return (int)head;
 }
-static int launch_whdiv_rht(const NmfGeom& g, const float* V, const float* W, const float* H, float* U, float* rowsumH, int batch, hipStream_t s) {
+static WhdivRhtArgs whdiv_rht_args(const NmfGeom& g, const float* V, const float* W, const float* H, float* U, float* rowsumH, int batch) {
     WhdivRhtArgs a = {};
     a.W = W; a.sW = g.sW; a.lda = g.Kp;
     a.H = H; a.sH = g.sH; a.ldb = g.ld;
@@ -768,32 +803,73 @@ static int launch_whdiv_rht(const NmfGeom& g, const float* V, const float* W, co
     a.U = U; a.sU = g.sU; a.ldu = g.Kp;
     a.rowsumH = rowsumH; a.sVec = g.Kp;
     a.M = g.Fm; a.N = g.N; a.Kd = g.K; a.batch = batch;
-    return gccnmf_whdiv_rht_launch(a, s);
+    return a;
+}
+// the one-pass / two-pass W update (launch_update_w; the last stage of the short-dictionary chain).  sW, sU, sVec: per-file strides, 0 = shared
+static UpdateWArgs update_w_args(const NmfGeom& g, float* W, long sW, const float* U, long sU, const float* rowsumH, float* colsumW, float* hscale,
+                                 long sVec) {
+    UpdateWArgs a = {};
+    a.W = W; a.U = U; a.rowsumH = rowsumH; a.colsumW = colsumW; a.hscale = hscale;
+    a.F = g.F; a.K = g.K; a.Kp = g.Kp; a.sW = sW; a.sU = sU; a.sVec = sVec; a.sRowsum = sVec;
+    return a;
 }
 
-// ---- chained launches of the iteration (tuning key 21; gemm_dma.h: GemmSync, gccnmf_gemm_chain_kernel) ---------------------------------
-// Counters of one file group, behind everything else in the workspace: c12 [batch][tiles_n] (K1 -> K2, in 32-column blocks), c23
-// [batch][tiles_n] (K2 -> K3), c34 [batch] (K3 -> K4, items), c41 [batch] (K4 -> the next iteration's K1, items), error [1].  Zeroed once per gccnmf_klnmf call; iteration `it` waits for
-// (it + 1) x the per-iteration count, so nothing is reset between launches.
-// The ready counters are rounded up to a 128-byte line (32 words), the 32 status words follow: error [1], 7 unused, tickets [8], XCCs seen per list [8],
-// 8 unused.  Every block in front of the counters is a multiple of 64 floats, so the workspace is one too (a ragged batch's, with its tables: of 4) --
-// workspaces carved back to back out of ONE allocation (the engine's file groups) all start 16-byte aligned when the first does, which the float4 /
-// LDS-DMA accesses to R, U, Wt, Ht, Rt rely on (the entry points reject a workspace that is not 16-byte aligned).  Everything that locates the
-// counters, the status words or what lies behind them (the ragged tables) goes through these helpers.
-static long chain_ready_counters(const NmfGeom& g, int batch) { return (long)batch * (2L * gccnmf_ceil_div(g.N, 64) + 2); }
-static long chain_counter_floats(const NmfGeom& g, int batch) { return (chain_ready_counters(g, batch) + 31) / 32 * 32 + 32; }
-static unsigned* chain_status_words(unsigned* counters, const NmfGeom& g, int batch) { return counters + chain_counter_floats(g, batch) - 32; }
-static bool workspace_aligned(const void* workspace) { return ((uintptr_t)workspace & 15) == 0; }
-static long klnmf_workspace_base_floats(const NmfGeom& g, int batch) {
-    long n = (long)batch * (g.sV + g.sU + 3L * g.Kp);
-    if (batch == 1) n += GCCNMF_SPLITS * ((g.sV > g.sU ? g.sV : g.sU) + (long)g.Kp);
-    return n + direct_floats(g, batch);
+// ---- the workspace of gccnmf_klnmf / gccnmf_klnmf_ragged, carved in ONE place ---------------------------------------------------------
+// R [batch][Fp][Np] | U [batch][Fp][Kp] | colsumW, rowsumH, hscale [batch][Kp] each | (batch == 1) the split-K partials: GCCNMF_SPLITS x
+// max(Fp*Np, Fp*Kp) (W.H parts and R.H^T parts use the same memory at different stages) + GCCNMF_SPLITS x Kp | (batch <= GCCNMF_DIRECT_MAX_BATCH)
+// the transposed copies of the direct path: Wt [batch][Kp][Fp], Ht [batch][Np][Kp], Rt [batch][Np][Fp] | the ready counters of the chained
+// launches (tuning key 21; gemm_dma.h: GemmSync, gccnmf_gemm_chain_kernel) | the status words | (a ragged batch) its tables.
+// Counters of one file group: c12 [batch][tiles_n] (K1 -> K2, in 32-column blocks), c23 [batch][tiles_n] (K2 -> K3), c34 [batch] (K3 -> K4, items),
+// c41 [batch] (K4 -> the next iteration's K1, items).  Zeroed once per gccnmf_klnmf call; iteration `it` waits for (it + 1) x the per-iteration count,
+// so nothing is reset between launches.  (The short-dictionary chain keeps its [3][batch] counters at the same place.)
+// The ready counters are rounded up to a 128-byte line (32 words), the GCCNMF_STATUS_WORDS status words follow: error [1], 7 unused, tickets [8], XCCs
+// seen per list [8] (from GCCNMF_STATUS_XCC_SEEN on), 8 unused.  Every block in front of the counters is a multiple of 64 floats, so the workspace is
+// one too (a ragged batch's, with its tables: of 4) -- workspaces carved back to back out of ONE allocation (the engine's file groups) all start
+// 16-byte aligned when the first does, which the float4 / LDS-DMA accesses to R, U, Wt, Ht, Rt rely on (the entry points reject a workspace that is
+// not 16-byte aligned).  Everything that locates a block -- the size functions included: `floats` of a carve of no memory -- takes it from here.
+#define GCCNMF_STATUS_WORDS 32
+#define GCCNMF_STATUS_XCC_SEEN 16
+struct KlnmfWorkspace {
+    float *R, *U, *colsumW, *rowsumH, *hscale;
+    float *parts, *rowsum_parts;            // split-K partials (batch == 1: experiment builds use them, the product build keeps the room)
+    float* direct_base;                     // Wt | Ht | Rt (direct_bufs)
+    unsigned *c12, *c23, *c34, *c41;        // ready counters
+    unsigned *status, *xcc_seen;
+    int* ragged_tables;                     // the files' column counts [batch] | 8 lists of GEMM_RAGGED_LMAX + 1 words
+    long scratch_floats;                    // everything in front of the counters
+    long counter_words;                     // ready counters, their padding and the status words: what zero_chain_counters clears
+    long floats;                            // the whole workspace
+};
+static long ragged_table_ints(int batch) { return (long)gccnmf_round_up(batch + 8 * (GEMM_RAGGED_LMAX + 1), 4); }
+static KlnmfWorkspace carve(float* workspace, const NmfGeom& g, int batch, bool ragged) {
+    KlnmfWorkspace ws;
+    long end = 0;
+    auto take = [&](long n) { float* p = workspace ? workspace + end : nullptr; end += n; return p; };      // (nullptr: the size functions)
+    ws.R = take(batch * g.sV);
+    ws.U = take(batch * g.sU);
+    ws.colsumW = take((long)batch * g.Kp);
+    ws.rowsumH = take((long)batch * g.Kp);
+    ws.hscale = take((long)batch * g.Kp);
+    const long splits = batch == 1 ? GCCNMF_SPLITS : 0;
+    ws.parts = take(splits * (g.sV > g.sU ? g.sV : g.sU));
+    ws.rowsum_parts = take(splits * g.Kp);
+    ws.direct_base = take(direct_floats(g, batch));
+    ws.scratch_floats = end;
+    const long tn = gccnmf_ceil_div(g.N, 64);
+    ws.c12 = (unsigned*)take(batch * tn);
+    ws.c23 = (unsigned*)take(batch * tn);
+    ws.c34 = (unsigned*)take(batch);
+    ws.c41 = (unsigned*)take(batch);
+    end = ws.scratch_floats + (end - ws.scratch_floats + 31) / 32 * 32;
+    ws.status = (unsigned*)take(GCCNMF_STATUS_WORDS);
+    ws.xcc_seen = workspace ? ws.status + GCCNMF_STATUS_XCC_SEEN : nullptr;
+    ws.counter_words = end - ws.scratch_floats;
+    ws.ragged_tables = (int*)take(ragged ? ragged_table_ints(batch) : 0);
+    ws.floats = end;
+    return ws;
 }
-static unsigned* chain_counters(const float* workspace, const NmfGeom& g, int batch) { return (unsigned*)(workspace + klnmf_workspace_base_floats(g, batch)); }
-// Which iterations can be chained: the four GEMMs all on full-height LDS-DMA throughput tiles with one XCD-affine list per XCD, every
-// file's tiles on ONE XCD in every stage (batch a multiple of 8: list x holds the files x, x + 8, ... in all four GEMMs).
-static bool chain_capable(const NmfGeom& g, int batch, int flags, bool any_size = false);
-static bool chain_rule(int batch, int flags);
+static bool workspace_aligned(const void* workspace) { return ((uintptr_t)workspace & 15) == 0; }
+
 // The lists of a chained launch (tuning key 23): 1 = whole files per XCD (hand-over through that XCD's L2), 2 = the file-major tile list cut into equal
 // eighths (a file may straddle XCDs: agent-scope hand-over, the producer writes its L2 back before it signals), 0 = the plain launch's lists.
 // By rule (key 23 = 1): whole files where they balance -- the longest list at most 2.7 % above the mean, i.e. multiples of 8 and e.g. 102 files -- else the
@@ -808,42 +884,43 @@ static int chain_list_mode(int batch) {
     const int longest = (batch + 7) / 8;
     return 1000L * 8 * longest <= 1027L * batch ? 1 : 2;
 }
-static int chain_stages(const NmfGeom& g, int batch, int flags) {
-    const int want = gccnmf_tune_chain;
-    if (!want || !chain_capable(g, batch, flags) || ((batch & 7) && chain_list_mode(batch) == 0)) return 0;
-    if (gccnmf_tune_tile_policy != 1 && (long)batch * gccnmf_ceil_div(g.N, 64) < 256) return 0;      // (the small-batch tile's territory)
-    if (want != 1) return want;                                   // a forced form
-    // by rule: not beside another file group's launches (two chained launches that share the chip are slower than two plain ones: 155 k against 158 k
-    // frames/s end to end); whole-file lists from three files per XCD on, spread lists from 20 files on
-    if (flags & 4) return 0;
-    return batch >= (chain_list_mode(batch) == 1 ? 24 : 20) ? 8 : 0;
-}
-// the shape and tuning conditions of any chained launch: the four GEMMs all on full-height LDS-DMA throughput tiles (K2 half-height up to 256 atoms)
-// with one XCD-affine list per XCD
-static bool chain_capable(const NmfGeom& g, int batch, int flags, bool any_size) {
+// Which iterations can be chained -- the shape and tuning conditions of any chained launch: the four GEMMs all on full-height LDS-DMA throughput
+// tiles (K2 half-height up to 256 atoms) with one XCD-affine list per XCD
+static bool chain_capable(const NmfGeom& g, int batch, const KlnmfMode& m, bool any_size) {
     if (!gccnmf_tune_dma || gccnmf_tune_tile_policy == 2 || gccnmf_tune_tail_split > 1) return false;
-    if (direct_path(g, batch, concurrent_groups(flags)) || (flags & 3) || batch < 8) return false;
+    if (direct_path(g, batch, m.groups) || !m.xcd_affine || m.unfused_w_update || batch < 8) return false;
     // (K a multiple of 128: a K2 tile whose last wave is partly beyond M takes the generic epilogue h * (acc / den) for that wave, a plain
     // launch on half-height tiles the lean one (h * acc) * (s / den) for the same rows: a few ulp apart, so the forms would not be bitwise equal)
     if (g.K <= 128 || g.Fm <= 128 || g.Fm > 512 || (g.Fm & 127) || (g.K & 127) || (g.F % 16) != 1 || !g.tail) return false;
     // (a plain launch of a few files takes the two-launch W update -- other kernels, other summation order; a ragged batch has no plain form to agree with)
-    return any_size || can_fuse_w_update(g, batch, concurrent_groups(flags));
+    return any_size || can_fuse_w_update(g, batch, m.groups);
 }
-static bool chain_rule(int batch, int flags) {
+static bool chain_rule(int batch, const KlnmfMode& m) {
     // The rule (profiles/r06h_files_sweep_*.txt, one-stream iteration as a fraction of the f32 peak, plain launches -> whole-call chain):
     //   24 files 0.74 -> 0.78, 32: 0.81 -> 0.85, 40: 0.73 -> 0.86, 64: 0.83 -> 0.86, 72: 0.79 -> 0.86, 104: 0.80 -> 0.86 -- but 16 files (two per XCD:
     //   the four stages of so few files cannot fill 64 slots): 0.75 -> 0.59, and with whole-file lists the longest list sets the pace: 25
     //   files (4 on one XCD, 3 on the others) 0.77 -> 0.68, 51: a tie, 52 (7 | 6): 0.75 -> 0.80.  So: at least three files per XCD and a longest
-    //   list at most 8 % above the mean.  Not beside another file group's launches (flag bit 2): two chained launches that share the chip
-    //   are slower than two plain ones (155 k against 158 k frames/s end to end).
-    if (flags & 4) return false;
+    //   list at most 8 % above the mean.  Not beside another file group's launches (GCCNMF_FLAG_CONCURRENT_GROUPS): two chained launches that
+    //   share the chip are slower than two plain ones (155 k against 158 k frames/s end to end).
+    if (m.groups > 1) return false;
     const int longest = (batch + 7) / 8;
     return batch >= 24 && 100L * 8 * longest <= 108L * batch;
+}
+// every file's tiles on ONE XCD in every stage (batch a multiple of 8: list x holds the files x, x + 8, ... in all four GEMMs) unless the lists say otherwise
+static int chain_stages(const NmfGeom& g, int batch, const KlnmfMode& m) {
+    const int want = gccnmf_tune_chain;
+    if (!want || !chain_capable(g, batch, m, false) || ((batch & 7) && chain_list_mode(batch) == 0)) return 0;
+    if (gccnmf_tune_tile_policy != 1 && (long)batch * gccnmf_ceil_div(g.N, 64) < 256) return 0;      // (the small-batch tile's territory)
+    if (want != 1) return want;                                   // a forced form
+    // by rule: not beside another file group's launches (two chained launches that share the chip are slower than two plain ones: 155 k against 158 k
+    // frames/s end to end); whole-file lists from three files per XCD on, spread lists from 20 files on
+    if (m.groups > 1) return 0;
+    return batch >= (chain_list_mode(batch) == 1 ? 24 : 20) ? 8 : 0;
 }
 
 // A ragged batch (gccnmf_klnmf_ragged): files of different lengths in ONE chained launch.  g is the geometry of the LONGEST file (every file's V, H,
 // R live in blocks of that pitch); n[f] = the file's own column count.  The host deals the files out to the eight XCD lists (longest first, each to
-// the list with the least work so far); the device tables sit behind the counters in the workspace.
+// the list with the least work so far); the device tables sit behind the status words in the workspace.
 struct RaggedPlan {
     const int* n;                                   // host [batch]
     int lists[8][GEMM_RAGGED_LMAX + 1];             // host: count, files
@@ -851,41 +928,16 @@ struct RaggedPlan {
     const int* d_lists;
 };
 
-static int launch_klnmf_chain(int stages, const NmfGeom& g, const float* V, float* W, float* H, float* R, float* colsumW, float* hscale,
-                              float alpha, float eps, int batch, int flags, unsigned* counters, int it0, int iterations, hipStream_t s,
-                              const RaggedPlan* rg = nullptr) {
-    GemmArgs a[4] = {};
-    const int concurrent = (flags & 4) ? 1 : 0;
-    for (int i = 0; i < 4; ++i) {
-        a[i].batch = batch; a[i].xcd_affine = 1; a[i].concurrent = concurrent;
-        a[i].ablate = gccnmf_tune_ablate; a[i].exact_div = gccnmf_tune_exact_div;
-    }
-    for (int i = 0; i < 3; i += 2) {             // K1 (pending row scale of H on the B fragments) and K3: R = V / (W.H)  (launch_wh_div)
-        a[i].A = W; a[i].sA = g.sW; a[i].lda = g.Kp; a[i].a_clamp = g.Fp - 1;
-        a[i].B = H; a[i].sB = g.sH; a[i].ldb = g.ld; a[i].b_clamp = g.Np - 4;
-        a[i].M = g.Fm; a[i].N = g.N; a[i].Kd = g.K;
-        a[i].tail_row = g.F - 1;
-        a[i].C = R; a[i].sC = g.sV; a[i].ldc = g.ld;
-        a[i].E0 = V; a[i].sE0 = g.sV;
-    }
-    a[0].bscale = hscale; a[0].s_bscale = g.Kp;
-    // K2: H = (s*H) * (W^T.R) / (colsum W + alpha + eps)  (launch_update_h)
-    a[1].A = W; a[1].sA = g.sW; a[1].lda = g.Kp; a[1].a_clamp = g.Kp - 4;
-    a[1].B = R; a[1].sB = g.sV; a[1].ldb = g.ld; a[1].b_clamp = g.Np - 4;
-    a[1].M = g.K; a[1].N = g.N; a[1].Kd = g.F - 1;
-    a[1].ktailA = W + (long)(g.F - 1) * g.Kp; a[1].s_ktailA = g.sW;
-    a[1].ktailB = R + (long)(g.F - 1) * g.ld; a[1].s_ktailB = g.sV;
-    a[1].C = H; a[1].sC = g.sH; a[1].ldc = g.ld;
-    a[1].E1 = hscale; a[1].sE1 = g.Kp;
-    a[1].E2 = colsumW; a[1].sE2 = g.Kp;
-    a[1].alpha = alpha; a[1].eps = eps;
-    // K4: W = normalise(W * (R.H^T) / rowsum H), column sums, norms  (launch_rht_update_w)
-    a[3].A = R; a[3].sA = g.sV; a[3].lda = g.ld; a[3].a_clamp = g.Fp - 1;
-    a[3].B = H; a[3].sB = g.sH; a[3].ldb = g.ld; a[3].b_clamp = g.Kp - 1;
-    a[3].M = g.Fm; a[3].N = g.K; a[3].Kd = g.N;
-    a[3].tail_row = g.F - 1;
-    a[3].C = W; a[3].sC = g.sW; a[3].ldc = g.Kp;
-    a[3].out_colsum = colsumW; a[3].out_norm = hscale; a[3].s_out = g.Kp;
+// stages: 2 = K1 | K2, 4 = the four GEMMs; iterations [it0, it0 + iterations) in one launch; rg: the lists of a ragged batch, else nullptr
+static int launch_klnmf_chain(int stages, const NmfGeom& g, const float* V, float* W, float* H, const KlnmfWorkspace& ws, float alpha, float eps,
+                              int batch, const KlnmfMode& m, int it0, int iterations, hipStream_t s, const RaggedPlan* rg) {
+    const int concurrent = m.groups > 1 ? 1 : 0;      // (intended today: a chained launch says THAT other groups run beside it, not how many)
+    // the operands of the plain launches, from the same builders (K1 with the pending row scale of H on the B fragments, K3 without)
+    GemmArgs a[4] = {wh_div_args(g, V, W, g.sW, H, ws.hscale, g.Kp, ws.R, batch, 1, concurrent),
+                     update_h_args(g, W, g.sW, ws.R, H, ws.hscale, g.Kp, ws.colsumW, g.Kp, alpha, eps, batch, 1, concurrent),
+                     wh_div_args(g, V, W, g.sW, H, nullptr, 0, ws.R, batch, 1, concurrent),
+                     rht_update_w_args(g, ws.R, H, W, ws.colsumW, ws.hscale, batch, 1, concurrent)};
+    for (GemmArgs& x : a) x.ablate = gccnmf_tune_ablate, x.exact_div = gccnmf_tune_exact_div;
     const int tm1 = g.K <= 256 ? 2 : 4;            // K2's outputs are the K atoms: at most 256 rows -> half-height tiles, as in a plain launch
     GemmChain ch = {};
     for (int i = 0; i < 4; ++i) {
@@ -914,16 +966,12 @@ static int launch_klnmf_chain(int stages, const NmfGeom& g, const float* V, floa
         ch.first[i + 1] = ch.first[i] + len;
     }
     const int tn = gccnmf_ceil_div(g.N, 64);
-    unsigned* c12 = counters;
-    unsigned* c23 = c12 + (long)batch * tn;
-    unsigned* c34 = c23 + (long)batch * tn;
-    unsigned* c41 = c34 + batch;
-    unsigned* err = chain_status_words(counters, g, batch);      // (behind the padding of the ready counters)
+    unsigned *c12 = ws.c12, *c23 = ws.c23, *c34 = ws.c34, *c41 = ws.c41;
     const bool wide = !rg && chain_list_mode(batch) == 2;          // a file's tiles spread over the XCDs: agent-scope hand-over, no XCC check
     for (int i = 0; i < 4; ++i) {
-        ch.sync[i].error = err;
+        ch.sync[i].error = ws.status;
         ch.sync[i].timeout = gccnmf_tune_chain_fault ? 0 : GEMM_SYNC_TIMEOUT;      // (lab build, key 25: every consumer that has to wait gives up at once)
-        ch.sync[i].xcc_seen = wide ? nullptr : err + 16;
+        ch.sync[i].xcc_seen = wide ? nullptr : ws.xcc_seen;
         ch.sync[i].wide = wide ? 1 : 0;
     }
     // does a producer run a file's ragged last column tile as ONE narrow item?  (a uniform batch: decided for the launch; a ragged one: per file)
@@ -973,39 +1021,29 @@ static int launch_klnmf_chain(int stages, const NmfGeom& g, const float* V, floa
 // Short dictionaries (K <= 128): the three launches of an iteration -- K1 + K2 on column tiles, K3 + K4a on bin slabs, the one-pass W update --
 // chained the same way (direct.hip: gccnmf_short_chain_kernel).  Shapes both fused kernels and the one-pass W update take; the same batch
 // rule as the throughput chain.  Returns the atoms per W-update group (16 / 32: what the plain launch would use at this batch), 0 = no chain.
-static int short_chain_group(const NmfGeom& g, int batch, int flags) {
+static int short_chain_group(const NmfGeom& g, int batch, const KlnmfMode& m) {
     const int want = gccnmf_tune_chain;
     if (!want || want == 2 || want == 4 || !gccnmf_tune_fused_k12 || !gccnmf_tune_fused_k34 || gccnmf_tune_tile_policy != 0) return 0;
-    if (direct_path(g, batch, concurrent_groups(flags)) || (flags & 3) || batch < 8 || !g.tail || g.Fm < 64 || g.Fm > 512 || (g.Fm % 64) != 0 || g.K > 128) return 0;
+    if (direct_path(g, batch, m.groups) || !m.xcd_affine || m.unfused_w_update || batch < 8 || !g.tail || g.Fm < 64 || g.Fm > 512 || (g.Fm % 64) != 0 || g.K > 128) return 0;
     if ((g.Fm / 64) * 16 < 32 * gccnmf_ceil_div(g.K, 32) || g.F > 64 * 9 || !gccnmf_tune_ring || (long)batch * (g.Kp / 64) >= 256) return 0;
     // by rule: only where the plain call runs the SAME three item programs for every file (both fused launches, no files left to the two-launch
     // form) -- the chained call is then bit for bit the plain one, and a file's bits keep following the batch size exactly as before
-    if (want == 1 && !(chain_rule(batch, flags) && fused_wh_updh(g, batch, flags) && fused_whdiv_rht_files(g, batch, flags) == batch)) return 0;
+    if (want == 1 && !(chain_rule(batch, m) && fused_wh_updh(g, batch, m) && fused_whdiv_rht_files(g, batch, m) == batch)) return 0;
     if (gccnmf_tune_ablate == 64) return 0;
     return ((long)batch * (g.Kp / 32) >= 256 && gccnmf_tune_wide_update_w) ? 32 : 16;
 }
 
-static int launch_short_chain(const NmfGeom& g, const float* V, float* W, float* H, float* U, float* colsumW, float* rowsumH, float* hscale,
-                              float alpha, float eps, int batch, int group, unsigned* counters, int it0, int iterations, hipStream_t s) {
+static int launch_short_chain(const NmfGeom& g, const float* V, float* W, float* H, const KlnmfWorkspace& ws, float alpha, float eps, int batch,
+                              int group, int it0, int iterations, hipStream_t s) {
     ShortChainArgs c = {};
-    c.a12.W = W; c.a12.sW = g.sW; c.a12.lda = g.Kp;
-    c.a12.H = H; c.a12.sH = g.sH; c.a12.ldb = g.ld;
-    c.a12.V = V; c.a12.sV = g.sV; c.a12.ldv = g.ld;
-    c.a12.scale = hscale; c.a12.colsum = colsumW; c.a12.sVec = g.Kp;
-    c.a12.M = g.Fm; c.a12.N = g.N; c.a12.Kd = g.K; c.a12.batch = batch;
-    c.a12.alpha = alpha; c.a12.eps = eps;
-    c.a34.W = W; c.a34.sW = g.sW; c.a34.lda = g.Kp;
-    c.a34.H = H; c.a34.sH = g.sH; c.a34.ldb = g.ld;
-    c.a34.V = V; c.a34.sV = g.sV; c.a34.ldv = g.ld;
-    c.a34.U = U; c.a34.sU = g.sU; c.a34.ldu = g.Kp;
-    c.a34.rowsumH = rowsumH; c.a34.sVec = g.Kp;
-    c.a34.M = g.Fm; c.a34.N = g.N; c.a34.Kd = g.K; c.a34.batch = batch;
-    c.aw.W = W; c.aw.U = U; c.aw.rowsumH = rowsumH; c.aw.colsumW = colsumW; c.aw.hscale = hscale;
-    c.aw.F = g.F; c.aw.K = g.K; c.aw.Kp = g.Kp; c.aw.sW = g.sW; c.aw.sU = g.sU; c.aw.sVec = g.Kp; c.aw.sRowsum = g.Kp;
+    // the arguments of the three plain launches, from the same builders
+    c.a12 = wh_updh_args(g, V, W, H, ws.hscale, ws.colsumW, alpha, eps, batch);
+    c.a34 = whdiv_rht_args(g, V, W, H, ws.U, ws.rowsumH, batch);
+    c.aw = update_w_args(g, W, g.sW, ws.U, g.sU, ws.rowsumH, ws.colsumW, ws.hscale, g.Kp);
     c.it0 = it0; c.iterations = iterations; c.atoms_per_group = group; c.solo = gccnmf_tune_chain_solo;
-    c.counters = counters;
-    c.error = chain_status_words(counters, g, batch);
-    c.xcc_seen = c.error + 16;
+    c.counters = ws.c12;
+    c.error = ws.status;
+    c.xcc_seen = ws.xcc_seen;
     c.timeout = gccnmf_tune_chain_fault ? 0 : GEMM_SYNC_TIMEOUT;
     return gccnmf_short_chain_launch(c, s);
 }
@@ -1014,7 +1052,7 @@ static int launch_short_chain(const NmfGeom& g, const float* V, float* W, float*
 // L2 is then not guaranteed): the factors cannot be trusted -- make them NaN so that nothing downstream looks plausible
 __global__ void nmf_chain_poison_kernel(const unsigned* __restrict__ err, float* __restrict__ W, float* __restrict__ H, long nW, long nH) {
     bool bad = err[0] != 0u;
-    for (int l = 0; l < 8; ++l) bad = bad || __popc(err[16 + l]) > 1;
+    for (int l = 0; l < 8; ++l) bad = bad || __popc(err[GCCNMF_STATUS_XCC_SEEN + l]) > 1;
     if (!bad) return;
     const float nan = __int_as_float(0x7fc00000);
     for (long i = blockIdx.x * 256L + threadIdx.x; i < nW; i += 256L * gridDim.x) W[i] = nan;
@@ -1023,57 +1061,35 @@ __global__ void nmf_chain_poison_kernel(const unsigned* __restrict__ err, float*
 
 extern "C" {
 
-// R [batch][Fp][Np] | U [batch][Fp][Kp] | colsumW, rowsumH, hscale [batch][Kp] each | (batch == 1) the split-K partials:
-// GCCNMF_SPLITS x max(Fp*Np, Fp*Kp) (W.H parts and R.H^T parts use the same memory at different stages) + GCCNMF_SPLITS x Kp
-// | (batch <= GCCNMF_DIRECT_MAX_BATCH) the transposed copies of the direct path: Wt [batch][Kp][Fp], Ht [batch][Np][Kp], Rt [batch][Np][Fp]
+// the end of the carve (KlnmfWorkspace states the layout)
 long gccnmf_klnmf_workspace_floats(int F, int N, int K, int batch) {
     GCCNMF_ENTER();
     if (F < 2 || N < 1 || K < 1 || batch < 1) return -1;
-    NmfGeom g = make_geom(F, N, K);
-    // R | U | colsumW | rowsumH | hscale | split-K scratch (one file) | Wt | Ht | Rt of the direct path (a handful of files at most) | chain counters
-    return klnmf_workspace_base_floats(g, batch) + chain_counter_floats(g, batch);
-}
-
-// GCCNMF_FLAG_FREE_ATOMS(n): the last n atoms of every file's W are learned beside a dictionary in its first K - n columns (semi-supervised
-// KL-NMF).  The argument rules, decided before anything is launched: 0 = a valid call.
-#define GCCNMF_FREE_BITS (255 << 18)
-static int free_atoms(int flags) { return (flags >> 18) & 255; }
-static int semi_check(int F, int K, int flags) {
-    const int n = free_atoms(flags);
-    if ((flags & (GCCNMF_FLAG_FIXED_W | GCCNMF_FLAG_H_ONES | GCCNMF_FLAG_CONCURRENT_GROUPS | GCCNMF_FLAG_UNFUSED_W_UPDATE)) || n > 128 || n >= K) return GCCNMF_ERR_ARG;
-    return gccnmf_klnmf_semi_supported(F, K, n) ? GCCNMF_OK : GCCNMF_ERR_UNSUPPORTED;      // (K - n) % 16, K > 1024, F > 2049
+    return carve(nullptr, make_geom(F, N, K), batch, false).floats;
 }
 
 // One launch group of the iteration, addressable on its own so that tests and the benchmark can time /
 // check each kernel in isolation.  stage: 0 prepare | 1 K1 | 2 K2 | 3 K3 | 4 K4a | 5 K4b | 6 final H rescale | 7 KL divergence of the current factors
-static int klnmf_stage(int stage, const float* V, float* W, float* H, float* workspace, const NmfGeom& g, int batch,
-                       float alpha, float eps, int flags, hipStream_t s) {
-    float* R = workspace;
-    float* U = R + (long)batch * g.sV;
-    float* colsumW = U + (long)batch * g.sU;
-    float* rowsumH = colsumW + (long)batch * g.Kp;
-    float* hscale = rowsumH + (long)batch * g.Kp;
-    float* parts = hscale + (long)batch * g.Kp;                                   // batch == 1 only
-    float* rowsum_parts = parts + GCCNMF_SPLITS * (g.sV > g.sU ? g.sV : g.sU);
-    float* direct_base = batch == 1 ? rowsum_parts + GCCNMF_SPLITS * (long)g.Kp : parts;
+static int klnmf_stage(int stage, const float* V, float* W, float* H, const KlnmfWorkspace& ws, const NmfGeom& g, int batch, float alpha, float eps,
+                       const KlnmfMode& m, hipStream_t s) {
+    float *R = ws.R, *U = ws.U, *colsumW = ws.colsumW, *rowsumH = ws.rowsumH, *hscale = ws.hscale;
     if (stage == 7) {
         // D(V || W.H) of the current (materialised) factors, divergence.hip: tile partials (float64) in each file's R block, the batch
         // results (float64) at the start of the U region; one launch form whatever the batch or the tuning.  V, W, H are read only.
         // (float64 partials and results: the workspace is 16-byte aligned -- the entry point checked -- and both offsets are multiples of 4096 bytes)
-        return gccnmf_kl_divergence_launch(V, W, (flags & GCCNMF_FLAG_FIXED_W) ? 0 : g.sW, H, g.F, g.N, g.K, g.Fp, g.Kp, g.Np, batch, (double*)R, g.sV / 2,
-                                           (double*)U, s);
+        return gccnmf_kl_divergence_launch(V, W, m.fixed_w ? 0 : g.sW, H, g.F, g.N, g.K, g.Fp, g.Kp, g.Np, batch, (double*)R, g.sV / 2, (double*)U, s);
     }
     // Free atoms (semi-supervised): stage 4 reads a materialised R [batch][Fp][Np] with zero padding, so stages 1-3 take the forms that leave
     // one in the workspace whatever the tuning keys say -- never the direct kernels (they keep Rt), never the K3 + K4a slab launch.  K1 + K2
     // fused stays: stage 3 rewrites R.  Stages 4 and 5 are nmf_semi.hip's, on the free columns alone.
-    const int nfree = free_atoms(flags);
+    const int nfree = m.free_atoms;
     const bool semi = nfree > 0;
-    const bool fused12 = fused_wh_updh(g, batch, flags);
-    const int head34 = semi ? 0 : fused_whdiv_rht_files(g, batch, flags), rest34 = batch - head34;      // files on the slab launch | behind it on the two launches
+    const bool fused12 = fused_wh_updh(g, batch, m);
+    const int head34 = semi ? 0 : fused_whdiv_rht_files(g, batch, m), rest34 = batch - head34;      // files on the slab launch | behind it on the two launches
     const bool fused34 = head34 > 0;
-    const int groups = concurrent_groups(flags);      // launch forms that follow the launch size are chosen for all groups together (GCCNMF_FLAG_GROUPS)
-    if (!semi && direct_path(g, batch, groups)) {
-        const DirectBufs d = direct_bufs(g, direct_base, batch);
+    const int groups = m.groups;      // launch forms that follow the launch size are chosen for all groups together (GCCNMF_FLAG_GROUPS)
+    if (!semi && stage != 6 && direct_path(g, batch, groups)) {      // (stage 6 is the same launch on every path: below)
+        const DirectBufs d = direct_bufs(g, ws.direct_base, batch);
         switch (stage) {
             case 0: {
                 // zero: R's padding (reduction operand of K2), Rt / Ht rows n >= N (reduction operands of K4), Wt columns f >= F
@@ -1087,13 +1103,7 @@ static int klnmf_stage(int stage, const float* V, float* W, float* H, float* wor
             case 2: return direct_update_h(g, d, W, R, H, hscale, colsumW, alpha, eps, batch, s);
             case 3: return direct_wh_div(g, d, V, W, H, nullptr, R, true, batch, s);
             case 4: return direct_rht(g, d, R, U, rowsumH, batch, s);
-            case 5:
-                return launch_update_w(W, U, rowsumH, colsumW, hscale, g.F, g.Fp, g.K, g.Kp, g.sW, g.sU, (long)g.Kp, (long)g.Kp, batch, s, 1, 0, 0,
-                                       d.Wt, d.sWt, d.ldwt, groups);
-            case 6:
-                hipLaunchKernelGGL(nmf_scale_h_kernel, dim3(batch * g.K), dim3(256), 0, s, H, hscale, (long)g.Kp, g.K, g.sH, g.ld, g.Np);
-                GCCNMF_CHECK_LAUNCH();
-                return GCCNMF_OK;
+            case 5: return launch_update_w(update_w_args(g, W, g.sW, U, g.sU, rowsumH, colsumW, hscale, g.Kp), batch, groups, s, 1, 0, 0, d.Wt, d.sWt, d.ldwt);
             default: return GCCNMF_ERR_ARG;
         }
     }
@@ -1103,7 +1113,7 @@ static int klnmf_stage(int stage, const float* V, float* W, float* H, float* wor
 #else
     constexpr bool split_rht = false;              // the split-K path is compiled out of the product library
 #endif
-    const int xcd = ((flags & 1) ? 0 : 1) | ((flags & 4) ? groups << 1 : 0);      // above bit 0: the file groups whose launches run side by side (0: this one alone)
+    const int xa = m.xcd_affine, conc = m.groups > 1 ? m.groups : 0;      // GemmArgs.concurrent: the file groups whose launches run side by side (0: this one alone)
     const int vec_grid = batch * (g.Kp / 16);
     switch (stage) {
         case 0:
@@ -1112,41 +1122,42 @@ static int klnmf_stage(int stage, const float* V, float* W, float* H, float* wor
             hipLaunchKernelGGL(nmf_prepare_kernel, dim3(vec_grid), dim3(256), 0, s, W, colsumW, hscale, g.F, g.Fp, g.Kp);
             break;
         case 1:
-            if (fused12) return launch_wh_updh(g, V, W, H, hscale, colsumW, alpha, eps, batch, s);                         // K1 + K2
+            if (fused12) return gccnmf_wh_updh_launch(wh_updh_args(g, V, W, H, hscale, colsumW, alpha, eps, batch), s);    // K1 + K2
 #ifdef GCCNMF_EXPERIMENTS
-            if (split_wh) return launch_wh_div_split(g, V, W, H, hscale, parts, R, s);
+            if (split_wh) return launch_wh_div_split(g, V, W, H, hscale, ws.parts, R, s);
 #endif
-            return launch_wh_div(g, V, W, g.sW, H, hscale, g.Kp, R, batch, xcd, s);
+            return launch_wh_div(g, wh_div_args(g, V, W, g.sW, H, hscale, g.Kp, R, batch, xa, conc), s);
         case 2:
             if (fused12) return GCCNMF_OK;                                                                             // done by stage 1
-            return launch_update_h(g, W, g.sW, R, H, hscale, g.Kp, colsumW, g.Kp, alpha, eps, batch, xcd, s);
+            return launch_update_h(update_h_args(g, W, g.sW, R, H, hscale, g.Kp, colsumW, g.Kp, alpha, eps, batch, xa, conc), s);
         case 3:
             if (fused34) {                                                                                             // K3 + K4a
-                const int rc = launch_whdiv_rht(g, V, W, H, U, rowsumH, head34, s);
+                const int rc = gccnmf_whdiv_rht_launch(whdiv_rht_args(g, V, W, H, U, rowsumH, head34), s);
                 if (rc || !rest34) return rc;
-                return launch_wh_div(g, V + head34 * g.sV, W + head34 * g.sW, g.sW, H + head34 * g.sH, nullptr, 0, R + head34 * g.sV, rest34, xcd, s);
+                return launch_wh_div(g, wh_div_args(g, V + head34 * g.sV, W + head34 * g.sW, g.sW, H + head34 * g.sH, nullptr, 0, R + head34 * g.sV, rest34, xa, conc), s);
             }
 #ifdef GCCNMF_EXPERIMENTS
-            if (split_wh) return launch_wh_div_split(g, V, W, H, nullptr, parts, R, s);
+            if (split_wh) return launch_wh_div_split(g, V, W, H, nullptr, ws.parts, R, s);
 #endif
-            return launch_wh_div(g, V, W, g.sW, H, nullptr, 0, R, batch, xcd, s);
+            return launch_wh_div(g, wh_div_args(g, V, W, g.sW, H, nullptr, 0, R, batch, xa, conc), s);
         case 4:
             if (semi) return gccnmf_klnmf_semi_rht_launch(R, H, U, rowsumH, g.F, g.N, g.K, nfree, batch, s);           // U[:, K - n:], rowsumH[K - n:]
             if (fused34)                                                                                               // done by stage 3 ...
-                return rest34 ? launch_rht(g, R + head34 * g.sV, H + head34 * g.sH, U + head34 * g.sU, rowsumH + (long)head34 * g.Kp, rest34, xcd, s)
+                return rest34 ? launch_rht(g, rht_args(g, R + head34 * g.sV, H + head34 * g.sH, U + head34 * g.sU, rowsumH + (long)head34 * g.Kp, rest34, xa, conc), s)
                               : GCCNMF_OK;                                                                             // ... but for the rest
 #ifdef GCCNMF_EXPERIMENTS
-            if (split_rht) return launch_rht_split(g, R, H, parts, rowsum_parts, s);
+            if (split_rht) return launch_rht_split(g, R, H, ws.parts, ws.rowsum_parts, s);
 #endif
-            if (can_fuse_w_update(g, batch, groups) && !(flags & 2)) return launch_rht_update_w(g, R, H, W, colsumW, hscale, batch, xcd, s);
-            return launch_rht(g, R, H, U, rowsumH, batch, xcd, s);
+            if (can_fuse_w_update(g, batch, groups) && !m.unfused_w_update)
+                return launch_rht_update_w(g, rht_update_w_args(g, R, H, W, colsumW, hscale, batch, xa, conc), s);
+            return launch_rht(g, rht_args(g, R, H, U, rowsumH, batch, xa, conc), s);
         case 5:
             if (semi) return gccnmf_klnmf_semi_update_w_launch(W, U, rowsumH, colsumW, hscale, g.F, g.K, nfree, batch, s);
-            if (split_rht)
-                return launch_update_w(W, parts, rowsum_parts, colsumW, hscale, g.F, g.Fp, g.K, g.Kp, g.sW, g.sU, (long)g.Kp, (long)g.Kp, batch,
-                                       s, gccnmf_tune_rht_splits, g.sU, (long)g.Kp);
-            if (can_fuse_w_update(g, batch, groups) && !(flags & 2) && !fused34) return GCCNMF_OK;     // done by stage 4's epilogue
-            return launch_update_w(W, U, rowsumH, colsumW, hscale, g.F, g.Fp, g.K, g.Kp, g.sW, g.sU, (long)g.Kp, (long)g.Kp, batch, s, 1, 0, 0, nullptr, 0, 0, groups);
+            if (split_rht)      // (the parts are sized as one launch: no file groups beside a single file)
+                return launch_update_w(update_w_args(g, W, g.sW, ws.parts, g.sU, ws.rowsum_parts, colsumW, hscale, g.Kp), batch, 1, s, gccnmf_tune_rht_splits,
+                                       g.sU, (long)g.Kp, nullptr, 0, 0);
+            if (can_fuse_w_update(g, batch, groups) && !m.unfused_w_update && !fused34) return GCCNMF_OK;     // done by stage 4's epilogue
+            return launch_update_w(update_w_args(g, W, g.sW, U, g.sU, rowsumH, colsumW, hscale, g.Kp), batch, groups, s, 1, 0, 0, nullptr, 0, 0);
         case 6:
             hipLaunchKernelGGL(nmf_scale_h_kernel, dim3(batch * g.K), dim3(256), 0, s, H, hscale, (long)g.Kp, g.K, g.sH, g.ld, g.Np);
             break;
@@ -1156,33 +1167,53 @@ static int klnmf_stage(int stage, const float* V, float* W, float* H, float* wor
     return GCCNMF_OK;
 }
 
-// GCCNMF_FLAG_FIXED_W alone or with GCCNMF_FLAG_H_ONES, nothing else
-#define GCCNMF_FIXED_BITS (GCCNMF_FLAG_FIXED_W | GCCNMF_FLAG_H_ONES)
-static bool fixed_flags_ok(int flags) { return (flags & GCCNMF_FLAG_FIXED_W) && !(flags & ~GCCNMF_FIXED_BITS); }
+// ---- the prologue and the epilogue of a call --------------------------------------------------------------------------------------
+// The status words describe THIS call (gccnmf_klnmf_chain_status): a call that does not chain clears what an earlier, chained one may have left.
+static int clear_chain_status(const KlnmfWorkspace& ws, hipStream_t s) {
+    return hipMemsetAsync(ws.status, 0, GCCNMF_STATUS_WORDS * sizeof(unsigned), s) == hipSuccess ? GCCNMF_OK : GCCNMF_ERR_LAUNCH;
+}
+// A call that chains starts its ready counters at zero, once (and with them the status words behind them).
+static int zero_chain_counters(const KlnmfWorkspace& ws, hipStream_t s) {
+    return hipMemsetAsync(ws.c12, 0, sizeof(unsigned) * ws.counter_words, s) == hipSuccess ? GCCNMF_OK : GCCNMF_ERR_LAUNCH;
+}
+// The end of every iterating call: W and H become NaN if a chained launch of this call failed to hand over (the call is never silent about it),
+// then stage 6 materialises the pending row scale of H.
+static int finish_call(bool chained, const float* V, float* W, float* H, const KlnmfWorkspace& ws, const NmfGeom& g, int batch, float alpha, float eps,
+                       const KlnmfMode& m, hipStream_t s) {
+    if (chained) {
+        hipLaunchKernelGGL(nmf_chain_poison_kernel, dim3(64), dim3(256), 0, s, ws.status, W, H, (long)batch * g.sW, (long)batch * g.sH);
+        GCCNMF_CHECK_LAUNCH();
+    }
+    return klnmf_stage(6, V, W, H, ws, g, batch, alpha, eps, m, s);
+}
 
 // Which launches gccnmf_klnmf would use for this problem under the current tuning: bit 0 the direct latency kernels, bit 1 the fused
 // K1 + K2 launch, bit 2 the fused K3 + K4a slab launch, bit 3 chained launches of the iteration (benchmarks and tests name the kernel they
-// time by this; the engine keeps ONE file group when the library chains), bit 4 the fused fixed-dictionary launch (GCCNMF_FLAG_FIXED_W).
+// time by this; the engine keeps ONE file group when the library chains), bit 4 the fused fixed-dictionary launch (GCCNMF_FLAG_FIXED_W),
+// bit 5 the semi-supervised iteration (GCCNMF_FLAG_FREE_ATOMS; bits 4 and 5: then no other bit).
 int gccnmf_klnmf_plan(int F, int N, int K, int batch, int flags) {
     GCCNMF_ENTER();
     if (F < 2 || N < 1 || K < 1 || batch < 1) return -1;
-    if (flags & GCCNMF_FIXED_BITS) return fixed_flags_ok(flags) && gccnmf_klnmf_fixed_supported(F, K) ? 16 : -1;
-    if (flags & GCCNMF_FREE_BITS) return semi_check(F, K, flags) == GCCNMF_OK ? 32 : -1;      // bit 5: the semi-supervised iteration (then no other bit)
+    KlnmfMode m;
+    if (decode_mode(flags, F, K, m)) return -1;
+    if (m.fixed_w) return gccnmf_klnmf_fixed_supported(F, K) ? 16 : -1;
+    if (m.free_atoms) return 32;
     const NmfGeom g = make_geom(F, N, K);
-    return (direct_path(g, batch, concurrent_groups(flags)) ? 1 : 0) | (fused_wh_updh(g, batch, flags) ? 2 : 0) | (fused_whdiv_rht_files(g, batch, flags) > 0 ? 4 : 0) |
-           ((chain_stages(g, batch, flags) || short_chain_group(g, batch, flags)) ? 8 : 0);
+    return (direct_path(g, batch, m.groups) ? 1 : 0) | (fused_wh_updh(g, batch, m) ? 2 : 0) | (fused_whdiv_rht_files(g, batch, m) > 0 ? 4 : 0) |
+           ((chain_stages(g, batch, m) || short_chain_group(g, batch, m)) ? 8 : 0);
 }
 
 int gccnmf_klnmf_stage(const float* V, float* W, float* H, float* workspace, int F, int N, int K, int batch,
                        float sparsity_alpha, float epsilon, int flags, int stage, void* stream) {
     GCCNMF_ENTER();
-    // (a fixed dictionary -- one W for every file -- exists for stage 7 alone: the divergence against it; the iteration stages have no such form)
-    if (!V || !W || !H || !workspace || F < 2 || N < 1 || K < 1 || batch < 1 || ((flags & GCCNMF_FIXED_BITS) && !(stage == 7 && flags == GCCNMF_FLAG_FIXED_W)))
-        return GCCNMF_ERR_ARG;
+    if (!V || !W || !H || !workspace || F < 2 || N < 1 || K < 1 || batch < 1) return GCCNMF_ERR_ARG;
     if (!workspace_aligned(workspace)) return GCCNMF_ERR_ARG;          // float4 / LDS-DMA accesses to its blocks; stage 7's float64 partials and results
-    if (flags & GCCNMF_FREE_BITS)
-        if (const int rc = semi_check(F, K, flags)) return rc;
-    return klnmf_stage(stage, V, W, H, workspace, make_geom(F, N, K), batch, sparsity_alpha, epsilon, flags, (hipStream_t)stream);
+    KlnmfMode m;
+    if (const int rc = decode_mode(flags, F, K, m)) return rc;
+    // (a fixed dictionary -- one W for every file -- exists for stage 7 alone: the divergence against it; the iteration stages have no such form)
+    if (m.fixed_w && (stage != 7 || m.h_ones)) return GCCNMF_ERR_ARG;
+    const NmfGeom g = make_geom(F, N, K);
+    return klnmf_stage(stage, V, W, H, carve(workspace, g, batch, false), g, batch, sparsity_alpha, epsilon, m, (hipStream_t)stream);
 }
 
 int gccnmf_klnmf(const float* V, float* W, float* H, float* workspace, int F, int N, int K, int batch, int iterations,
@@ -1191,89 +1222,64 @@ int gccnmf_klnmf(const float* V, float* W, float* H, float* workspace, int F, in
     if (!V || !W || !H || !workspace || F < 2 || N < 1 || K < 1 || batch < 1 || iterations < 0) return GCCNMF_ERR_ARG;
     if (!workspace_aligned(workspace)) return GCCNMF_ERR_ARG;          // R, U, Wt, Ht, Rt are read with float4 loads and LDS-DMA: 16 bytes
     hipStream_t s = (hipStream_t)stream;
-    NmfGeom g = make_geom(F, N, K);
-    if ((flags & GCCNMF_FREE_BITS) && !(flags & GCCNMF_FIXED_BITS)) {
+    KlnmfMode m;
+    int rc;
+    if ((rc = decode_mode(flags, F, K, m))) return rc;
+    const NmfGeom g = make_geom(F, N, K);
+    const KlnmfWorkspace ws = carve(workspace, g, batch, false);
+    const float alpha = sparsity_alpha, eps = epsilon;
+    if (m.free_atoms) {
         // semi-supervised: the dictionary in W[:, :K - n] of every file stays as it is, the n free atoms behind it and all of H are learned.
-        // Plain launches (klnmf_stage keeps R materialised); nothing chains: the status words are cleared for this call.
-        int rc;
-        if ((rc = semi_check(F, K, flags))) return rc;
-        if (hipMemsetAsync(chain_status_words(chain_counters(workspace, g, batch), g, batch), 0, 32 * sizeof(unsigned), s) != hipSuccess) return GCCNMF_ERR_LAUNCH;
-        if ((rc = klnmf_stage(0, V, W, H, workspace, g, batch, sparsity_alpha, epsilon, flags, s))) return rc;
+        // Plain launches (klnmf_stage keeps R materialised); nothing chains.
+        if ((rc = clear_chain_status(ws, s))) return rc;
+        if ((rc = klnmf_stage(0, V, W, H, ws, g, batch, alpha, eps, m, s))) return rc;
         for (int it = 0; it < iterations; ++it)
             for (int stage = 1; stage <= 5; ++stage)
-                if ((rc = klnmf_stage(stage, V, W, H, workspace, g, batch, sparsity_alpha, epsilon, flags, s))) return rc;
-        return klnmf_stage(6, V, W, H, workspace, g, batch, sparsity_alpha, epsilon, flags, s);
+                if ((rc = klnmf_stage(stage, V, W, H, ws, g, batch, alpha, eps, m, s))) return rc;
+        return finish_call(false, V, W, H, ws, g, batch, alpha, eps, m, s);
     }
-    if (flags & GCCNMF_FIXED_BITS) {
+    if (m.fixed_w) {
         // fixed dictionary: W is read only, H holds the initial coefficients (or, with H_ONES, is output only); one launch runs every
-        // iteration.  Nothing chains: the status words of gccnmf_klnmf_chain_status are cleared for this call.
-        if (!fixed_flags_ok(flags)) return GCCNMF_ERR_ARG;
-        if (!gccnmf_klnmf_fixed_supported(F, K) || gccnmf_klnmf_fixed_workspace_floats(F, K) > klnmf_workspace_base_floats(g, batch))
-            return GCCNMF_ERR_UNSUPPORTED;
-        unsigned* status = chain_status_words(chain_counters(workspace, g, batch), g, batch);
-        if (hipMemsetAsync(status, 0, 32 * sizeof(unsigned), s) != hipSuccess) return GCCNMF_ERR_LAUNCH;
-        return gccnmf_klnmf_fixed_launch(V, W, H, workspace, F, N, K, batch, iterations, sparsity_alpha, epsilon,
-                                         (flags & GCCNMF_FLAG_H_ONES) != 0, s);
+        // iteration (and leaves H materialised).  Nothing chains.
+        if (!gccnmf_klnmf_fixed_supported(F, K) || gccnmf_klnmf_fixed_workspace_floats(F, K) > ws.scratch_floats) return GCCNMF_ERR_UNSUPPORTED;
+        if ((rc = clear_chain_status(ws, s))) return rc;
+        return gccnmf_klnmf_fixed_launch(V, W, H, workspace, F, N, K, batch, iterations, alpha, eps, m.h_ones, s);
     }
-    int rc;
-    if ((rc = klnmf_stage(0, V, W, H, workspace, g, batch, sparsity_alpha, epsilon, flags, s))) return rc;
-    const int chained = chain_stages(g, batch, flags);          // 0 | 2: K1 | K2 in one launch | 4: the whole iteration | 8: the whole call
-    unsigned* counters = chain_counters(workspace, g, batch);
-    const int short_group = chained ? 0 : short_chain_group(g, batch, flags);      // K <= 128: the three launches of every iteration as one chained launch
-    // the status words describe THIS call (gccnmf_klnmf_chain_status): a call that does not chain clears what an earlier, chained one may have left
-    if (!chained && !short_group && hipMemsetAsync(chain_status_words(counters, g, batch), 0, 32 * sizeof(unsigned), s) != hipSuccess) return GCCNMF_ERR_LAUNCH;
-    if (short_group && iterations > 0) {
-        if (hipMemsetAsync(counters, 0, sizeof(unsigned) * chain_counter_floats(g, batch), s) != hipSuccess) return GCCNMF_ERR_LAUNCH;
-        float* R0 = workspace;
-        float* U0 = R0 + (long)batch * g.sV;
-        float* colsum0 = U0 + (long)batch * g.sU;
-        float* rowsum0 = colsum0 + (long)batch * g.Kp;
-        float* hscale0 = rowsum0 + (long)batch * g.Kp;
+    if ((rc = klnmf_stage(0, V, W, H, ws, g, batch, alpha, eps, m, s))) return rc;
+    const int chained = chain_stages(g, batch, m);          // 0 | 2: K1 | K2 in one launch | 4: the whole iteration | 8: the whole call
+    const int short_group = chained ? 0 : short_chain_group(g, batch, m);      // K <= 128: the three launches of every iteration as one chained launch
+    const bool chains = (chained || short_group) && iterations > 0;
+    if (!chained && !short_group && (rc = clear_chain_status(ws, s))) return rc;
+    if (chains && (rc = zero_chain_counters(ws, s))) return rc;
+    if (short_group) {                                      // the short chain: every iteration of the call
         for (int it0 = 0; it0 < iterations; it0 += GCCNMF_CHAIN_MAX_ITERATIONS)
-            if ((rc = launch_short_chain(g, V, W, H, U0, colsum0, rowsum0, hscale0, sparsity_alpha, epsilon, batch, short_group, counters, it0,
-                                         std::min(GCCNMF_CHAIN_MAX_ITERATIONS, iterations - it0), s)))
-                return rc;
-        hipLaunchKernelGGL(nmf_chain_poison_kernel, dim3(64), dim3(256), 0, s, chain_status_words(counters, g, batch), W, H, (long)batch * g.sW, (long)batch * g.sH);
-        GCCNMF_CHECK_LAUNCH();
-        return klnmf_stage(6, V, W, H, workspace, g, batch, sparsity_alpha, epsilon, flags, s);
-    }
-    if (chained && iterations > 0 && hipMemsetAsync(counters, 0, sizeof(unsigned) * chain_counter_floats(g, batch), s) != hipSuccess) return GCCNMF_ERR_LAUNCH;
-    float* R = workspace;
-    float* colsumW = R + (long)batch * g.sV + (long)batch * g.sU;
-    float* hscale = colsumW + 2L * batch * g.Kp;
-    if (chained == 8 && iterations > 0) {
+            if ((rc = launch_short_chain(g, V, W, H, ws, alpha, eps, batch, short_group, it0, std::min(GCCNMF_CHAIN_MAX_ITERATIONS, iterations - it0), s))) return rc;
+    } else if (chained == 8) {                              // chained, the whole call
         for (int it0 = 0; it0 < iterations; it0 += GCCNMF_CHAIN_MAX_ITERATIONS)      // (one launch; a call of thousands of iterations: a few, the grid stays below 2^30 workgroups)
-            if ((rc = launch_klnmf_chain(4, g, V, W, H, R, colsumW, hscale, sparsity_alpha, epsilon, batch, flags, counters, it0,
-                                         std::min(GCCNMF_CHAIN_MAX_ITERATIONS, iterations - it0), s)))
-                return rc;
-    } else {
+            if ((rc = launch_klnmf_chain(4, g, V, W, H, ws, alpha, eps, batch, m, it0, std::min(GCCNMF_CHAIN_MAX_ITERATIONS, iterations - it0), s, nullptr))) return rc;
+    } else {                                                // chained per iteration (the first 2 or 4 stages), or plain
         for (int it = 0; it < iterations; ++it) {
-            if (chained && (rc = launch_klnmf_chain(chained, g, V, W, H, R, colsumW, hscale, sparsity_alpha, epsilon, batch, flags, counters, it, 1, s))) return rc;
+            if (chained && (rc = launch_klnmf_chain(chained, g, V, W, H, ws, alpha, eps, batch, m, it, 1, s, nullptr))) return rc;
             for (int stage = chained + 1; stage <= 5; ++stage)
-                if ((rc = klnmf_stage(stage, V, W, H, workspace, g, batch, sparsity_alpha, epsilon, flags, s))) return rc;
+                if ((rc = klnmf_stage(stage, V, W, H, ws, g, batch, alpha, eps, m, s))) return rc;
         }
     }
-    if (chained && iterations > 0) {
-        hipLaunchKernelGGL(nmf_chain_poison_kernel, dim3(64), dim3(256), 0, s, chain_status_words(counters, g, batch), W, H, (long)batch * g.sW, (long)batch * g.sH);
-        GCCNMF_CHECK_LAUNCH();
-    }
-    return klnmf_stage(6, V, W, H, workspace, g, batch, sparsity_alpha, epsilon, flags, s);
+    return finish_call(chains, V, W, H, ws, g, batch, alpha, eps, m, s);
 }
 
 // Did the chained launches of the LAST gccnmf_klnmf / gccnmf_klnmf_ragged call on this workspace hand over cleanly?  (The call itself is
-// asynchronous and poisons W, H with NaN if they did not; this is the explicit check: a blocking 4-byte read.)  status: 0 = clean (or the call
-// did not chain), bit 0 = a consumer gave up waiting for its producer (GEMM_SYNC_TIMEOUT), bit 1 = the workgroups of some list ran on more
+// asynchronous and poisons W, H with NaN if they did not; this is the explicit check: a blocking read of the status words.)  status: 0 = clean (or
+// the call did not chain), bit 0 = a consumer gave up waiting for its producer (GEMM_SYNC_TIMEOUT), bit 1 = the workgroups of some list ran on more
 // than one XCC (the hand-over through one XCD's L2 is then not guaranteed).  N: the column count the workspace was sized with (Nmax for a ragged batch).
 int gccnmf_klnmf_chain_status(const float* workspace, int F, int N, int K, int batch, int* status) {
     GCCNMF_ENTER();
     if (!workspace || !status || F < 2 || N < 1 || K < 1 || batch < 1) return GCCNMF_ERR_ARG;
-    NmfGeom g = make_geom(F, N, K);
-    const unsigned* words = chain_status_words(chain_counters(workspace, g, batch), g, batch);
-    unsigned host[32];
-    if (hipMemcpy(host, words, sizeof(host), hipMemcpyDeviceToHost) != hipSuccess) return GCCNMF_ERR_LAUNCH;
+    const KlnmfWorkspace ws = carve(const_cast<float*>(workspace), make_geom(F, N, K), batch, false);
+    unsigned host[GCCNMF_STATUS_WORDS];
+    if (hipMemcpy(host, ws.status, sizeof(host), hipMemcpyDeviceToHost) != hipSuccess) return GCCNMF_ERR_LAUNCH;
     int st = host[0] ? 1 : 0;
     for (int l = 0; l < 8; ++l)
-        if (__builtin_popcount(host[16 + l]) > 1) st |= 2;
+        if (__builtin_popcount(host[GCCNMF_STATUS_XCC_SEEN + l]) > 1) st |= 2;
     *status = st;
     return GCCNMF_OK;
 }
@@ -1285,20 +1291,20 @@ struct RaggedTables {
 __global__ void nmf_store_ragged_tables_kernel(RaggedTables t, int* dst, int n) {
     for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = t.v[i];
 }
-static long ragged_table_ints(int batch) { return (long)gccnmf_round_up(batch + 8 * (GEMM_RAGGED_LMAX + 1), 4); }
 
 long gccnmf_klnmf_ragged_workspace_floats(int F, int Nmax, int K, int batch) {
     GCCNMF_ENTER();
     if (F < 2 || Nmax < 1 || K < 1 || batch < 1 || batch > GCCNMF_RAGGED_MAX_BATCH) return -1;
-    NmfGeom g = make_geom(F, Nmax, K);
-    return klnmf_workspace_base_floats(g, batch) + chain_counter_floats(g, batch) + ragged_table_ints(batch);
+    return carve(nullptr, make_geom(F, Nmax, K), batch, true).floats;
 }
 
 int gccnmf_klnmf_ragged(const float* V, float* W, float* H, float* workspace, int F, const int* N, int Nmax, int K, int batch, int iterations,
                         float sparsity_alpha, float epsilon, int flags, void* stream) {
     GCCNMF_ENTER();
-    if (!V || !W || !H || !workspace || !N || F < 2 || Nmax < 1 || K < 1 || batch < 1 || iterations < 0 || (flags & (GCCNMF_FIXED_BITS | GCCNMF_FREE_BITS)))
-        return GCCNMF_ERR_ARG;
+    if (!V || !W || !H || !workspace || !N || F < 2 || Nmax < 1 || K < 1 || batch < 1 || iterations < 0) return GCCNMF_ERR_ARG;
+    KlnmfMode m;
+    if (decode_mode(flags, F, K, m) || m.fixed_w || m.free_atoms) return GCCNMF_ERR_ARG;
+    m.groups = 1;      // (intended today: the concurrent-groups bit is masked off -- a ragged batch exists in ONE form, whatever runs beside it)
     if (!workspace_aligned(workspace)) return GCCNMF_ERR_ARG;
     if (batch > GCCNMF_RAGGED_MAX_BATCH) return GCCNMF_ERR_UNSUPPORTED;
     long tiles = 0;
@@ -1307,10 +1313,10 @@ int gccnmf_klnmf_ragged(const float* V, float* W, float* H, float* workspace, in
         tiles += gccnmf_ceil_div(N[f], 64);
     }
     hipStream_t s = (hipStream_t)stream;
-    NmfGeom g = make_geom(F, Nmax, K);
+    const NmfGeom g = make_geom(F, Nmax, K);
     // a ragged batch exists only as a chained launch (the plain launches take one N for the whole batch): where that form is not available
     // -- short dictionaries, a handful of files -- the caller runs the files of each length as a batch of their own
-    if (!gccnmf_tune_chain || !chain_capable(g, batch, flags & ~4, true) || (gccnmf_tune_tile_policy != 1 && tiles < 256)) return GCCNMF_ERR_UNSUPPORTED;
+    if (!gccnmf_tune_chain || !chain_capable(g, batch, m, true) || (gccnmf_tune_tile_policy != 1 && tiles < 256)) return GCCNMF_ERR_UNSUPPORTED;
     // deal the files out to the eight lists: longest first, each to the list with the fewest column tiles so far (ties: the lower list)
     RaggedPlan rg = {};
     rg.n = N;
@@ -1328,31 +1334,24 @@ int gccnmf_klnmf_ragged(const float* V, float* W, float* H, float* workspace, in
         load[best] += gccnmf_ceil_div(N[f], 64);
     }
     for (int l = 0; l < 8; ++l) std::sort(rg.lists[l] + 1, rg.lists[l] + 1 + rg.lists[l][0]);      // a list serves its files in ascending order
-    unsigned* counters = chain_counters(workspace, g, batch);
-    int* tables = (int*)(counters + chain_counter_floats(g, batch));
+    const KlnmfWorkspace ws = carve(workspace, g, batch, true);
     RaggedTables t = {};
     for (int f = 0; f < batch; ++f) t.v[f] = N[f];
     for (int l = 0; l < 8; ++l)
         for (int k = 0; k <= GEMM_RAGGED_LMAX; ++k) t.v[batch + l * (GEMM_RAGGED_LMAX + 1) + k] = rg.lists[l][k];
-    hipLaunchKernelGGL(nmf_store_ragged_tables_kernel, dim3(1), dim3(256), 0, s, t, tables, batch + 8 * (GEMM_RAGGED_LMAX + 1));
+    hipLaunchKernelGGL(nmf_store_ragged_tables_kernel, dim3(1), dim3(256), 0, s, t, ws.ragged_tables, batch + 8 * (GEMM_RAGGED_LMAX + 1));
     GCCNMF_CHECK_LAUNCH();
-    rg.d_n = tables;
-    rg.d_lists = tables + batch;
+    rg.d_n = ws.ragged_tables;
+    rg.d_lists = ws.ragged_tables + batch;
     int rc;
-    if ((rc = klnmf_stage(0, V, W, H, workspace, g, batch, sparsity_alpha, epsilon, flags, s))) return rc;
+    if ((rc = klnmf_stage(0, V, W, H, ws, g, batch, sparsity_alpha, epsilon, m, s))) return rc;
     if (iterations > 0) {
-        if (hipMemsetAsync(counters, 0, sizeof(unsigned) * chain_counter_floats(g, batch), s) != hipSuccess) return GCCNMF_ERR_LAUNCH;
-        float* R = workspace;
-        float* colsumW = R + (long)batch * g.sV + (long)batch * g.sU;
-        float* hscale = colsumW + 2L * batch * g.Kp;
+        if ((rc = zero_chain_counters(ws, s))) return rc;
         for (int it0 = 0; it0 < iterations; it0 += GCCNMF_CHAIN_MAX_ITERATIONS)
-            if ((rc = launch_klnmf_chain(4, g, V, W, H, R, colsumW, hscale, sparsity_alpha, epsilon, batch, flags & ~4, counters, it0,
-                                         std::min(GCCNMF_CHAIN_MAX_ITERATIONS, iterations - it0), s, &rg)))
+            if ((rc = launch_klnmf_chain(4, g, V, W, H, ws, sparsity_alpha, epsilon, batch, m, it0, std::min(GCCNMF_CHAIN_MAX_ITERATIONS, iterations - it0), s, &rg)))
                 return rc;
-        hipLaunchKernelGGL(nmf_chain_poison_kernel, dim3(64), dim3(256), 0, s, chain_status_words(counters, g, batch), W, H, (long)batch * g.sW, (long)batch * g.sH);
-        GCCNMF_CHECK_LAUNCH();
     }
-    return klnmf_stage(6, V, W, H, workspace, g, batch, sparsity_alpha, epsilon, flags, s);
+    return finish_call(iterations > 0, V, W, H, ws, g, batch, sparsity_alpha, epsilon, m, s);
 }
 
 // ---- shared dictionary (one W for every file / rank) ------------------------------------------
@@ -1398,7 +1397,7 @@ static long shared_split_floats(const NmfGeom& g) { return GCCNMF_SPLITS * ((g.s
 static SharedShard make_shard(const float* V, float* H, float* ws, int F, int N, int K, int batch, int ld) {
     SharedShard sh;
     sh.g = make_geom(F, N, K);
-    sh.direct = shared_single_file_layout(sh.g, batch, ld) && direct_path(sh.g, 1);
+    sh.direct = shared_single_file_layout(sh.g, batch, ld) && direct_path(sh.g, 1, 1);
     sh.latency = sh.direct || shared_latency_shard(sh.g, batch, ld);
     if (ld > 0) {
         sh.g.ld = ld;
@@ -1475,9 +1474,9 @@ static int shared_gemms(const SharedShard& sh, const float* W, const float* cols
                         bool beside_others, hipStream_t s) {
     const NmfGeom& g = sh.g;
     int rc;
-    // bit 1 = another unit's launches run beside these on a side stream: the tile-layout cost model of gemm_dma.h prices a launch that
-    // has the chip to itself, so such units keep full tiles (their partial rounds overlap the neighbours' kernels)
-    const int xcd = 1 | (beside_others ? 2 : 0);
+    // another unit's launches run beside these on a side stream: the tile-layout cost model of gemm_dma.h prices a launch that has the chip
+    // to itself, so such units keep full tiles (their partial rounds overlap the neighbours' kernels)
+    const int xa = 1, conc = beside_others ? 1 : 0;      // (intended today: 1, not the number of units)
     if (sh.direct) {                            // one file alone: the direct-to-register kernels (csrc/direct.hip), W transposed per iteration
         if ((rc = gccnmf_transpose_launch(W, 0, g.Kp, sh.d.Wt, sh.d.sWt, sh.d.ldwt, g.F, g.Kp, 1, s))) return rc;
         if ((rc = direct_wh_div(g, sh.d, sh.V, W, sh.H, hscale, sh.R, false, 1, s))) return rc;
@@ -1488,18 +1487,18 @@ static int shared_gemms(const SharedShard& sh, const float* W, const float* cols
 #ifdef GCCNMF_EXPERIMENTS
     if (sh.latency) {                           // one file alone: the split-K launches of the round-3 latency path
         if ((rc = launch_wh_div_split(g, sh.V, W, sh.H, hscale, sh.parts, sh.R, s))) return rc;
-        if ((rc = launch_update_h(g, W, 0, sh.R, sh.H, hscale, 0, colsumW, 0, alpha, eps, 1, 0, s))) return rc;
+        if ((rc = launch_update_h(update_h_args(g, W, 0, sh.R, sh.H, hscale, 0, colsumW, 0, alpha, eps, 1, 0, 0), s))) return rc;
         if ((rc = launch_wh_div_split(g, sh.V, W, sh.H, nullptr, sh.parts, sh.R, s))) return rc;
         return launch_rht_split(g, sh.R, sh.H, sh.parts, sh.rowsum_parts, s);
     }
 #endif
     // files are independent inside K1-K3 and per file inside K4a: keep every tile of a file on one XCD (its H / R panels are shared
     // through that XCD's L2), exactly as the per-file-dictionary path does
-    if ((rc = launch_wh_div(g, sh.V, W, 0, sh.H, hscale, 0, sh.R, sh.batch, xcd, s))) return rc;
-    if ((rc = launch_update_h(g, W, 0, sh.R, sh.H, hscale, 0, colsumW, 0, alpha, eps, sh.batch, xcd, s))) return rc;
+    if ((rc = launch_wh_div(g, wh_div_args(g, sh.V, W, 0, sh.H, hscale, 0, sh.R, sh.batch, xa, conc), s))) return rc;
+    if ((rc = launch_update_h(update_h_args(g, W, 0, sh.R, sh.H, hscale, 0, colsumW, 0, alpha, eps, sh.batch, xa, conc), s))) return rc;
     // (H now carries the previous normalisation; K3 below takes no scale, and step B rewrites hscale before anyone reads it again)
-    if ((rc = launch_wh_div(g, sh.V, W, 0, sh.H, nullptr, 0, sh.R, sh.batch, xcd, s))) return rc;
-    return launch_rht(g, sh.R, sh.H, sh.Upart, sh.rowsum_part, sh.batch, xcd, s);
+    if ((rc = launch_wh_div(g, wh_div_args(g, sh.V, W, 0, sh.H, nullptr, 0, sh.R, sh.batch, xa, conc), s))) return rc;
+    return launch_rht(g, rht_args(g, sh.R, sh.H, sh.Upart, sh.rowsum_part, sh.batch, xa, conc), s);
 }
 
 // partial (+)= [sum_files Upart || sum_files rowsum_part], files in ascending order (deterministic)
@@ -1559,7 +1558,7 @@ static int shared_step_a_all(const SharedShard* sh, int n, const float* W, const
 
 static int shared_step_b(float* W, const float* partial, float* colsumW, float* hscale, int F, int K, hipStream_t s) {
     NmfGeom g = make_geom(F, 1, K);
-    return launch_update_w(W, partial, partial + g.sU, colsumW, hscale, g.F, g.Fp, g.K, g.Kp, 0L, 0L, 0L, 0L, 1, s);
+    return launch_update_w(update_w_args(g, W, 0, partial, 0, partial + g.sU, colsumW, hscale, 0), 1, 1, s, 1, 0, 0, nullptr, 0, 0);
 }
 
 static int shared_finish(const SharedShard* sh, int n, float* hscale, int K, hipStream_t s) {

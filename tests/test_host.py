@@ -122,6 +122,36 @@ def test_every_workspace_size_is_a_multiple_of_four_floats():
     assert valid['klnmf_shared'] > tuples // 4 and valid['klnmf_shared_shard'] > tuples // 4        # (a batch of shared-dictionary files needs whole column tiles)
 
 
+def test_klnmf_workspace_sizes_follow_the_layout_in_closed_form():
+    """The KL-NMF workspace is R | U | colsumW, rowsumH, hscale | split-K scratch (one file) | Wt, Ht, Rt (up to 8 files) | ready counters,
+    rounded up to 32 words | 32 status words, and for a ragged batch the tables behind them (the files' column counts + 8 lists of 32 words,
+    rounded up to 4): both size functions agree with that layout written out here, for every tuple of the sweep."""
+    from gcc_nmf_amd import _hip
+    lib = _hip.lib()
+    up = lambda n, m: -(-n // m) * m
+    bad = []
+    for F in SWEEP_F:
+        for N in SWEEP_N:
+            for K in SWEEP_K:
+                for batch in SWEEP_BATCH:
+                    Fp, Kp, Np = up(F, 16), up(K, 64), up(N, 64)
+                    sV, sU, sH = Fp * Np, Fp * Kp, Kp * Np
+                    klnmf = batch * (sV + sU + 3 * Kp)
+                    if batch == 1:
+                        klnmf += 4 * (max(sV, sU) + Kp)
+                    if batch <= 8:
+                        klnmf += batch * (sU + sH + sV)
+                    klnmf += up(batch * (2 * -(-N // 64) + 2), 32) + 32
+                    ragged = klnmf + up(batch + 8 * 32, 4)
+                    got = (lib.gccnmf_klnmf_workspace_floats(F, N, K, batch), lib.gccnmf_klnmf_ragged_workspace_floats(F, N, K, batch))
+                    if got != (klnmf, ragged):
+                        bad.append((F, N, K, batch, got, (klnmf, ragged)))
+    assert not bad, '%d sizes differ from the closed form, e.g. %s' % (len(bad), bad[:4])
+    assert lib.gccnmf_klnmf_ragged_workspace_floats(513, 1244, 1024, 248) > 0
+    assert lib.gccnmf_klnmf_ragged_workspace_floats(513, 1244, 1024, 249) == -1           # more files than the eight lists hold
+    assert lib.gccnmf_klnmf_workspace_floats(513, 1244, 1024, 249) > 0
+
+
 def test_klnmf_entry_points_reject_a_workspace_that_is_not_16_byte_aligned():
     """gccnmf_klnmf, gccnmf_klnmf_ragged and every stage of gccnmf_klnmf_stage: a workspace address = 8 (mod 16) -- what the second file
     group's carve used to be for an odd batch -- with otherwise valid arguments is GCCNMF_ERR_ARG, decided before any HIP call."""
