@@ -724,7 +724,9 @@ __global__ __launch_bounds__(256) void rt_wh_kernel(const float* __restrict__ W,
         }
         if (lane == 0) {
             const float2 xl = X[(long)f * Tc + t], xr = X[((long)F + f) * Tc + t];
-            *(float2*)(Rv + (long)f * ncol + 2 * t) = make_float2(hypotf(xl.x, xl.y) / s0, hypotf(xr.x, xr.y) / s1);
+            // W h = 0: the channel was silent in this frame (|X| = 0 in every bin), the first update left it no coefficients; 0, not 0 / 0
+            *(float2*)(Rv + (long)f * ncol + 2 * t) =
+                make_float2(s0 == 0.f ? 0.f : hypotf(xl.x, xl.y) / s0, s1 == 0.f ? 0.f : hypotf(xr.x, xr.y) / s1);
         }
     }
 }
@@ -798,7 +800,7 @@ __global__ __launch_bounds__(256) void rt_tfmask_h_kernel(const float* __restric
             d1 += __shfl_xor(d1, o);
         }
         if (lane == 0) {
-            const float m0 = n0 / d0, m1 = n1 / d1;
+            const float m0 = d0 == 0.f ? 0.f : n0 / d0, m1 = d1 == 0.f ? 0.f : n1 / d1;      // no coefficients (a silent channel): mask 0, Y = 0
             tfMask[(long)f * Tc + t] = m0;
             tfMask[((long)F + f) * Tc + t] = m1;
             const float2 a = X[(long)f * Tc + t], b = X[((long)F + f) * Tc + t];
@@ -867,7 +869,7 @@ __global__ __launch_bounds__(256) void rt_tfmask_h_multi_kernel(const float* __r
 #pragma unroll
             for (int i = 0; i < RT_MAX_TARGETS; ++i) {
                 if (i < nt) {
-                    const float m0 = n0[i] / d0, m1 = n1[i] / d1;
+                    const float m0 = d0 == 0.f ? 0.f : n0[i] / d0, m1 = d1 == 0.f ? 0.f : n1[i] / d1;      // (as rt_tfmask_h)
                     tfMask[i * yplane + (long)f * Tc + t] = m0;
                     tfMask[i * yplane + ((long)F + f) * Tc + t] = m1;
                     Y[i * yplane + (long)f * Tc + t] = make_float2(m0 * a.x, m0 * a.y);

@@ -478,7 +478,10 @@ int gccnmf_rt_process_block(const float* block_in, float* block_out, float* in_r
  *   numHUpdates > 0                per-frame coefficient inference: that many KL-NMF H updates with W fixed
  *                                  (gccNMFFunctions.py:76), h0 = 1, per channel; the mask becomes W.(h*HMask) / W.h per channel,
  *                                  tfMask is then [2][F][Tc].  colsumW [Kp] = sum_f W, Hcoef [Kp][2*Tc], Rv [F][2*Tc] scratch.
- *                                  numHUpdates = 0 is exactly gccnmf_rt_process_block (h = 1).
+ *                                  numHUpdates = 0 is exactly gccnmf_rt_process_block (h = 1).  A channel that is silent in a
+ *                                  frame (|X| = 0 in every bin) gets no coefficients: its Rv, Hcoef, mask and Y are 0 (W.h = 0 is
+ *                                  answered with 0, not 0 / 0: a NaN frame would stay in the overlap-add buffer for eight blocks).
+ *                                  Columns K..Kp-1 of W may hold anything: no kernel of the call reads them into a result.
  *   frames_mode bits               1 = frames mode; 2 = everything but the localisation kernel; 4 = only the localisation kernel
  *                                  (2 then 4 on the same stream = one call; lets a host fetch block_out before the tracking update)
  *                                  8 = stream bank: S = (bits 8..19) + 1 independent streams of this configuration, advanced

@@ -142,8 +142,8 @@ class GCCNMFProcessorOracle(object):
                 for c in range(2):
                     v = np.abs(X[c]).astype(np.float64)
                     for _ in range(self.numHUpdates):
-                        Hc[c] *= np.dot(W64.T, v / np.dot(W64, Hc[c])) / np.sum(W64, axis=0)[:, np.newaxis]
-                tfMask = np.stack([np.dot(W64, Hc[c] * HMask) / np.dot(W64, Hc[c]) for c in range(2)])
+                        Hc[c] *= np.dot(W64.T, ratio0(v, np.dot(W64, Hc[c]))) / np.sum(W64, axis=0)[:, np.newaxis]
+                tfMask = np.stack([ratio0(np.dot(W64, Hc[c] * HMask), np.dot(W64, Hc[c])) for c in range(2)])
                 outputSpectrogram = tfMask * X
         else:
             HMask = argmaxTDOA = tfMask = None
@@ -158,6 +158,12 @@ class GCCNMFProcessorOracle(object):
             return out, dict(X=X, C=coherenceV, HMask=HMask, argmaxTDOA=argmaxTDOA, tfMask=tfMask, gccPHAT=gccPHAT,
                              targetTDOAIndex=float(self.targetTDOAIndex))
         return out
+
+
+def ratio0(num, den):
+    """num / den, 0 where den is 0: a channel that is silent in a frame gets no coefficients (W h = 0) and a zero mask, not 0 / 0."""
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return np.where(den == 0, 0.0, num / den)
 
 
 class OverlapAddOracle(object):

@@ -94,8 +94,8 @@ class MultiTargetOracle(object):
                 for c in range(2):
                     v = np.abs(X[c]).astype(np.float64)
                     for _ in range(b.numHUpdates):
-                        Hc[c] *= np.dot(W64.T, v / np.dot(W64, Hc[c])) / np.sum(W64, axis=0)[:, np.newaxis]
-                tfMask = np.stack([np.stack([np.dot(W64, Hc[c] * M[i]) / np.dot(W64, Hc[c]) for c in range(2)]) for i in range(N)])
+                        Hc[c] *= np.dot(W64.T, R.ratio0(v, np.dot(W64, Hc[c]))) / np.sum(W64, axis=0)[:, np.newaxis]
+                tfMask = np.stack([np.stack([R.ratio0(np.dot(W64, Hc[c] * M[i]), np.dot(W64, Hc[c])) for c in range(2)]) for i in range(N)])
                 Y = tfMask * X[np.newaxis]
         else:
             tfMask = None
