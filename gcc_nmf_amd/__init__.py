@@ -3,6 +3,7 @@
     gcc_nmf_amd.gccNMFFunctions   drop-in for the reference's gccNMF/gccNMFFunctions.py (NumPy in / out)
     gcc_nmf_amd.librosaSTFT       stft / istft with the reference's signatures
     gcc_nmf_amd.engine            GCCNMFEngine: a whole batch of mixtures resident in HBM
+                                  (GCCNMFEnhancementEngine: one talker against noise, [talker, noise] outputs)
     gcc_nmf_amd.dropin            install(): run the reference's runGCCNMF.py unchanged on top of this package
     gcc_nmf_amd.distributed       file sharding and shared-dictionary training across ranks (RCCL)
 

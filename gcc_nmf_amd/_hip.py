@@ -382,6 +382,50 @@ def target_scores_masks(CC, trig, idx, W, F, T, K, D, S, batch, ws, scores, argm
            argmax, stream=stream)
 
 
+GCCNMF_SCORES_ATOM_TDOA = 0x200         # include/gccnmf_hip.h: the full-grid atom TDOA arg-max, a mode of gccnmf_target_scores_masks
+GCCNMF_SCORES_ENHANCEMENT_MASKS = 0x400  # include/gccnmf_hip.h: talker / noise masks from the atom TDOA image, likewise
+ATOM_TDOA_MAX_D = 1024                  # csrc/atom_tdoa.h: the streaming limit
+TARGET_MODE_BOXCAR, TARGET_MODE_WINDOW_FUNCTION = 0, 2      # gccNMF/realtime/gccNMFProcessor.py:35,:37 (realtime.py exports the same)
+
+
+def atom_tdoa_indexes(CC, trig, W, F, T, K, D, batch, atom_tdoa, atom_score=None, stream=None):
+    """GCCNMF_ATOM_TDOA_INDEXES: every atom's arg-max over the whole TDOA grid -> atom_tdoa [batch][Kp][Tp] uint16 (a torch.int16
+    tensor's bits), atom_score [batch][Kp][Tp] float32 or None.  No workspace."""
+    _stage('gccnmf_target_scores_masks', CC, trig, None, W, F, T, K, D, GCCNMF_SCORES_ATOM_TDOA, batch, None, atom_score, atom_tdoa,
+           stream=stream, what='gccnmf_target_scores_masks (atom TDOA)')
+
+
+def check_enhancement_target(targetMode, targetTDOAEpsilon, targetTDOABeta, targetTDOANoiseFloor):
+    """The mask settings of the enhancement path (gccNMF/realtime/config.py:56-58) as the library takes them; no device needed.
+    Returns (window, eps, beta, noiseFloor): window 0 = TARGET_MODE_BOXCAR, 1 = TARGET_MODE_WINDOW_FUNCTION; eps > 0, beta > 0,
+    noiseFloor >= 0, all finite (checked whatever the mode, so a bad value cannot wait for the switch).  ValueError otherwise."""
+    modes = {'boxcar': 0, 'window': 1, TARGET_MODE_BOXCAR: 0, TARGET_MODE_WINDOW_FUNCTION: 1}
+    if isinstance(targetMode, bool) or targetMode not in modes:
+        raise ValueError("targetMode must be TARGET_MODE_BOXCAR / 'boxcar' or TARGET_MODE_WINDOW_FUNCTION / 'window', got %r" % (targetMode,))
+    out = []
+    for name, v, low_ok in (('targetTDOAEpsilon', targetTDOAEpsilon, False), ('targetTDOABeta', targetTDOABeta, False),
+                            ('targetTDOANoiseFloor', targetTDOANoiseFloor, True)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or not math.isfinite(v) or v < 0 or (v == 0 and not low_ok):
+            raise ValueError('%s must be a finite number %s 0, got %r' % (name, '>=' if low_ok else '>', v))
+        v32 = ctypes.c_float(float(v)).value
+        if not math.isfinite(v32) or (v32 == 0 and not low_ok):
+            raise ValueError('%s=%r is not a float32 number %s 0' % (name, v, '>=' if low_ok else '>'))
+        out.append(v32)
+    return (modes[targetMode],) + tuple(out)
+
+
+def enhancement_masks(atom_tdoa, target, T, K, batch, image, masks, window=0, eps=5.0, beta=2.0, noise_floor=0.0, per_frame=False, stream=None):
+    """GCCNMF_ENHANCEMENT_MASKS: atom_tdoa [batch][Kp][Tp] uint16 and target [batch] int32 (per_frame: [batch][Tp]) -> image
+    [batch][Kp][Tp] uint8 (0 talker, 1 noise) and / or masks [batch][2][Kp][Tp] float32 (talker, noise); either may be None.
+    window: 0 = boxcar, 1 = window function.  (eps, beta, noise_floor) travel as three host floats, read during the call."""
+    if window not in (0, 1):
+        raise ValueError('window must be 0 (boxcar) or 1 (window function), got %r' % (window,))
+    params = (c_float * 3)(eps, beta, noise_floor)
+    word = GCCNMF_SCORES_ENHANCEMENT_MASKS | int(window) | (GCCNMF_SCORES_TRACKS if per_frame else 0)
+    _stage('gccnmf_target_scores_masks', atom_tdoa, ctypes.addressof(params), target, None, 0, T, K, 0, word, batch, None, masks, image,
+           stream=stream, what='gccnmf_target_scores_masks (enhancement masks)')
+
+
 def argmax_targets(scores, K, T, S, batch, argmax, stream=None):
     _stage('gccnmf_argmax_targets', scores, K, T, S, batch, argmax, stream=stream)
 

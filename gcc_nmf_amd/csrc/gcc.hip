@@ -11,6 +11,7 @@
 #include "ratio.h"
 #include "spatial.h"
 #include "angular_nl.h"
+#include "atom_tdoa.h"
 #include "../../include/gccnmf_hip.h"
 
 
@@ -433,6 +434,22 @@ int gccnmf_target_scores_masks(const float* CC, const float* trig, const int* td
     GCCNMF_ENTER();
     // per-(target, frame) indexes ride above the low byte of S (GCCNMF_SCORES_TRACKS); every check comes before the first HIP call
     const int mode = S & ~0xff;
+    // offline enhancement (atom_tdoa.hip): two further modes of this call, the arguments re-read as the header says
+    if (S > 0 && mode == GCCNMF_SCORES_ATOM_TDOA) {
+        if (S & 0xff) return GCCNMF_ERR_ARG;
+        if (!CC || !trig || !W || !argmax || F < 2 || T < 1 || K < 1 || D < 1 || batch < 1) return GCCNMF_ERR_ARG;
+        if (D > ATOM_TDOA_MAX_D || batch > 65535 || T > (1 << 19)) return GCCNMF_ERR_UNSUPPORTED;
+        return gccnmf_launch_atom_tdoa(CC, trig, W, F, T, K, D, batch, (unsigned short*)argmax, scores, (hipStream_t)stream);
+    }
+    if (S > 0 && (mode & ~GCCNMF_SCORES_TRACKS) == GCCNMF_SCORES_ENHANCEMENT_MASKS) {
+        const int window = S & 0xff;
+        if (window > 1 || !CC || !trig || !tdoa_idx || (!scores && !argmax) || T < 1 || K < 1 || batch < 1) return GCCNMF_ERR_ARG;
+        const float eps = trig[0], beta = trig[1], nf = trig[2];            // three HOST floats
+        if (!(eps > 0.f && eps < INFINITY && beta > 0.f && beta < INFINITY && nf >= 0.f && nf < INFINITY)) return GCCNMF_ERR_ARG;
+        if (batch > 65535 || K > 65535 - 63) return GCCNMF_ERR_UNSUPPORTED;
+        return gccnmf_launch_enhancement_masks((const unsigned short*)CC, tdoa_idx, (mode & GCCNMF_SCORES_TRACKS) ? 1 : 0, window, eps,
+                                               beta, nf, T, K, batch, argmax, scores, (hipStream_t)stream);
+    }
     if (S < 0 || (mode & ~GCCNMF_SCORES_TRACKS)) return GCCNMF_ERR_ARG;
     S &= 0xff;
     const bool tracks = mode == GCCNMF_SCORES_TRACKS;

@@ -786,6 +786,114 @@ class GCCNMFEngine(object):
         return s.reshape(self.batch, g.S, 2, g.F, g.T)
 
 
+def check_enhancement_target_index(targetTDOAIndex, batch, numTDOAs):
+    """The ``targetTDOAIndex`` keyword of GCCNMFEnhancementEngine, no device needed: None (localise), one index for every file or one
+    per file, whole numbers in [0, numTDOAs).  Returns None or an int32 (batch,) array; ValueError otherwise."""
+    if targetTDOAIndex is None:
+        return None
+    tg = np.asarray(targetTDOAIndex)
+    if tg.ndim not in (0, 1) or tg.dtype.kind not in 'iuf' or (tg.ndim == 1 and tg.shape[0] != int(batch)):
+        raise ValueError('targetTDOAIndex must be None, one index or one index per file (%d), got shape %s' % (batch, tg.shape))
+    if not np.isfinite(tg).all() or not np.array_equal(tg, np.round(tg)) or tg.min() < 0 or tg.max() >= int(numTDOAs):
+        raise ValueError('targetTDOAIndex must be whole numbers in [0, %d), got %r' % (numTDOAs, targetTDOAIndex))
+    return np.ascontiguousarray(np.broadcast_to(tg, (int(batch),)), dtype=np.int32)
+
+
+class GCCNMFEnhancementEngine(GCCNMFEngine):
+    """Offline speech enhancement of a batch: ONE talker against noise (the reference's "offline speech enhancement" workflow; DESIGN
+    section 4e).  Every atom of every frame goes to the talker or to the noise by the atom's OWN TDOA -- the arg-max of its GCC-NMF
+    score over the whole TDOA grid (csrc/atom_tdoa.hip; gccNMF/realtime/gccNMFProcessor.py:254,:259) -- compared with the talker's:
+
+    ``targetMode='boxcar'``: talker where |i - target| < ``targetTDOAEpsilon`` (:263); ``'window'``: the soft mask
+    exp(-(|i - target| / epsilon) ** ``targetTDOABeta``) / (1 + ``targetTDOANoiseFloor``) + noiseFloor (:265), noise = 1 - talker.
+    (The constants TARGET_MODE_BOXCAR / TARGET_MODE_WINDOW_FUNCTION of realtime.py are taken too.)
+
+    ``localize()`` picks ONE peak of each file's mean angular spectrum as the talker's direction (with ``tdoaTracking``: one per frame);
+    ``targetTDOAIndex`` -- one index, or one per file -- skips the pick.  ``separate()`` returns (batch, 2, 2, L) waveforms ordered
+    [talker, noise], and so do ``separate_batches`` and ``separate_pcm16``; ``get_atom_tdoa_indexes()`` (batch, K, T).  Everything in
+    front of the masks is GCCNMFEngine's: ``dictionaryW``, ``numFreeAtoms``, ``tolerance``, ``reconstruction``, ``gccPHATNLEnabled``.
+    There is no ``numTargets`` keyword (two outputs), and no ragged form: ``lengths=`` raises ValueError."""
+
+    def __init__(self, n_samples, *args, **kwargs):
+        if 'numTargets' in kwargs:
+            raise TypeError('GCCNMFEnhancementEngine takes no numTargets keyword: its outputs are the talker and the noise')
+        if kwargs.pop('lengths', None) is not None:
+            raise ValueError('GCCNMFEnhancementEngine has no ragged form: lengths= is not available')
+        names = ('sampleRate', 'windowSize', 'hopSize', 'numTDOAs', 'microphoneSeparationInMetres')
+        if len(args) > len(names):
+            raise TypeError('GCCNMFEnhancementEngine takes at most %d positional arguments besides n_samples' % len(names))
+        kwargs.update(zip(names, args))
+        self.targetMode, self.targetTDOAEpsilon, self.targetTDOABeta, self.targetTDOANoiseFloor = _hip.check_enhancement_target(
+            kwargs.pop('targetMode', 'boxcar'), kwargs.pop('targetTDOAEpsilon', 5.0), kwargs.pop('targetTDOABeta', 2.0),
+            kwargs.pop('targetTDOANoiseFloor', 0.0))
+        numTDOAs = int(kwargs.get('numTDOAs', 128))
+        if not 3 <= numTDOAs <= _hip.ATOM_TDOA_MAX_D:
+            raise ValueError('enhancement takes 3 to %d TDOAs, got %d' % (_hip.ATOM_TDOA_MAX_D, numTDOAs))
+        fixed = check_enhancement_target_index(kwargs.pop('targetTDOAIndex', None), kwargs.get('batch', 1), numTDOAs)
+        super(GCCNMFEnhancementEngine, self).__init__(n_samples, numTargets=2, **kwargs)
+        g, B, dev = self.g, self.batch, self.device
+        with torch.cuda.device(dev):
+            self.scores = self.ws_scores = None              # the per-target score stage does not run here
+            self.fixedTargetTDOAIndex = fixed is not None
+            self.tdoa_idx = torch.zeros((B, 1), dtype=torch.int32, device=dev)
+            if fixed is not None:
+                self.tdoa_idx.copy_(torch.from_numpy(fixed).view(B, 1))
+            if self.tdoaTracking:
+                self.tracks = torch.zeros((B, 1, g.Tp), dtype=torch.int32, device=dev)
+            self.atom_tdoa = torch.zeros((B, g.Kp, g.Tp), dtype=torch.int16, device=dev)         # uint16 bits
+            self.soft_masks = torch.zeros((B, 2, g.Kp, g.Tp), dtype=torch.float32, device=dev) if self.targetMode else None
+
+    def _per_frame(self):
+        return self.tdoaTracking and not self.fixedTargetTDOAIndex
+
+    @_on_device
+    def localize(self):
+        g = self.g
+        _hip.angular_spectrogram(self.CC, self.trig, g.F, g.T, g.D, self.batch, self.ang, self.mean_ang,
+                                 nl_alpha=self.gccPHATNLAlpha if self.gccPHATNLEnabled else None)
+        if self.fixedTargetTDOAIndex:
+            return
+        _hip.pick_tdoa_peaks(self.mean_ang, g.D, g.Dp, 1, self.batch, self.tdoa_idx, self.status)
+        if self.tdoaTracking:
+            _hip.pick_tdoa_tracks(self.ang, g.D, g.T, 1, self.localizationWindowSize, self.batch, self.tracks, self.track_status)
+
+    def file_status(self):
+        if self.fixedTargetTDOAIndex:
+            return torch.zeros_like(self.status)
+        return super(GCCNMFEnhancementEngine, self).file_status()
+
+    @_on_device
+    def masks(self):
+        g = self.g
+        _hip.atom_tdoa_indexes(self.CC, self.trig, self.W, g.F, g.T, g.K, g.D, self.batch, self.atom_tdoa)
+        _hip.enhancement_masks(self.atom_tdoa, self.tracks if self._per_frame() else self.tdoa_idx, g.T, g.K, self.batch,
+                               None if self.targetMode else self.argmax, self.soft_masks, window=self.targetMode,
+                               eps=self.targetTDOAEpsilon, beta=self.targetTDOABeta, noise_floor=self.targetTDOANoiseFloor,
+                               per_frame=self._per_frame())
+
+    @_on_device
+    def reconstruct(self):
+        g = self.g
+        if self.reconstruction == 'spatial' and self.ws_cov is None:
+            self.ws_cov = torch.zeros(self._reconstruct_workspace_floats(), dtype=torch.float32, device=self.device)
+        _hip.reconstruct(self.W, self.H, None if self.targetMode else self.argmax, self.soft_masks, self.X, self.V, g.F, g.T, g.K, 2,
+                         self.batch, self.spec, mode=self.reconstruction,
+                         workspace=self.ws_cov if self.reconstruction == 'spatial' else self.ws_rec)
+
+    def get_atom_tdoa_indexes(self):
+        """(batch, K, T) int32: the TDOA index of every atom in every frame (after masks())."""
+        g = self.g
+        return (self.atom_tdoa[:, :g.K, :g.T].to(torch.int32) & 0xffff).cpu().numpy()
+
+    def get_enhancement_masks(self):
+        """(batch, 2, K, T) float32 [talker, noise] (after masks()): the soft masks, or the boxcar image expanded to 0 / 1."""
+        g = self.g
+        if self.targetMode:
+            return self.soft_masks[:, :, :g.K, :g.T].cpu().numpy()
+        noise = self.argmax[:, :g.K, :g.T].to(torch.float32)
+        return torch.stack([1 - noise, noise], dim=1).cpu().numpy()
+
+
 class RaggedGCCNMFEngine(object):
     """A batch of mixtures of DIFFERENT lengths (the reference separates a file of any length per call, gccNMF/runGCCNMF.py:30-36; sharding
     "independent mixture files" over GPUs means files as they come).  ``lengths``: samples per file, in the caller's order.

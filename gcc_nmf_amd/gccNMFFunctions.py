@@ -434,6 +434,83 @@ def getTargetCoefficientMasks(targetTDOAGCCNMFs, numTargets):
     return masks
 
 
+def check_atom_tdoa_arguments(coherenceV, numTDOAs, frequenciesInHz, W):
+    """Arguments of getAtomTDOAIndexes, no device needed.  Returns (C (F, T), W (F, K), numTDOAs)."""
+    C, W = np.asarray(coherenceV), np.asarray(W)
+    if C.ndim != 2 or C.dtype.kind not in 'cfiu' or C.shape[0] < 2 or C.shape[1] < 1:
+        raise ValueError('coherenceV must be an (F, T) array with F >= 2 and T >= 1, got %s %s' % (C.dtype, C.shape))
+    if W.ndim != 2 or W.dtype.kind not in 'fiu' or W.shape[0] != C.shape[0] or W.shape[1] < 1:
+        raise ValueError('W must be a real (%d, K) array, got %s %s' % (C.shape[0], W.dtype, W.shape))
+    if isinstance(numTDOAs, bool) or int(numTDOAs) != numTDOAs or not 1 <= int(numTDOAs) <= _hip.ATOM_TDOA_MAX_D:
+        raise ValueError('numTDOAs must be a whole number from 1 to %d, got %r' % (_hip.ATOM_TDOA_MAX_D, numTDOAs))
+    if np.size(frequenciesInHz) != C.shape[0]:
+        raise ValueError('frequenciesInHz must have one entry per row of coherenceV (%d), got %d' % (C.shape[0], np.size(frequenciesInHz)))
+    return C, W, int(numTDOAs)
+
+
+def getAtomTDOAIndexes(coherenceV, microphoneSeparationInMetres, numTDOAs, frequenciesInHz, W):
+    """Every atom's own TDOA in every frame (not in the reference's offline module; the streaming processor computes it per frame,
+    gccNMF/realtime/gccNMFProcessor.py:254,:259): argmax over the WHOLE grid of sum_f W[f, k] Re(C[f, t] exp(-2j pi f tau_d)).  First
+    index wins an exact tie, NaN scores are ignored, an all-NaN column gives 0.  Returns an int64 (K, T) array.  No (K, numTDOAs, T)
+    array is formed anywhere: the scores live in matrix-core accumulators (csrc/atom_tdoa.hip)."""
+    C, W, D = check_atom_tdoa_arguments(coherenceV, numTDOAs, frequenciesInHz, W)
+    F, T = C.shape
+    K = W.shape[1]
+    _, dev = _hip.lib(), _device()
+    g = Geometry(F, T, K, D)
+    trig = _trig_table(frequenciesInHz, microphoneSeparationInMetres, D, g, dev)
+    with _staging.Scope(dev) as sc:
+        dC = _upload_coherence(sc, C, g)
+        dW = _device_W(sc, W, g, dev)
+        atom = sc.dev('atom_tdoa', (g.Kp, g.Tp), torch.int16)
+        _hip.atom_tdoa_indexes(dC, trig, dW, F, T, K, D, 1, atom)
+        out = sc.download(atom[:K, :T].to(torch.int32) & 0xffff)
+    return out.astype(np.int64)
+
+
+def check_enhancement_mask_arguments(atomTDOAIndexes, targetTDOAIndex):
+    """Arguments of getEnhancementCoefficientMasks, no device needed.  Returns (uint16 (K, T) indexes, int32 target array, per frame?)."""
+    A = np.asarray(atomTDOAIndexes)
+    if A.ndim != 2 or A.size == 0 or A.dtype.kind not in 'iu' or A.min() < 0 or A.max() > 65535:
+        raise ValueError('atomTDOAIndexes must be a (K, T) array of whole numbers in [0, 65535], got %s %s' % (A.dtype, A.shape))
+    tg = np.asarray(targetTDOAIndex)
+    if tg.ndim not in (0, 1) or tg.dtype.kind not in 'iuf' or (tg.ndim == 1 and tg.shape[0] != A.shape[1]):
+        raise ValueError('targetTDOAIndex must be a number or one number per frame (%d), got shape %s' % (A.shape[1], tg.shape))
+    if not np.isfinite(tg).all() or not np.array_equal(tg, np.round(tg)) or np.abs(tg).max() >= 2 ** 24:
+        raise ValueError('targetTDOAIndex must be whole numbers')
+    return np.ascontiguousarray(A, dtype=np.uint16), np.ascontiguousarray(np.atleast_1d(tg), dtype=np.int32), tg.ndim == 1
+
+
+def getEnhancementCoefficientMasks(atomTDOAIndexes, targetTDOAIndex, targetMode=_hip.TARGET_MODE_WINDOW_FUNCTION, targetTDOAEpsilon=5.0,
+                                   targetTDOABeta=2.0, targetTDOANoiseFloor=0.0):
+    """The talker's and the noise's coefficient masks of offline speech enhancement, [talker, noise] = (m, 1 - m), from every atom's own
+    TDOA index i (getAtomTDOAIndexes) and the talker's ``targetTDOAIndex`` (a number, or one per frame):
+        TARGET_MODE_BOXCAR           m = |i - target| < epsilon                                          (realtime/gccNMFProcessor.py:263)
+        TARGET_MODE_WINDOW_FUNCTION  m = exp(-(|i - target| / epsilon) ** beta) / (1 + noiseFloor) + noiseFloor, unclamped     (:265)
+    ``targetMode``: the constants realtime.py exports (or 'boxcar' / 'window'); the defaults are the reference's (processor :193,
+    realtime/config.py:56-58).  Returns float32 (2, K, T): pass it to getTargetSpectrogramEstimates as its masks."""
+    window, eps, beta, nf = _hip.check_enhancement_target(targetMode, targetTDOAEpsilon, targetTDOABeta, targetTDOANoiseFloor)
+    A, tg, per_frame = check_enhancement_mask_arguments(atomTDOAIndexes, targetTDOAIndex)
+    K, T = A.shape
+    _, dev = _hip.lib(), _device()
+    g = Geometry(2, T, K, 1, 2)
+    with _staging.Scope(dev) as sc:
+        atom = sc.dev('atom_tdoa', (g.Kp, g.Tp), torch.int16, corner=(K, T))
+        atom[:K, :T].copy_(sc.upload(A.view(np.int16), 'atom', np.int16))
+        if per_frame:
+            dT = sc.dev('target_tracks', (g.Tp,), torch.int32, corner=(T,))
+            dT[:T].copy_(sc.upload(tg, 'target', np.int32))
+        else:
+            dT = sc.upload(tg, 'target', np.int32)
+        image = sc.dev('argmax', (g.Kp, g.Tp), torch.uint8)
+        dM = sc.dev('enh_masks', (2, g.Kp, g.Tp))
+        _hip.enhancement_masks(atom, dT, T, K, 1, image, dM, window=window, eps=eps, beta=beta, noise_floor=nf, per_frame=per_frame)
+        masks = sc.download(dM[:, :K, :T], shape=(2, K, T))
+        if not window:                   # resident mode: the reconstruction takes the one-hot image the boxcar masks are an expansion of
+            sc.remember(masks, 'M', dict(argmax=image), dict(S=2, K=K, T=T))
+    return masks
+
+
 def getTargetSpectrogramEstimates(targetCoefficientMasks, complexMixtureSpectrogram, W, stereoH, reconstruction='direct'):
     """gccNMF/gccNMFFunctions.py:145-151.  Returns (numTargets, 2, F, T) complex64.
 

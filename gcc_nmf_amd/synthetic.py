@@ -96,3 +96,30 @@ def reverberant_mixture(seed, numSamples=96000, sampleRate=16000, delays=(-20, 3
     pcm = np.round(x * scale * 32768).astype(np.int16)
     x = (pcm.astype('float32') / 32768).astype(np.float32)
     return (x, images * scale) if returnSources else x
+
+
+def speech_in_noise_mixture(seed, snrDb, numSamples=64000, sampleRate=16000, delay=12, bandCentresHz=(300.0, 700.0, 1200.0, 2000.0, 3000.0),
+                            bandWidthHz=160.0, noiseCutoffHz=3000.0):
+    """One talker against diffuse noise -- the offline speech-enhancement case.  The talker: one ``bandWidthHz``-wide band of noise at
+    each of ``bandCentresHz``, each with its own squared half-sine syllabic envelope sin^2(pi r t + phi) (r = 2.5, 3.1, ... syllables
+    per second); the right channel holds roll(talker, delay), so at 16 kHz, 1 m and 128 TDOAs the default puts the talker near index
+    47.  The noise: independent ``noiseCutoffHz`` low-passed Gaussian noise in each channel (no direction), scaled so that the stereo
+    talker-to-noise energy ratio is ``snrDb``.  int16-representable float32 samples as in synthetic_mixture.
+    Returns (mixture (2, numSamples) float32, clean talker (2, numSamples) float64 on the mixture's scale)."""
+    from scipy.signal import butter, lfilter
+    rng = np.random.default_rng(20261019 + seed)
+    t = np.arange(numSamples) / float(sampleRate)
+    freqs = np.fft.rfftfreq(numSamples, 1.0 / sampleRate)
+    talker = np.zeros(numSamples)
+    for j, centre in enumerate(bandCentresHz):
+        s = np.fft.irfft(np.fft.rfft(rng.standard_normal(numSamples)) * (np.abs(freqs - centre) < bandWidthHz / 2.0), numSamples)
+        phi = rng.uniform(0, np.pi)
+        talker += s / np.std(s) * np.sin(np.pi * (2.5 + 0.6 * j) * t + phi) ** 2
+    clean = np.stack([talker, np.roll(talker, delay)])
+    b, a = butter(4, noiseCutoffHz / (sampleRate / 2.0))
+    noise = np.stack([lfilter(b, a, rng.standard_normal(numSamples)) for _ in range(2)])
+    noise *= np.sqrt(np.sum(clean ** 2) / np.sum(noise ** 2) * 10.0 ** (-snrDb / 10.0))
+    x = clean + noise
+    scale = 0.1 / np.max(np.abs(x))
+    pcm = np.round(x * scale * 32768).astype(np.int16)
+    return (pcm.astype('float32') / 32768).astype(np.float32), clean * scale

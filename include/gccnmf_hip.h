@@ -356,8 +356,46 @@ int gccnmf_pick_tdoa_peaks(const double* mean_ang, int D, int Dp, int S, int bat
  * Per-frame target directions: pass S | GCCNMF_SCORES_TRACKS (the mode rides above the low byte of S, like GCCNMF_RECONSTRUCT_RATIO;
  * any other bit there: GCCNMF_ERR_ARG) and tdoa_idx is [batch][S][Tp] int32, 16-byte aligned -- one index per (target, frame), as the
  * tracks mode of gccnmf_pick_tdoa_peaks writes them: G_i[k,t] = Re sum_f W[f,k] C[f,t] exp(-2j pi f tau_{i,t}).  Only the steering
- * table lookup in front of the GEMM changes (indexes are clamped to [0, D) as before); constant tracks give the bits of the plain form. */
+ * table lookup in front of the GEMM changes (indexes are clamped to [0, D) as before); constant tracks give the bits of the plain form.
+ *
+ * Offline speech enhancement (one talker against noise: every atom of every frame goes to the talker or to the noise by the atom's OWN
+ * TDOA, gccNMF/realtime/gccNMFProcessor.py:254,:259-265) is two further modes of this call, not entry points of their own
+ * (csrc/atom_tdoa.hip); the macros below spell the two calls out.
+ *
+ * GCCNMF_ATOM_TDOA_INDEXES -- S = GCCNMF_SCORES_ATOM_TDOA, nothing in the low byte -- scores every atom against the WHOLE grid,
+ *     score[k,d,t] = sum_f W[f,k] (Cr[f,t] cos[f,d] + Ci[f,t] sin[f,d])                                   (gccNMFProcessor.py:254)
+ * and keeps only the arg-max over d < D (:259): first index wins an exact tie, NaN scores are ignored, an all-NaN column gives 0.
+ *   CC, trig, W  as above (W [batch][Fp][Kp]); tdoa_idx and workspace are not read and may be NULL (there is no workspace: no
+ *                (K, D, T) or (F, D, T) array exists anywhere, the scores live in matrix-core accumulators)
+ *   atom_tdoa    [batch][Kp][Tp] uint16 out, 4-byte aligned, passed as `argmax`; every element is written, padded positions as 0
+ *   atom_score   [batch][Kp][Tp] float32 out or NULL, 8-byte aligned, passed as `scores`: the winning score (NaN where the column had
+ *                no number, 0 in padded positions)
+ *   The f sum of one (k, d, t) is one f32 fma chain in ascending f over a = fma(Cr, cos, Ci * sin) -- exact-f32 MFMA -- whatever the
+ *   batch, the file's place in it or the grid: a file's image is bit-identical alone and in any batch.
+ *   GCCNMF_ERR_UNSUPPORTED: D > 1024 (the streaming limit), batch > 65535, T > 2^19.  GCCNMF_ERR_ARG: a null CC / trig / W /
+ *   atom_tdoa, a non-positive size, anything in the low byte of S.  All checks come before the first HIP call.
+ *
+ * GCCNMF_ENHANCEMENT_MASKS -- S = GCCNMF_SCORES_ENHANCEMENT_MASKS | window [| GCCNMF_SCORES_TRACKS] -- turns the index image into the
+ * talker's and the noise's coefficient masks around a target index; with i = atom_tdoa[k,t] and dist = |i - target| in float32:
+ *     window = 0 (TARGET_MODE_BOXCAR, :263):            m = dist < eps
+ *     window = 1 (TARGET_MODE_WINDOW_FUNCTION, :265):   m = expf(-powf(dist / eps, beta)) / (1 + nf) + nf       (not clamped)
+ *   atom_tdoa [batch][Kp][Tp] uint16, passed as `CC`;  target [batch] int32, or with GCCNMF_SCORES_TRACKS [batch][Tp] int32 (one per
+ *             frame), passed as `tdoa_idx`;  params = {eps, beta, nf}: three floats in HOST memory, read before the call returns,
+ *             passed as `trig` (eps > 0, beta > 0, nf >= 0, all finite, else GCCNMF_ERR_ARG)
+ *   image     [batch][Kp][Tp] uint8 out or NULL, passed as `argmax`: 0 where dist < eps (talker), else 1 (noise) -- gccnmf_reconstruct
+ *             takes it as its one-hot arg-max image with S = 2
+ *   masks     [batch][2][Kp][Tp] float32 out or NULL, passed as `scores`: (m, 1 - m) -- gccnmf_reconstruct's `masks` with S = 2
+ *   Padded positions of both outputs are written as 0.  W, F, D and workspace are not read.  GCCNMF_ERR_ARG: both outputs NULL, a
+ *   null input, a non-positive T / K / batch, window > 1. */
 #define GCCNMF_SCORES_TRACKS 0x100
+#define GCCNMF_SCORES_ATOM_TDOA 0x200
+#define GCCNMF_SCORES_ENHANCEMENT_MASKS 0x400
+#define GCCNMF_ATOM_TDOA_INDEXES(CC, trig, W, F, T, K, D, batch, atom_tdoa, atom_score, stream)                                          \
+    gccnmf_target_scores_masks(CC, trig, 0, W, F, T, K, D, GCCNMF_SCORES_ATOM_TDOA, batch, 0, atom_score, (unsigned char*)(atom_tdoa), stream)
+#define GCCNMF_ENHANCEMENT_MASKS(atom_tdoa, target, per_frame, window, params, T, K, batch, image, masks, stream)                        \
+    gccnmf_target_scores_masks((const float*)(atom_tdoa), params, target, 0, 0, T, K, 0,                                                 \
+                               GCCNMF_SCORES_ENHANCEMENT_MASKS | (window) | ((per_frame) ? GCCNMF_SCORES_TRACKS : 0), batch, 0, masks,   \
+                               image, stream)
 long gccnmf_scores_workspace_floats(int F, int T, int S, int batch);
 int gccnmf_target_scores_masks(const float* CC, const float* trig, const int* tdoa_idx, const float* W, int F,
                                int T, int K, int D, int S, int batch, float* workspace, float* scores,
