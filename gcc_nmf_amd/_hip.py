@@ -382,6 +382,66 @@ def target_scores_masks(CC, trig, idx, W, F, T, K, D, S, batch, ws, scores, argm
            argmax, stream=stream)
 
 
+GCCNMF_PEAKS_COUNT_BIT = 1 << 30        # include/gccnmf_hip.h: the count mode of gccnmf_pick_tdoa_peaks (numSources='auto')
+GCCNMF_SCORES_COUNTED = 0x800           # include/gccnmf_hip.h: negative indexes are absent targets in gccnmf_target_scores_masks
+MAX_AUTO_SOURCES = 8                    # the default cap of numSources='auto' (the ratio and spatial reconstructions' limit)
+ENGINE_MAX_AUTO_TARGETS = 8             # GCCNMFEngine(numTargets='auto', maxTargets=...): RATIO_MAX_TARGETS, whatever the reconstruction
+
+
+def check_auto_sources(numSources, maxSources=MAX_AUTO_SOURCES):
+    """The ``numSources`` argument where 'auto' is accepted, and the cap that goes with it; no device needed.  Returns True for 'auto'
+    (the count comes from the angular spectrum, ``maxSources`` at the most: a whole number from 1 to 255) and False for anything that is
+    not a string (the callers' own rules for a fixed count apply: None, 0 and every other falsy value keep raising there).  ValueError:
+    any other string, a cap that is no whole number in [1, 255]."""
+    if isinstance(numSources, str):
+        if numSources != 'auto':
+            raise ValueError("numSources must be a number of sources or 'auto', got %r" % (numSources,))
+        m = maxSources
+        if isinstance(m, bool) or not isinstance(m, numbers.Integral) or not 1 <= m <= 255:
+            raise ValueError('maxSources must be a whole number from 1 to 255, got %r' % (m,))
+        return True
+    return False
+
+
+def check_auto_targets(numTargets, maxTargets, tdoaTracking=False):
+    """The ``numTargets`` / ``maxTargets`` keywords of the engines; no device needed.  Returns (auto, S): for numTargets='auto' the
+    buffers' target count S is ``maxTargets`` (default 4; a whole number from 1 to 8), otherwise S is ``numTargets`` as given.
+    ValueError: 'auto' with tdoaTracking (the tracks kernel takes one count per launch), maxTargets without 'auto', another string."""
+    if check_auto_sources(numTargets, 1):
+        if tdoaTracking:
+            raise ValueError("numTargets='auto' cannot be combined with tdoaTracking (every frame's peak set takes one count per launch)")
+        m = 4 if maxTargets is None else maxTargets
+        if isinstance(m, bool) or not isinstance(m, numbers.Integral) or not 1 <= m <= ENGINE_MAX_AUTO_TARGETS:
+            raise ValueError('maxTargets must be a whole number from 1 to %d, got %r' % (ENGINE_MAX_AUTO_TARGETS, m))
+        return True, int(m)
+    if maxTargets is not None:
+        raise ValueError("maxTargets needs numTargets='auto'")
+    return False, numTargets
+
+
+def peaks_count_word(maxSources):
+    """The S argument of gccnmf_pick_tdoa_peaks in its count mode: GCCNMF_PEAKS_COUNT(Smax) of include/gccnmf_hip.h."""
+    check_auto_sources('auto', maxSources)
+    return int(maxSources) | GCCNMF_PEAKS_COUNT_BIT
+
+
+def count_tdoa_peaks(mean_ang, D, Dp, maxSources, batch, idx, status, stream=None):
+    """The same entry point in its count mode: every file keeps as many peaks as it has talkers (the exact 2-means split of its peak
+    heights), ``maxSources`` at the most -> idx [batch][maxSources] (ascending, then -1), status [batch] (0, 1 = nothing to count,
+    2 = capped)."""
+    _stage('gccnmf_pick_tdoa_peaks', mean_ang, D, Dp, peaks_count_word(maxSources), batch, idx, status, stream=stream,
+           what='gccnmf_pick_tdoa_peaks (count)')
+
+
+def target_scores_masks_counted(CC, trig, idx, W, F, T, K, D, S, batch, ws, scores, argmax, counted=False, stream=None):
+    """target_scores_masks with fixed indexes; counted: idx [batch][S] as count_tdoa_peaks writes it -- a negative index is a target
+    the file does not have (NaN scores, never the arg-max).  counted=False is the plain call."""
+    if not 1 <= int(S) <= 255:
+        raise ValueError('the score stage takes 1 to 255 targets, got %r' % (S,))
+    _stage('gccnmf_target_scores_masks', CC, trig, idx, W, F, T, K, D, int(S) | GCCNMF_SCORES_COUNTED if counted else int(S), batch, ws,
+           scores, argmax, stream=stream, what='gccnmf_target_scores_masks (counted)' if counted else None)
+
+
 GCCNMF_SCORES_ATOM_TDOA = 0x200         # include/gccnmf_hip.h: the full-grid atom TDOA arg-max, a mode of gccnmf_target_scores_masks
 GCCNMF_SCORES_ENHANCEMENT_MASKS = 0x400  # include/gccnmf_hip.h: talker / noise masks from the atom TDOA image, likewise
 ATOM_TDOA_MAX_D = 1024                  # csrc/atom_tdoa.h: the streaming limit

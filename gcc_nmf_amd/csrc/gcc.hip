@@ -12,6 +12,7 @@
 #include "spatial.h"
 #include "angular_nl.h"
 #include "atom_tdoa.h"
+#include "source_count.h"
 #include "../../include/gccnmf_hip.h"
 
 
@@ -201,7 +202,10 @@ __device__ __forceinline__ float4 gcc_steer4(float4 cr, float4 ci, float4 c, flo
 // TRACKS: tdoa_idx is [batch][S][Tp], one index per (target, frame) -- the four frames' indexes are one 16-byte load, their table
 // entries four lookups in row f of the steering table (512 bytes at D = 128: they hit the vector cache); the same products in the
 // same order (gcc_steer4), so constant tracks give the bits of the fixed-index form.
-template <bool TRACKS>
+// COUNTED (fixed indexes only; numSources='auto'): a negative index is a target the file does not have -- its
+// column is quiet NaN where a present target's holds a product, so the GEMM behind it gives NaN scores and the arg-max, which
+// ignores NaN, never hands it an atom; a non-negative index takes the path it always took.
+template <bool TRACKS, bool COUNTED>
 __global__ __launch_bounds__(256) void gcc_steer_kernel(const float* __restrict__ CC, const float* __restrict__ trig,
                                                         const int* __restrict__ tdoa_idx, int F, int Fp, int T, int Tp, int D,
                                                         int Dp, int S, float* __restrict__ P) {
@@ -219,12 +223,14 @@ __global__ __launch_bounds__(256) void gcc_steer_kernel(const float* __restrict_
         int4 tau;
         if (TRACKS) tau = *(const int4*)(tdoa_idx + ((long)b * S + i) * Tp + t);
         else tau.x = tau.y = tau.z = tau.w = tdoa_idx[(long)b * S + i];
+        const bool absent = COUNTED && tau.x < 0;
         tau.x = tau.x < 0 ? 0 : (tau.x >= D ? D - 1 : tau.x);
         tau.y = tau.y < 0 ? 0 : (tau.y >= D ? D - 1 : tau.y);
         tau.z = tau.z < 0 ? 0 : (tau.z >= D ? D - 1 : tau.z);
         tau.w = tau.w < 0 ? 0 : (tau.w >= D ? D - 1 : tau.w);
         out = gcc_steer4(cr, ci, make_float4(cos_row[tau.x], cos_row[tau.y], cos_row[tau.z], cos_row[tau.w]),
                          make_float4(sin_row[tau.x], sin_row[tau.y], sin_row[tau.z], sin_row[tau.w]));
+        if (absent) out.x = out.y = out.z = out.w = __builtin_nanf("");
         if (t + 1 >= T) out.y = 0.f;
         if (t + 2 >= T) out.z = 0.f;
         if (t + 3 >= T) out.w = 0.f;
@@ -401,6 +407,13 @@ int gccnmf_pick_tdoa_peaks(const double* mean_ang, int D, int Dp, int S, int bat
     GCCNMF_ENTER();
     // time-varying tracks ride above the low byte of S (GCCNMF_PEAKS_TRACKS: bit 8, the window length L in bits 9-30); nothing above
     // the low byte = the whole-file estimate, every call as it was.  Every check comes before the first HIP call.
+    // The count mode (GCCNMF_PEAKS_COUNT: bit 30 alone above the low byte, which no tracks word is -- those carry bit 8) keeps as many
+    // peaks as the file has talkers (source_count.hip).
+    if (S > 0 && (S & ~0xff) == GCCNMF_PEAKS_COUNT_BIT) {
+        S &= 0xff;
+        if (!mean_ang || !tdoa_idx || !status || D < 3 || D > SOURCE_COUNT_MAX_D || Dp < D || S < 1 || batch < 1) return GCCNMF_ERR_ARG;
+        return gccnmf_launch_count_peaks(mean_ang, D, Dp, S, batch, tdoa_idx, status, (hipStream_t)stream);
+    }
     if (S & ~0xff) {
         const int L = (S >> 9) & 0x3fffff, T = Dp;              // ang's pitches follow from D and T: the Dp argument carries T
         if (S < 0 || !(S & GCCNMF_PEAKS_TRACKS_BIT) || L < 1) return GCCNMF_ERR_ARG;
@@ -450,9 +463,10 @@ int gccnmf_target_scores_masks(const float* CC, const float* trig, const int* td
         return gccnmf_launch_enhancement_masks((const unsigned short*)CC, tdoa_idx, (mode & GCCNMF_SCORES_TRACKS) ? 1 : 0, window, eps,
                                                beta, nf, T, K, batch, argmax, scores, (hipStream_t)stream);
     }
-    if (S < 0 || (mode & ~GCCNMF_SCORES_TRACKS)) return GCCNMF_ERR_ARG;
+    // absent targets (GCCNMF_SCORES_COUNTED: a negative index is a target the file does not have) -- with the fixed indexes only
+    if (S < 0 || ((mode & ~GCCNMF_SCORES_TRACKS) && mode != GCCNMF_SCORES_COUNTED)) return GCCNMF_ERR_ARG;
     S &= 0xff;
-    const bool tracks = mode == GCCNMF_SCORES_TRACKS;
+    const bool tracks = mode == GCCNMF_SCORES_TRACKS, counted = mode == GCCNMF_SCORES_COUNTED;
     if (!CC || !trig || !tdoa_idx || !W || !workspace || !scores || F < 2 || T < 1 || K < 1 || D < 1 || S < 1 || batch < 1)
         return GCCNMF_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
@@ -460,11 +474,14 @@ int gccnmf_target_scores_masks(const float* CC, const float* trig, const int* td
     const int Dp = gccnmf_round_up(D, 64);
     const int ncol = S * p.Tp;
     float* P = workspace;
-    if (tracks)
-        hipLaunchKernelGGL(gcc_steer_kernel<true>, dim3(gccnmf_ceil_div(ncol, 1024), p.Fp, batch), dim3(256), 0, s, CC, trig, tdoa_idx,
+    if (counted)
+        hipLaunchKernelGGL((gcc_steer_kernel<false, true>), dim3(gccnmf_ceil_div(ncol, 1024), p.Fp, batch), dim3(256), 0, s, CC, trig,
+                           tdoa_idx, F, p.Fp, T, p.Tp, D, Dp, S, P);
+    else if (tracks)
+        hipLaunchKernelGGL((gcc_steer_kernel<true, false>), dim3(gccnmf_ceil_div(ncol, 1024), p.Fp, batch), dim3(256), 0, s, CC, trig, tdoa_idx,
                            F, p.Fp, T, p.Tp, D, Dp, S, P);
     else
-        hipLaunchKernelGGL(gcc_steer_kernel<false>, dim3(gccnmf_ceil_div(ncol, 1024), p.Fp, batch), dim3(256), 0, s, CC, trig, tdoa_idx,
+        hipLaunchKernelGGL((gcc_steer_kernel<false, false>), dim3(gccnmf_ceil_div(ncol, 1024), p.Fp, batch), dim3(256), 0, s, CC, trig, tdoa_idx,
                            F, p.Fp, T, p.Tp, D, Dp, S, P);
     GCCNMF_CHECK_LAUNCH();
     GemmArgs a = {};

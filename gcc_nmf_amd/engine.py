@@ -246,6 +246,13 @@ class GCCNMFEngine(object):
     the previous frame's set).  Target i of a frame is its i-th peak from the left: talkers whose directions cross swap outputs.
     ``get_tdoa_indexes()`` stays the whole-file estimate.  A window of 2T - 1 frames or more gives the static path bit for bit.
 
+    ``numTargets='auto'`` / ``maxTargets``: every file is split into as many targets as its own mean angular
+    spectrum shows -- ``localize()`` counts them (the exact two-cluster split of the peak heights, the count mode of
+    gccnmf_pick_tdoa_peaks) and ``masks()`` scores the atoms against each file's own directions.  All buffers and outputs have
+    ``maxTargets`` (default 4, at most 8) slots per file; the slots at and beyond a file's count are all zero.  ``get_num_sources()``
+    (batch,), ``get_tdoa_indexes()`` (batch, maxTargets) with -1 beyond the count, ``get_count_status()`` (batch,): 0, 1 = no peak
+    (``check_status()`` raises), 2 = more than maxTargets found, the highest kept (not raised).  Not with tdoaTracking.
+
     ``tolerance`` / ``checkEvery``: with a tolerance, ``numIterations`` is the MAXIMUM -- ``klnmf()`` runs the
     library in chunks of ``checkEvery`` iterations and stops each file once its KL divergence D(V || W.H) has stopped falling
     (converge_klnmf states the rule; a rise stops a file too, which is intended for sparsityAlpha > 0).  ``get_iterations()`` (batch,),
@@ -266,7 +273,8 @@ class GCCNMFEngine(object):
                  sparsityAlpha=0, epsilon=1e-16, seedValue=0, batch=1, windowFunction=np.hanning,
                  device='cuda:0', klnmf_flags=0, nmf_groups=None, dictionaryW=None, initialH='random', reconstruction='direct',
                  gccPHATNLEnabled=False, gccPHATNLAlpha=2.0, tdoaTracking=False, localizationWindowSize=None, tolerance=None, checkEvery=10,
-                 numFreeAtoms=0):
+                 numFreeAtoms=0, maxTargets=None):
+        self.autoTargets, numTargets = _hip.check_auto_targets(numTargets, maxTargets, tdoaTracking)
         if initialH not in ('random', 'ones'):
             raise ValueError("initialH must be 'random' or 'ones'")
         self.initialH = initialH
@@ -510,6 +518,9 @@ class GCCNMFEngine(object):
         g = self.g
         _hip.angular_spectrogram(self.CC, self.trig, g.F, g.T, g.D, self.batch, self.ang, self.mean_ang,
                                  nl_alpha=self.gccPHATNLAlpha if self.gccPHATNLEnabled else None)
+        if self.autoTargets:
+            _hip.count_tdoa_peaks(self.mean_ang, g.D, g.Dp, g.S, self.batch, self.tdoa_idx, self.status)
+            return
         _hip.pick_tdoa_peaks(self.mean_ang, g.D, g.Dp, g.S, self.batch, self.tdoa_idx, self.status)
         if self.tdoaTracking:
             _hip.pick_tdoa_tracks(self.ang, g.D, g.T, g.S, self.localizationWindowSize, self.batch, self.tracks, self.track_status)
@@ -517,6 +528,10 @@ class GCCNMFEngine(object):
     @_on_device
     def masks(self):
         g = self.g
+        if self.autoTargets:
+            _hip.target_scores_masks_counted(self.CC, self.trig, self.tdoa_idx, self.W, g.F, g.T, g.K, g.D, g.S, self.batch, self.ws_scores,
+                                             self.scores, self.argmax, counted=True)
+            return
         _hip.target_scores_masks(self.CC, self.trig, self.tracks if self.tdoaTracking else self.tdoa_idx, self.W, g.F, g.T, g.K, g.D, g.S,
                                  self.batch, self.ws_scores, self.scores, self.argmax, tracks=self.tdoaTracking)
 
@@ -650,7 +665,7 @@ class GCCNMFEngine(object):
                 ev_out[slot].synchronize()
                 st = status[slot].numpy()
                 if st.any():
-                    raise ValueError('fewer than %d angular-spectrum peaks in file(s) %s' % (g.S, np.nonzero(st)[0].tolist()))
+                    raise ValueError(self._too_few_peaks(st))
                 return hy[slot].numpy().copy()
 
             try:
@@ -704,15 +719,24 @@ class GCCNMFEngine(object):
 
     def file_status(self):
         """int32 [batch] on the device, non-zero = the file cannot be separated: too few peaks in its mean angular spectrum -- with
-        tdoaTracking, in every frame's windowed mean (bit 1 of any frame's track status; the whole-file estimate is then only reported)."""
+        tdoaTracking, in every frame's windowed mean (bit 1 of any frame's track status; the whole-file estimate is then only reported);
+        with numTargets='auto', no peak at all (count status 1; a capped count, status 2, is no failure)."""
+        if self.autoTargets:
+            return (self.status == 1).to(torch.int32)
         return (self.track_status[:, 0] & 2) if self.tdoaTracking else self.status
+
+    def _too_few_peaks(self, st):
+        files = np.nonzero(st)[0].tolist()
+        if self.autoTargets:
+            return 'no angular-spectrum peak to count in file(s) %s' % files
+        return 'fewer than %d angular-spectrum peaks in file(s) %s' % (self.g.S, files)
 
     @_on_device
     def check_status(self):
         self.check_chain_status()
         st = self.file_status().cpu().numpy()
         if st.any():
-            raise ValueError('fewer than %d angular-spectrum peaks in file(s) %s' % (self.g.S, np.nonzero(st)[0].tolist()))
+            raise ValueError(self._too_few_peaks(st))
 
     @_on_device
     def _chain_status(self):
@@ -757,7 +781,20 @@ class GCCNMFEngine(object):
         return self.ang[:, :g.D, :g.T].cpu().numpy(), self.mean_ang[:, :g.D].cpu().numpy()
 
     def get_tdoa_indexes(self):
+        """(batch, S) int32, ascending per file; with numTargets='auto' S = maxTargets and the slots beyond a file's count hold -1."""
         return self.tdoa_idx.cpu().numpy()
+
+    def get_num_sources(self):
+        """(batch,) int64: the targets of every file -- with numTargets='auto' the count ``localize()`` found, else numTargets."""
+        if not self.autoTargets:
+            return np.full((self.batch,), self.g.S, dtype=np.int64)
+        return (self.tdoa_idx >= 0).sum(dim=1).cpu().numpy().astype(np.int64)
+
+    def get_count_status(self):
+        """(batch,) int32 (numTargets='auto' only): 0 = counted, 1 = no peak to count, 2 = more than maxTargets, the highest kept."""
+        if not self.autoTargets:
+            raise ValueError("get_count_status needs numTargets='auto'")
+        return self.status.cpu().numpy()
 
     def get_tdoa_tracks(self):
         """(batch, S, T) int32: the TDOA index of target i in frame t (tdoaTracking only)."""
@@ -907,11 +944,13 @@ class RaggedGCCNMFEngine(object):
     def __init__(self, lengths, sampleRate=16000, windowSize=1024, hopSize=256, numTDOAs=128, microphoneSeparationInMetres=1.0,
                  numTargets=3, dictionarySize=None, numIterations=100, sparsityAlpha=0, epsilon=1e-16, seedValue=0,
                  windowFunction=np.hanning, device='cuda:0', klnmf_flags=0, dictionaryW=None, initialH='random', reconstruction='direct',
-                 gccPHATNLEnabled=False, gccPHATNLAlpha=2.0, tdoaTracking=False, localizationWindowSize=None, tolerance=None, checkEvery=10):
+                 gccPHATNLEnabled=False, gccPHATNLAlpha=2.0, tdoaTracking=False, localizationWindowSize=None, tolerance=None, checkEvery=10,
+                 maxTargets=None):
         self.tolerance, self.checkEvery, numIterations = _hip.check_convergence(tolerance, checkEvery, numIterations)
-        self.reconstruction = check_reconstruction(reconstruction, numTargets)
+        self.autoTargets, slots = _hip.check_auto_targets(numTargets, maxTargets, tdoaTracking)
+        self.reconstruction = check_reconstruction(reconstruction, slots)
         self.gccPHATNLEnabled, self.gccPHATNLAlpha = check_gcc_phat_nl(gccPHATNLEnabled, gccPHATNLAlpha)
-        self.tdoaTracking, self.localizationWindowSize = check_tdoa_tracking(tdoaTracking, localizationWindowSize, numTargets)
+        self.tdoaTracking, self.localizationWindowSize = check_tdoa_tracking(tdoaTracking, localizationWindowSize, slots)
         if not torch.cuda.is_available():
             raise _hip.HipLibraryError('no ROCm device visible: the GCC-NMF HIP path has no CPU fallback')
         self.lib = _hip.lib()
@@ -928,7 +967,7 @@ class RaggedGCCNMFEngine(object):
                   windowFunction=windowFunction, device=device, klnmf_flags=klnmf_flags, dictionaryW=dictionaryW, initialH=initialH,
                   reconstruction=reconstruction, gccPHATNLEnabled=gccPHATNLEnabled, gccPHATNLAlpha=gccPHATNLAlpha,
                   tdoaTracking=tdoaTracking, localizationWindowSize=localizationWindowSize,     # (each file's windows end at its own T)
-                  tolerance=tolerance, checkEvery=checkEvery)
+                  tolerance=tolerance, checkEvery=checkEvery, maxTargets=maxTargets)
         # one ordinary engine per distinct length: its files (caller's indexes, ascending) are its batch
         self.files_of = {}
         for i, n in enumerate(self.lengths):
@@ -1026,6 +1065,10 @@ class RaggedGCCNMFEngine(object):
         """One (checks_i + 1,) float64 array per file, in the caller's order (the files of each length run, and are checked, as a batch
         of their own).  Needs a tolerance."""
         return self._per_file(dict((n, e.get_divergence_trace().T) for n, e in self.sub.items()))
+
+    def get_num_sources(self):
+        """(batch,) int64 in the caller's order: the targets of every file (numTargets='auto': the count found in it)."""
+        return np.array(self._per_file(dict((n, e.get_num_sources()) for n, e in self.sub.items())), dtype=np.int64)
 
     def get_tdoa_tracks(self):
         """One (S, T_i) int32 array per file, in the caller's order (tdoaTracking only)."""

@@ -303,10 +303,49 @@ def getAngularSpectrogram(spectralCoherenceV, frequenciesInHz, microphoneSeparat
     return out
 
 
+MAX_AUTO_SOURCES = _hip.MAX_AUTO_SOURCES      # the cap of numSources='auto'
+
+
+def _report_auto_sources(count, status, maxSources, where):
+    """What the named functions do with a count: status 1 is the reference's failure, status 2 is logged."""
+    if status == 1:
+        raise ValueError("didn't find enough peaks in %s" % where)
+    if status == 2:
+        logging.info('more than %d sources found, keeping the %d highest peaks' % (maxSources, maxSources))
+    logging.info('numSources not provided, found %d sources' % count)
+
+
+def estimateNumSourcesFromAngularSpectrum(angularSpectrum, maxSources=MAX_AUTO_SOURCES):
+    """How many sources a mean angular spectrum shows (the count mode of gccnmf_pick_tdoa_peaks, csrc/source_count.hip; DESIGN section
+    4f): the exact two-cluster k-means split of the heights of its strict local maxima, the upper cluster kept -- what the reference's
+    ``numSources=None`` branch declares with KMeans(n_clusters=2) (gccNMFFunctions.py:105-110).  Returns (count, indexes, status):
+    ``indexes`` the sorted list of the ``count`` kept peaks (np.int64), ``status`` 0, 1 (no peak, or heights without a finite sum:
+    count 0) or 2 (more than ``maxSources`` found: the highest ``maxSources`` kept)."""
+    _hip.check_auto_sources('auto', maxSources)
+    spectrum = np.ascontiguousarray(angularSpectrum, dtype=np.float64)
+    if spectrum.ndim != 1:
+        raise ValueError('angularSpectrum must be one-dimensional (the time mean), got shape %s' % (spectrum.shape,))
+    D, S = spectrum.shape[0], int(maxSources)
+    _, dev = _hip.lib(), _device()
+    with _staging.Scope(dev) as sc:
+        dM = sc.upload(spectrum, 'meanA')
+        res = sc.dev('counted', (S + 1,), torch.int32)                # [0..S): indexes, [S]: status
+        _hip.count_tdoa_peaks(dM, D, D, S, 1, res, res.data_ptr() + 4 * S)
+        out = sc.download(res)
+    indexes = sorted(np.int64(i) for i in out[:S] if i >= 0)
+    return len(indexes), indexes, int(out[S])
+
+
 def estimateTargetTDOAIndexesFromAngularSpectrum(angularSpectrum, microphoneSeparationInMetres, numTDOAs, numSources):
     """gccNMF/gccNMFFunctions.py:94-116: strict local maxima, top ``numSources`` by value, sorted
     ascending.  The reference's failure branches are NameErrors (:104 ``os``, :106 ``KMeans``);
-    here they raise ValueError."""
+    here they raise ValueError.  ``numSources='auto'``: what the :105-110 branch was meant to return -- the peaks of the upper of two
+    height clusters, MAX_AUTO_SOURCES at the most (estimateNumSourcesFromAngularSpectrum); None and 0 keep raising."""
+    if _hip.check_auto_sources(numSources, MAX_AUTO_SOURCES):
+        count, sourcePeakIndexes, status = estimateNumSourcesFromAngularSpectrum(angularSpectrum, MAX_AUTO_SOURCES)
+        _report_auto_sources(count, status, MAX_AUTO_SOURCES, 'estimateTargetTDOAIndexesFromAngularSpectrum')
+        logging.info('Found target TDOAs: %s' % str(sourcePeakIndexes))
+        return sourcePeakIndexes
     if not numSources:
         raise ValueError('numSources is required (the reference KMeans branch cannot run: gccNMFFunctions.py:106)')
     spectrum = np.ascontiguousarray(angularSpectrum, dtype=np.float64)
@@ -584,8 +623,12 @@ def getTargetTDOAEstimates(complexMixtureSpectrogram, sampleRate, microphoneSepa
     """Convenience wrapper over the reference's three-step TDOA estimation
     (runGCCNMF.py:44-47): coherence -> getAngularSpectrogram -> time mean ->
     estimateTargetTDOAIndexesFromAngularSpectrum.  Returns (targetTDOAIndexes, meanAngularSpectrum).
-    ``gccPHATNLEnabled`` / ``gccPHATNLAlpha``: as for getAngularSpectrogram (the peaks of the GCC-NONLIN spectrum)."""
+    ``gccPHATNLEnabled`` / ``gccPHATNLAlpha``: as for getAngularSpectrogram (the peaks of the GCC-NONLIN spectrum).
+    ``numSources='auto'``: the file's own count (estimateNumSourcesFromAngularSpectrum), MAX_AUTO_SOURCES at the most."""
     nl, alpha = _hip.check_gcc_phat_nl(gccPHATNLEnabled, gccPHATNLAlpha)
+    auto = _hip.check_auto_sources(numSources, MAX_AUTO_SOURCES)
+    if auto:
+        numSources = MAX_AUTO_SOURCES
     X = np.asarray(complexMixtureSpectrogram).astype(complex64)
     C, F, T = X.shape
     _, dev = _hip.lib(), _device()
@@ -601,6 +644,11 @@ def getTargetTDOAEstimates(complexMixtureSpectrogram, sampleRate, microphoneSepa
     status = torch.zeros((1,), dtype=torch.int32, device=dev)
     _hip.coherence(dX, F, T, 1, dC)
     _hip.angular_spectrogram(dC, trig, F, T, g.D, 1, ang, meanA, nl_alpha=alpha if nl else None)
+    if auto:
+        _hip.count_tdoa_peaks(meanA, g.D, g.Dp, g.S, 1, idx, status)
+        found = sorted(np.int64(i) for i in idx.cpu().numpy() if i >= 0)
+        _report_auto_sources(len(found), int(status.cpu()[0]), g.S, 'getTargetTDOAEstimates')
+        return found, meanA[:g.D].cpu().numpy()
     _hip.pick_tdoa_peaks(meanA, g.D, g.Dp, g.S, 1, idx, status)
     if int(status.cpu()[0]) != 0:
         raise ValueError("didn't find enough peaks in getTargetTDOAEstimates")

@@ -341,9 +341,27 @@ int gccnmf_angular_spectrogram(const float* CC, const float* trig, int F, int T,
  *   Target i of a frame is its i-th peak from the left, as in the whole-file form: two talkers whose directions cross swap outputs.
  *   L >= 2T - 1 makes every window the whole file (constant tracks).  Frames >= T are not written.  1 <= S <= 255, batch <= 65535.
  * Nothing above the low byte of S = the whole-file form: every call that existed before computes what it computed (S <= 255, the
- * score stage's limit).  GCCNMF_ERR_ARG: bits above the low byte without bit 8, L = 0, a negative S, and what the plain form rejects. */
+ * score stage's limit).  GCCNMF_ERR_ARG: bits above the low byte without bit 8, L = 0, a negative S, and what the plain form rejects.
+ *
+ * Counting the talkers (numSources = 'auto'; the reference declares it -- KMeans(n_clusters=2) on the peak heights, keep the upper
+ * cluster, gccNMFFunctions.py:105-110 -- and cannot run it) is a mode of this call too: pass GCCNMF_PEAKS_COUNT(Smax) as S -- bit 30
+ * alone above the low byte, 1 <= Smax <= 255; bit 30 belongs to L wherever bit 8 is set -- and every file keeps as many peaks as it
+ * has talkers, Smax at the most:
+ *     gccnmf_pick_tdoa_peaks(mean_ang, D, Dp, GCCNMF_PEAKS_COUNT(Smax), batch, tdoa_idx, status, stream)
+ *   The peaks are those of the plain form, P of them, ordered by height descending (the larger index first among equal heights).  With
+ *   c_j the sum of the j highest, added in that order, the count is the smallest j in [1, P) that maximises
+ *       b_j = c_j * c_j / j + (c_P - c_j) * (c_P - c_j) / (P - j)
+ *   -- the exact two-cluster k-means optimum of the heights (in one dimension a threshold on the sorted values), the upper cluster
+ *   kept -- every product, quotient and sum a float64 operation rounded on its own.  P = 1 counts 1.
+ *   tdoa_idx [batch][Smax] int32 out: the counted peaks in ascending index order, then -1 (what GCCNMF_SCORES_COUNTED reads)
+ *   status   [batch] int32 out: 0 = counted; 1 = no peak, or two or more whose heights have no finite sum (count 0, every index -1); 2 = more
+ *            than Smax counted, the Smax highest kept
+ *   mean_ang, D (3 to 4096), Dp >= D as in the plain form; one workgroup per file, a file's result depends on its own row only.
+ *   GCCNMF_ERR_ARG: Smax = 0, any other bit beside bit 30 above the low byte, and what the plain form rejects. */
 #define GCCNMF_PEAKS_TRACKS_BIT 0x100
 #define GCCNMF_PEAKS_TRACKS(S, L) ((S) | GCCNMF_PEAKS_TRACKS_BIT | ((L) << 9))
+#define GCCNMF_PEAKS_COUNT_BIT (1 << 30)
+#define GCCNMF_PEAKS_COUNT(Smax) ((Smax) | GCCNMF_PEAKS_COUNT_BIT)
 int gccnmf_pick_tdoa_peaks(const double* mean_ang, int D, int Dp, int S, int batch, int* tdoa_idx, int* status,
                            void* stream);
 
@@ -357,6 +375,12 @@ int gccnmf_pick_tdoa_peaks(const double* mean_ang, int D, int Dp, int S, int bat
  * any other bit there: GCCNMF_ERR_ARG) and tdoa_idx is [batch][S][Tp] int32, 16-byte aligned -- one index per (target, frame), as the
  * tracks mode of gccnmf_pick_tdoa_peaks writes them: G_i[k,t] = Re sum_f W[f,k] C[f,t] exp(-2j pi f tau_{i,t}).  Only the steering
  * table lookup in front of the GEMM changes (indexes are clamped to [0, D) as before); constant tracks give the bits of the plain form.
+ * Files with different numbers of targets: pass S | GCCNMF_SCORES_COUNTED (S = the most any file has; not together with
+ * GCCNMF_SCORES_TRACKS or the enhancement modes: GCCNMF_ERR_ARG) and tdoa_idx [batch][S] is read as the count mode of
+ * gccnmf_pick_tdoa_peaks writes it: an index >= 0 is a target as before (clamped to [0, D)), an index < 0 a target the file does not
+ * have.  The scores of an absent target are quiet NaN for every k < K, t < T (its steering column is NaN; padded positions are what
+ * they are for a present target), so the arg-max, which ignores NaN, never gives it an atom.  With every index non-negative the
+ * scores and the arg-max are bit for bit those of the plain form at the same S.
  *
  * Offline speech enhancement (one talker against noise: every atom of every frame goes to the talker or to the noise by the atom's OWN
  * TDOA, gccNMF/realtime/gccNMFProcessor.py:254,:259-265) is two further modes of this call, not entry points of their own
@@ -390,6 +414,7 @@ int gccnmf_pick_tdoa_peaks(const double* mean_ang, int D, int Dp, int S, int bat
 #define GCCNMF_SCORES_TRACKS 0x100
 #define GCCNMF_SCORES_ATOM_TDOA 0x200
 #define GCCNMF_SCORES_ENHANCEMENT_MASKS 0x400
+#define GCCNMF_SCORES_COUNTED 0x800
 #define GCCNMF_ATOM_TDOA_INDEXES(CC, trig, W, F, T, K, D, batch, atom_tdoa, atom_score, stream)                                          \
     gccnmf_target_scores_masks(CC, trig, 0, W, F, T, K, D, GCCNMF_SCORES_ATOM_TDOA, batch, 0, atom_score, (unsigned char*)(atom_tdoa), stream)
 #define GCCNMF_ENHANCEMENT_MASKS(atom_tdoa, target, per_frame, window, params, T, K, batch, image, masks, stream)                        \
