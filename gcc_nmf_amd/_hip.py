@@ -445,7 +445,7 @@ def target_scores_masks_counted(CC, trig, idx, W, F, T, K, D, S, batch, ws, scor
 GCCNMF_SCORES_ATOM_TDOA = 0x200         # include/gccnmf_hip.h: the full-grid atom TDOA arg-max, a mode of gccnmf_target_scores_masks
 GCCNMF_SCORES_ENHANCEMENT_MASKS = 0x400  # include/gccnmf_hip.h: talker / noise masks from the atom TDOA image, likewise
 ATOM_TDOA_MAX_D = 1024                  # csrc/atom_tdoa.h: the streaming limit
-TARGET_MODE_BOXCAR, TARGET_MODE_WINDOW_FUNCTION = 0, 2      # gccNMF/realtime/gccNMFProcessor.py:35,:37 (realtime.py exports the same)
+TARGET_MODE_BOXCAR, TARGET_MODE_MULTIPLE, TARGET_MODE_WINDOW_FUNCTION = 0, 1, 2      # gccNMF/realtime/gccNMFProcessor.py:35-37 (realtime.py exports the same)
 
 
 def atom_tdoa_indexes(CC, trig, W, F, T, K, D, batch, atom_tdoa, atom_score=None, stream=None):
@@ -539,3 +539,51 @@ def reconstruct(W, H, argmax, masks, X, V, F, T, K, S, batch, spec, mode='direct
     if mode != 'direct':
         S |= GCCNMF_RECONSTRUCT_RATIO
     _stage('gccnmf_reconstruct', W, H, argmax, masks, X, V, F, T, K, S, batch, None if mode == 'ratio' else workspace, spec, stream=stream)
+
+
+# frames_mode_bits of gccnmf_rt_process_block_ll (include/gccnmf_hip.h, csrc/rt.hip)
+RT_FRAMES, RT_SKIP_LOCALIZE, RT_ONLY_LOCALIZE = 1, 2, 4
+RT_BANK_LAYOUT, MAX_BANK_STREAMS = 1 << 3, 4096         # + (S - 1) << 8, bits 8..19
+RT_MULTI_LAYOUT, MAX_SOURCES = 1 << 20, 8               # + (N - 1) << 21, bits 21..23
+RT_ROW8_LAYOUT = 1 << 24                # single-stream call: the target row has 8 words, word 6 = gccPHATNLAlpha
+RT_LOCALIZE = {'with': 0, 'skip': RT_SKIP_LOCALIZE, 'only': RT_ONLY_LOCALIZE}
+
+
+def rt_mode_word(frames=False, localize='with', streams=None, targets=None, nl_row=False, target_mode=TARGET_MODE_MULTIPLE):
+    """frames_mode_bits for the keywords of ``rt_process_block``; ValueError for what the entry point rejects."""
+    if not isinstance(localize, str) or localize not in RT_LOCALIZE:
+        raise ValueError("localize must be 'with', 'skip' or 'only', got %r" % (localize,))
+    word = (RT_FRAMES if frames else 0) | RT_LOCALIZE[localize] | (RT_ROW8_LAYOUT if nl_row else 0)
+    if nl_row and (streams is not None or targets is not None):
+        raise ValueError('nl_row is the single-stream, single-target row: the bank and multi-target rows always have word 6')
+    if streams is not None:
+        if frames:
+            raise ValueError('a bank of streams has no frames mode')
+        if not 1 <= int(streams) <= MAX_BANK_STREAMS:
+            raise ValueError('a bank holds 1 to %d streams, got %r' % (MAX_BANK_STREAMS, streams))
+        word |= RT_BANK_LAYOUT | (int(streams) - 1) << 8
+    if targets is not None:
+        if int(target_mode) != TARGET_MODE_MULTIPLE:
+            raise ValueError('the multi-target layout needs TARGET_MODE_MULTIPLE, got target_mode %r' % (target_mode,))
+        if not 1 <= int(targets) <= MAX_SOURCES:
+            raise ValueError('the multi-target layout takes 1 to %d targets, got %r' % (MAX_SOURCES, targets))
+        word |= RT_MULTI_LAYOUT | (int(targets) - 1) << 21
+    return word
+
+
+def rt_process_block(block_in, block_out, in_ring, out_ring, X, Y, C, HMask, argmaxTDOA, tfMask, hist, hist_pos, target, gccphat, W, cosT,
+                     sinT, window, synthesis_window, twiddle, colsumW, Hcoef, Rv, windowSize, hopSize, blockSize, K, Kp, D, Dp, numTDOAHistory,
+                     target_mode, separation_enabled, localization_enabled, localization_window, numHUpdates=0, out_delay_blocks=2,
+                     frames=False, localize='with', streams=None, targets=None, nl_row=False, stream=None):
+    """One real-time block call (csrc/rt.hip); the buffers and geometry in the header's order, the modes as keywords.
+    frames: GCCNMFProcessor.processFrames on its own (in_ring / out_ring are the frames, no shift or overlap-add).
+    localize: 'with' the tracking update, 'skip' it, or 'only' it ('skip' then 'only' = the same work in two calls, so that a host can
+    fetch block_out before the tracking update has run).
+    streams = S: the buffers hold a bank of S streams (8-word target rows).  targets = N: the multi-target layout of
+    TARGET_MODE_MULTIPLE (16-word rows, N masks and outputs per stream).  nl_row: the single-stream target row has 8 words, word 6 =
+    gccPHATNLAlpha (the other two layouts always have it)."""
+    word = rt_mode_word(frames, localize, streams, targets, nl_row, target_mode)
+    _stage('gccnmf_rt_process_block_ll', block_in, block_out, in_ring, out_ring, X, Y, C, HMask, argmaxTDOA, tfMask, hist, hist_pos, target,
+           gccphat, W, cosT, sinT, window, synthesis_window, twiddle, colsumW, Hcoef, Rv, windowSize, hopSize, blockSize, K, Kp, D, Dp,
+           numTDOAHistory, int(target_mode), int(bool(separation_enabled)), int(bool(localization_enabled)), localization_window, word,
+           int(numHUpdates), int(out_delay_blocks), stream=stream)

@@ -24,8 +24,9 @@
 //
 // Multiple mode (frames_mode bit 20, TARGET_MODE_MULTIPLE): N <= 8 target TDOA indexes per stream (words 8.. of a 16-word row), one-hot
 // arg-max-over-targets masks from the scores rt_gccnmf already sums, N masked spectra, N synthesis rings (blockIdx.y), the N largest
-// gccPHAT peaks tracked.  Its kernels are new kernels or the `true` / 16-word instantiations of templates whose other instantiation is
-// the single-target kernel unchanged (LABBOOK R7.3).
+// gccPHAT peaks tracked.  Every one of its kernels is the `true` / 16-word / RT_MAX_TARGETS instantiation of a template whose other
+// instantiation is the single-target kernel (LABBOOK R7.3); the entry point picks between the two in one place
+// (RT_KERNEL).  Eleven kernels are launched from here.
 #include "fft_core.h"
 #include "angular_nl.h"
 
@@ -264,47 +265,21 @@ __global__ __launch_bounds__(64 * RT_G_WAVES) void rt_gccnmf_kernel(const float2
 }
 
 // ---- rt_tfmask: one wave per frequency row; grid = (ceil(F/4), 1, S) ------------------------------------------------------
-// (tfMask's per-stream image is [2][F][Tc] here too, the size the coefficient-inference mask needs)
+// MAXT = 1: the single-target layout (8-word rows; nt is not read).  tfMask's per-stream image is [2][F][Tc] here too, the size the
+// coefficient-inference mask needs.
+// MAXT = RT_MAX_TARGETS: the multi-target layout (frames_mode bit 20, 16-word rows): HMask [nt][Kp][Tc], Y and tfMask [nt][2][F][Tc] per
+// stream.  One pass over the row of W makes all nt numerators (the loads of W are shared); numerator i is summed in the denominator's
+// order (the lane-strided chain, the same shuffle tree), so with nt = 1 (HMask = 1) every quotient is 1.0 exactly.
+// No contraction in the body: every fused operation is an fmaf, every other one rounds on its own (what the build always produced here).
+template <int MAXT>
 __global__ __launch_bounds__(256) void rt_tfmask_kernel(const float* __restrict__ W, const float* __restrict__ HMask, int F, int K,
-                                                        int Kp, int Tc, const float2* __restrict__ X, float2* __restrict__ Y, float* __restrict__ tfMask,
-                                                        const float* __restrict__ rows) {
+                                                        int Kp, int Tc, const float2* __restrict__ X, float2* __restrict__ Y,
+                                                        float* __restrict__ tfMask, const float* __restrict__ rows, int nt) {
+#pragma clang fp contract(off)
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int f = blockIdx.x * 4 + wave;
-    if (f >= F || rt_switched_off(rows, 4)) return;
-    const long sid = blockIdx.z;
-    HMask += sid * Kp * Tc;
-    X += sid * 2 * F * Tc;
-    Y += sid * 2 * F * Tc;
-    tfMask += sid * 2 * F * Tc;
-    const float* Wr = W + (long)f * Kp;
-    float rec = 0.f;
-    for (int k = lane; k < K; k += 64) rec += Wr[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) rec += __shfl_xor(rec, o);
-    for (int t = 0; t < Tc; ++t) {
-        float s = 0.f;
-        for (int k = lane; k < K; k += 64) s = fmaf(Wr[k], HMask[(long)k * Tc + t], s);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-        if (lane == 0) {
-            const float m = s / rec;
-            tfMask[(long)f * Tc + t] = m;
-            const float2 a = X[(long)f * Tc + t], b = X[((long)F + f) * Tc + t];
-            Y[(long)f * Tc + t] = make_float2(m * a.x, m * a.y);
-            Y[((long)F + f) * Tc + t] = make_float2(m * b.x, m * b.y);
-        }
-    }
-}
-
-// ---- multi-target layout (frames_mode bit 20): HMask [N][Kp][Tc], Y and tfMask [N][2][F][Tc] per stream ------------------------
-// One pass over the row of W makes all N numerators (the loads of W are shared); numerator i is summed in the denominator's order (the
-// lane-strided chain, the same shuffle tree), so with N = 1 (HMask = 1) every quotient is 1.0 exactly.  grid = (ceil(F/4), 1, S)
-__global__ __launch_bounds__(256) void rt_tfmask_multi_kernel(const float* __restrict__ W, const float* __restrict__ HMask, int F, int K,
-                                                              int Kp, int Tc, const float2* __restrict__ X, float2* __restrict__ Y,
-                                                              float* __restrict__ tfMask, const float* __restrict__ rows, int nt) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int f = blockIdx.x * 4 + wave;
-    if (f >= F || rt_switched_off<RT_ROW_MULTI>(rows, 4)) return;
+    if (f >= F || rt_switched_off<MAXT == 1 ? RT_ROW : RT_ROW_MULTI>(rows, 4)) return;
+    if (MAXT == 1) nt = 1;
     const long sid = blockIdx.z;
     const long hplane = (long)Kp * Tc, yplane = 2L * F * Tc;
     HMask += sid * nt * hplane;
@@ -317,17 +292,17 @@ __global__ __launch_bounds__(256) void rt_tfmask_multi_kernel(const float* __res
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) rec += __shfl_xor(rec, o);
     for (int t = 0; t < Tc; ++t) {
-        float s[RT_MAX_TARGETS];
+        float s[MAXT];
 #pragma unroll
-        for (int i = 0; i < RT_MAX_TARGETS; ++i) s[i] = 0.f;
+        for (int i = 0; i < MAXT; ++i) s[i] = 0.f;
         for (int k = lane; k < K; k += 64) {
             const float w = Wr[k];
 #pragma unroll
-            for (int i = 0; i < RT_MAX_TARGETS; ++i)
+            for (int i = 0; i < MAXT; ++i)
                 if (i < nt) s[i] = fmaf(w, HMask[i * hplane + (long)k * Tc + t], s[i]);
         }
 #pragma unroll
-        for (int i = 0; i < RT_MAX_TARGETS; ++i) {
+        for (int i = 0; i < MAXT; ++i) {
             if (i < nt) {
 #pragma unroll
                 for (int o = 32; o > 0; o >>= 1) s[i] += __shfl_xor(s[i], o);
@@ -336,7 +311,7 @@ __global__ __launch_bounds__(256) void rt_tfmask_multi_kernel(const float* __res
         if (lane == 0) {
             const float2 a = X[(long)f * Tc + t], b = X[((long)F + f) * Tc + t];
 #pragma unroll
-            for (int i = 0; i < RT_MAX_TARGETS; ++i) {
+            for (int i = 0; i < MAXT; ++i) {
                 if (i < nt) {
                     const float m = s[i] / rec;
                     tfMask[i * yplane + (long)f * Tc + t] = m;
@@ -763,64 +738,23 @@ __global__ __launch_bounds__(256) void rt_hupdate_kernel(const float* __restrict
     }
 }
 
-// per-channel mask with inferred coefficients: m_c[f][t] = sum_k W h_c HMask / sum_k W h_c;  Y_c = m_c X_c;  tfMask [2][F][Tc];
-// grid = (ceil(F/4), 1, S)
+// per-channel mask with inferred coefficients: m_{i,c}[f][t] = sum_k W h_c M_i / sum_k W h_c;  Y_{i,c} = m_{i,c} X_c;  layouts and MAXT as
+// rt_tfmask (single-target tfMask [2][F][Tc]); all nt targets in one pass over the row of W (and h); grid = (ceil(F/4), 1, S).
+// No contraction in the body, and the two denominators are stated apart:
+//   MAXT = 1: d = fmaf(w, h, d), the numerator fmaf(round(w * h), hm, n).  That is what the compiler's default contraction has always made
+//   of `d += w * h` in this kernel -- the hot one of the streaming configuration with numHUpdates > 0 -- so the rounding is written down
+//   here, where a compiler update cannot change the bits.
+//   multi-target: d += round(w * h), as the numerators' fmaf(round(w * h), 1, .) add it, so nt = 1 gives 1.0 exactly.
+template <int MAXT>
 __global__ __launch_bounds__(256) void rt_tfmask_h_kernel(const float* __restrict__ W, const float* __restrict__ HMask,
                                                           const float* __restrict__ Hc, int F, int K, int Kp, int Tc,
                                                           const float2* __restrict__ X, float2* __restrict__ Y, float* __restrict__ tfMask,
-                                                          const float* __restrict__ rows) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int f = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
-    if (f >= F || rt_switched_off(rows, 4)) return;
-    const int ncol = 2 * Tc;
-    const long sid = blockIdx.z;
-    HMask += sid * Kp * Tc;
-    Hc += sid * Kp * ncol;
-    X += sid * 2 * F * Tc;
-    Y += sid * 2 * F * Tc;
-    tfMask += sid * 2 * F * Tc;
-    const float* Wr = W + (long)f * Kp;
-    for (int t = 0; t < Tc; ++t) {                         // both channels of a frame in one pass over the row of W
-        float n0 = 0.f, d0 = 0.f, n1 = 0.f, d1 = 0.f;
-#pragma unroll 4
-        for (int k = lane; k < K; k += 64) {
-            const float w = Wr[k], hm = HMask[(long)k * Tc + t];
-            const float2 h = *(const float2*)(Hc + (long)k * ncol + 2 * t);
-            const float wh0 = w * h.x, wh1 = w * h.y;
-            d0 += wh0;
-            d1 += wh1;
-            n0 = fmaf(wh0, hm, n0);
-            n1 = fmaf(wh1, hm, n1);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            n0 += __shfl_xor(n0, o);
-            d0 += __shfl_xor(d0, o);
-            n1 += __shfl_xor(n1, o);
-            d1 += __shfl_xor(d1, o);
-        }
-        if (lane == 0) {
-            const float m0 = d0 == 0.f ? 0.f : n0 / d0, m1 = d1 == 0.f ? 0.f : n1 / d1;      // no coefficients (a silent channel): mask 0, Y = 0
-            tfMask[(long)f * Tc + t] = m0;
-            tfMask[((long)F + f) * Tc + t] = m1;
-            const float2 a = X[(long)f * Tc + t], b = X[((long)F + f) * Tc + t];
-            Y[(long)f * Tc + t] = make_float2(m0 * a.x, m0 * a.y);
-            Y[((long)F + f) * Tc + t] = make_float2(m1 * b.x, m1 * b.y);
-        }
-    }
-}
-
-// multi-target layout: m_{i,c} = sum_k W h_c M_i / sum_k W h_c for all N targets in one pass over the row of W (and h); numerator i
-// in the denominator's order, so N = 1 gives 1.0 exactly (no contraction here: the denominator adds the rounded products w * h as the
-// numerators' fmaf(w * h, 1, .) do).  HMask [N][Kp][Tc], Y and tfMask [N][2][F][Tc] per stream; grid = (ceil(F/4), 1, S)
-__global__ __launch_bounds__(256) void rt_tfmask_h_multi_kernel(const float* __restrict__ W, const float* __restrict__ HMask,
-                                                                const float* __restrict__ Hc, int F, int K, int Kp, int Tc,
-                                                                const float2* __restrict__ X, float2* __restrict__ Y,
-                                                                float* __restrict__ tfMask, const float* __restrict__ rows, int nt) {
+                                                          const float* __restrict__ rows, int nt) {
 #pragma clang fp contract(off)
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int f = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
-    if (f >= F || rt_switched_off<RT_ROW_MULTI>(rows, 4)) return;
+    if (f >= F || rt_switched_off<MAXT == 1 ? RT_ROW : RT_ROW_MULTI>(rows, 4)) return;
+    if (MAXT == 1) nt = 1;
     const int ncol = 2 * Tc;
     const long sid = blockIdx.z;
     const long hplane = (long)Kp * Tc, yplane = 2L * F * Tc;
@@ -831,17 +765,23 @@ __global__ __launch_bounds__(256) void rt_tfmask_h_multi_kernel(const float* __r
     tfMask += sid * nt * yplane;
     const float* Wr = W + (long)f * Kp;
     for (int t = 0; t < Tc; ++t) {                         // both channels of a frame in one pass over the row of W
-        float d0 = 0.f, d1 = 0.f, n0[RT_MAX_TARGETS], n1[RT_MAX_TARGETS];
+        float d0 = 0.f, d1 = 0.f, n0[MAXT], n1[MAXT];
 #pragma unroll
-        for (int i = 0; i < RT_MAX_TARGETS; ++i) n0[i] = n1[i] = 0.f;
+        for (int i = 0; i < MAXT; ++i) n0[i] = n1[i] = 0.f;
+#pragma unroll MAXT == 1 ? 4 : 1                           // as the two kernels this template replaces were built
         for (int k = lane; k < K; k += 64) {
             const float w = Wr[k];
             const float2 h = *(const float2*)(Hc + (long)k * ncol + 2 * t);
             const float wh0 = w * h.x, wh1 = w * h.y;
-            d0 += wh0;
-            d1 += wh1;
+            if (MAXT == 1) {
+                d0 = fmaf(w, h.x, d0);
+                d1 = fmaf(w, h.y, d1);
+            } else {
+                d0 += wh0;
+                d1 += wh1;
+            }
 #pragma unroll
-            for (int i = 0; i < RT_MAX_TARGETS; ++i) {
+            for (int i = 0; i < MAXT; ++i) {
                 if (i < nt) {
                     const float hm = HMask[i * hplane + (long)k * Tc + t];
                     n0[i] = fmaf(wh0, hm, n0[i]);
@@ -855,7 +795,7 @@ __global__ __launch_bounds__(256) void rt_tfmask_h_multi_kernel(const float* __r
             d1 += __shfl_xor(d1, o);
         }
 #pragma unroll
-        for (int i = 0; i < RT_MAX_TARGETS; ++i) {
+        for (int i = 0; i < MAXT; ++i) {
             if (i < nt) {
 #pragma unroll
                 for (int o = 32; o > 0; o >>= 1) {
@@ -867,9 +807,10 @@ __global__ __launch_bounds__(256) void rt_tfmask_h_multi_kernel(const float* __r
         if (lane == 0) {
             const float2 a = X[(long)f * Tc + t], b = X[((long)F + f) * Tc + t];
 #pragma unroll
-            for (int i = 0; i < RT_MAX_TARGETS; ++i) {
+            for (int i = 0; i < MAXT; ++i) {
                 if (i < nt) {
-                    const float m0 = d0 == 0.f ? 0.f : n0[i] / d0, m1 = d1 == 0.f ? 0.f : n1[i] / d1;      // (as rt_tfmask_h)
+                    // no coefficients (a silent channel): mask 0, Y = 0
+                    const float m0 = d0 == 0.f ? 0.f : n0[i] / d0, m1 = d1 == 0.f ? 0.f : n1[i] / d1;
                     tfMask[i * yplane + (long)f * Tc + t] = m0;
                     tfMask[i * yplane + ((long)F + f) * Tc + t] = m1;
                     Y[i * yplane + (long)f * Tc + t] = make_float2(m0 * a.x, m0 * a.y);
@@ -879,6 +820,10 @@ __global__ __launch_bounds__(256) void rt_tfmask_h_multi_kernel(const float* __r
         }
     }
 }
+
+// The instantiation of a kernel template that goes with the call's layout: (single-target, multi-target) template arguments, picked by the
+// entry point's `multi`.  Every launch of a templated kernel below goes through it.
+#define RT_KERNEL(kernel, single, multiple) (multi ? kernel<multiple> : kernel<single>)
 
 extern "C" {
 
@@ -934,13 +879,10 @@ int gccnmf_rt_process_block_ll(const float* block_in, float* block_out, float* i
     const size_t lds = sizeof(float2) * (windowSize + windowSize / 2);
     int Dq = 64;
     while (Dq < D) Dq *= 2;                 // power of two so that 1024 % Dq == 0
+    // NT = 1 and grid y = 1 outside the multi-target layout (checked above), nl_row = 1 inside it: one argument list serves both layouts
     auto localize = [&]() {
-        if (multi)
-            hipLaunchKernelGGL(rt_localize_kernel<true>, dim3(1, 1, S), dim3(1024), 0, s, (const float2*)C, cosT, sinT, F, D, Dp, Dq, Tc, hist,
-                               numTDOAHistory, hist_pos, localization_enabled, localization_window, target, gccphat, bank, NT, 1);
-        else
-            hipLaunchKernelGGL(rt_localize_kernel<false>, dim3(1, 1, S), dim3(1024), 0, s, (const float2*)C, cosT, sinT, F, D, Dp, Dq, Tc, hist,
-                               numTDOAHistory, hist_pos, localization_enabled, localization_window, target, gccphat, bank, 1, nl_row);
+        hipLaunchKernelGGL(RT_KERNEL(rt_localize_kernel, false, true), dim3(1, 1, S), dim3(1024), 0, s, (const float2*)C, cosT, sinT, F, D, Dp,
+                           Dq, Tc, hist, numTDOAHistory, hist_pos, localization_enabled, localization_window, target, gccphat, bank, NT, nl_row);
     };
     if (only_localize) {
         localize();
@@ -948,18 +890,16 @@ int gccnmf_rt_process_block_ll(const float* block_in, float* block_out, float* i
         return GCCNMF_OK;
     }
     if (!frames_mode) {
-        if (multi)
-            hipLaunchKernelGGL(rt_shift_kernel<true>, dim3(1, NT, S), dim3(1024), 0, s, in_ring, out_ring, block_in, blockSize, ring);
-        else
-            hipLaunchKernelGGL(rt_shift_kernel<false>, dim3(1, 1, S), dim3(1024), 0, s, in_ring, out_ring, block_in, blockSize, ring);
+        hipLaunchKernelGGL(RT_KERNEL(rt_shift_kernel, false, true), dim3(1, NT, S), dim3(1024), 0, s, in_ring, out_ring, block_in, blockSize,
+                           ring);
         GCCNMF_CHECK_LAUNCH();
     }
     const size_t lds_dft = sizeof(float2) * (2 * windowSize + 2);
     if (!pow2 && lds_dft + 4096 > 64 * 1024) {
         // windows above ~3800 samples: the table + frame image (+ the analysis kernel's 4 KB of static LDS) pass the 64 KB a launch gets by default
         if (hipFuncSetAttribute((const void*)rt_frames_dft_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dft) != hipSuccess ||
-            hipFuncSetAttribute((const void*)(multi ? rt_synth_dft_kernel<true> : rt_synth_dft_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_dft) != hipSuccess)
+            hipFuncSetAttribute((const void*)RT_KERNEL(rt_synth_dft_kernel, false, true), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds_dft) != hipSuccess)
             return GCCNMF_ERR_LAUNCH;
     }
     if (pow2) {
@@ -971,44 +911,30 @@ int gccnmf_rt_process_block_ll(const float* block_in, float* block_out, float* i
     }
     GCCNMF_CHECK_LAUNCH();
     if (separation_enabled) {
-        if (multi)
-            hipLaunchKernelGGL(rt_gccnmf_kernel<true>, dim3(Kp / 32, Tc, S), dim3(64 * RT_G_WAVES), 0, s, (const float2*)C, cosT, sinT, W, F, K,
-                               Kp, D, Dp, Tc, target, target_mode, bank, HMask, argmaxTDOA, NT);
-        else
-            hipLaunchKernelGGL(rt_gccnmf_kernel<false>, dim3(Kp / 32, Tc, S), dim3(64 * RT_G_WAVES), 0, s, (const float2*)C, cosT, sinT, W, F, K,
-                               Kp, D, Dp, Tc, target, target_mode, bank, HMask, argmaxTDOA, 1);
+        hipLaunchKernelGGL(RT_KERNEL(rt_gccnmf_kernel, false, true), dim3(Kp / 32, Tc, S), dim3(64 * RT_G_WAVES), 0, s, (const float2*)C, cosT,
+                           sinT, W, F, K, Kp, D, Dp, Tc, target, target_mode, bank, HMask, argmaxTDOA, NT);
         GCCNMF_CHECK_LAUNCH();
         if (numHUpdates == 0) {
-            if (multi)
-                hipLaunchKernelGGL(rt_tfmask_multi_kernel, dim3(gccnmf_ceil_div(F, 4), 1, S), dim3(256), 0, s, W, HMask, F, K, Kp, Tc,
-                                   (const float2*)X, (float2*)Y, tfMask, rows, NT);
-            else
-                hipLaunchKernelGGL(rt_tfmask_kernel, dim3(gccnmf_ceil_div(F, 4), 1, S), dim3(256), 0, s, W, HMask, F, K, Kp, Tc, (const float2*)X,
-                                   (float2*)Y, tfMask, rows);
+            hipLaunchKernelGGL(RT_KERNEL(rt_tfmask_kernel, 1, RT_MAX_TARGETS), dim3(gccnmf_ceil_div(F, 4), 1, S), dim3(256), 0, s, W, HMask, F, K,
+                               Kp, Tc, (const float2*)X, (float2*)Y, tfMask, rows, NT);
             GCCNMF_CHECK_LAUNCH();
         } else {
             // the coefficient updates do not depend on the targets: the same kernels, reading the switches at the layout's row stride
-            auto wh = multi ? rt_wh_kernel<RT_ROW_MULTI> : rt_wh_kernel<RT_ROW>;
-            auto hupdate = multi ? rt_hupdate_kernel<RT_ROW_MULTI> : rt_hupdate_kernel<RT_ROW>;
             for (int it = 0; it < numHUpdates; ++it) {      // h0 = 1 is implicit in the first update (no fill pass)
-                hipLaunchKernelGGL(wh, dim3(gccnmf_ceil_div(F, 4), 1, S), dim3(256), 0, s, W, Hcoef, (const float2*)X, Rv, F, K, Kp,
-                                   Tc, it == 0 ? 1 : 0, rows);
+                hipLaunchKernelGGL(RT_KERNEL(rt_wh_kernel, RT_ROW, RT_ROW_MULTI), dim3(gccnmf_ceil_div(F, 4), 1, S), dim3(256), 0, s, W, Hcoef,
+                                   (const float2*)X, Rv, F, K, Kp, Tc, it == 0 ? 1 : 0, rows);
                 GCCNMF_CHECK_LAUNCH();
-                hipLaunchKernelGGL(hupdate, dim3(Kp / 16, 1, S), dim3(256), 0, s, W, Rv, colsumW, Hcoef, F, K, Kp, Tc, it == 0 ? 1 : 0,
-                                   rows);
+                hipLaunchKernelGGL(RT_KERNEL(rt_hupdate_kernel, RT_ROW, RT_ROW_MULTI), dim3(Kp / 16, 1, S), dim3(256), 0, s, W, Rv, colsumW,
+                                   Hcoef, F, K, Kp, Tc, it == 0 ? 1 : 0, rows);
                 GCCNMF_CHECK_LAUNCH();
             }
-            if (multi)
-                hipLaunchKernelGGL(rt_tfmask_h_multi_kernel, dim3(gccnmf_ceil_div(F, 4), 1, S), dim3(256), 0, s, W, HMask, Hcoef, F, K, Kp, Tc,
-                                   (const float2*)X, (float2*)Y, tfMask, rows, NT);
-            else
-                hipLaunchKernelGGL(rt_tfmask_h_kernel, dim3(gccnmf_ceil_div(F, 4), 1, S), dim3(256), 0, s, W, HMask, Hcoef, F, K, Kp, Tc,
-                                   (const float2*)X, (float2*)Y, tfMask, rows);
+            hipLaunchKernelGGL(RT_KERNEL(rt_tfmask_h_kernel, 1, RT_MAX_TARGETS), dim3(gccnmf_ceil_div(F, 4), 1, S), dim3(256), 0, s, W, HMask,
+                               Hcoef, F, K, Kp, Tc, (const float2*)X, (float2*)Y, tfMask, rows, NT);
             GCCNMF_CHECK_LAUNCH();
         }
     }
     if (pow2) {
-        hipLaunchKernelGGL(multi ? rt_synth_kernel<true> : rt_synth_kernel<false>, dim3(1, multi ? NT : 1, S), dim3(FFT_NT), lds, s,
+        hipLaunchKernelGGL(RT_KERNEL(rt_synth_kernel, false, true), dim3(1, NT, S), dim3(FFT_NT), lds, s,
                            (const float2*)(separation_enabled ? Y : X), windowSize, logN,
                            start0, start_step, frames_mode ? 0 : 1, Tc, ring, blockSize, out_delay_blocks, synthesis_window,
                            (const float2*)twiddle, out_ring, block_out, (const float2*)X, rows);
@@ -1016,8 +942,7 @@ int gccnmf_rt_process_block_ll(const float* block_in, float* block_out, float* i
         // positions that receive a frame this call, plus the block handed out (it may lie in front of them)
         const int h0 = ring - (out_delay_blocks + 1) * blockSize;
         const int s_lo = frames_mode ? 0 : (start0 < h0 ? start0 : (h0 > 0 ? h0 : 0));
-        hipLaunchKernelGGL(multi ? rt_synth_dft_kernel<true> : rt_synth_dft_kernel<false>, dim3(gccnmf_ceil_div(ring - s_lo, 256), multi ? NT : 1, S),
-                           dim3(256), lds_dft, s,
+        hipLaunchKernelGGL(RT_KERNEL(rt_synth_dft_kernel, false, true), dim3(gccnmf_ceil_div(ring - s_lo, 256), NT, S), dim3(256), lds_dft, s,
                            (const float2*)(separation_enabled ? Y : X), windowSize, start0, start_step, frames_mode ? 0 : 1, Tc, ring, blockSize,
                            out_delay_blocks, s_lo, synthesis_window, (const float2*)twiddle, out_ring, block_out, (const float2*)X, rows);
     }

@@ -7,7 +7,7 @@
 block-in / block-out path (input ring, frames, mask, synthesis, overlap-add and TDOA tracking all on device).
 ``StreamingGCCNMFBank`` runs S such streams of one configuration in the same device call per block, each bit for bit a
 ``StreamingGCCNMF`` of its own.
-``targetMode = TARGET_MODE_MULTIPLE`` separates ``numSources`` talkers per stream instead of enhancing one (frames_mode bit 20): one-hot
+``targetMode = TARGET_MODE_MULTIPLE`` separates ``numSources`` talkers per stream instead of enhancing one (the ``targets`` layout of ``_hip.rt_process_block``): one-hot
 arg-max-over-targets coefficient masks, one output per target, the N largest peaks of the gccPHAT window mean tracked online.
 No CPU fallback: without the library / a device the constructor raises ``HipLibraryError``.
 """
@@ -15,15 +15,13 @@ import numpy as np
 import torch
 
 from . import _hip
-from .engine import padded, fft_twiddles, _ptr, _stream, _on_device
+from ._hip import MAX_SOURCES, MAX_BANK_STREAMS           # noqa: F401  (the limits of the block call's layouts, public here)
+from .engine import padded, fft_twiddles, _on_device
 
 SPEED_OF_SOUND_IN_METRES_PER_SECOND = 340.29
 TARGET_MODE_BOXCAR = 0                   # gccNMFProcessor.py:35-37
 TARGET_MODE_MULTIPLE = 1
 TARGET_MODE_WINDOW_FUNCTION = 2
-MAX_SOURCES = 8                          # frames_mode bits 21..23 (csrc/rt.hip)
-_MULTI_LAYOUT = 1 << 20
-_ROW8_LAYOUT = 1 << 24                   # single-stream call: the target row has 8 words, word 6 = gccPHATNLAlpha (csrc/rt.hip)
 
 
 def asymmetricWindows(windowSize, synthesisSize):
@@ -226,8 +224,17 @@ class GCCNMFProcessor(object):
             self._target_value, self._target_dirty = float(self._target_pin[0]), False
         return self._target_value
 
+    def _tables(self):
+        """The read-only pointer arguments of the block call, in its order: W .. colsumW."""
+        return self.dW, self.dCos, self.dSin, self.dWindow, self.dSynthWindow, self.dTwiddle, self.dColsum
+
+    def _settings(self, hop, block):
+        """The integer arguments of the block call in front of its mode word, in its order: windowSize .. localization_window."""
+        return (self.windowSize, hop, block, self.numAtom, self.Kp, self.numTDOAs, self.Dp, self.numTDOAHistory, self.targetMode,
+                self.separationEnabled, self.localizationEnabled, self.localizationWindowSize)
+
     @_on_device
-    def _call(self, block_in, block_out, in_ring, out_ring, hop, block, frames_mode, out_delay_blocks=2):
+    def _call(self, block_in, block_out, in_ring, out_ring, hop, block, out_delay_blocks=2, frames=False, localize='with'):
         """out_ring / block_out: [N][2][...] in multiple mode."""
         self._calls += 1
         multi = self.multiple()
@@ -236,19 +243,12 @@ class GCCNMFProcessor(object):
                 self._indexes_dirty = True
             else:
                 self._target_dirty = True
-        if multi:
-            frames_mode |= _MULTI_LAYOUT | ((self._sources - 1) << 21)
-        elif self._nl_word > 0:             # the multi-target row always has word 6; the single-target call is told that its row does
-            frames_mode |= _ROW8_LAYOUT
         Y, HMask, tfMask = (self.dYm, self.dHMaskm, self.dTfMaskm) if multi else (self.dY, self.dHMask, self.dTfMask)
-        _hip.check(self.lib.gccnmf_rt_process_block_ll(
-            _ptr(block_in), _ptr(block_out), _ptr(in_ring), _ptr(out_ring), _ptr(self.dX), _ptr(Y), _ptr(self.dC), _ptr(HMask),
-            _ptr(self.dArgmax), _ptr(tfMask), _ptr(self.dHist), _ptr(self.dHistPos), _ptr(self.dTarget), _ptr(self.dGccPhat),
-            _ptr(self.dW), _ptr(self.dCos), _ptr(self.dSin), _ptr(self.dWindow), _ptr(self.dSynthWindow), _ptr(self.dTwiddle),
-            _ptr(self.dColsum), _ptr(self.dHcoef), _ptr(self.dRv), self.windowSize, hop, block,
-            self.numAtom, self.Kp, self.numTDOAs, self.Dp, self.numTDOAHistory, int(self.targetMode), int(bool(self.separationEnabled)),
-            int(bool(self.localizationEnabled)), self.localizationWindowSize, frames_mode, int(self.numHUpdates), int(out_delay_blocks),
-            _stream()), 'gccnmf_rt_process_block_ll')
+        # the multi-target row always has word 6; the single-target call is told when its row does
+        _hip.rt_process_block(block_in, block_out, in_ring, out_ring, self.dX, Y, self.dC, HMask, self.dArgmax, tfMask, self.dHist,
+                              self.dHistPos, self.dTarget, self.dGccPhat, *self._tables(), self.dHcoef, self.dRv,
+                              *self._settings(hop, block), self.numHUpdates, out_delay_blocks, frames=frames, localize=localize,
+                              targets=self._sources if multi else None, nl_row=not multi and self._nl_word > 0)
 
     @_on_device
     def processFrames(self, windowedSamples):
@@ -261,10 +261,10 @@ class GCCNMFProcessor(object):
         self.dFramesIn.copy_(torch.from_numpy(np.ascontiguousarray(ws.transpose(0, 2, 1))))
         # hop = windowSize, block = Tc * windowSize describes Tc back-to-back frames to the kernels' start0/step arithmetic
         if self.multiple():
-            self._call(None, None, self.dFramesIn, self.dFramesOutM, self.windowSize, Tc * self.windowSize, 1)
+            self._call(None, None, self.dFramesIn, self.dFramesOutM, self.windowSize, Tc * self.windowSize, frames=True)
             out = self.dFramesOutM.cpu().numpy().transpose(0, 1, 3, 2)
         else:
-            self._call(None, None, self.dFramesIn, self.dFramesOut, self.windowSize, Tc * self.windowSize, 1)
+            self._call(None, None, self.dFramesIn, self.dFramesOut, self.windowSize, Tc * self.windowSize, frames=True)
             out = self.dFramesOut.cpu().numpy().transpose(0, 2, 1)
         self.fill_histories()
         return out
@@ -292,23 +292,16 @@ class GCCNMFProcessor(object):
         F, Tc, K, D = self.numFrequencies, self.numTimePerChunk, self.numAtom, self.numTDOAs
         cplx = lambda i: m[o[i]:o[i] + n[i]].reshape(2, F, Tc, 2).copy().view(np.complex64)[..., 0]
         X = cplx(0)
-        if multi:                   # N masks and outputs: no output-spectrogram or coefficient-mask mirror in this mode
-            if self.inputSpectrogramHistory is not None:
-                self.inputSpectrogramHistory.set(-np.mean(np.abs(X), axis=0) ** (1 / 3.0))
-            if self.gccPHATHistory is not None:
-                self.gccPHATHistory.set(m[o[3]:o[3] + n[3]].reshape(D, Tc).copy())
-            if self.tdoaHistory is not None:
-                self.tdoaHistory.set(self._indexes_host.reshape(N, 1).copy())
-            return
-        if self.separationEnabled and self.coefficientMaskHistories:
+        # multiple mode has N masks and outputs: no coefficient-mask or output-spectrogram mirror there
+        if not multi and self.separationEnabled and self.coefficientMaskHistories:
             self.coefficientMaskHistories[self.dictionarySize].set(1 - m[o[2]:o[2] + n[2]].reshape(self.Kp, Tc)[:K])          # :211-212
         if self.inputSpectrogramHistory is not None:
             self.inputSpectrogramHistory.set(-np.mean(np.abs(X), axis=0) ** (1 / 3.0))                                      # :216-217
         if self.gccPHATHistory is not None:
             self.gccPHATHistory.set(m[o[3]:o[3] + n[3]].reshape(D, Tc).copy())                                                 # :218-219
-        if self.tdoaHistory is not None:
-            self.tdoaHistory.set(np.array([[np.float32(m[o[4]])]]))                                                            # :220-227
-        if self.outputSpectrogramHistory is not None:
+        if self.tdoaHistory is not None:                                                                                       # :220-227
+            self.tdoaHistory.set(self._indexes_host.reshape(N, 1).copy() if multi else np.array([[np.float32(m[o[4]])]]))
+        if not multi and self.outputSpectrogramHistory is not None:
             Y = cplx(1) if self.separationEnabled else X                                                                      # :213-214
             with np.errstate(invalid='ignore'):
                 self.outputSpectrogramHistory.set(-np.nanmean(np.abs(Y), axis=0) ** (1 / 3.0))                                # :228-229
@@ -316,19 +309,16 @@ class GCCNMFProcessor(object):
     # ---- device results of the last call, in the reference's shapes --------------------------------------------------
     @_on_device
     def intermediates(self):
-        F, K, D = self.numFrequencies, self.numAtom, self.numTDOAs
+        F, K, Tc = self.numFrequencies, self.numAtom, self.numTimePerChunk
         if self.multiple():         # HMask (N, K, Tc) one-hot; tfMask (N, F, Tc) without coefficient inference, (N, 2, F, Tc) with
-            return dict(X=torch.view_as_complex(self.dX).cpu().numpy(), C=torch.view_as_complex(self.dC).cpu().numpy(),
-                        Y=torch.view_as_complex(self.dYm).cpu().numpy(), HMask=self.dHMaskm[:, :K].cpu().numpy(),
-                        argmaxTDOA=self.dArgmax[:K].cpu().numpy(),
-                        tfMask=self.dTfMaskm.cpu().numpy() if self.numHUpdates else self.dTfMaskm[:, 0].cpu().numpy(),
-                        Hcoef=self.dHcoef[:K].permute(2, 0, 1).contiguous().cpu().numpy(),
-                        gccPHAT=self.dGccPhat.cpu().numpy(), targetTDOAIndexes=self.targetTDOAIndexes)
-        return dict(X=torch.view_as_complex(self.dX).cpu().numpy(), C=torch.view_as_complex(self.dC).cpu().numpy(),
-                    HMask=self.dHMask[:K].cpu().numpy(), argmaxTDOA=self.dArgmax[:K].cpu().numpy(),
-                    tfMask=(self.dTfMask.cpu().numpy() if self.numHUpdates else self.dTfMask.view(-1)[:F * self.numTimePerChunk].view(F, -1).cpu().numpy()),
-                    Hcoef=self.dHcoef[:K].permute(2, 0, 1).contiguous().cpu().numpy(),
-                    gccPHAT=self.dGccPhat.cpu().numpy(), targetTDOAIndex=self.targetTDOAIndex)
+            HMask, tfMask = self.dHMaskm[:, :K], self.dTfMaskm if self.numHUpdates else self.dTfMaskm[:, 0]
+            own = dict(Y=torch.view_as_complex(self.dYm).cpu().numpy(), targetTDOAIndexes=self.targetTDOAIndexes)
+        else:                       # HMask (K, Tc); tfMask (F, Tc) without coefficient inference, (2, F, Tc) with
+            HMask, tfMask = self.dHMask[:K], self.dTfMask if self.numHUpdates else self.dTfMask.view(-1)[:F * Tc].view(F, -1)
+            own = dict(targetTDOAIndex=self.targetTDOAIndex)
+        return dict(own, X=torch.view_as_complex(self.dX).cpu().numpy(), C=torch.view_as_complex(self.dC).cpu().numpy(),
+                    HMask=HMask.cpu().numpy(), argmaxTDOA=self.dArgmax[:K].cpu().numpy(), tfMask=tfMask.cpu().numpy(),
+                    Hcoef=self.dHcoef[:K].permute(2, 0, 1).contiguous().cpu().numpy(), gccPHAT=self.dGccPhat.cpu().numpy())
 
 
 def _check_num_sources(n):
@@ -379,18 +369,109 @@ def _check_stream_shape(processor, hopSize, blockSize, outputDelayBlocks):
     return outputDelayBlocks
 
 
-class StreamingGCCNMF(object):
+class _BlockDriver(object):
+    """The host side that ``StreamingGCCNMF`` and ``StreamingGCCNMFBank`` share: page-locked blocks in and out, the block call split in
+    two so that the finished block is fetched before the tracking update runs, its fixed front captured once into a HIP graph, and the
+    whole-signal loop.  A subclass has ``p``, ``device``, ``blockSize``, ``in_ring`` and ``block_in`` and supplies ``_outputs()`` ->
+    (out_ring, block_out) of the current layout (allocating them when it changed), ``_call(block_in, block_out, localize)``,
+    ``_state()`` (the tensors a call changes), ``_key()`` (what the captured launches depend on besides buffer contents),
+    ``_check_block(block)`` and ``_after_block()``."""
+
+    def __init__(self, use_graph):
+        self.use_graph = bool(use_graph)
+        self.capture_error = None          # the exception of a failed HIP-graph capture (process_block then launches directly)
+        self._pin_in, self._pin_out, self._ev_out = None, None, None      # made by the first process_block
+        self._graph, self._graph_key = None, None
+
+    def _check_block(self, block):
+        pass
+
+    def _after_block(self):
+        pass
+
+    def process_block(self, block):
+        """Host block(s) in -> host block(s) out.  The finished block is fetched (pinned buffer, its own event) BEFORE the tracking update
+        of the next block's target has run: that kernel only writes state the next call reads, so it stays off the latency path.
+        The fixed launch sequence (upload, kernels, download) is captured once into a HIP graph and replayed per block."""
+        block = np.ascontiguousarray(block, dtype=np.float32)
+        self._check_block(block)
+        with torch.cuda.device(self.device):
+            block_out = self._outputs()[1]
+            if self._pin_in is None:
+                self._pin_in = torch.zeros(self.block_in.shape, dtype=torch.float32).pin_memory()
+                self._ev_out = torch.cuda.Event()
+            if self._pin_out is None or self._pin_out.shape != block_out.shape:
+                self._pin_out = torch.zeros(block_out.shape, dtype=torch.float32).pin_memory()
+            self._pin_in.copy_(torch.from_numpy(block))
+            key = self._key()              # re-capture when one of these changes
+            if not self.use_graph:
+                self._graph, self._graph_key = None, None
+            elif self._graph_key != key:
+                self._graph, self._graph_key = self._capture(), key
+            if self._graph is not None:
+                self._graph.replay()
+            else:
+                self._launch_front()
+            self._ev_out.record()
+            self._call(self.block_in, block_out, localize='only')
+            self._ev_out.synchronize()
+            out = self._pin_out.numpy().copy()
+            self._after_block()
+        return out
+
+    def _launch_front(self):
+        block_out = self._outputs()[1]
+        self.block_in.copy_(self._pin_in, non_blocking=True)
+        self._call(self.block_in, block_out, localize='skip')
+        self._pin_out.copy_(block_out, non_blocking=True)
+
+    def _capture(self):
+        """upload -> kernels (all but the tracking update) -> download as one HIP graph: a single serial chain on one stream.  A failed
+        capture is not silent: it is kept in ``capture_error`` and warned about once (the direct launches are correct but ~2x the p99
+        latency); use_graph=False opts out."""
+        try:
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            held = self._state()
+            saved = [t.clone() for t in held]
+            with torch.cuda.graph(g):
+                self._launch_front()
+            for t, s0 in zip(held, saved):          # capture does not execute on ROCm; restore in case a runtime runs the body once
+                t.copy_(s0)
+            torch.cuda.synchronize()
+            self.capture_error = None
+            return g
+        except Exception as e:
+            import warnings
+            if self.capture_error is None:
+                warnings.warn('%s: HIP graph capture failed (%s: %s); falling back to direct launches'
+                              % (type(self).__name__, type(e).__name__, e), RuntimeWarning)
+            self.capture_error = e
+            return None
+
+    def _process_signal(self, x):
+        """Device signal(s) (..., 2, n) -> host (lead of block_out..., n_blocks * blockSize): every block is one device call."""
+        B = self.blockSize
+        n_blocks = x.shape[-1] // B
+        xb = x[..., :n_blocks * B].reshape(x.shape[:-1] + (n_blocks, B)).movedim(-2, 0).contiguous()      # [block][...][2][B]
+        lead = tuple(self._outputs()[1].shape[:-1])
+        out = torch.zeros((n_blocks,) + lead + (B,), dtype=torch.float32, device=self.device)
+        for b in range(n_blocks):
+            self.process_block_device(xb[b], out[b])
+        return out.movedim(0, -2).reshape(lead + (n_blocks * B,)).cpu().numpy()
+
+
+class StreamingGCCNMF(_BlockDriver):
     """``OverlapAddProcessor.processFrames(GCCNMFProcessor.processFrames)`` (utils.py:99-116) as one device call per block:
     ``process_block((2, blockSize)) -> (2, blockSize)``, output delayed by two blocks like the reference.  In multiple mode
     (``processor.targetMode = TARGET_MODE_MULTIPLE``) every target has its own output ring: ``(2, blockSize) -> (numSources, 2,
     blockSize)``; the single-target ring is kept apart, so a stream can switch modes."""
 
     def __init__(self, processor, hopSize, blockSize, outputDelayBlocks=2, use_graph=True):
-        self.use_graph = bool(use_graph)
-        self.capture_error = None          # the exception of a failed HIP-graph capture (process_block then launches directly)
+        _BlockDriver.__init__(self, use_graph)
         self.outputDelayBlocks = _check_stream_shape(processor, hopSize, blockSize, outputDelayBlocks)
         self.p, self.hopSize, self.blockSize = processor, int(hopSize), int(blockSize)
-        dev = processor.device
+        dev = self.device = processor.device
         self.in_ring = torch.zeros((2, 8 * blockSize), dtype=torch.float32, device=dev)
         self.out_ring = torch.zeros((2, 8 * blockSize), dtype=torch.float32, device=dev)
         self.block_in = torch.zeros((2, blockSize), dtype=torch.float32, device=dev)
@@ -409,95 +490,36 @@ class StreamingGCCNMF(object):
             self._multi_state = key + (z(N, 2, 8 * B), z(N, 2, B))
         return self._multi_state[2], self._multi_state[3]
 
+    def _call(self, block_in, block_out, localize='with'):
+        self.p._call(block_in, block_out, self.in_ring, self._outputs()[0], self.hopSize, self.blockSize, self.outputDelayBlocks,
+                     localize=localize)
+
+    def _state(self):
+        return self.in_ring, self._outputs()[0], self.p.dHist, self.p.dHistPos, self.p.dTarget
+
+    def _key(self):
+        p = self.p
+        return (int(p.targetMode), bool(p.separationEnabled), bool(p.localizationEnabled), int(p.localizationWindowSize),
+                int(p.numHUpdates), p.dW.data_ptr(), p.dTarget.data_ptr(), p.generation,      # reset() re-allocates every buffer
+                p._sources if p.multiple() else 0, self._outputs()[0].data_ptr(), self._pin_out.data_ptr())
+
+    def _after_block(self):
+        self.p.fill_histories()            # host mirrors (only when history objects were given): after the tracking update
+
     def process_block_device(self, block_in, block_out):
         """Device tensors in/out, asynchronous on the current stream (what a capture/playback loop would call); block_out is
         [numSources][2][blockSize] in multiple mode."""
-        out_ring = self._outputs()[0]
-        self.p._call(block_in, block_out, self.in_ring, out_ring, self.hopSize, self.blockSize, 0, self.outputDelayBlocks)
-
-    def process_block(self, block):
-        """Host block in -> host block out.  The finished block is fetched (pinned buffer, its own event) BEFORE the tracking update
-        of the next block's target has run: that kernel only writes state the next call reads, so it stays off the latency path.
-        The fixed launch sequence (upload, kernels, download) is captured once into a HIP graph and replayed per block."""
-        if getattr(self, '_pin_in', None) is None:
-            self._pin_in = torch.zeros((2, self.blockSize), dtype=torch.float32).pin_memory()
-            self._pin_out = None
-            self._ev_out = torch.cuda.Event()
-            self._graph, self._graph_key = None, None
-        p = self.p
-        with torch.cuda.device(p.device):
-            self._pin_in.copy_(torch.from_numpy(np.ascontiguousarray(block, dtype=np.float32)))
-            out_ring, block_out = self._outputs()
-            if self._pin_out is None or self._pin_out.shape != block_out.shape:
-                self._pin_out = torch.zeros(block_out.shape, dtype=torch.float32).pin_memory()
-            # everything the captured launches depend on besides buffer contents: re-capture when one of them changes
-            key = (int(p.targetMode), bool(p.separationEnabled), bool(p.localizationEnabled), int(p.localizationWindowSize),
-                   int(p.numHUpdates), p.dW.data_ptr(), p.dTarget.data_ptr(), p.generation,      # reset() re-allocates every buffer
-                   p._sources if p.multiple() else 0, out_ring.data_ptr(), self._pin_out.data_ptr())
-            if self.use_graph and self._graph_key != key:
-                self._graph, self._graph_key = self._capture(), key
-            if self._graph is not None:
-                self._graph.replay()
-            else:
-                self._launch_front()
-            self._ev_out.record()
-            p._call(self.block_in, block_out, self.in_ring, out_ring, self.hopSize, self.blockSize, 4, self.outputDelayBlocks)
-            self._ev_out.synchronize()
-            out = self._pin_out.numpy().copy()
-            p.fill_histories()                 # host mirrors (only when history objects were given): after the tracking update
-        return out
-
-    def _launch_front(self):
-        out_ring, block_out = self._outputs()
-        self.block_in.copy_(self._pin_in, non_blocking=True)
-        self.p._call(self.block_in, block_out, self.in_ring, out_ring, self.hopSize, self.blockSize, 2, self.outputDelayBlocks)
-        self._pin_out.copy_(block_out, non_blocking=True)
-
-    def _capture(self):
-        """upload -> kernels (all but the tracking update) -> download as one HIP graph.  A failed capture is not silent: it is kept in
-        ``capture_error`` and warned about once (the direct launches are correct but ~2x the p99 latency); use_graph=False opts out."""
-        try:
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            held = (self.in_ring, self._outputs()[0], self.p.dHist, self.p.dHistPos, self.p.dTarget)
-            state = [t.clone() for t in held]
-            with torch.cuda.graph(g):
-                self._launch_front()
-            # capture does not execute on ROCm, but restore the state anyway in case a runtime runs the body once
-            for t, s0 in zip(held, state):
-                t.copy_(s0)
-            torch.cuda.synchronize()
-            self.capture_error = None
-            return g
-        except Exception as e:
-            import warnings
-            if getattr(self, 'capture_error', None) is None:
-                warnings.warn('StreamingGCCNMF: HIP graph capture failed (%s: %s); falling back to direct launches' % (type(e).__name__, e),
-                              RuntimeWarning)
-            self.capture_error = e
-            return None
+        self._call(block_in, block_out)
 
     def process_stream(self, stereoSamples):
         """(2, n) -> (2, n_blocks*blockSize) (multiple mode: (numSources, 2, n_blocks*blockSize)); the whole signal is uploaded once,
         every block is one device call."""
-        x = torch.from_numpy(np.ascontiguousarray(stereoSamples, dtype=np.float32)).to(self.p.device)
-        B = self.blockSize
-        n_blocks = x.shape[1] // B
-        xb = x[:, :n_blocks * B].reshape(2, n_blocks, B).permute(1, 0, 2).contiguous()      # [block][2][B]
-        lead = tuple(self._outputs()[1].shape[:-1])                                        # (2,) or (N, 2)
-        out = torch.zeros((n_blocks,) + lead + (B,), dtype=torch.float32, device=self.p.device)
-        for b in range(n_blocks):
-            self.process_block_device(xb[b], out[b])
-        return out.movedim(0, -2).reshape(lead + (n_blocks * B,)).cpu().numpy()
+        return self._process_signal(torch.from_numpy(np.ascontiguousarray(stereoSamples, dtype=np.float32)).to(self.device))
 
 
-MAX_BANK_STREAMS = 4096                  # frames_mode bits 8..19 (csrc/rt.hip)
-_BANK_LAYOUT = 8
-
-
-class StreamingGCCNMFBank(object):
+class StreamingGCCNMFBank(_BlockDriver):
     """S independent real-time streams of one configuration, advanced together: one device call per block runs all of them
-    (frames_mode bit 3 of ``gccnmf_rt_process_block_ll``).  Stream s produces bit for bit what a ``StreamingGCCNMF`` over its own
+    (the ``streams`` layout of ``_hip.rt_process_block``).  Stream s produces bit for bit what a ``StreamingGCCNMF`` over its own
     ``GCCNMFProcessor`` of the same configuration produces when fed the same blocks.
 
     ``processor`` is the shared configuration: its dictionary, TDOA grid, windows, twiddles, ``targetMode``, ``numHUpdates`` and
@@ -515,13 +537,11 @@ class StreamingGCCNMFBank(object):
     def __init__(self, processor, numStreams, hopSize, blockSize, outputDelayBlocks=2, use_graph=True):
         if int(numStreams) != numStreams or not 1 <= int(numStreams) <= MAX_BANK_STREAMS:
             raise ValueError('numStreams=%r: a bank holds 1 to %d streams' % (numStreams, MAX_BANK_STREAMS))
+        _BlockDriver.__init__(self, use_graph)
         self.outputDelayBlocks = _check_stream_shape(processor, hopSize, blockSize, outputDelayBlocks)
         self.p, self.numStreams, self.hopSize, self.blockSize = processor, int(numStreams), int(hopSize), int(blockSize)
-        self.use_graph = bool(use_graph)
-        self.capture_error = None          # as StreamingGCCNMF.capture_error
         self.device = processor.device
         self._generation = None
-        self._graph, self._graph_key = None, None
         self._alloc()
 
     # ---- per-stream state ----------------------------------------------------------------------------------------------
@@ -651,20 +671,31 @@ class StreamingGCCNMFBank(object):
         return (self._tindexes if self._multi else self._targets).copy()
 
     # ---- device calls -----------------------------------------------------------------------------------------------------
+    def _outputs(self):
+        self._ensure_state()
+        return self.out_ring, self.block_out
+
     @_on_device
-    def _call(self, block_in, block_out, bits):
+    def _call(self, block_in, block_out, localize='with'):
         p = self.p
-        if p.localizationEnabled and not bits & 2:
+        if p.localizationEnabled and localize != 'skip':
             self._targets_dirty = True
-        multi = (_MULTI_LAYOUT | ((self._sources - 1) << 21)) if self._multi else 0
-        _hip.check(p.lib.gccnmf_rt_process_block_ll(
-            _ptr(block_in), _ptr(block_out), _ptr(self.in_ring), _ptr(self.out_ring), _ptr(self.dX), _ptr(self.dY), _ptr(self.dC),
-            _ptr(self.dHMask), _ptr(self.dArgmax), _ptr(self.dTfMask), _ptr(self.dHist), _ptr(self.dHistPos), _ptr(self.dTarget),
-            _ptr(self.dGccPhat), _ptr(p.dW), _ptr(p.dCos), _ptr(p.dSin), _ptr(p.dWindow), _ptr(p.dSynthWindow), _ptr(p.dTwiddle),
-            _ptr(p.dColsum), _ptr(self.dHcoef), _ptr(self.dRv), p.windowSize, self.hopSize, self.blockSize,
-            p.numAtom, p.Kp, p.numTDOAs, p.Dp, p.numTDOAHistory, int(p.targetMode), int(bool(p.separationEnabled)),
-            int(bool(p.localizationEnabled)), p.localizationWindowSize, bits | _BANK_LAYOUT | ((self.numStreams - 1) << 8) | multi,
-            int(p.numHUpdates), self.outputDelayBlocks, _stream()), 'gccnmf_rt_process_block_ll')
+        _hip.rt_process_block(block_in, block_out, self.in_ring, self.out_ring, self.dX, self.dY, self.dC, self.dHMask, self.dArgmax,
+                              self.dTfMask, self.dHist, self.dHistPos, self.dTarget, self.dGccPhat, *p._tables(), self.dHcoef, self.dRv,
+                              *p._settings(self.hopSize, self.blockSize), p.numHUpdates, self.outputDelayBlocks, localize=localize,
+                              streams=self.numStreams, targets=self._sources if self._multi else None)
+
+    def _state(self):
+        return self.in_ring, self.out_ring, self.dHist, self.dHistPos, self.dTarget
+
+    def _key(self):
+        p = self.p
+        return (int(p.targetMode), bool(p.separationEnabled), bool(p.localizationEnabled), int(p.localizationWindowSize),
+                int(p.numHUpdates), p.dW.data_ptr(), self.dTarget.data_ptr(), p.generation, self._layout_key, self._pin_out.data_ptr())
+
+    def _check_block(self, blocks):
+        if blocks.shape != (self.numStreams, 2, self.blockSize):
+            raise ValueError('expected blocks of shape %s, got %s' % ((self.numStreams, 2, self.blockSize), blocks.shape))
 
     def _check_blocks(self, t, shape):
         if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
@@ -673,81 +704,14 @@ class StreamingGCCNMFBank(object):
     def process_block_device(self, block_in, block_out):
         """(S, 2, blockSize) device tensors in, (S, 2, blockSize) ((S, N, 2, blockSize) in multiple mode) out, asynchronous on the
         current stream."""
-        self._ensure_state()
         self._check_blocks(block_in, (self.numStreams, 2, self.blockSize))
-        self._check_blocks(block_out, tuple(self.block_out.shape))
-        self._call(block_in, block_out, 0)
-
-    def process_block(self, blocks):
-        """(S, 2, blockSize) host blocks in -> (S, 2, blockSize) out, as ``StreamingGCCNMF.process_block``: one captured HIP graph
-        (upload, every kernel but the tracking update, download), the output fetched before the tracking update runs."""
-        blocks = np.ascontiguousarray(blocks, dtype=np.float32)
-        if blocks.shape != (self.numStreams, 2, self.blockSize):
-            raise ValueError('expected blocks of shape %s, got %s' % ((self.numStreams, 2, self.blockSize), blocks.shape))
-        p = self.p
-        with torch.cuda.device(self.device):
-            self._ensure_state()
-            if getattr(self, '_pin_in', None) is None:
-                self._pin_in = torch.zeros((self.numStreams, 2, self.blockSize), dtype=torch.float32).pin_memory()
-                self._pin_out = None
-                self._ev_out = torch.cuda.Event()
-            if self._pin_out is None or self._pin_out.shape != self.block_out.shape:
-                self._pin_out = torch.zeros(self.block_out.shape, dtype=torch.float32).pin_memory()
-            self._pin_in.copy_(torch.from_numpy(blocks))
-            key = (int(p.targetMode), bool(p.separationEnabled), bool(p.localizationEnabled), int(p.localizationWindowSize),
-                   int(p.numHUpdates), p.dW.data_ptr(), self.dTarget.data_ptr(), p.generation, self._layout_key,
-                   self._pin_out.data_ptr())
-            if self.use_graph and self._graph_key != key:
-                self._graph, self._graph_key = self._capture(), key
-            if self.use_graph and self._graph is not None:
-                self._graph.replay()
-            else:
-                self._launch_front()
-            self._ev_out.record()
-            self._call(self.block_in, self.block_out, 4)
-            self._ev_out.synchronize()
-            return self._pin_out.numpy().copy()
-
-    def _launch_front(self):
-        self.block_in.copy_(self._pin_in, non_blocking=True)
-        self._call(self.block_in, self.block_out, 2)
-        self._pin_out.copy_(self.block_out, non_blocking=True)
-
-    def _capture(self):
-        """upload -> kernels (all but the tracking update) -> download as one HIP graph: a single serial chain on one stream.  A failed
-        capture is kept in ``capture_error``, warned about once, and the block is launched directly."""
-        state = (self.in_ring, self.out_ring, self.dHist, self.dHistPos, self.dTarget)
-        try:
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            saved = [t.clone() for t in state]
-            with torch.cuda.graph(g):
-                self._launch_front()
-            for t, s0 in zip(state, saved):         # capture does not execute on ROCm; restore in case a runtime runs the body once
-                t.copy_(s0)
-            torch.cuda.synchronize()
-            self.capture_error = None
-            return g
-        except Exception as e:
-            import warnings
-            if self.capture_error is None:
-                warnings.warn('StreamingGCCNMFBank: HIP graph capture failed (%s: %s); falling back to direct launches'
-                              % (type(e).__name__, e), RuntimeWarning)
-            self.capture_error = e
-            return None
+        self._check_blocks(block_out, tuple(self._outputs()[1].shape))
+        self._call(block_in, block_out)
 
     def process_streams(self, x):
         """(S, 2, n) -> (S, 2, n_blocks * blockSize) ((S, N, 2, ...) in multiple mode); the whole signal is uploaded once, every block
         is one device call."""
         x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(self.device)
-        S, B = self.numStreams, self.blockSize
-        if x.dim() != 3 or x.shape[0] != S or x.shape[1] != 2:
-            raise ValueError('expected signals of shape (%d, 2, n)' % S)
-        self._ensure_state()
-        n_blocks = x.shape[2] // B
-        xb = x[:, :, :n_blocks * B].reshape(S, 2, n_blocks, B).permute(2, 0, 1, 3).contiguous()      # [block][S][2][B]
-        lead = tuple(self.block_out.shape[:-1])                                                       # (S, 2) or (S, N, 2)
-        out = torch.zeros((n_blocks,) + lead + (B,), dtype=torch.float32, device=self.device)
-        for b in range(n_blocks):
-            self.process_block_device(xb[b], out[b])
-        return out.movedim(0, -2).reshape(lead + (n_blocks * B,)).cpu().numpy()
+        if x.dim() != 3 or x.shape[0] != self.numStreams or x.shape[1] != 2:
+            raise ValueError('expected signals of shape (%d, 2, n)' % self.numStreams)
+        return self._process_signal(x)

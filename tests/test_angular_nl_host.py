@@ -188,13 +188,13 @@ def test_packed_alpha_of_the_c_call():
 def test_row8_bit_of_the_streaming_call():
     """frames_mode bit 24 (the single-stream target row has word 6 = gccPHATNLAlpha) is an error together with the bank or multi-target
     layouts, whose rows always have the word; nothing above bit 24."""
-    from gcc_nmf_amd import _hip, realtime as rt
+    from gcc_nmf_amd import _hip
     buf = (ctypes.c_float * 16)()
     p = ctypes.cast(buf, ctypes.c_void_p)
 
     def call(bits, mode=2):
         return _hip.lib().gccnmf_rt_process_block_ll(*([p] * 23), 1024, 512, 512, 128, 128, 64, 64, 128, mode, 1, 1, 6, bits, 0, 2, None)
-    assert rt._ROW8_LAYOUT == 1 << 24
+    assert _hip.RT_ROW8_LAYOUT == 1 << 24 == _hip.rt_mode_word(nl_row=True)
     for bits, mode in (((1 << 24) | 8, 2), ((1 << 24) | (1 << 20), 1), (1 << 25, 2), ((1 << 24) | (1 << 25), 2), ((1 << 24) | (3 << 21), 2)):
         assert call(bits, mode) == 1, bits
 

@@ -70,7 +70,7 @@ def tables_of(p):
 @pytest.mark.parametrize('alpha', [0.5, 2.0, 8.0])
 @pytest.mark.parametrize('name', list(CONFIGS))
 def test_gccphat_of_a_given_coherence(name, alpha):
-    """The localisation kernel alone (frames_mode 1 | 4) on a coherence written into the processor's buffer: random unit-modulus bins, a
+    """The localisation kernel alone (frames mode, localize='only') on a coherence written into the processor's buffer: random unit-modulus bins, a
     tenth of them NaN (zero magnitude: skipped, not counted), one frame with an exact grid delay, one frame of NaN only."""
     ws, hop, B, K, D, nh, syn, _ = CONFIGS[name]
     from gcc_nmf_amd.realtime import GCCNMFProcessor
@@ -84,7 +84,7 @@ def test_gccphat_of_a_given_coherence(name, alpha):
     C[:, 1] = np.exp(2j * np.pi * p.frequenciesInHz.astype(np.float64) * float(p.hypothesisTDOAs[D // 3])).astype(np.complex64)
     C[:, 3] = np.nan
     p.dC.copy_(torch.view_as_real(torch.from_numpy(C)).to(p.device))
-    p._call(None, None, p.dFramesIn, p.dFramesOut, ws, Tc * ws, 1 | 4)
+    p._call(None, None, p.dFramesIn, p.dFramesOut, ws, Tc * ws, frames=True, localize='only')
     torch.cuda.synchronize()
     got = p.dGccPhat.cpu().numpy().astype(np.float64)
     cos64, sin64, cos32, sin32 = tables_of(p)
@@ -104,7 +104,7 @@ def test_gccphat_of_a_given_coherence(name, alpha):
     for kw in (dict(gccPHATNLEnabled=False, gccPHATNLAlpha=alpha), {}):
         q = GCCNMFProcessor(FS, ws, Tc, {'P': {64: W}}, 'P', 64, 0, SPACING, False, 6, numTDOAs=D, **kw)
         q.dC.copy_(torch.view_as_real(torch.from_numpy(C)).to(q.device))
-        q._call(None, None, q.dFramesIn, q.dFramesOut, ws, Tc * ws, 1 | 4)
+        q._call(None, None, q.dFramesIn, q.dFramesOut, ws, Tc * ws, frames=True, localize='only')
         outs.append(q.dGccPhat.cpu().numpy())
     assert np.array_equal(outs[0], outs[1], equal_nan=True)
     phat = np.nanmean((C[:, :, None] * p.expJOmegaTau[:, None]).real.astype(np.float64), axis=0).T

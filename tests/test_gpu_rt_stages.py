@@ -1,4 +1,4 @@
-"""-m gpu: every stage of the real-time block call (csrc/rt.hip: thirteen kernels behind gccnmf_rt_process_block_ll) element-wise against
+"""-m gpu: every stage of the real-time block call (csrc/rt.hip: eleven kernels behind gccnmf_rt_process_block_ll) element-wise against
 float64, each from the device's own inputs to that stage (tests/rt_checks.py states the nine rules and derives their bars; the CPU suite
 tests/test_rt_checks.py shows they are sound and sensitive).
 

@@ -149,6 +149,53 @@ def test_thin_wrappers_keep_the_header_order(stub):
     assert last(stub, 'gccnmf_argmax_targets') == (1, 16, 59, 3, 4, 2, STREAM)
 
 
+RT_POINTERS = tuple(range(0x100, 0x100 + 23))               # block_in .. Rv as raw addresses
+RT_GEOMETRY = (512, 64, 64, 256, 256, 64, 64, 128)          # windowSize, hopSize, blockSize, K, Kp, D, Dp, numTDOAHistory
+BANK, MULTI, ROW8 = 8, 1 << 20, 1 << 24                     # frames_mode_bits of include/gccnmf_hip.h
+
+
+def rt_call(target_mode=_hip.TARGET_MODE_WINDOW_FUNCTION, **mode):
+    _hip.rt_process_block(*RT_POINTERS, *RT_GEOMETRY, target_mode, True, False, 6, 3, 1, stream=STREAM, **mode)
+
+
+@pytest.mark.parametrize('mode,word', [
+    ({}, 0), (dict(frames=True), 1), (dict(localize='skip'), 2), (dict(localize='only'), 4), (dict(frames=True, localize='only'), 5),
+    (dict(streams=1), BANK), (dict(streams=3), BANK | 2 << 8), (dict(streams=4096), BANK | 4095 << 8),
+    (dict(targets=1), MULTI), (dict(targets=8), MULTI | 7 << 21),
+    (dict(streams=3, targets=2, localize='skip'), 2 | BANK | 2 << 8 | MULTI | 1 << 21), (dict(nl_row=True), ROW8)],
+    ids=lambda v: ' '.join('%s=%s' % kv for kv in v.items()) or 'plain' if isinstance(v, dict) else None)
+def test_rt_process_block_word(stub, mode, word):
+    target_mode = _hip.TARGET_MODE_MULTIPLE if 'targets' in mode else _hip.TARGET_MODE_WINDOW_FUNCTION
+    rt_call(target_mode, **mode)
+    args = last(stub, 'gccnmf_rt_process_block_ll')
+    assert args[35] == word == _hip.rt_mode_word(**mode)
+    # every other argument in the header's order (the switches as 0 / 1), the stream last
+    assert args[:35] + args[36:] == RT_POINTERS + RT_GEOMETRY + (target_mode, 1, 0, 6, 3, 1, STREAM)
+
+
+def test_rt_process_block_defaults_and_pointers(stub, monkeypatch):
+    t = torch.zeros(4)
+    monkeypatch.setattr(_hip, '_stream', lambda device=None: 99)              # no stream given: torch's current one
+    _hip.rt_process_block(None, t, *RT_POINTERS[2:], *RT_GEOMETRY, 0, 0, 1, 6)
+    args = last(stub, 'gccnmf_rt_process_block_ll')
+    assert args[:2] == (0, t.data_ptr()) and args[31:] == (0, 0, 1, 6, 0, 0, 2, 99)      # numHUpdates 0, the reference's hand-out of 2
+    assert (_hip.MAX_BANK_STREAMS, _hip.MAX_SOURCES, _hip.RT_BANK_LAYOUT, _hip.RT_MULTI_LAYOUT, _hip.RT_ROW8_LAYOUT) == (4096, 8, BANK, MULTI, ROW8)
+    assert (_hip.RT_FRAMES, _hip.RT_SKIP_LOCALIZE, _hip.RT_ONLY_LOCALIZE) == (1, 2, 4)
+
+
+@pytest.mark.parametrize('mode', [
+    dict(streams=2, frames=True), dict(nl_row=True, streams=2), dict(nl_row=True, targets=2), dict(nl_row=True, streams=2, targets=2),
+    dict(targets=2, target_mode=_hip.TARGET_MODE_WINDOW_FUNCTION), dict(targets=2, target_mode=_hip.TARGET_MODE_BOXCAR),
+    dict(streams=0), dict(streams=4097), dict(streams=-1), dict(targets=0), dict(targets=9), dict(localize='never'), dict(localize=4)],
+    ids=lambda v: ' '.join('%s=%s' % kv for kv in v.items()))
+def test_rt_process_block_checks_come_before_the_library(stub, mode):
+    mode = dict(mode)
+    target_mode = mode.pop('target_mode', _hip.TARGET_MODE_MULTIPLE)
+    with pytest.raises(ValueError):
+        rt_call(target_mode, **mode)
+    assert stub.calls == []
+
+
 STAGES = [
     ('gccnmf_stft_stereo', lambda: _hip.stft_stereo(1, 16000, 1024, 256, 59, 4, 2, 3, 4, 5, 6, stream=STREAM)),
     ('gccnmf_stft_stereo_pcm16', lambda: _hip.stft_stereo(1, 16000, 1024, 256, 59, 4, 2, 3, 4, 5, 6, pcm16=True, stream=STREAM)),
@@ -166,6 +213,7 @@ STAGES = [
     ('gccnmf_target_scores_masks', lambda: _hip.target_scores_masks(1, 2, 3, 4, 513, 40, 16, 128, 3, 8, 5, 6, 7, stream=STREAM)),
     ('gccnmf_argmax_targets', lambda: _hip.argmax_targets(1, 16, 59, 3, 4, 2, stream=STREAM)),
     ('gccnmf_reconstruct', lambda: _hip.reconstruct(1, 2, 3, None, 5, 6, 513, 40, 16, 3, 8, 9, mode='ratio', stream=STREAM)),
+    ('gccnmf_rt_process_block_ll', lambda: rt_call(localize='skip')),
 ]
 
 
