@@ -547,6 +547,33 @@ RT_BANK_LAYOUT, MAX_BANK_STREAMS = 1 << 3, 4096         # + (S - 1) << 8, bits 8
 RT_MULTI_LAYOUT, MAX_SOURCES = 1 << 20, 8               # + (N - 1) << 21, bits 21..23
 RT_ROW8_LAYOUT = 1 << 24                # single-stream call: the target row has 8 words, word 6 = gccPHATNLAlpha
 RT_LOCALIZE = {'with': 0, 'skip': RT_SKIP_LOCALIZE, 'only': RT_ONLY_LOCALIZE}
+RT_SEPARATION_SPATIAL = 2               # bit 1 of separation_enabled: the online spatial filter behind the mask kernel (csrc/rt_spatial.hip)
+DEFAULT_SPATIAL_FILTER_FRAMES = 128.0   # spatialFilterFrames: the best tau of scripts/rt_spatial_filter_study.py
+
+
+def rt_spatial_state_offset(D, numTDOAHistory, S=1):
+    """Where the history ends and the spatial filter's state begins in the buffer behind ``hist``, in floats:
+    GCCNMF_RT_SPATIAL_STATE_OFFSET(S, D, Lh) of include/gccnmf_hip.h, the first multiple of 4 behind the S history images."""
+    return -(-(int(S) * int(D) * int(numTDOAHistory)) // 4) * 4
+
+
+def rt_spatial_state_floats(F, NC, S=1):
+    """Floats of that state, [S][NC][F][4]: GCCNMF_RT_SPATIAL_STATE_FLOATS(S, NC, F).  NC = 2 in the single-target modes (talker,
+    residual), the number of targets in multiple mode."""
+    return 4 * int(S) * int(NC) * int(F)
+
+
+def check_spatial_filter(spatialFilterEnabled, spatialFilterFrames):
+    """The ``spatialFilterEnabled`` / ``spatialFilterFrames`` settings of the real-time classes; no device needed.  Returns (enabled, tau):
+    tau the time constant of the recursive covariance in frames, a finite number >= 1 that is a float32 (checked whether or not the
+    filter is enabled, so a bad value cannot wait for the switch).  ValueError otherwise."""
+    t = spatialFilterFrames
+    if isinstance(t, bool) or not isinstance(t, numbers.Real) or not math.isfinite(t) or not t >= 1:
+        raise ValueError('spatialFilterFrames must be a finite number of frames >= 1, got %r' % (t,))
+    t32 = ctypes.c_float(float(t)).value
+    if not math.isfinite(t32):
+        raise ValueError('spatialFilterFrames=%r is not a float32' % (t,))
+    return bool(spatialFilterEnabled), float(t32)
 
 
 def rt_mode_word(frames=False, localize='with', streams=None, targets=None, nl_row=False, target_mode=TARGET_MODE_MULTIPLE):
@@ -574,16 +601,23 @@ def rt_mode_word(frames=False, localize='with', streams=None, targets=None, nl_r
 def rt_process_block(block_in, block_out, in_ring, out_ring, X, Y, C, HMask, argmaxTDOA, tfMask, hist, hist_pos, target, gccphat, W, cosT,
                      sinT, window, synthesis_window, twiddle, colsumW, Hcoef, Rv, windowSize, hopSize, blockSize, K, Kp, D, Dp, numTDOAHistory,
                      target_mode, separation_enabled, localization_enabled, localization_window, numHUpdates=0, out_delay_blocks=2,
-                     frames=False, localize='with', streams=None, targets=None, nl_row=False, stream=None):
+                     frames=False, localize='with', streams=None, targets=None, nl_row=False, spatial=False, stream=None):
     """One real-time block call (csrc/rt.hip); the buffers and geometry in the header's order, the modes as keywords.
     frames: GCCNMFProcessor.processFrames on its own (in_ring / out_ring are the frames, no shift or overlap-add).
     localize: 'with' the tracking update, 'skip' it, or 'only' it ('skip' then 'only' = the same work in two calls, so that a host can
     fetch block_out before the tracking update has run).
     streams = S: the buffers hold a bank of S streams (8-word target rows).  targets = N: the multi-target layout of
     TARGET_MODE_MULTIPLE (16-word rows, N masks and outputs per stream).  nl_row: the single-stream target row has 8 words, word 6 =
-    gccPHATNLAlpha (the other two layouts always have it)."""
+    gccPHATNLAlpha (the other two layouts always have it).
+    spatial: the online spatial filter runs behind the mask kernel for every stream whose row word 7 holds a time constant >= 1 frames
+    (separation word 3 = 1 | RT_SEPARATION_SPATIAL; with the separation off the word is 0 and nothing is filtered).  ``hist`` is then
+    followed by the filter's state (rt_spatial_state_offset, rt_spatial_state_floats); needs a row with a word 7, so nl_row in the
+    single-stream, single-target call."""
     word = rt_mode_word(frames, localize, streams, targets, nl_row, target_mode)
+    if spatial and not (nl_row or streams is not None or targets is not None):
+        raise ValueError('spatial needs a target row with a word 7: nl_row, a bank of streams or the multi-target layout')
+    separation = (1 | (RT_SEPARATION_SPATIAL if spatial else 0)) if separation_enabled else 0
     _stage('gccnmf_rt_process_block_ll', block_in, block_out, in_ring, out_ring, X, Y, C, HMask, argmaxTDOA, tfMask, hist, hist_pos, target,
            gccphat, W, cosT, sinT, window, synthesis_window, twiddle, colsumW, Hcoef, Rv, windowSize, hopSize, blockSize, K, Kp, D, Dp,
-           numTDOAHistory, int(target_mode), int(bool(separation_enabled)), int(bool(localization_enabled)), localization_window, word,
+           numTDOAHistory, int(target_mode), separation, int(bool(localization_enabled)), localization_window, word,
            int(numHUpdates), int(out_delay_blocks), stream=stream)

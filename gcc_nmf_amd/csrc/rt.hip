@@ -27,8 +27,14 @@
 // gccPHAT peaks tracked.  Every one of its kernels is the `true` / 16-word / RT_MAX_TARGETS instantiation of a template whose other
 // instantiation is the single-target kernel (LABBOOK R7.3); the entry point picks between the two in one place
 // (RT_KERNEL).  Eleven kernels are launched from here.
+//
+// Online spatial filter (separation_enabled bit 1, GCCNMF_RT_SEPARATION_SPATIAL): one more launch between the mask and the synthesis kernel,
+// in a file of its own (rt_spatial.hip), so that the code objects of the kernels below are what they were.  Its per-stream state lies
+// behind the history images of `hist`; a stream's word 7 of the target row holds its time constant.
 #include "fft_core.h"
 #include "angular_nl.h"
+#include "rt_spatial.h"
+#include "../../include/gccnmf_hip.h"
 
 typedef float rt_f32x16 __attribute__((ext_vector_type(16)));
 
@@ -857,6 +863,10 @@ int gccnmf_rt_process_block_ll(const float* block_in, float* block_out, float* i
     const bool row8 = (frames_mode_bits >> 24) & 1;
     if ((frames_mode_bits & ~0x1ffffff) || (bank && frames_mode) || (!bank && S > 1) || (row8 && (bank || multi))) return GCCNMF_ERR_ARG;
     const int nl_row = (bank || multi || row8) ? 1 : 0;
+    // separation_enabled bit 1: the online spatial filter behind the mask kernel.  Its switch is word 7 of the stream's target row, which
+    // the 4-word single-stream row does not have; its state is read and written as float4 behind the history images of hist.
+    const bool spatial = (separation_enabled & GCCNMF_RT_SEPARATION_SPATIAL) != 0;
+    if (spatial && (!nl_row || ((size_t)hist & 15))) return GCCNMF_ERR_ARG;
     if ((multi && target_mode != 1) || (!multi && NT > 1)) return GCCNMF_ERR_ARG;
     const float* rows = bank ? target : nullptr;          // the per-stream switches the mask and synthesis kernels read
     // powers of two from 64 up: the radix-2 LDS transform (twiddle = N/2 values of exp(-2 pi j k / N)); every other even size: the direct
@@ -931,6 +941,11 @@ int gccnmf_rt_process_block_ll(const float* block_in, float* block_out, float* i
             hipLaunchKernelGGL(RT_KERNEL(rt_tfmask_h_kernel, 1, RT_MAX_TARGETS), dim3(gccnmf_ceil_div(F, 4), 1, S), dim3(256), 0, s, W, HMask,
                                Hcoef, F, K, Kp, Tc, (const float2*)X, (float2*)Y, tfMask, rows, NT);
             GCCNMF_CHECK_LAUNCH();
+        }
+        if (spatial) {
+            const int rc = gccnmf_launch_rt_spatial(X, Y, target, multi ? RT_ROW_MULTI : RT_ROW, bank,
+                                                    hist + gccnmf_rt_spatial_state_offset(S, D, numTDOAHistory), F, Tc, multi, NT, S, s);
+            if (rc != GCCNMF_OK) return rc;
         }
     }
     if (pow2) {

@@ -64,13 +64,22 @@ class GCCNMFProcessor(object):
     Attributes and constructor keywords; a new value takes effect with ``reset()``.  When enabled, gccPHAT is
     nanmean_f 1 - tanh(alpha sqrt(max(0, 1 - Re(C e^{-j w tau})))) (Blandin, Ozerov & Vincent 2012; BSS-Locate's sqrt(2 - 2 re) form
     is this one with alpha * sqrt(2)) in all three target modes; the history, window mean and arg-max / peak rule are unchanged and the
-    GCC-NMF scores stay PHAT."""
+    GCC-NMF scores stay PHAT.
+
+    ``spatialFilterEnabled`` (default False) / ``spatialFilterFrames`` (default 128, 0.5 s at the low-latency hop): the online spatial
+    (multichannel Wiener) filter behind the mask, the streaming form of the offline ``reconstruction='spatial'`` (no counterpart in the
+    reference).  The masked
+    spectra give each component (multiple mode: the N targets; the single-target modes: the talker and the residual X - Y) a power and
+    a 2 x 2 spatial covariance, the latter a trace-normalised exponential average with a time constant of ``spatialFilterFrames`` frames
+    that is carried from block to block; the stereo mixture vector is then filtered per component (include/gccnmf_hip.h states the
+    recursion).  Attributes and constructor keywords; a new value takes effect with the next call (no ``reset()`` needed); ``reset()``
+    clears the covariances."""
 
     def __init__(self, sampleRate, windowSize, numTimePerChunk, dictionariesW, dictionaryType, dictionarySize, numHUpdates,
                  microphoneSeparationInMetres, localizationEnabled, localizationWindowSize, gccPHATHistory=None, tdoaHistory=None,
                  inputSpectrogramHistory=None, outputSpectrogramHistory=None, coefficientMaskHistories=None, numTDOAs=64,
                  numTDOAHistory=128, analysisWindow=None, synthesisWindow=None, numSources=2, gccPHATNLEnabled=False,
-                 gccPHATNLAlpha=2.0):
+                 gccPHATNLAlpha=2.0, spatialFilterEnabled=False, spatialFilterFrames=_hip.DEFAULT_SPATIAL_FILTER_FRAMES):
         # any even size like the reference (numpy.fft.rfft / irfft, gccNMFProcessor.py:202,:231): powers of two from 64 up take the
         # radix-2 LDS transform, every other even size the direct-sum kernels of csrc/rt.hip
         if int(windowSize) != windowSize or int(windowSize) < 4 or int(windowSize) > 4096 or int(windowSize) % 2:
@@ -78,6 +87,8 @@ class GCCNMFProcessor(object):
         _check_num_sources(numSources)
         self.gccPHATNLEnabled, self.gccPHATNLAlpha = gccPHATNLEnabled, gccPHATNLAlpha
         self._gcc_phat_nl()               # ValueError before the constructor looks for a device
+        self.spatialFilterEnabled, self.spatialFilterFrames = spatialFilterEnabled, spatialFilterFrames
+        self._spatial_word()
         self.lib = _hip.lib()
         self.device = _device()
         self.sampleRate, self.windowSize, self.numTimePerChunk = sampleRate, int(windowSize), int(numTimePerChunk)
@@ -113,6 +124,23 @@ class GCCNMFProcessor(object):
         """Word 6 of the target row for the current attributes: gccPHATNLAlpha when GCC-NONLIN is enabled, 0.0 (PHAT) when not."""
         enabled, alpha = _hip.check_gcc_phat_nl(self.gccPHATNLEnabled, self.gccPHATNLAlpha)
         return np.float32(alpha if enabled else 0.0)
+
+    def _spatial_word(self):
+        """Word 7 of the target row for the current attributes: spatialFilterFrames when the filter is enabled, 0.0 (off) when not."""
+        enabled, frames = _hip.check_spatial_filter(self.spatialFilterEnabled, self.spatialFilterFrames)
+        return np.float32(frames if enabled else 0.0)
+
+    def _apply_spatial(self):
+        """Before a call (never inside a graph capture): the row word follows the attributes, and the covariances start over when the
+        components change meaning (into or out of multiple mode).  Returns whether the call runs the filter."""
+        word, multi = self._spatial_word(), self.multiple()
+        if word != self._spatial_row:
+            self.dTarget[7] = float(word)
+            self._spatial_row = word
+        if word > 0 and self._spatial_multi != multi:
+            self.dSpatial.zero_()
+            self._spatial_multi = multi
+        return bool(word > 0)
 
     # ---- reference API ------------------------------------------------------------------------------------------
     @_on_device
@@ -155,11 +183,17 @@ class GCCNMFProcessor(object):
         self.dX, self.dY, self.dC = part(0, 2, F, Tc, 2), part(1, 2, F, Tc, 2), z(F, Tc, 2)
         self.dHMask, self.dArgmax = part(2, self.Kp, Tc), z(self.Kp, Tc, dtype=torch.int32)
         self.dTfMask, self.dGccPhat = z(2, F, Tc), part(3, D, Tc)     # tfMask: [F][Tc] used without coefficient inference, [2][F][Tc] with
-        self.dHist, self.dHistPos = z(D, self.numTDOAHistory), z(1, dtype=torch.int32)
+        # the gccPHAT history and, behind it, the spatial filter's covariances [NC][F][4] (NC = 2 or numSources): one buffer, the block
+        # call's `hist`
+        at = _hip.rt_spatial_state_offset(D, self.numTDOAHistory)
+        self.dHistState = z(at + _hip.rt_spatial_state_floats(F, max(NS, 2)))
+        self.dHist, self.dSpatial = self.dHistState[:D * self.numTDOAHistory].view(D, self.numTDOAHistory), self.dHistState[at:]
+        self.dHistPos = z(1, dtype=torch.int32)
         self.dTarget = part(4, 16)
         self.dTarget[:4].copy_(torch.from_numpy(self._target_host))
         self._nl_word = nl_word                           # GCC-NONLIN as this reset() saw it: alpha, or 0 = PHAT
         self.dTarget[6] = float(nl_word)
+        self._spatial_row, self._spatial_multi, self._spatial_on = np.float32(0.0), None, False      # word 7 as the device has it
         self._mirror_offs, self._mirror_sizes, self._mirror_host = offs, sizes, None
         # _target_dirty: a device call ran with the online localisation on since the value was last known on the host
         self._calls, self._target_dirty, self._target_value, self._target_pin = 0, False, float(self._target_host[0]), None
@@ -238,6 +272,7 @@ class GCCNMFProcessor(object):
         """out_ring / block_out: [N][2][...] in multiple mode."""
         self._calls += 1
         multi = self.multiple()
+        spatial = self._spatial_on and bool(self.separationEnabled)
         if self.localizationEnabled:
             if multi:
                 self._indexes_dirty = True
@@ -248,7 +283,8 @@ class GCCNMFProcessor(object):
         _hip.rt_process_block(block_in, block_out, in_ring, out_ring, self.dX, Y, self.dC, HMask, self.dArgmax, tfMask, self.dHist,
                               self.dHistPos, self.dTarget, self.dGccPhat, *self._tables(), self.dHcoef, self.dRv,
                               *self._settings(hop, block), self.numHUpdates, out_delay_blocks, frames=frames, localize=localize,
-                              targets=self._sources if multi else None, nl_row=not multi and self._nl_word > 0)
+                              targets=self._sources if multi else None, nl_row=not multi and (self._nl_word > 0 or spatial),
+                              spatial=spatial)
 
     @_on_device
     def processFrames(self, windowedSamples):
@@ -259,6 +295,7 @@ class GCCNMFProcessor(object):
         if ws.shape != (2, self.windowSize, Tc):
             raise ValueError('expected windowedSamples of shape %s, got %s' % ((2, self.windowSize, Tc), ws.shape))
         self.dFramesIn.copy_(torch.from_numpy(np.ascontiguousarray(ws.transpose(0, 2, 1))))
+        self._spatial_on = self._apply_spatial()
         # hop = windowSize, block = Tc * windowSize describes Tc back-to-back frames to the kernels' start0/step arithmetic
         if self.multiple():
             self._call(None, None, self.dFramesIn, self.dFramesOutM, self.windowSize, Tc * self.windowSize, frames=True)
@@ -315,7 +352,9 @@ class GCCNMFProcessor(object):
             own = dict(Y=torch.view_as_complex(self.dYm).cpu().numpy(), targetTDOAIndexes=self.targetTDOAIndexes)
         else:                       # HMask (K, Tc); tfMask (F, Tc) without coefficient inference, (2, F, Tc) with
             HMask, tfMask = self.dHMask[:K], self.dTfMask if self.numHUpdates else self.dTfMask.view(-1)[:F * Tc].view(F, -1)
-            own = dict(targetTDOAIndex=self.targetTDOAIndex)
+            own = dict(Y=torch.view_as_complex(self.dY).cpu().numpy(), targetTDOAIndex=self.targetTDOAIndex)
+        NC = self._sources if self.multiple() else 2          # the spatial filter's state (p0, p1, Re q, Im q) per component and bin
+        own['spatialCovariance'] = self.dSpatial[:4 * NC * F].view(NC, F, 4).cpu().numpy()
         return dict(own, X=torch.view_as_complex(self.dX).cpu().numpy(), C=torch.view_as_complex(self.dC).cpu().numpy(),
                     HMask=HMask.cpu().numpy(), argmaxTDOA=self.dArgmax[:K].cpu().numpy(), tfMask=tfMask.cpu().numpy(),
                     Hcoef=self.dHcoef[:K].permute(2, 0, 1).contiguous().cpu().numpy(), gccPHAT=self.dGccPhat.cpu().numpy())
@@ -375,7 +414,7 @@ class _BlockDriver(object):
     whole-signal loop.  A subclass has ``p``, ``device``, ``blockSize``, ``in_ring`` and ``block_in`` and supplies ``_outputs()`` ->
     (out_ring, block_out) of the current layout (allocating them when it changed), ``_call(block_in, block_out, localize)``,
     ``_state()`` (the tensors a call changes), ``_key()`` (what the captured launches depend on besides buffer contents),
-    ``_check_block(block)`` and ``_after_block()``."""
+    ``_check_block(block)``, ``_before_block()`` and ``_after_block()``."""
 
     def __init__(self, use_graph):
         self.use_graph = bool(use_graph)
@@ -387,6 +426,10 @@ class _BlockDriver(object):
         pass
 
     def _after_block(self):
+        pass
+
+    def _before_block(self):
+        """Settings that reach the device as buffer contents are written here: in front of every block, never inside a capture."""
         pass
 
     def process_block(self, block):
@@ -403,6 +446,7 @@ class _BlockDriver(object):
             if self._pin_out is None or self._pin_out.shape != block_out.shape:
                 self._pin_out = torch.zeros(block_out.shape, dtype=torch.float32).pin_memory()
             self._pin_in.copy_(torch.from_numpy(block))
+            self._before_block()
             key = self._key()              # re-capture when one of these changes
             if not self.use_graph:
                 self._graph, self._graph_key = None, None
@@ -495,11 +539,14 @@ class StreamingGCCNMF(_BlockDriver):
                      localize=localize)
 
     def _state(self):
-        return self.in_ring, self._outputs()[0], self.p.dHist, self.p.dHistPos, self.p.dTarget
+        return self.in_ring, self._outputs()[0], self.p.dHistState, self.p.dHistPos, self.p.dTarget
+
+    def _before_block(self):
+        self.p._spatial_on = self.p._apply_spatial()
 
     def _key(self):
         p = self.p
-        return (int(p.targetMode), bool(p.separationEnabled), bool(p.localizationEnabled), int(p.localizationWindowSize),
+        return (int(p.targetMode), bool(p.separationEnabled), p._spatial_on, bool(p.localizationEnabled), int(p.localizationWindowSize),
                 int(p.numHUpdates), p.dW.data_ptr(), p.dTarget.data_ptr(), p.generation,      # reset() re-allocates every buffer
                 p._sources if p.multiple() else 0, self._outputs()[0].data_ptr(), self._pin_out.data_ptr())
 
@@ -509,6 +556,7 @@ class StreamingGCCNMF(_BlockDriver):
     def process_block_device(self, block_in, block_out):
         """Device tensors in/out, asynchronous on the current stream (what a capture/playback loop would call); block_out is
         [numSources][2][blockSize] in multiple mode."""
+        self._before_block()
         self._call(block_in, block_out)
 
     def process_stream(self, stereoSamples):
@@ -525,8 +573,8 @@ class StreamingGCCNMFBank(_BlockDriver):
     ``processor`` is the shared configuration: its dictionary, TDOA grid, windows, twiddles, ``targetMode``, ``numHUpdates`` and
     ``localizationWindowSize``, and its ``separationEnabled`` / ``localizationEnabled`` as master switches.  The bank allocates its
     own per-stream state (rings, spectra, masks, history ring, target row) and never touches the processor's.  Each stream has a
-    target row {index, epsilon, beta, noiseFloor, separation, localisation, nlAlpha}: a stream separates (localises) when the processor's
-    switch and its own are both on, and localises on GCC-NONLIN when its nlAlpha word is > 0 (``setGCCPHATNL``).  After ``processor.reset()`` the next call re-allocates all per-stream state.
+    target row {index, epsilon, beta, noiseFloor, separation, localisation, nlAlpha, spatialFilterFrames}: a stream separates (localises) when the processor's
+    switch and its own are both on, and localises on GCC-NONLIN when its nlAlpha word is > 0 (``setGCCPHATNL``), and runs the online spatial filter behind its mask when its last word holds a time constant (``setSpatialFilter``).  After ``processor.reset()`` the next call re-allocates all per-stream state.
 
     The GUI's host mirrors (``GCCNMFProcessor.fill_histories``) are not produced for a bank.
 
@@ -546,7 +594,7 @@ class StreamingGCCNMFBank(_BlockDriver):
 
     # ---- per-stream state ----------------------------------------------------------------------------------------------
     def _initial_row(self):
-        row = np.concatenate([self.p._target_host, np.array([1, 1, self.p._nl_word, 0], np.float32)]).astype(np.float32)
+        row = np.concatenate([self.p._target_host, np.array([1, 1, self.p._nl_word, self.p._spatial_word()], np.float32)]).astype(np.float32)
         if self._multi:                    # + the processor's target indexes (words 8..)
             tau = np.zeros(8, np.float32)
             tau[:self._sources] = self.p.targetTDOAIndexes
@@ -572,7 +620,9 @@ class StreamingGCCNMFBank(_BlockDriver):
         self.dTfMask, self.dGccPhat = z(*lead, 2, F, Tc), z(S, D, Tc)
         self.dHist, self.dHistPos = z(S, D, p.numTDOAHistory), z(S, dtype=torch.int32)
         self.dHcoef, self.dRv = None, None     # coefficient-inference scratch: allocated with the first call that needs it
+        self.dHistState, self.dSpatial = self.dHist, None      # the spatial filter's covariances behind the histories: likewise
         self._row0 = self._initial_row()
+        self._spatial_rows = np.full(S, self._row0[7], np.float32)      # host copy of word 7 of every row
         self.dTarget = torch.from_numpy(np.tile(self._row0, (S, 1))).to(self.device)
         self._targets = self._row0[0].repeat(S).astype(np.float32)      # host copy of the tracked indexes
         self._tindexes = np.tile(self._row0[8:8 + self._sources], (S, 1)) if self._multi else None    # multiple mode's, (S, N)
@@ -587,6 +637,18 @@ class StreamingGCCNMFBank(_BlockDriver):
             S, F, Tc, Kp = self.numStreams, self.p.numFrequencies, self.p.numTimePerChunk, self.p.Kp
             self.dHcoef = torch.zeros((S, Kp, Tc, 2), dtype=torch.float32, device=self.device)
             self.dRv = torch.zeros((S, F, Tc, 2), dtype=torch.float32, device=self.device)
+        if self._spatial_call() and self.dSpatial is None:
+            # the block call finds the covariances [S][NC][F][4] behind the S history images: one buffer, the histories carried over
+            S, F, D, Lh = self.numStreams, self.p.numFrequencies, self.p.numTDOAs, self.p.numTDOAHistory
+            NC = self._sources if self._multi else 2
+            at = _hip.rt_spatial_state_offset(D, Lh, S)
+            both = torch.zeros(at + _hip.rt_spatial_state_floats(F, NC, S), dtype=torch.float32, device=self.device)
+            both[:S * D * Lh].copy_(self.dHist.reshape(-1))
+            self.dHistState, self.dHist, self.dSpatial = both, both[:S * D * Lh].view(S, D, Lh), both[at:].view(S, NC, F, 4)
+
+    def _spatial_call(self):
+        """The call-level switch of the spatial filter: some stream's row word 7 holds a time constant."""
+        return bool((self._spatial_rows > 0).any())
 
     def _stream_index(self, s):
         if int(s) != s or not 0 <= int(s) < self.numStreams:
@@ -628,6 +690,19 @@ class StreamingGCCNMFBank(_BlockDriver):
         self.dTarget[s, 6] = a if on else 0.0
 
     @_on_device
+    def setSpatialFilter(self, s, enabled, frames=None):
+        """Word 7 of stream s's row: the online spatial filter for this stream alone (``spatialFilterEnabled`` / ``spatialFilterFrames``;
+        initially the processor's).  frames: the time constant of its covariances, None = the processor's ``spatialFilterFrames``.  Takes
+        effect with the next block and keeps the stream's covariances (``reset_stream`` clears them).  Switching the first stream on (or
+        the last one off) changes the call itself, so a captured graph is taken again; every other toggle only writes the row."""
+        s = self._stream_index(s)
+        on, tau = _hip.check_spatial_filter(enabled, self.p.spatialFilterFrames if frames is None else frames)
+        self._ensure_state()
+        self._spatial_rows[s] = tau if on else 0.0
+        self._ensure_state()
+        self.dTarget[s, 7] = float(self._spatial_rows[s])
+
+    @_on_device
     def setTargetTDOAIndexes(self, s, indexes):
         """Multiple mode: words 8.. of stream s's row (``GCCNMFProcessor.setTargetTDOAIndexes`` for one stream)."""
         s = self._stream_index(s)
@@ -645,9 +720,11 @@ class StreamingGCCNMFBank(_BlockDriver):
         touched."""
         s = self._stream_index(s)
         self._ensure_state()
-        for t in (self.in_ring, self.out_ring, self.dHist, self.dHistPos):
+        for t in (self.in_ring, self.out_ring, self.dHist, self.dHistPos) + (() if self.dSpatial is None else (self.dSpatial,)):
             t[s].zero_()
         row = self._initial_row()
+        self._spatial_rows[s] = row[7]
+        self._ensure_state()
         self.dTarget[s].copy_(torch.from_numpy(row))
         self._targets[s] = row[0]
         if self._multi:
@@ -683,15 +760,17 @@ class StreamingGCCNMFBank(_BlockDriver):
         _hip.rt_process_block(block_in, block_out, self.in_ring, self.out_ring, self.dX, self.dY, self.dC, self.dHMask, self.dArgmax,
                               self.dTfMask, self.dHist, self.dHistPos, self.dTarget, self.dGccPhat, *p._tables(), self.dHcoef, self.dRv,
                               *p._settings(self.hopSize, self.blockSize), p.numHUpdates, self.outputDelayBlocks, localize=localize,
-                              streams=self.numStreams, targets=self._sources if self._multi else None)
+                              streams=self.numStreams, targets=self._sources if self._multi else None,
+                              spatial=self._spatial_call() and bool(p.separationEnabled))
 
     def _state(self):
-        return self.in_ring, self.out_ring, self.dHist, self.dHistPos, self.dTarget
+        return self.in_ring, self.out_ring, self.dHistState, self.dHistPos, self.dTarget
 
     def _key(self):
         p = self.p
         return (int(p.targetMode), bool(p.separationEnabled), bool(p.localizationEnabled), int(p.localizationWindowSize),
-                int(p.numHUpdates), p.dW.data_ptr(), self.dTarget.data_ptr(), p.generation, self._layout_key, self._pin_out.data_ptr())
+                int(p.numHUpdates), p.dW.data_ptr(), self.dTarget.data_ptr(), p.generation, self._layout_key, self._pin_out.data_ptr(),
+                self._spatial_call(), self.dHist.data_ptr())
 
     def _check_block(self, blocks):
         if blocks.shape != (self.numStreams, 2, self.blockSize):

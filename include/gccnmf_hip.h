@@ -576,8 +576,40 @@ int gccnmf_rt_process_block(const float* block_in, float* block_out, float* in_r
  *                                  bank and leaves both signatures alone.  The bank and multi-target rows always have word 6; the
  *                                  single-stream row is 4 words unless 1 << 24 says it has 8 (words 4, 5, 7 unused there).
  *                                  GCCNMF_ERR_ARG: 1 << 24 together with 8 or 1 << 20, any bit above 24.
+ *   separation_enabled bit 1       GCCNMF_RT_SEPARATION_SPATIAL (callers pass 3): the online spatial (multichannel Wiener) filter, one
+ *                                  more launch (csrc/rt_spatial.hip) between the mask and the synthesis kernel, which rewrites Y in place.
+ *                                  It is the local Gaussian model of gccnmf_reconstruct's spatial mode with a recursive covariance in
+ *                                  place of the sum over the file.  Per stream and bin f, components j < NC, frames in ascending order:
+ *                                    multi-target layout: NC = N, E_j,c = Y_j,c as the mask kernel wrote it; single-target layouts:
+ *                                    NC = 2, E_0 = Y (the talker), E_1 = X - E_0 (the residual; component-wise, float32)
+ *                                    c_j = (|E_j,0|^2, |E_j,1|^2, Re E_j,0 conj E_j,1, Im E_j,0 conj E_j,1),  v_j = 1/2 (c_j.p0 + c_j.p1)
+ *                                    P_j <- a P_j + b c_j, b = 1 / tau, a = 1 - b, BEFORE use, and only when X and every c_j of the
+ *                                    (bin, frame) are finite: otherwise the bin's state stays bit for bit (a NaN block does not
+ *                                    poison a stream; NaN / Inf still propagate into that frame's Y)
+ *                                    R_j = P_j / n_j, n_j = 1/2 (P_j.p0 + P_j.p1), R_j = I when n_j < 2^-126 (nothing averaged yet);
+ *                                    R~_j = R_j + GCCNMF_SPATIAL_LOADING I;  Sigma = sum_j v_j R~_j, y = Sigma^-1 X, Y'_j = v_j R~_j y,
+ *                                    0 where sum_j v_j = 0 -- float32, the offline filter's arithmetic (and its power-of-two scaling
+ *                                    of the v_j) statement for statement; 1 / tau and 1 / n_j are one IEEE division each
+ *                                    written: Y_j <- Y'_j for all j (multi-target), Y <- Y'_0 (single-target)
+ *                                  So the N outputs of the multi-target layout add up to X, N = 1 returns X, swapping the input channels
+ *                                  swaps the output channels, tau = 1 has no memory, and a call of Tc frames equals Tc calls of one.
+ *                                  Per stream: word 7 of the target row is tau in frames; a finite float >= 1 switches the stream's
+ *                                  filter on, anything else reads as off.  A stream whose separation is off (row word 4 in the bank,
+ *                                  or separation_enabled = 0) skips the stage and leaves its state alone.  The 4-word single-stream
+ *                                  row has no word 7: the bit there needs 1 << 24 (GCCNMF_ERR_ARG otherwise, before any launch).
+ *                                  State: behind the S history images of `hist` -- the call's other persistent statistic that a reset
+ *                                  clears -- starting at float GCCNMF_RT_SPATIAL_STATE_OFFSET(S, D, numTDOAHistory) (the first multiple
+ *                                  of 4), [S][NC][F][4] float32 = (p0, p1, Re q, Im q): GCCNMF_RT_SPATIAL_STATE_FLOATS(S, NC, F) floats;
+ *                                  `hist` must then be 16-byte aligned (GCCNMF_ERR_ARG).  All zeros = a fresh stream: its first
+ *                                  frame sees its own rank-1 covariance plus the loading, and the trace normalisation makes a bias
+ *                                  correction of the zero start unnecessary.  The localisation-only call (bit 4 of frames_mode) does
+ *                                  not touch the state.  Without bit 1 a call computes what it computed before the filter existed,
+ *                                  whatever word 7 holds, and `hist` needs no more than its S images.
  *   out_delay_blocks               which finished block is handed out: 2 = the reference (utils.py:116); 1 is complete when
  *                                  the synthesis window spans at most two hops */
+#define GCCNMF_RT_SEPARATION_SPATIAL 2
+#define GCCNMF_RT_SPATIAL_STATE_OFFSET(S, D, Lh) ((((long)(S) * (D) * (Lh) + 3) / 4) * 4)
+#define GCCNMF_RT_SPATIAL_STATE_FLOATS(S, NC, F) (4L * (S) * (NC) * (F))
 int gccnmf_rt_process_block_ll(const float* block_in, float* block_out, float* in_ring, float* out_ring, float* X, float* Y, float* C,
                                float* HMask, int* argmaxTDOA, float* tfMask, float* hist, int* hist_pos, float* target,
                                float* gccphat, const float* W, const float* cosT, const float* sinT, const float* window,
