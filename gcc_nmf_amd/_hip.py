@@ -495,6 +495,8 @@ GCCNMF_RECONSTRUCT_RATIO = 0x100        # include/gccnmf_hip.h: the ratio-mask m
 RATIO_MAX_TARGETS = 8                   # csrc/ratio.h, csrc/spatial.h
 GCCNMF_RECONSTRUCT_SPATIAL_BIT = 1 << 16  # include/gccnmf_hip.h: the spatial filter behind the ratio stage, in the upper half of gccnmf_reconstruct's batch
 GCCNMF_SPATIAL_LOADING = 1e-3           # include/gccnmf_hip.h: the diagonal loading of the spatial covariances
+GCCNMF_RECONSTRUCT_SPATIAL_ITERATIONS_SHIFT = 20   # include/gccnmf_hip.h: GCCNMF_RECONSTRUCT_SPATIAL_ITERATIONS(n), bits 20-27 of gccnmf_reconstruct's S
+MAX_SPATIAL_ITERATIONS = 255
 
 
 def check_reconstruction(reconstruction, numTargets):
@@ -504,6 +506,27 @@ def check_reconstruction(reconstruction, numTargets):
     if reconstruction != 'direct' and not 1 <= int(numTargets) <= RATIO_MAX_TARGETS:
         raise ValueError("reconstruction=%r takes 1 to %d targets, got %d" % (reconstruction, RATIO_MAX_TARGETS, int(numTargets)))
     return reconstruction
+
+
+def check_spatial_iterations(spatialIterations, reconstruction):
+    """The ``spatialIterations`` keyword (EM iterations behind reconstruction='spatial', csrc/spatial_em.hip); ValueError before any
+    device work.  An int from 0 to 255; above 0 only with 'spatial'."""
+    n = spatialIterations
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or not 0 <= int(n) <= MAX_SPATIAL_ITERATIONS:
+        raise ValueError('spatialIterations must be an int from 0 to %d, got %r' % (MAX_SPATIAL_ITERATIONS, n))
+    if int(n) and reconstruction != 'spatial':
+        raise ValueError("spatialIterations=%d needs reconstruction='spatial', got %r" % (int(n), reconstruction))
+    return int(n)
+
+
+def reconstruct_word(S, mode, iterations=0):
+    """The S argument of gccnmf_reconstruct: the target count with the mode above its low byte (GCCNMF_RECONSTRUCT_RATIO for 'ratio'
+    and 'spatial', GCCNMF_RECONSTRUCT_SPATIAL_ITERATIONS(n) for the EM refinement of 'spatial')."""
+    iterations = check_spatial_iterations(iterations, mode)
+    word = int(S)
+    if mode != 'direct':
+        word |= GCCNMF_RECONSTRUCT_RATIO
+    return word | (iterations << GCCNMF_RECONSTRUCT_SPATIAL_ITERATIONS_SHIFT)
 
 
 def reconstruct_spatial_batch(batch):
@@ -518,26 +541,35 @@ def reconstruct_spatial_workspace_floats(batch, S, Fp):
     return 4 * int(batch) * int(S) * int(Fp)
 
 
-def reconstruct_workspace_floats(mode, T, K, S, batch, Fp):
+def reconstruct_spatial_em_workspace_floats(batch, S, Fp, Tp):
+    """Floats of that workspace with EM iterations: GCCNMF_RECONSTRUCT_SPATIAL_EM_WORKSPACE_FLOATS(batch, S, Fp, Tp), the covariances
+    followed by the powers [batch][S][Fp][Tp]; Tp = round_up(T, 64)."""
+    return reconstruct_spatial_workspace_floats(batch, S, Fp) + int(batch) * int(S) * int(Fp) * int(Tp)
+
+
+def reconstruct_workspace_floats(mode, T, K, S, batch, Fp, iterations=0):
     """Floats of the workspace ``reconstruct`` takes in that mode: the masked H of 'direct', nothing for 'ratio' (one fused launch),
-    the covariances [batch][S][Fp][4] of 'spatial'."""
+    the covariances [batch][S][Fp][4] of 'spatial', followed by the powers [batch][S][Fp][Tp] when it runs EM iterations."""
+    iterations = check_spatial_iterations(iterations, mode)
     if mode == 'direct':
         return lib().gccnmf_reconstruct_workspace_floats(T, K, S, batch)
+    if mode == 'spatial' and iterations:
+        return reconstruct_spatial_em_workspace_floats(batch, S, Fp, -(-int(T) // 64) * 64)
     return reconstruct_spatial_workspace_floats(batch, S, Fp) if mode == 'spatial' else 0
 
 
-def reconstruct(W, H, argmax, masks, X, V, F, T, K, S, batch, spec, mode='direct', workspace=None, stream=None):
+def reconstruct(W, H, argmax, masks, X, V, F, T, K, S, batch, spec, mode='direct', workspace=None, iterations=0, stream=None):
     """Target spectrograms from the arg-max image or the masks (either may be None).  'ratio' reads neither V nor a workspace;
     'spatial' is the ratio launch, then the covariance reduction and the 2 x 2 filter over spec in place, with the covariances in
-    ``workspace`` (a missing 'direct' workspace is the library's GCCNMF_ERR_ARG, as a missing V is)."""
+    ``workspace`` (a missing 'direct' workspace is the library's GCCNMF_ERR_ARG, as a missing V is); ``iterations`` EM iterations run
+    between the two in one launch, and ``workspace`` then holds the powers too (reconstruct_workspace_floats(..., iterations))."""
     if mode not in RECONSTRUCTIONS:
         raise ValueError('unknown reconstruction mode %r' % (mode,))
+    S = reconstruct_word(S, mode, iterations)
     if mode == 'spatial':
         if workspace is None:
             raise ValueError("reconstruction='spatial' needs its covariance workspace (reconstruct_workspace_floats)")
         batch = reconstruct_spatial_batch(batch)
-    if mode != 'direct':
-        S |= GCCNMF_RECONSTRUCT_RATIO
     _stage('gccnmf_reconstruct', W, H, argmax, masks, X, V, F, T, K, S, batch, None if mode == 'ratio' else workspace, spec, stream=stream)
 
 

@@ -553,12 +553,14 @@ int gccnmf_reconstruct(const float* W, const float* H, const unsigned char* argm
     // every check comes before the first HIP call
     const int mode = S & ~0xff;
     S &= 0xff;
-    if (mode & ~GCCNMF_RECONSTRUCT_RATIO) return GCCNMF_ERR_ARG;
-    const bool ratio = mode == GCCNMF_RECONSTRUCT_RATIO;      // needs neither V nor the masked-H workspace
+    if (mode & ~(GCCNMF_RECONSTRUCT_RATIO | GCCNMF_RECONSTRUCT_SPATIAL_ITERATIONS(0xff))) return GCCNMF_ERR_ARG;
+    const bool ratio = (mode & GCCNMF_RECONSTRUCT_RATIO) != 0;      // needs neither V nor the masked-H workspace
+    const int iterations = (mode >> 20) & 0xff;              // EM iterations of the spatial mode: the powers follow the covariances in workspace
     if (batch < 1 || (batch & ~(0xffff | GCCNMF_RECONSTRUCT_SPATIAL_BIT))) return GCCNMF_ERR_ARG;
     const bool spatial = (batch & GCCNMF_RECONSTRUCT_SPATIAL_BIT) != 0;     // the spatial filter behind the ratio stage: covariances in workspace
     batch &= 0xffff;
     if (spatial && !ratio) return GCCNMF_ERR_ARG;
+    if (iterations && !spatial) return GCCNMF_ERR_ARG;
     if (!W || !H || (!argmax && !masks) || !X || (!ratio && (!V || !workspace)) || !spec || F < 2 || T < 1 || K < 1 || S < 1 || batch < 1)
         return GCCNMF_ERR_ARG;
     if (spatial && (!workspace || ((uintptr_t)workspace & 15))) return GCCNMF_ERR_ARG;
@@ -567,7 +569,10 @@ int gccnmf_reconstruct(const float* W, const float* H, const unsigned char* argm
     if (ratio) {
         const int rc = gccnmf_launch_ratio(W, H, argmax, masks, X, F, T, K, S, batch, spec, s);
         if (rc != GCCNMF_OK || !spatial) return rc;
-        return gccnmf_launch_spatial(X, F, T, S, batch, workspace, spec, s);
+        if (!iterations) return gccnmf_launch_spatial(X, F, T, S, batch, workspace, spec, s);
+        GccNmfPitches p = gccnmf_make_pitches(F, T, 1);
+        float* powers = workspace + GCCNMF_RECONSTRUCT_SPATIAL_WORKSPACE_FLOATS(batch, S, p.Fp);
+        return gccnmf_launch_spatial_em(X, F, T, S, batch, iterations, workspace, powers, spec, s);
     }
     GccNmfPitches p = gccnmf_make_pitches(F, T, K);
     const int ncol = 2 * S * p.Tp;

@@ -71,9 +71,10 @@ __global__ __launch_bounds__(256) void gcc_spatial_cov_kernel(const float2* __re
     }
 }
 
-template <int S>
-__global__ __launch_bounds__(256) void gcc_spatial_filter_kernel(const float2* __restrict__ X, const float4* __restrict__ cov, int F, int Fp,
-                                                                 int T, int Tp, float2* spec) {
+// WS: the powers come from the workspace of the EM refinement (spatial_em.hip) instead of the estimates in spec, which is then only written.
+template <int S, bool WS>
+__global__ __launch_bounds__(256) void gcc_spatial_filter_kernel(const float2* __restrict__ X, const float4* __restrict__ cov,
+                                                                 const float* __restrict__ powers, int F, int Fp, int T, int Tp, float2* spec) {
     const int lane = threadIdx.x & 63;
     const int f = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // < Fp: Fp is a multiple of 16
     const int b = blockIdx.y;
@@ -92,19 +93,32 @@ __global__ __launch_bounds__(256) void gcc_spatial_filter_kernel(const float2* _
 #pragma unroll
     for (int i = 0; i < S; ++i) r[i] = cov[((long)b * S + i) * Fp + f];
     for (int t = 2 * lane; t < Tp; t += 128) {                 // frames t, t + 1 < Tp
-        float4 e0[S], e1[S];
-#pragma unroll
-        for (int i = 0; i < S; ++i) {
-            e0[i] = *(const float4*)(O + (2 * i) * plane + t);
-            e1[i] = *(const float4*)(O + (2 * i + 1) * plane + t);
-        }
-        const float4 xa = *(const float4*)(x0 + t);
-        const float4 xb = *(const float4*)(x1 + t);
         float va[S], vb[S];
+        float4 xa, xb;
+        if constexpr (WS) {
+            const float* __restrict__ P = powers + (long)b * S * plane + (long)f * Tp + t;
 #pragma unroll
-        for (int i = 0; i < S; ++i) {
-            va[i] = spatial_power(e0[i].x, e0[i].y, e1[i].x, e1[i].y);
-            vb[i] = spatial_power(e0[i].z, e0[i].w, e1[i].z, e1[i].w);
+            for (int i = 0; i < S; ++i) {                      // written for the frames t < T only (t even: the pair of T - 1 too)
+                const float2 p = t < T ? *(const float2*)(P + i * plane) : make_float2(0.f, 0.f);
+                va[i] = p.x;
+                vb[i] = p.y;
+            }
+            xa = *(const float4*)(x0 + t);
+            xb = *(const float4*)(x1 + t);
+        } else {
+            float4 e0[S], e1[S];
+#pragma unroll
+            for (int i = 0; i < S; ++i) {
+                e0[i] = *(const float4*)(O + (2 * i) * plane + t);
+                e1[i] = *(const float4*)(O + (2 * i + 1) * plane + t);
+            }
+            xa = *(const float4*)(x0 + t);
+            xb = *(const float4*)(x1 + t);
+#pragma unroll
+            for (int i = 0; i < S; ++i) {
+                va[i] = spatial_power(e0[i].x, e0[i].y, e1[i].x, e1[i].y);
+                vb[i] = spatial_power(e0[i].z, e0[i].w, e1[i].z, e1[i].w);
+            }
         }
         float2 a0[S], a1[S], b0[S], b1[S];
         spatial_frame<S>(r, va, xa.x, xa.y, xb.x, xb.y, t < T, a0, a1);
@@ -118,27 +132,44 @@ __global__ __launch_bounds__(256) void gcc_spatial_filter_kernel(const float2* _
 }
 
 template <int S>
-static void spatial_filter_launch(const float* X, const float* cov, int F, int Fp, int T, int Tp, int batch, float* spec, hipStream_t s) {
-    hipLaunchKernelGGL((gcc_spatial_filter_kernel<S>), dim3(Fp / 4, batch), dim3(256), 0, s, (const float2*)X, (const float4*)cov, F, Fp, T,
-                       Tp, (float2*)spec);
+static void spatial_filter_launch(const float* X, const float* cov, const float* powers, int F, int Fp, int T, int Tp, int batch, float* spec,
+                                  hipStream_t s) {
+    if (powers)
+        hipLaunchKernelGGL((gcc_spatial_filter_kernel<S, true>), dim3(Fp / 4, batch), dim3(256), 0, s, (const float2*)X, (const float4*)cov,
+                           powers, F, Fp, T, Tp, (float2*)spec);
+    else
+        hipLaunchKernelGGL((gcc_spatial_filter_kernel<S, false>), dim3(Fp / 4, batch), dim3(256), 0, s, (const float2*)X, (const float4*)cov,
+                           powers, F, Fp, T, Tp, (float2*)spec);
 }
 
-int gccnmf_launch_spatial(const float* X, int F, int T, int S, int batch, float* cov, float* spec, hipStream_t s) {
+int gccnmf_launch_spatial_cov(int F, int T, int S, int batch, const float* spec, float* cov, hipStream_t s) {
     if (S < 1 || S > GCCNMF_SPATIAL_MAX_TARGETS || batch > 65535) return GCCNMF_ERR_UNSUPPORTED;
     GccNmfPitches p = gccnmf_make_pitches(F, T, 1);
     hipLaunchKernelGGL(gcc_spatial_cov_kernel, dim3(gccnmf_ceil_div(F, 4), S, batch), dim3(256), 0, s, (const float2*)spec, F, p.Fp, T, p.Tp,
                        S, (float4*)cov);
     GCCNMF_CHECK_LAUNCH();
+    return GCCNMF_OK;
+}
+
+int gccnmf_launch_spatial_filter(const float* X, const float* cov, const float* powers, int F, int T, int S, int batch, float* spec,
+                                 hipStream_t s) {
+    if (S < 1 || S > GCCNMF_SPATIAL_MAX_TARGETS || batch > 65535) return GCCNMF_ERR_UNSUPPORTED;
+    GccNmfPitches p = gccnmf_make_pitches(F, T, 1);
     switch (S) {
-        case 1: spatial_filter_launch<1>(X, cov, F, p.Fp, T, p.Tp, batch, spec, s); break;
-        case 2: spatial_filter_launch<2>(X, cov, F, p.Fp, T, p.Tp, batch, spec, s); break;
-        case 3: spatial_filter_launch<3>(X, cov, F, p.Fp, T, p.Tp, batch, spec, s); break;
-        case 4: spatial_filter_launch<4>(X, cov, F, p.Fp, T, p.Tp, batch, spec, s); break;
-        case 5: spatial_filter_launch<5>(X, cov, F, p.Fp, T, p.Tp, batch, spec, s); break;
-        case 6: spatial_filter_launch<6>(X, cov, F, p.Fp, T, p.Tp, batch, spec, s); break;
-        case 7: spatial_filter_launch<7>(X, cov, F, p.Fp, T, p.Tp, batch, spec, s); break;
-        default: spatial_filter_launch<8>(X, cov, F, p.Fp, T, p.Tp, batch, spec, s); break;
+        case 1: spatial_filter_launch<1>(X, cov, powers, F, p.Fp, T, p.Tp, batch, spec, s); break;
+        case 2: spatial_filter_launch<2>(X, cov, powers, F, p.Fp, T, p.Tp, batch, spec, s); break;
+        case 3: spatial_filter_launch<3>(X, cov, powers, F, p.Fp, T, p.Tp, batch, spec, s); break;
+        case 4: spatial_filter_launch<4>(X, cov, powers, F, p.Fp, T, p.Tp, batch, spec, s); break;
+        case 5: spatial_filter_launch<5>(X, cov, powers, F, p.Fp, T, p.Tp, batch, spec, s); break;
+        case 6: spatial_filter_launch<6>(X, cov, powers, F, p.Fp, T, p.Tp, batch, spec, s); break;
+        case 7: spatial_filter_launch<7>(X, cov, powers, F, p.Fp, T, p.Tp, batch, spec, s); break;
+        default: spatial_filter_launch<8>(X, cov, powers, F, p.Fp, T, p.Tp, batch, spec, s); break;
     }
     GCCNMF_CHECK_LAUNCH();
     return GCCNMF_OK;
+}
+
+int gccnmf_launch_spatial(const float* X, int F, int T, int S, int batch, float* cov, float* spec, hipStream_t s) {
+    const int rc = gccnmf_launch_spatial_cov(F, T, S, batch, spec, cov, s);
+    return rc != GCCNMF_OK ? rc : gccnmf_launch_spatial_filter(X, cov, nullptr, F, T, S, batch, spec, s);
 }

@@ -232,6 +232,8 @@ class GCCNMFEngine(object):
     csrc/ratio.hip; at most 8 targets); 'spatial' = the ratio mask followed by a multichannel Wiener filter (csrc/spatial.hip; DESIGN
     section 4c): one 2 x 2 spatial covariance per target and bin from the masked estimates, then the stereo mixture vector filtered with
     v_i R_i (sum_j v_j R_j)^-1 per (bin, frame) -- the targets still add up to the mixture, and the inter-channel phase is used.
+    ``spatialIterations`` (0 to 255, default 0; with 'spatial' only): that many EM iterations of the local Gaussian
+    model refine v_i and R_i between the two steps, in one launch (csrc/spatial_em.hip); 0 is the filter alone, bit for bit.
     Everything up to the coefficient masks is the same in all modes.
 
     ``gccPHATNLEnabled`` / ``gccPHATNLAlpha`` (the reference's settings, gccNMF/realtime/config.py:42-43): localise on the GCC-NONLIN
@@ -273,7 +275,7 @@ class GCCNMFEngine(object):
                  sparsityAlpha=0, epsilon=1e-16, seedValue=0, batch=1, windowFunction=np.hanning,
                  device='cuda:0', klnmf_flags=0, nmf_groups=None, dictionaryW=None, initialH='random', reconstruction='direct',
                  gccPHATNLEnabled=False, gccPHATNLAlpha=2.0, tdoaTracking=False, localizationWindowSize=None, tolerance=None, checkEvery=10,
-                 numFreeAtoms=0, maxTargets=None):
+                 numFreeAtoms=0, maxTargets=None, spatialIterations=0):
         self.autoTargets, numTargets = _hip.check_auto_targets(numTargets, maxTargets, tdoaTracking)
         if initialH not in ('random', 'ones'):
             raise ValueError("initialH must be 'random' or 'ones'")
@@ -286,6 +288,7 @@ class GCCNMFEngine(object):
         self.iterations_used = self.divergence_trace = None
         self.tdoaTracking, self.localizationWindowSize = check_tdoa_tracking(tdoaTracking, localizationWindowSize, numTargets)
         self.reconstruction = check_reconstruction(reconstruction, numTargets)
+        self.spatialIterations = _hip.check_spatial_iterations(spatialIterations, self.reconstruction)
         if self.reconstruction == 'spatial':
             _hip.reconstruct_spatial_batch(batch)          # at most 65535 files per call: ValueError here, not at the first reconstruct()
         self.gccPHATNLEnabled, self.gccPHATNLAlpha = check_gcc_phat_nl(gccPHATNLEnabled, gccPHATNLAlpha)
@@ -388,7 +391,8 @@ class GCCNMFEngine(object):
             self.scores = z(B, g.Kp, g.S * g.Tp)
             self.argmax = torch.zeros((B, g.Kp, g.Tp), dtype=torch.uint8, device=dev)
             self.ws_rec = z(self._reconstruct_workspace_floats()) if self.reconstruction == 'direct' else None
-            # the spatial mode's covariances [B][S][Fp][4]; an engine switched to 'spatial' later allocates them at its first reconstruct()
+            # the spatial mode's covariances [B][S][Fp][4], with spatialIterations followed by the powers [B][S][Fp][Tp]; an engine switched
+            # to 'spatial' or given more iterations later allocates them at its next reconstruct()
             self.ws_cov = z(self._reconstruct_workspace_floats()) if self.reconstruction == 'spatial' else None
             self.spec = z(B, 2 * g.S, g.Fp, g.Tp, 2)
             # windowed time frames [B][2S][T][n_fft]: only the two-kernel iSTFT needs them (allocated on first use); the default is the
@@ -537,15 +541,23 @@ class GCCNMFEngine(object):
 
     def _reconstruct_workspace_floats(self):
         g = self.g
-        return _hip.reconstruct_workspace_floats(self.reconstruction, g.T, g.K, g.S, self.batch, g.Fp)
+        return _hip.reconstruct_workspace_floats(self.reconstruction, g.T, g.K, g.S, self.batch, g.Fp, self.spatialIterations)
+
+    def _reconstruct_workspace(self):
+        """The workspace of the current mode; the spatial one is (re)allocated here when the mode or spatialIterations grew past it."""
+        if self.reconstruction != 'spatial':
+            _hip.check_spatial_iterations(self.spatialIterations, self.reconstruction)
+            return self.ws_rec
+        need = self._reconstruct_workspace_floats()
+        if self.ws_cov is None or self.ws_cov.numel() < need:
+            self.ws_cov = torch.zeros(need, dtype=torch.float32, device=self.device)
+        return self.ws_cov
 
     @_on_device
     def reconstruct(self):
         g = self.g
-        if self.reconstruction == 'spatial' and self.ws_cov is None:
-            self.ws_cov = torch.zeros(self._reconstruct_workspace_floats(), dtype=torch.float32, device=self.device)
         _hip.reconstruct(self.W, self.H, self.argmax, None, self.X, self.V, g.F, g.T, g.K, g.S, self.batch, self.spec, mode=self.reconstruction,
-                         workspace=self.ws_cov if self.reconstruction == 'spatial' else self.ws_rec)
+                         workspace=self._reconstruct_workspace(), iterations=self.spatialIterations)
 
     @_on_device
     def istft(self, keep_frames=False):
@@ -848,7 +860,8 @@ class GCCNMFEnhancementEngine(GCCNMFEngine):
     ``localize()`` picks ONE peak of each file's mean angular spectrum as the talker's direction (with ``tdoaTracking``: one per frame);
     ``targetTDOAIndex`` -- one index, or one per file -- skips the pick.  ``separate()`` returns (batch, 2, 2, L) waveforms ordered
     [talker, noise], and so do ``separate_batches`` and ``separate_pcm16``; ``get_atom_tdoa_indexes()`` (batch, K, T).  Everything in
-    front of the masks is GCCNMFEngine's: ``dictionaryW``, ``numFreeAtoms``, ``tolerance``, ``reconstruction``, ``gccPHATNLEnabled``.
+    front of the masks is GCCNMFEngine's: ``dictionaryW``, ``numFreeAtoms``, ``tolerance``, ``reconstruction``,
+    ``spatialIterations``, ``gccPHATNLEnabled``.
     There is no ``numTargets`` keyword (two outputs), and no ragged form: ``lengths=`` raises ValueError."""
 
     def __init__(self, n_samples, *args, **kwargs):
@@ -911,11 +924,9 @@ class GCCNMFEnhancementEngine(GCCNMFEngine):
     @_on_device
     def reconstruct(self):
         g = self.g
-        if self.reconstruction == 'spatial' and self.ws_cov is None:
-            self.ws_cov = torch.zeros(self._reconstruct_workspace_floats(), dtype=torch.float32, device=self.device)
         _hip.reconstruct(self.W, self.H, None if self.targetMode else self.argmax, self.soft_masks, self.X, self.V, g.F, g.T, g.K, 2,
-                         self.batch, self.spec, mode=self.reconstruction,
-                         workspace=self.ws_cov if self.reconstruction == 'spatial' else self.ws_rec)
+                         self.batch, self.spec, mode=self.reconstruction, workspace=self._reconstruct_workspace(),
+                         iterations=self.spatialIterations)
 
     def get_atom_tdoa_indexes(self):
         """(batch, K, T) int32: the TDOA index of every atom in every frame (after masks())."""
@@ -945,10 +956,11 @@ class RaggedGCCNMFEngine(object):
                  numTargets=3, dictionarySize=None, numIterations=100, sparsityAlpha=0, epsilon=1e-16, seedValue=0,
                  windowFunction=np.hanning, device='cuda:0', klnmf_flags=0, dictionaryW=None, initialH='random', reconstruction='direct',
                  gccPHATNLEnabled=False, gccPHATNLAlpha=2.0, tdoaTracking=False, localizationWindowSize=None, tolerance=None, checkEvery=10,
-                 maxTargets=None):
+                 maxTargets=None, spatialIterations=0):
         self.tolerance, self.checkEvery, numIterations = _hip.check_convergence(tolerance, checkEvery, numIterations)
         self.autoTargets, slots = _hip.check_auto_targets(numTargets, maxTargets, tdoaTracking)
         self.reconstruction = check_reconstruction(reconstruction, slots)
+        self.spatialIterations = _hip.check_spatial_iterations(spatialIterations, self.reconstruction)
         self.gccPHATNLEnabled, self.gccPHATNLAlpha = check_gcc_phat_nl(gccPHATNLEnabled, gccPHATNLAlpha)
         self.tdoaTracking, self.localizationWindowSize = check_tdoa_tracking(tdoaTracking, localizationWindowSize, slots)
         if not torch.cuda.is_available():
@@ -967,7 +979,7 @@ class RaggedGCCNMFEngine(object):
                   windowFunction=windowFunction, device=device, klnmf_flags=klnmf_flags, dictionaryW=dictionaryW, initialH=initialH,
                   reconstruction=reconstruction, gccPHATNLEnabled=gccPHATNLEnabled, gccPHATNLAlpha=gccPHATNLAlpha,
                   tdoaTracking=tdoaTracking, localizationWindowSize=localizationWindowSize,     # (each file's windows end at its own T)
-                  tolerance=tolerance, checkEvery=checkEvery, maxTargets=maxTargets)
+                  tolerance=tolerance, checkEvery=checkEvery, maxTargets=maxTargets, spatialIterations=spatialIterations)
         # one ordinary engine per distinct length: its files (caller's indexes, ascending) are its batch
         self.files_of = {}
         for i, n in enumerate(self.lengths):

@@ -550,7 +550,8 @@ def getEnhancementCoefficientMasks(atomTDOAIndexes, targetTDOAIndex, targetMode=
     return masks
 
 
-def getTargetSpectrogramEstimates(targetCoefficientMasks, complexMixtureSpectrogram, W, stereoH, reconstruction='direct'):
+def getTargetSpectrogramEstimates(targetCoefficientMasks, complexMixtureSpectrogram, W, stereoH, reconstruction='direct',
+                                  spatialIterations=0):
     """gccNMF/gccNMFFunctions.py:145-151.  Returns (numTargets, 2, F, T) complex64.
 
     ``reconstruction='ratio'`` (not in the reference): the Wiener-like ratio mask X_c * W.(H_c o M_i) / den instead of W.(H_c o M_i) with
@@ -558,11 +559,13 @@ def getTargetSpectrogramEstimates(targetCoefficientMasks, complexMixtureSpectrog
     the targets add up to the mixture); any other mask array takes the soft form (den = W.H_c).  At most 8 targets.
 
     ``reconstruction='spatial'``: either form of the ratio mask followed by the multichannel Wiener filter of csrc/spatial.hip (one 2 x 2
-    spatial covariance per target and bin from the masked estimates, then v_i R_i (sum_j v_j R_j)^-1 applied to the stereo mixture)."""
+    spatial covariance per target and bin from the masked estimates, then v_i R_i (sum_j v_j R_j)^-1 applied to the stereo mixture);
+    ``spatialIterations`` (0 to 255) EM iterations of the local Gaussian model refine v_i and R_i in between (csrc/spatial_em.hip)."""
     M = np.asarray(targetCoefficientMasks)
     X = np.asarray(complexMixtureSpectrogram)
     S, K, T = M.shape
     check_reconstruction(reconstruction, S)
+    spatialIterations = _hip.check_spatial_iterations(spatialIterations, reconstruction)
     C, F, _ = X.shape
     if C != 2:
         raise ValueError('stereo spectrogram expected')
@@ -588,9 +591,9 @@ def getTargetSpectrogramEstimates(targetCoefficientMasks, complexMixtureSpectrog
         dH[:K, :g.N].unflatten(1, (2, T)).copy_(sc.upload(np.asarray(stereoH), 'stereoH', float32).permute(1, 0, 2))   # (K, [L | R])
         ws = None
         if reconstruction != 'ratio':
-            ws = sc.dev('ws_cov' if reconstruction == 'spatial' else 'ws_rec', (_hip.reconstruct_workspace_floats(reconstruction, T, K, S, 1, g.Fp),))
+            ws = sc.dev('ws_cov' if reconstruction == 'spatial' else 'ws_rec', (_hip.reconstruct_workspace_floats(reconstruction, T, K, S, 1, g.Fp, spatialIterations),))
         spec = sc.dev('spec', (2 * S, g.Fp, g.Tp, 2))
-        _hip.reconstruct(dW, dH, dA, dM, dX, dV, F, T, K, S, 1, spec, mode=reconstruction, workspace=ws)
+        _hip.reconstruct(dW, dH, dA, dM, dX, dV, F, T, K, S, 1, spec, mode=reconstruction, workspace=ws, iterations=spatialIterations)
         out = sc.download(torch.view_as_complex(spec)[:, :F, :T], shape=(S, 2, F, T))
         sc.remember(out, 'S', dict(spec=spec), dict(nsig=2 * S, F=F, T=T))
     return out

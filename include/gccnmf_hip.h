@@ -473,11 +473,38 @@ int gccnmf_magnitude(const float* X, int F, int T, int batch, float* V, void* st
  * channels swaps the output channels.  `workspace` holds the covariances, [batch][S][Fp][4] float32 = (R~00, R~11, Re R~01, Im R~01):
  * GCCNMF_RECONSTRUCT_SPATIAL_WORKSPACE_FLOATS(batch, S, Fp) floats, Fp = round_up(F, 16); it must be non-NULL and 16-byte aligned, else
  * GCCNMF_ERR_ARG.  `V` is not read.  A file's spec does not depend on the batch it is in or on its place there.  GCCNMF_ERR_ARG: the
- * spatial bit without GCCNMF_RECONSTRUCT_RATIO, any other bit above the low half of batch (so: a batch above 65535 in any mode). */
+ * spatial bit without GCCNMF_RECONSTRUCT_RATIO, any other bit above the low half of batch (so: a batch above 65535 in any mode).
+ *
+ * EM refinement of the spatial mode: pass S | GCCNMF_RECONSTRUCT_RATIO | GCCNMF_RECONSTRUCT_SPATIAL_ITERATIONS(n), 1 <= n <= 255 (bits
+ * 20-27 of S), with GCCNMF_RECONSTRUCT_SPATIAL_BATCH(batch).  The spatial mode above is step zero of the EM of the local Gaussian model
+ * (Duong, Vincent & Gribonval 2010); n iterations of it run in ONE launch (csrc/spatial_em.hip) between the covariance launch, whose
+ * bits are unchanged, and the filter launch.  Every (file, bin) row is independent.  Start: v_i and R~_i as above.  Iteration
+ * m = 1 ... n, for every bin f < F:
+ *   1. for every frame t < T, against the OLD R~, on w_j = v_j 2^-e as above:
+ *        Sigma = sum_j v_j R~_j (ascending j),  G_i = v_i R~_i Sigma^-1 (closed 2 x 2 Hermitian inverse),  s_i = G_i X,
+ *        C_i = s_i s_i^H + (I - G_i) v_i R~_i,   v'_i = max(0, 1/2 Re tr(R~_i^-1 C_i))   (stored unscaled),
+ *        v'_i = 0 for every i where sum_j v_j = 0.
+ *      Evaluated as v'_i = w_i v"_i, C_i = w_i C"_i with y = Sigma_w^-1 X, u_i = R~_i y, N_i = sum_{j != i} w_j R~_j (ascending j):
+ *        v"_i = 1/2 (w_i Re(y^H u_i) + 2^e tr(Sigma_w^-1 N_i)),   C"_i = w_i u_i u_i^H + 2^e N_i Sigma_w^-1 R~_i
+ *      (2 - tr G_i = tr(Sigma_w^-1 N_i) and (I - G_i) R~_i = N_i Sigma_w^-1 R~_i: sums of non-negative parts where the literal
+ *      forms cancel), float32, each product and sum rounded on its own.
+ *   2. A_i = sum over the frames with v'_i != 0 of C_i / v'_i (= C"_i / v"_i: float32 terms, the real parts of the diagonal and
+ *      the (0, 1) element; a NaN power counts), n_i = the number of those frames; the sum is float64, in an order fixed by T alone, as
+ *      the covariance launch does it.  R'_i = A_i / n_i, R'_i = I when n_i = 0;  R~'_i = R'_i + GCCNMF_SPATIAL_LOADING * 1/2 tr(R'_i) * I,
+ *      rounded to float32 once.  No trace renormalisation: only v R~ enters, and the per-frame M-step keeps the trace near 2.
+ *   3. v <- v', R~ <- R~'.
+ * Output: S'_i = v_i R~_i Sigma^-1 X by the filter above, on the final v and R~; every target 0 where sum_j v_j = 0; rows >= F and
+ * frames >= T are zeros; NaN / Inf propagate, and a NaN in one bin of X stays in that bin.  A power that is exactly 0 stays 0 (G_i = 0),
+ * so the frames a target skips are fixed by the input.  `workspace`: GCCNMF_RECONSTRUCT_SPATIAL_EM_WORKSPACE_FLOATS(batch, S, Fp, Tp)
+ * floats, 16-byte aligned: the covariances [batch][S][Fp][4] (the final R~ on return), then the powers [batch][S][Fp][Tp] float32 (the
+ * final v on return, frames < T of rows < F; not touched without the iteration bits).  GCCNMF_ERR_ARG, before any HIP call: the
+ * iteration bits without GCCNMF_RECONSTRUCT_RATIO or without the spatial bit of batch; bits 9-19 and 28-31 of S. */
 #define GCCNMF_RECONSTRUCT_RATIO 0x100
 #define GCCNMF_RECONSTRUCT_SPATIAL_BIT (1 << 16)
 #define GCCNMF_RECONSTRUCT_SPATIAL_BATCH(batch) ((batch) | GCCNMF_RECONSTRUCT_SPATIAL_BIT)
 #define GCCNMF_RECONSTRUCT_SPATIAL_WORKSPACE_FLOATS(batch, S, Fp) (4L * (batch) * (S) * (Fp))
+#define GCCNMF_RECONSTRUCT_SPATIAL_ITERATIONS(n) ((n) << 20)
+#define GCCNMF_RECONSTRUCT_SPATIAL_EM_WORKSPACE_FLOATS(batch, S, Fp, Tp) (4L * (batch) * (S) * (Fp) + (long)(batch) * (S) * (Fp) * (Tp))
 #define GCCNMF_SPATIAL_LOADING 1e-3
 long gccnmf_reconstruct_workspace_floats(int T, int K, int S, int batch);
 int gccnmf_reconstruct(const float* W, const float* H, const unsigned char* argmax, const float* masks,
