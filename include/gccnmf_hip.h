@@ -243,7 +243,28 @@ int gccnmf_klnmf_stage(const float* V, float* W, float* H, float* workspace, int
  *   step A: H update with the current W, then partial[0:Fp*Kp] = sum_files (V/WH).H^T and
  *           partial[Fp*Kp : Fp*Kp+Kp] = sum_files rowsum(H)   (deterministic file-order sum)
  *   step B: W *= num/den, atom normalisation, and the compensating H rescale (applied lazily
- *           through `workspace`; gccnmf_klnmf_shared_finish materialises it). */
+ *           through `workspace`; gccnmf_klnmf_shared_finish materialises it).
+ * Where the four calls keep their intermediates (tests read them by offset; floats from `workspace`; V [batch][Fp][Np], H [batch][Kp][Np],
+ * W [Fp][Kp] with zero padding, as everywhere):
+ *     R            [batch][Fp][Np]   zero outside f < F, n < N from begin on (a reduction operand of K2 and K4a)
+ *     Upart        [batch][Fp][Kp]   per file (V/WH).H^T; its padding is nobody's operand and keeps whatever the workspace held
+ *     rowsum_part  [batch][Kp]       per file rowsum(H)
+ *     (batch == 1 only: 4 * (max(Fp * Np, Fp * Kp) + Kp) floats kept for the lab build's split reductions, then the direct kernels'
+ *      transposed copies  Wt [Kp][Fp] | Ht [Np][Kp] | Rt [Np][Fp])
+ *     colsumW      [Kp]              one vector for every file, as W is one dictionary
+ *     hscale       [Kp]              the lazy atom scale: the H of the algorithm is hscale * H until finish
+ *   = gccnmf_klnmf_shared_workspace_floats(F, N, K, batch) floats.  partial = num [Fp][Kp] | den [Kp] = gccnmf_klnmf_shared_partial_floats.
+ * A shard of gccnmf_klnmf_shared_run (below) has the same workspace without the two trailing vectors -- they are the call's `vec`,
+ * colsumW [Kp] | hscale [Kp] -- and, for ld > 0, R as ONE [Fp][ld] matrix with file b at columns [b*N, b*N + N) (from column 0 whatever
+ * column of the caller's matrix V and H point at); the single-file blocks are present for batch == 1 with ld == 0 or ld == Np.
+ * Which call writes what (everything else keeps its bits; the padding of W, H, R and Rt stays zero):
+ *     begin    colsumW = sum_f W, hscale = 1, R = 0 (single-file layout: Wt = Ht = Rt = 0 as well)
+ *     step A   H, R (= V / W.H with the new H), Upart, rowsum_part, partial: per shard s = 0; s += part[b] for b = 0, 1, ... in float32,
+ *              partial = s for the call's first shard, partial + s for each later one.  One file under the default tuning takes the direct
+ *              kernels: Wt = W^T, Ht = (new H)^T, the final quotient is written transposed to Rt and, of R itself, to bin F - 1 alone
+ *              (F = 16 n + 1) -- the rest of R keeps K1's quotient.
+ *     step B   W, hscale, colsumW from partial (num, den); Wt is not touched (step A transposes W anew every time)
+ *     finish   H *= hscale, then hscale = 1 (all Kp entries) */
 long gccnmf_klnmf_shared_workspace_floats(int F, int N, int K, int batch);
 long gccnmf_klnmf_shared_partial_floats(int F, int K);
 int gccnmf_klnmf_shared_begin(const float* W, float* workspace, int F, int N, int K, int batch, void* stream);

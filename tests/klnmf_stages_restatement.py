@@ -171,17 +171,19 @@ def zero_lines(F, N, b):
     return (F // 3 + 7 * b) % (F - 1), ((N // 2 + 3 * b) % (N - 1) if N >= 8 else None)
 
 
-def problem(F, N, K, files, lines=True):
-    """`files` independent problems: V (files, F, N) low rank plus noise with isolated exact zeros and, with `lines`, one all-zero row and one
-    all-zero column per file (zero_lines); W (files, F, K), H (files, K, N) positive; s (files, K) in [0.5, 2) -- the lazy scale a stage-1 /
-    stage-2 launch meets in every iteration but the first.  float32, read-only."""
+def problem(F, N, K, files, lines=True, frames=True):
+    """`files` independent problems: V (files, F, N) low rank plus noise with isolated exact zeros and, with `lines`, one all-zero row and --
+    unless `frames` is off -- one all-zero column per file (zero_lines); W (files, F, K), H (files, K, N) positive; s (files, K) in
+    [0.5, 2) -- the lazy scale a stage-1 / stage-2 launch meets in every iteration but the first.  float32, read-only.
+    frames=False is for callers that cannot restore H between the H update and stage 3 (the shared-dictionary step A,
+    tests/shared_protocol_restatement.py): a silent frame's column of H is exactly 0 after stage 2 and stage 3 divides 0 by 0 there."""
     rng = np.random.RandomState(F * 7 + N * 3 + K)
     V = np.stack([low_rank_plus_noise(F, N, 5, 0.3, F + N + 17 * b) for b in range(files)])
     if lines:
         for b in range(files):
             f0, n0 = zero_lines(F, N, b)
             V[b, f0, :] = 0
-            if n0 is not None:
+            if frames and n0 is not None:
                 V[b, :, n0] = 0
     W = (rng.rand(files, F, K) + 0.01).astype(np.float32)
     H = (rng.rand(files, K, N) + 0.01).astype(np.float32)
