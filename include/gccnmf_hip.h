@@ -490,6 +490,13 @@ int gccnmf_magnitude(const float* X, int F, int T, int batch, float* V, void* st
  *   the binary exponent of sum_j v_j: S'_i = w_i R~_i (sum_j w_j R~_j)^-1 X is the same quantity, has the same roundings while every
  *   intermediate of the unscaled form is a normal float32 number, and stays accurate where that form's determinant would underflow (a
  *   nearly silent frame).
+ *   The order of the float64 frame sums (p_0, p_1, Re q, Im q here; the four sums of A_i in the EM refinement below), which makes R~ a
+ *   function of the row's bits alone: the frames are dealt to 64 lanes; lane l adds its frames 2l, 2l+1, 2l+128, 2l+129, ... (those
+ *   below T) one after the other to +0.0, each term formed in float64 from the float32 estimates (|S|^2 = re re + im im: two exact
+ *   products, one rounded sum; likewise the two parts of q); the 64 partial sums x[0 .. 63] are then combined in six steps
+ *   k = 1, 2, 4, 8, 16, 32 of x[l] <- x[l] + x[l ^ k], every l at once, after which every lane holds the same sum.  Then, in float64,
+ *   n = 1/2 (p_0 + p_1), the four quotients by n, + GCCNMF_SPATIAL_LOADING on the diagonal, and the one rounding to float32.
+ *   tests/spatial_checks.py restates this order (device_sum); with it a float32 NumPy evaluation equals the device bit for bit.
  * The targets still add up to the mixture (sum_i S'_i = Sigma y = X up to rounding), one target returns it, and swapping the input
  * channels swaps the output channels.  `workspace` holds the covariances, [batch][S][Fp][4] float32 = (R~00, R~11, Re R~01, Im R~01):
  * GCCNMF_RECONSTRUCT_SPATIAL_WORKSPACE_FLOATS(batch, S, Fp) floats, Fp = round_up(F, 16); it must be non-NULL and 16-byte aligned, else
@@ -512,7 +519,10 @@ int gccnmf_magnitude(const float* X, int F, int T, int batch, float* V, void* st
  *   2. A_i = sum over the frames with v'_i != 0 of C_i / v'_i (= C"_i / v"_i: float32 terms, the real parts of the diagonal and
  *      the (0, 1) element; a NaN power counts), n_i = the number of those frames; the sum is float64, in an order fixed by T alone, as
  *      the covariance launch does it.  R'_i = A_i / n_i, R'_i = I when n_i = 0;  R~'_i = R'_i + GCCNMF_SPATIAL_LOADING * 1/2 tr(R'_i) * I,
- *      rounded to float32 once.  No trace renormalisation: only v R~ enters, and the per-frame M-step keeps the trace near 2.
+ *      rounded to float32 once.  The order is the one stated for the covariance launch above: lane l adds the float32 terms of its
+ *      frames 2l, 2l+1, 2l+128, ... to +0.0 in float64 and counts them, a frame whose v'_i is 0 adding nothing and not counting; the
+ *      same six-step combination; then A_i / n_i, + GCCNMF_SPATIAL_LOADING * (1/2 (R'00 + R'11)) on the diagonal, one rounding.
+ *      No trace renormalisation: only v R~ enters, and the per-frame M-step keeps the trace near 2.
  *   3. v <- v', R~ <- R~'.
  * Output: S'_i = v_i R~_i Sigma^-1 X by the filter above, on the final v and R~; every target 0 where sum_j v_j = 0; rows >= F and
  * frames >= T are zeros; NaN / Inf propagate, and a NaN in one bin of X stays in that bin.  A power that is exactly 0 stays 0 (G_i = 0),

@@ -89,11 +89,13 @@ def filter_with(v, R, X, dtype=np.float64, scaled=None):
     return out
 
 
-def em_step(v, R, X, dtype=np.float64, scaled=None, order='v_first', weighting='normalised'):
+def em_step(v, R, X, dtype=np.float64, scaled=None, order='v_first', weighting='normalised', frame_sum=None, close=None):
     """One iteration.  v (S, F, T) in dtype, R (S, F, 4) float32 -> (v' in dtype, R~' float32).  ``order`` / ``weighting``: the two
     variants scripts/spatial_em_study.py keeps on record ('r_first': A_i = sum C_i / v_i with the OLD power, then v'_i against the NEW
     R~'_i, the same C_i; 'power': A_i = sum C_i / 1/2 sum tr C_i);
-    the contract is the default of both."""
+    the contract is the default of both.  ``frame_sum`` (float64 (F, T) -> (F,)) replaces the order in which the frames' terms are
+    added; ``close(sums, use)`` (the four sums (F,) and the frames counted (F, T) -> R~' (F, 4) float64 before its rounding) replaces
+    step 2's quotient and loading (tests/spatial_checks.py: the device's order, and planted mistakes)."""
     v = np.asarray(v, dtype)
     S, F, T = v.shape
     R32 = np.asarray(R, np.float32)
@@ -148,7 +150,9 @@ def em_step(v, R, X, dtype=np.float64, scaled=None, order='v_first', weighting='
             else:
                 rv = dtype(1.0) / v2
                 terms = [np.where(use, ck * rv, 0).astype(np.float64) for ck in c]
-            if dtype == np.float64:
+            if frame_sum is not None:
+                sums = [frame_sum(tk) for tk in terms]
+            elif dtype == np.float64:
                 sums = [np.cumsum(tk, axis=-1)[..., -1] for tk in terms]                   # ascending frames
             else:
                 sums = [np.sum(tk, axis=-1) for tk in terms]                               # pairwise: another order
@@ -159,7 +163,7 @@ def em_step(v, R, X, dtype=np.float64, scaled=None, order='v_first', weighting='
             r00, r11 = np.where(none, 1.0, sums[0] / den), np.where(none, 1.0, sums[1] / den)
             rr, ri = np.where(none, 0.0, sums[2] / den), np.where(none, 0.0, sums[3] / den)
             load = LOADING * (0.5 * (r00 + r11))
-            Rn[i] = np.stack([r00 + load, r11 + load, rr, ri], axis=-1)
+            Rn[i] = np.stack([r00 + load, r11 + load, rr, ri], axis=-1) if close is None else close(sums, use)
             if order == 'r_first':                             # ... and v'_i = 1/2 Re tr(R~'_i^-1 C_i) against the NEW covariance
                 q00, q11, qr, qi = (Rn[i, :, k].astype(np.float32).astype(dtype)[:, None] for k in range(4))
                 tr = (q11 * c[0] + q00 * c[1] - two * (qr * c[2] + qi * c[3])) / (q00 * q11 - (qr * qr + qi * qi))

@@ -22,13 +22,14 @@ LOADING = 1e-3              # GCCNMF_SPATIAL_LOADING (include/gccnmf_hip.h)
 BAR_FACTOR = 4.0            # covers the other association order of the 2 x 2 products and the reciprocal
 
 
-def covariances(E, loading=LOADING):
+def covariances(E, loading=LOADING, frame_sum=None):
     """E (S, 2, F, T) complex -> R~ as (S, F, 4) float32: (R~00, R~11, Re R~01, Im R~01).  The sums run over the frames in ascending
-    order in float64 (np.cumsum adds sequentially)."""
+    order in float64 (np.cumsum adds sequentially); ``frame_sum`` (float64 (..., T) -> (...)) adds them in another order
+    (tests/spatial_checks.py: the device's)."""
     E = np.asarray(E).astype(np.complex64).astype(np.complex128)
     S, _, F, T = E.shape
     with np.errstate(invalid='ignore', over='ignore'):
-        last = lambda a: np.cumsum(a, axis=-1)[..., -1]
+        last = frame_sum or (lambda a: np.cumsum(a, axis=-1)[..., -1])
         p0 = last(E[:, 0].real ** 2 + E[:, 0].imag ** 2)
         p1 = last(E[:, 1].real ** 2 + E[:, 1].imag ** 2)
         qr = last(E[:, 0].real * E[:, 1].real + E[:, 0].imag * E[:, 1].imag)
