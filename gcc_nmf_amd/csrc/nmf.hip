@@ -64,7 +64,7 @@ static const GccNmfKnob gccnmf_knobs[GCCNMF_TUNE_KEYS] = {
     {0, 0, 1, 1},                       // 18 persistent
     {1, 0, 1, 1},                       // 19 prefetch
     {1, 0, 1, 1},                       // 20 wide_update_w
-    {1, 0, 8, 0},                       // 21 chain: 1 = the whole call as one chained launch where the rule in chain_stages says so; 0 off; forced forms (tests, A/B):
+    {1, 0, 8, 0},                       // 21 chain: 1 = the whole call as one chained launch where the rule in plan_klnmf says so; 0 off; forced forms (tests, A/B):
                                         //    2 = K1 | K2, 4 = K1 | K2 | K3 | K4 per iteration, 8 = every iteration of the call
     {0, 0, 1, 1},                       // 22 chain_solo: chained launches with one workgroup per CU (the freedom-from-deadlock test)
     {1, 0, 3, 0},                       // 23 chain_lists: 1 by rule (whole files per XCD where they balance, else spread) | 0 the plain launch's lists (batch a multiple of 8) |
@@ -401,6 +401,18 @@ static bool small_batch_tile(const GemmArgs& a) {
     return tall_tiles < 256;
 }
 
+enum GemmFamily { GEMM_RING, GEMM_SMALL_BATCH, GEMM_DMA, GEMM_TALL, GEMM_WIDE };
+template <bool A_KC, bool B_KC, int EPI, bool TAIL>
+static int launch_gemm_family(GemmFamily family, const GemmArgs& a, hipStream_t s) {
+    switch (family) {
+        case GEMM_RING: return gccnmf_launch_gemm_ring<A_KC, B_KC, EPI, TAIL>(a, s);
+        case GEMM_SMALL_BATCH: return gccnmf_launch_gemm<4, 1, A_KC, B_KC, EPI, TAIL, 1>(a, s);
+        case GEMM_DMA: return gccnmf_launch_gemm_dma<A_KC, B_KC, EPI, TAIL>(a, s);
+        case GEMM_TALL: return gccnmf_launch_gemm<4, 1, A_KC, B_KC, EPI, TAIL>(a, s);
+        default: return gccnmf_launch_gemm<1, 4, A_KC, B_KC, EPI, TAIL>(a, s);
+    }
+}
+
 template <bool A_KC, bool B_KC, int EPI>
 static int dispatch_gemm(const GemmArgs& a, bool tail, hipStream_t s) {
     const bool tall = a.M > 128;
@@ -408,27 +420,10 @@ static int dispatch_gemm(const GemmArgs& a, bool tail, hipStream_t s) {
     // register-staged wide tile (128 x 256 per workgroup, one k-tile prefetched): 154 us per launch for 64 files at K = 128 = 0.43 of the
     // matrix peak.  The LDS-DMA ring kernel's 128 x 64 tiles (six stages in flight, image-layout epilogue) take it instead (key 14).
     const bool short_updh = !tall && EPI == EPI_UPDH && gccnmf_tune_short_updh && gccnmf_tune_tile_policy != 1 && a.N >= 256;
-    if ((small_batch_tile(a) || short_updh) && gccnmf_tune_ring && gccnmf_ring_supports(a.Kd)) {   // (longer reductions: the register-staged tile below)
-        if (A_KC) return tail ? gccnmf_launch_gemm_ring<A_KC, B_KC, EPI, A_KC>(a, s) : gccnmf_launch_gemm_ring<A_KC, B_KC, EPI, false>(a, s);
-        if (tail) return GCCNMF_ERR_ARG;
-        return gccnmf_launch_gemm_ring<A_KC, B_KC, EPI, false>(a, s);
-    }
-    if (small_batch_tile(a)) {
-        if (A_KC) return tail ? gccnmf_launch_gemm<4, 1, A_KC, B_KC, EPI, A_KC, 1>(a, s) : gccnmf_launch_gemm<4, 1, A_KC, B_KC, EPI, false, 1>(a, s);
-        if (tail) return GCCNMF_ERR_ARG;
-        return gccnmf_launch_gemm<4, 1, A_KC, B_KC, EPI, false, 1>(a, s);
-    }
-    if (tall && gccnmf_tune_dma) {
-        if (A_KC) return tail ? gccnmf_launch_gemm_dma<A_KC, B_KC, EPI, A_KC>(a, s) : gccnmf_launch_gemm_dma<A_KC, B_KC, EPI, false>(a, s);
-        if (tail) return GCCNMF_ERR_ARG;
-        return gccnmf_launch_gemm_dma<A_KC, B_KC, EPI, false>(a, s);
-    }
-    if (A_KC) {
-        if (tall) return tail ? gccnmf_launch_gemm<4, 1, A_KC, B_KC, EPI, A_KC>(a, s) : gccnmf_launch_gemm<4, 1, A_KC, B_KC, EPI, false>(a, s);
-        return tail ? gccnmf_launch_gemm<1, 4, A_KC, B_KC, EPI, A_KC>(a, s) : gccnmf_launch_gemm<1, 4, A_KC, B_KC, EPI, false>(a, s);
-    }
-    if (tail) return GCCNMF_ERR_ARG;
-    return tall ? gccnmf_launch_gemm<4, 1, A_KC, B_KC, EPI, false>(a, s) : gccnmf_launch_gemm<1, 4, A_KC, B_KC, EPI, false>(a, s);
+    const bool ring = (small_batch_tile(a) || short_updh) && gccnmf_tune_ring && gccnmf_ring_supports(a.Kd);   // (longer reductions: the register-staged tile)
+    const GemmFamily family = ring ? GEMM_RING : small_batch_tile(a) ? GEMM_SMALL_BATCH : !tall ? GEMM_WIDE : gccnmf_tune_dma ? GEMM_DMA : GEMM_TALL;
+    if (tail && !A_KC) return GCCNMF_ERR_ARG;      // the VALU tail row needs a reduction-contiguous A
+    return tail ? launch_gemm_family<A_KC, B_KC, EPI, A_KC>(family, a, s) : launch_gemm_family<A_KC, B_KC, EPI, false>(family, a, s);
 }
 
 struct NmfGeom {
@@ -551,12 +546,6 @@ static int launch_update_h(const GemmArgs& a, hipStream_t s) { return dispatch_g
 static int launch_rht(const NmfGeom& g, const GemmArgs& a, hipStream_t s) { return dispatch_gemm<true, true, EPI_STORE>(a, g.tail, s); }
 
 // W = normalise(W * (R.H^T) / rowsumH), colsumW, hscale -- K4a and K4b in one launch (tall tile, all F rows in one workgroup)
-static bool can_fuse_w_update(const NmfGeom& g, int batch, int groups) {
-    // the fused epilogue needs the tall tile; tiny launches prefer the small-batch tile and the two-launch form
-    if (g.Fm <= 128 || g.Fm > 512 || gccnmf_tune_tile_policy == 2) return false;
-    return gccnmf_tune_tile_policy == 1 || (long)batch * groups * gccnmf_ceil_div(g.K, 64) >= 256;
-}
-
 static int launch_rht_update_w(const NmfGeom& g, const GemmArgs& a, hipStream_t s) {
     // the LDS-DMA kernel carries only the full-tile form of this epilogue (every wave entirely inside or outside M, no
     // ragged atom tile); anything else takes the register-staged kernel with the generic one
@@ -739,21 +728,7 @@ static int direct_rht(const NmfGeom& g, const DirectBufs& d, const float* R, flo
     return gccnmf_direct_launch(a, DEPI_STORE, gccnmf_tune_direct_tile, s);
 }
 
-// Short dictionaries (K <= 128 -- the reference driver's K = 128): K1 and K2 as ONE launch (gccnmf_wh_updh_kernel: a workgroup per
-// 64-frame column tile with its scaled H resident in registers, W in 64-bin chunks through LDS), R never written.
-// Measured at K = 128, N = 1244 (profiles/r04w_fused_k12_sweep.txt; files: fused / two launches, us): 20: 82 / 92, 25: 86 / 109, 26: 127 / 123,
-// 40: 153 / 186, 50: 160 / 189, 64: 208 / 240, 96: 312 / 333, 128: 379 / 431; K = 64, 64 files: 116 / 195.  A full round of 512 workgroups
-// (two per CU) takes 78 us, a last round of at most 256 (one per CU) 45, a larger one 76; the two launches 25 + 0.17 us per column tile.
-// Both scale alike with K, so the choice is made in those units.  (GCCNMF_FLAG_GROUPS: the file groups that run side by side are priced together.)
-static bool fused_wh_updh(const NmfGeom& g, int batch, const KlnmfMode& m) {
-    if (!gccnmf_tune_fused_k12 || gccnmf_tune_tile_policy != 0 || direct_path(g, batch, m.groups) || batch < 2 || !g.tail || g.Fm < 64 || g.Fm > 512 ||
-        (g.Fm % 64) != 0 || g.K > 128)
-        return false;
-    if (gccnmf_tune_fused_k12 == 2) return true;
-    const long wgs = (long)batch * gccnmf_ceil_div(g.N, 64) * m.groups, rem = wgs % 512;
-    const long fused = 780 * (wgs / 512) + (rem == 0 ? 0 : rem <= 256 ? 450 : 760), two = 250 + 17 * wgs / 10;      // tenths of a microsecond
-    return fused < two;
-}
+// The operands of the short-dictionary launches (plan_klnmf says where they run).  K1 + K2 in one launch:
 static WhUpdhArgs wh_updh_args(const NmfGeom& g, const float* V, const float* W, float* H, const float* hscale, const float* colsumW, float alpha,
                                float eps, int batch) {
     WhUpdhArgs a = {};
@@ -766,35 +741,7 @@ static WhUpdhArgs wh_updh_args(const NmfGeom& g, const float* V, const float* W,
     return a;
 }
 
-// K3 and K4a as ONE launch (gccnmf_whdiv_rht_kernel: 64-bin slabs with their W rows in registers), K <= 128.
-// Every slab workgroup walks ALL column tiles of its file, so the launch costs one "round" (two workgroups per CU, 512 at a time) however
-// few workgroups it holds: measured at K = 128, N = 1244 a round takes 184 us against 3.72 us per file for the two launches it replaces
-// (64 files: 184 against 238 us; 40 files: 184 against 149).  Both scale alike with K and N, so the choice is a ratio.  Returns the number of
-// files (from the front of the batch) that take the slab launch: all of them, none, or whole rounds' worth with the REST of the files on
-// the two launches behind it (72 files: 64 + 8 -> 184 + 40 us against 268 for the two launches over all of them, 368 for two slab rounds).
-// (GCCNMF_FLAG_GROUPS: the file groups that run side by side share the rounds; they are not split.)
-static int fused_whdiv_rht_files(const NmfGeom& g, int batch, const KlnmfMode& m) {
-    if (!gccnmf_tune_fused_k34 || gccnmf_tune_tile_policy != 0 || direct_path(g, batch, m.groups) || batch < 2 || !g.tail || g.Fm < 64 || g.Fm > 512 ||
-        (g.Fm % 64) != 0 || g.K > 128 || (g.Fm / 64) * 16 < 32 * gccnmf_ceil_div(g.K, 32))
-        return 0;
-    if (gccnmf_tune_fused_k34 == 2) return batch;
-    const long slabs = g.Fm / 64, groups = m.groups, wgs = (long)batch * slabs * groups, rounds = (wgs + 511) / 512;
-    const long per_round = 512 / slabs;                          // files per round
-    // in hundredths of a microsecond: 3.72 us x slabs / 8 per file on the two launches, 184 us per round, 10 us for the extra launch pair
-    const long two = 372 * slabs / 8;
-    long best = two * batch * groups, head = 0;                  // all files on the two launches
-    if (18400 * rounds < best) {
-        best = 18400 * rounds;
-        head = batch;
-    }
-    if (groups == 1) {
-        const long r = batch / per_round;                        // whole rounds of files, the rest behind them on the two launches
-        // (+ 10 %: the two launches are dearer per file on a small rest than the straight line says -- 104 files: 64 + 40 measured 717 us
-        // per iteration against 699 for two slab rounds)
-        if (r >= 1 && r * per_round < batch && 11 * (18400 * r + two * (batch - r * per_round) + 1000) < 10 * best) head = r * per_round;
-    }
-    return (int)head;
-}
+// K3 + K4a in one launch:
 static WhdivRhtArgs whdiv_rht_args(const NmfGeom& g, const float* V, const float* W, const float* H, float* U, float* rowsumH, int batch) {
     WhdivRhtArgs a = {};
     a.W = W; a.sW = g.sW; a.lda = g.Kp;
@@ -885,15 +832,15 @@ static int chain_list_mode(int batch) {
     return 1000L * 8 * longest <= 1027L * batch ? 1 : 2;
 }
 // Which iterations can be chained -- the shape and tuning conditions of any chained launch: the four GEMMs all on full-height LDS-DMA throughput
-// tiles (K2 half-height up to 256 atoms) with one XCD-affine list per XCD
-static bool chain_capable(const NmfGeom& g, int batch, const KlnmfMode& m, bool any_size) {
-    if (!gccnmf_tune_dma || gccnmf_tune_tile_policy == 2 || gccnmf_tune_tail_split > 1) return false;
-    if (direct_path(g, batch, m.groups) || !m.xcd_affine || m.unfused_w_update || batch < 8) return false;
+// tiles (K2 half-height up to 256 atoms) with one XCD-affine list per XCD, enough column tiles (64 columns, all files) to fill the chip, not `latency`
+// (direct_path).  (gccnmf_klnmf asks more -- plan_klnmf; a ragged batch has no plain form to agree with and asks this alone.)
+static bool chain_capable(const NmfGeom& g, int batch, const KlnmfMode& m, bool latency, long column_tiles) {
+    if (!gccnmf_tune_chain || !gccnmf_tune_dma || gccnmf_tune_tile_policy == 2 || gccnmf_tune_tail_split > 1) return false;
+    if (latency || !m.xcd_affine || m.unfused_w_update || batch < 8) return false;
     // (K a multiple of 128: a K2 tile whose last wave is partly beyond M takes the generic epilogue h * (acc / den) for that wave, a plain
     // launch on half-height tiles the lean one (h * acc) * (s / den) for the same rows: a few ulp apart, so the forms would not be bitwise equal)
     if (g.K <= 128 || g.Fm <= 128 || g.Fm > 512 || (g.Fm & 127) || (g.K & 127) || (g.F % 16) != 1 || !g.tail) return false;
-    // (a plain launch of a few files takes the two-launch W update -- other kernels, other summation order; a ragged batch has no plain form to agree with)
-    return any_size || can_fuse_w_update(g, batch, m.groups);
+    return gccnmf_tune_tile_policy == 1 || column_tiles >= 256;      // (fewer: the small-batch tile's territory)
 }
 static bool chain_rule(int batch, const KlnmfMode& m) {
     // The rule (profiles/r06h_files_sweep_*.txt, one-stream iteration as a fraction of the f32 peak, plain launches -> whole-call chain):
@@ -906,16 +853,101 @@ static bool chain_rule(int batch, const KlnmfMode& m) {
     const int longest = (batch + 7) / 8;
     return batch >= 24 && 100L * 8 * longest <= 108L * batch;
 }
-// every file's tiles on ONE XCD in every stage (batch a multiple of 8: list x holds the files x, x + 8, ... in all four GEMMs) unless the lists say otherwise
-static int chain_stages(const NmfGeom& g, int batch, const KlnmfMode& m) {
+// ---- which launches a per-file-dictionary call is made of, decided ONCE at the entry point (gccnmf_klnmf / _stage / _plan / _ragged) ---------
+// plan_klnmf is the only code that reads the form-selecting tuning keys and shape rules; klnmf_stage and the call loops test these fields and no rule.
+enum KlnmfKind { KLNMF_BLIND, KLNMF_FIXED_W, KLNMF_FREE_ATOMS };      // W learned | one given W (GCCNMF_FLAG_FIXED_W) | free atoms beside a dictionary
+struct KlnmfPlan {
+    KlnmfKind kind;
+    bool direct;            // every stage on the direct latency kernels (direct.hip)
+    bool fused12;           // K1 + K2 in one launch: stage 1 runs it, stage 2 has nothing to do
+    int head34;             // files (from the front of the batch) on the K3 + K4a slab launch of stage 3; the rest on the two launches behind it
+    bool w_in_rht;          // the W update rides in stage 4's epilogue: stage 5 has nothing to do
+    int chain;              // 0 | 2: K1 | K2 in one chained launch | 4: the whole iteration | 8: the whole call
+    int short_group;        // K <= 128: the three launches of every iteration as one chained launch -- atoms per W-update group (16 | 32), 0 = no chain
+#ifdef GCCNMF_EXPERIMENTS
+    bool split_wh, split_rht;      // the round-3 latency path: one file's reductions (W.H over the atoms, R.H^T over the columns) as parts
+#else
+    static constexpr bool split_wh = false, split_rht = false;      // the split-K path is compiled out of the product library
+#endif
+};
+static KlnmfPlan plan_klnmf(const NmfGeom& g, int batch, const KlnmfMode& m) {
+    KlnmfPlan p = {};
+    p.kind = m.fixed_w ? KLNMF_FIXED_W : m.free_atoms ? KLNMF_FREE_ATOMS : KLNMF_BLIND;
+    if (p.kind == KLNMF_FIXED_W) return p;      // one launch runs every iteration (nmf_fixed.hip); of the stages only 7 exists, in one form
+    // Free atoms (semi-supervised): stage 4 reads a materialised R [batch][Fp][Np] with zero padding, so stages 1-3 take the forms that leave
+    // one in the workspace whatever the tuning keys say -- never the direct kernels (they keep Rt), never the K3 + K4a slab launch.  K1 + K2
+    // fused stays: stage 3 rewrites R.  Stages 4 and 5 are nmf_semi.hip's, on the free columns alone.  Nothing chains.
+    const bool semi = p.kind == KLNMF_FREE_ATOMS;
+    const int groups = m.groups;      // launch forms that follow the launch size are chosen for all groups together (GCCNMF_FLAG_GROUPS)
+    const bool latency = direct_path(g, batch, groups);
     const int want = gccnmf_tune_chain;
-    if (!want || !chain_capable(g, batch, m, false) || ((batch & 7) && chain_list_mode(batch) == 0)) return 0;
-    if (gccnmf_tune_tile_policy != 1 && (long)batch * gccnmf_ceil_div(g.N, 64) < 256) return 0;      // (the small-batch tile's territory)
-    if (want != 1) return want;                                   // a forced form
-    // by rule: not beside another file group's launches (two chained launches that share the chip are slower than two plain ones: 155 k against 158 k
-    // frames/s end to end); whole-file lists from three files per XCD on, spread lists from 20 files on
-    if (m.groups > 1) return 0;
-    return batch >= (chain_list_mode(batch) == 1 ? 24 : 20) ? 8 : 0;
+    p.direct = latency && !semi;
+#ifdef GCCNMF_EXPERIMENTS
+    p.split_wh = !semi && !latency && single_file_split(g, batch, g.Kp, gccnmf_tune_wh_splits);
+    p.split_rht = !semi && !latency && single_file_split(g, batch, g.Np, gccnmf_tune_rht_splits);
+#endif
+    // the shapes of the short-dictionary kernels (direct.hip), and of them those whose W rows fit the registers of the K3 + K4a slab workgroups
+    const bool short_shape = gccnmf_tune_tile_policy == 0 && !latency && batch >= 2 && g.tail && g.Fm >= 64 && g.Fm <= 512 && (g.Fm % 64) == 0 && g.K <= 128;
+    const bool slab_shape = short_shape && (g.Fm / 64) * 16 >= 32 * gccnmf_ceil_div(g.K, 32);
+    // Short dictionaries (K <= 128 -- the reference driver's K = 128): K1 and K2 as ONE launch (gccnmf_wh_updh_kernel: a workgroup per
+    // 64-frame column tile with its scaled H resident in registers, W in 64-bin chunks through LDS), R never written.
+    // Measured at K = 128, N = 1244 (profiles/r04w_fused_k12_sweep.txt; files: fused / two launches, us): 20: 82 / 92, 25: 86 / 109, 26: 127 / 123,
+    // 40: 153 / 186, 50: 160 / 189, 64: 208 / 240, 96: 312 / 333, 128: 379 / 431; K = 64, 64 files: 116 / 195.  A full round of 512 workgroups
+    // (two per CU) takes 78 us, a last round of at most 256 (one per CU) 45, a larger one 76; the two launches 25 + 0.17 us per column tile.
+    // Both scale alike with K, so the choice is made in those units.  (GCCNMF_FLAG_GROUPS: the file groups that run side by side are priced together.)
+    if (short_shape && gccnmf_tune_fused_k12) {
+        const long wgs = (long)batch * gccnmf_ceil_div(g.N, 64) * groups, rem = wgs % 512;
+        const long fused = 780 * (wgs / 512) + (rem == 0 ? 0 : rem <= 256 ? 450 : 760), two = 250 + 17 * wgs / 10;      // tenths of a microsecond
+        p.fused12 = fused < two || gccnmf_tune_fused_k12 == 2;
+    }
+    // K3 and K4a as ONE launch (gccnmf_whdiv_rht_kernel: 64-bin slabs with their W rows in registers), K <= 128.
+    // Every slab workgroup walks ALL column tiles of its file, so the launch costs one "round" (two workgroups per CU, 512 at a time) however
+    // few workgroups it holds: measured at K = 128, N = 1244 a round takes 184 us against 3.72 us per file for the two launches it replaces
+    // (64 files: 184 against 238 us; 40 files: 184 against 149).  Both scale alike with K and N, so the choice is a ratio.  head34 is the number of
+    // files (from the front of the batch) that take the slab launch: all of them, none, or whole rounds' worth with the REST of the files on
+    // the two launches behind it (72 files: 64 + 8 -> 184 + 40 us against 268 for the two launches over all of them, 368 for two slab rounds).
+    // (GCCNMF_FLAG_GROUPS: the file groups that run side by side share the rounds; they are not split.)
+    if (slab_shape && !semi && gccnmf_tune_fused_k34) {
+        const long slabs = g.Fm / 64, wgs = (long)batch * slabs * groups, rounds = (wgs + 511) / 512;
+        const long per_round = 512 / slabs;                          // files per round
+        // in hundredths of a microsecond: 3.72 us x slabs / 8 per file on the two launches, 184 us per round, 10 us for the extra launch pair
+        const long two = 372 * slabs / 8;
+        long best = two * batch * groups, head = 0;                  // all files on the two launches
+        if (18400 * rounds < best) {
+            best = 18400 * rounds;
+            head = batch;
+        }
+        if (groups == 1) {
+            const long r = batch / per_round;                        // whole rounds of files, the rest behind them on the two launches
+            // (+ 10 %: the two launches are dearer per file on a small rest than the straight line says -- 104 files: 64 + 40 measured 717 us
+            // per iteration against 699 for two slab rounds)
+            if (r >= 1 && r * per_round < batch && 11 * (18400 * r + two * (batch - r * per_round) + 1000) < 10 * best) head = r * per_round;
+        }
+        p.head34 = gccnmf_tune_fused_k34 == 2 ? batch : (int)head;
+    }
+    // K4a + K4b in one launch (launch_rht_update_w): the fused epilogue needs the tall tile; tiny launches prefer the small-batch tile and two launches
+    const bool tall_tile = gccnmf_tune_tile_policy == 1 || (gccnmf_tune_tile_policy == 0 && (long)batch * groups * gccnmf_ceil_div(g.K, 64) >= 256);
+    p.w_in_rht = g.Fm > 128 && g.Fm <= 512 && tall_tile && !m.unfused_w_update && !p.head34 && !semi && !p.direct && !p.split_rht;
+
+    // The chained launches: bit for bit the plain call, which is why they are derived from the fields above.  K > 128: a plain launch of a few files
+    // takes the two-launch W update -- other kernels, other summation order -- so the call chains only where the plain one has the W update in K4's
+    // epilogue.  Every file's tiles on ONE XCD in every stage (batch a multiple of 8: list x holds the files x, x + 8, ...) unless the lists say otherwise.
+    if (p.w_in_rht && chain_capable(g, batch, m, latency, (long)batch * gccnmf_ceil_div(g.N, 64)) && !((batch & 7) && chain_list_mode(batch) == 0)) {
+        // a forced form, or by rule: not beside another file group's launches (two chained launches that share the chip are slower than two plain ones:
+        // 155 k against 158 k frames/s end to end); whole-file lists from three files per XCD on, spread lists from 20 files on
+        p.chain = want != 1 ? want : groups == 1 && batch >= (chain_list_mode(batch) == 1 ? 24 : 20) ? 8 : 0;
+    }
+    // Short dictionaries (K <= 128): the three launches of an iteration -- K1 + K2 on column tiles, K3 + K4a on bin slabs, the one-pass W update --
+    // chained the same way (direct.hip: gccnmf_short_chain_kernel).  Shapes both fused kernels and the one-pass W update take; the same batch
+    // rule as the throughput chain.  short_group: the atoms per W-update group (16 / 32: what the plain launch would use at this batch).
+    if (!p.chain && !semi && (want == 1 || want == 8) && slab_shape && gccnmf_tune_fused_k12 && gccnmf_tune_fused_k34 && m.xcd_affine &&
+        !m.unfused_w_update && batch >= 8 && g.F <= 64 * 9 && gccnmf_tune_ring && (long)batch * (g.Kp / 64) < 256 && gccnmf_tune_ablate != 64) {
+        // by rule: only where the plain call runs the SAME three item programs for every file (both fused launches, no files left to the two-launch
+        // form) -- the chained call is then bit for bit the plain one, and a file's bits keep following the batch size exactly as before
+        if (want == 8 || (chain_rule(batch, m) && p.fused12 && p.head34 == batch))
+            p.short_group = ((long)batch * (g.Kp / 32) >= 256 && gccnmf_tune_wide_update_w) ? 32 : 16;
+    }
+    return p;
 }
 
 // A ragged batch (gccnmf_klnmf_ragged): files of different lengths in ONE chained launch.  g is the geometry of the LONGEST file (every file's V, H,
@@ -1018,21 +1050,7 @@ static int launch_klnmf_chain(int stages, const NmfGeom& g, const float* V, floa
     return GCCNMF_OK;
 }
 
-// Short dictionaries (K <= 128): the three launches of an iteration -- K1 + K2 on column tiles, K3 + K4a on bin slabs, the one-pass W update --
-// chained the same way (direct.hip: gccnmf_short_chain_kernel).  Shapes both fused kernels and the one-pass W update take; the same batch
-// rule as the throughput chain.  Returns the atoms per W-update group (16 / 32: what the plain launch would use at this batch), 0 = no chain.
-static int short_chain_group(const NmfGeom& g, int batch, const KlnmfMode& m) {
-    const int want = gccnmf_tune_chain;
-    if (!want || want == 2 || want == 4 || !gccnmf_tune_fused_k12 || !gccnmf_tune_fused_k34 || gccnmf_tune_tile_policy != 0) return 0;
-    if (direct_path(g, batch, m.groups) || !m.xcd_affine || m.unfused_w_update || batch < 8 || !g.tail || g.Fm < 64 || g.Fm > 512 || (g.Fm % 64) != 0 || g.K > 128) return 0;
-    if ((g.Fm / 64) * 16 < 32 * gccnmf_ceil_div(g.K, 32) || g.F > 64 * 9 || !gccnmf_tune_ring || (long)batch * (g.Kp / 64) >= 256) return 0;
-    // by rule: only where the plain call runs the SAME three item programs for every file (both fused launches, no files left to the two-launch
-    // form) -- the chained call is then bit for bit the plain one, and a file's bits keep following the batch size exactly as before
-    if (want == 1 && !(chain_rule(batch, m) && fused_wh_updh(g, batch, m) && fused_whdiv_rht_files(g, batch, m) == batch)) return 0;
-    if (gccnmf_tune_ablate == 64) return 0;
-    return ((long)batch * (g.Kp / 32) >= 256 && gccnmf_tune_wide_update_w) ? 32 : 16;
-}
-
+// the short-dictionary chain (plan_klnmf: short_group = `group`), iterations [it0, it0 + iterations) in one launch
 static int launch_short_chain(const NmfGeom& g, const float* V, float* W, float* H, const KlnmfWorkspace& ws, float alpha, float eps, int batch,
                               int group, int it0, int iterations, hipStream_t s) {
     ShortChainArgs c = {};
@@ -1068,27 +1086,21 @@ long gccnmf_klnmf_workspace_floats(int F, int N, int K, int batch) {
     return carve(nullptr, make_geom(F, N, K), batch, false).floats;
 }
 
-// One launch group of the iteration, addressable on its own so that tests and the benchmark can time /
-// check each kernel in isolation.  stage: 0 prepare | 1 K1 | 2 K2 | 3 K3 | 4 K4a | 5 K4b | 6 final H rescale | 7 KL divergence of the current factors
+// One launch group of the iteration, addressable on its own so that tests and the benchmark can time / check each kernel in isolation; which form
+// it takes, and whether another stage has done its work, the plan says.  stage: 0 prepare | 1 K1 | 2 K2 | 3 K3 | 4 K4a | 5 K4b | 6 final H rescale | 7 KL divergence of the current factors
 static int klnmf_stage(int stage, const float* V, float* W, float* H, const KlnmfWorkspace& ws, const NmfGeom& g, int batch, float alpha, float eps,
-                       const KlnmfMode& m, hipStream_t s) {
+                       const KlnmfMode& m, const KlnmfPlan& p, hipStream_t s) {
     float *R = ws.R, *U = ws.U, *colsumW = ws.colsumW, *rowsumH = ws.rowsumH, *hscale = ws.hscale;
     if (stage == 7) {
         // D(V || W.H) of the current (materialised) factors, divergence.hip: tile partials (float64) in each file's R block, the batch
         // results (float64) at the start of the U region; one launch form whatever the batch or the tuning.  V, W, H are read only.
         // (float64 partials and results: the workspace is 16-byte aligned -- the entry point checked -- and both offsets are multiples of 4096 bytes)
-        return gccnmf_kl_divergence_launch(V, W, m.fixed_w ? 0 : g.sW, H, g.F, g.N, g.K, g.Fp, g.Kp, g.Np, batch, (double*)R, g.sV / 2, (double*)U, s);
+        return gccnmf_kl_divergence_launch(V, W, p.kind == KLNMF_FIXED_W ? 0 : g.sW, H, g.F, g.N, g.K, g.Fp, g.Kp, g.Np, batch, (double*)R, g.sV / 2, (double*)U, s);
     }
-    // Free atoms (semi-supervised): stage 4 reads a materialised R [batch][Fp][Np] with zero padding, so stages 1-3 take the forms that leave
-    // one in the workspace whatever the tuning keys say -- never the direct kernels (they keep Rt), never the K3 + K4a slab launch.  K1 + K2
-    // fused stays: stage 3 rewrites R.  Stages 4 and 5 are nmf_semi.hip's, on the free columns alone.
-    const int nfree = m.free_atoms;
-    const bool semi = nfree > 0;
-    const bool fused12 = fused_wh_updh(g, batch, m);
-    const int head34 = semi ? 0 : fused_whdiv_rht_files(g, batch, m), rest34 = batch - head34;      // files on the slab launch | behind it on the two launches
-    const bool fused34 = head34 > 0;
-    const int groups = m.groups;      // launch forms that follow the launch size are chosen for all groups together (GCCNMF_FLAG_GROUPS)
-    if (!semi && stage != 6 && direct_path(g, batch, groups)) {      // (stage 6 is the same launch on every path: below)
+    const int nfree = m.free_atoms, groups = m.groups;      // (GCCNMF_FLAG_GROUPS: the W update kernel is sized for all groups together)
+    const bool semi = p.kind == KLNMF_FREE_ATOMS;
+    const int head34 = p.head34, rest34 = batch - head34;      // files on the slab launch | behind it on the two launches
+    if (p.direct && stage != 6) {      // (stage 6 is the same launch on every path: below)
         const DirectBufs d = direct_bufs(g, ws.direct_base, batch);
         switch (stage) {
             case 0: {
@@ -1107,12 +1119,6 @@ static int klnmf_stage(int stage, const float* V, float* W, float* H, const Klnm
             default: return GCCNMF_ERR_ARG;
         }
     }
-#ifdef GCCNMF_EXPERIMENTS
-    const bool split_wh = !semi && single_file_split(g, batch, g.Kp, gccnmf_tune_wh_splits);      // the round-3 latency path: one file's reductions as parts
-    const bool split_rht = !semi && single_file_split(g, batch, g.Np, gccnmf_tune_rht_splits);
-#else
-    constexpr bool split_rht = false;              // the split-K path is compiled out of the product library
-#endif
     const int xa = m.xcd_affine, conc = m.groups > 1 ? m.groups : 0;      // GemmArgs.concurrent: the file groups whose launches run side by side (0: this one alone)
     const int vec_grid = batch * (g.Kp / 16);
     switch (stage) {
@@ -1122,41 +1128,41 @@ static int klnmf_stage(int stage, const float* V, float* W, float* H, const Klnm
             hipLaunchKernelGGL(nmf_prepare_kernel, dim3(vec_grid), dim3(256), 0, s, W, colsumW, hscale, g.F, g.Fp, g.Kp);
             break;
         case 1:
-            if (fused12) return gccnmf_wh_updh_launch(wh_updh_args(g, V, W, H, hscale, colsumW, alpha, eps, batch), s);    // K1 + K2
+            if (p.fused12) return gccnmf_wh_updh_launch(wh_updh_args(g, V, W, H, hscale, colsumW, alpha, eps, batch), s);    // K1 + K2
 #ifdef GCCNMF_EXPERIMENTS
-            if (split_wh) return launch_wh_div_split(g, V, W, H, hscale, ws.parts, R, s);
+            if (p.split_wh) return launch_wh_div_split(g, V, W, H, hscale, ws.parts, R, s);
 #endif
             return launch_wh_div(g, wh_div_args(g, V, W, g.sW, H, hscale, g.Kp, R, batch, xa, conc), s);
         case 2:
-            if (fused12) return GCCNMF_OK;                                                                             // done by stage 1
+            if (p.fused12) return GCCNMF_OK;                                                                             // done by stage 1
             return launch_update_h(update_h_args(g, W, g.sW, R, H, hscale, g.Kp, colsumW, g.Kp, alpha, eps, batch, xa, conc), s);
         case 3:
-            if (fused34) {                                                                                             // K3 + K4a
+            if (head34) {                                                                                              // K3 + K4a
                 const int rc = gccnmf_whdiv_rht_launch(whdiv_rht_args(g, V, W, H, U, rowsumH, head34), s);
                 if (rc || !rest34) return rc;
                 return launch_wh_div(g, wh_div_args(g, V + head34 * g.sV, W + head34 * g.sW, g.sW, H + head34 * g.sH, nullptr, 0, R + head34 * g.sV, rest34, xa, conc), s);
             }
 #ifdef GCCNMF_EXPERIMENTS
-            if (split_wh) return launch_wh_div_split(g, V, W, H, nullptr, ws.parts, R, s);
+            if (p.split_wh) return launch_wh_div_split(g, V, W, H, nullptr, ws.parts, R, s);
 #endif
             return launch_wh_div(g, wh_div_args(g, V, W, g.sW, H, nullptr, 0, R, batch, xa, conc), s);
         case 4:
             if (semi) return gccnmf_klnmf_semi_rht_launch(R, H, U, rowsumH, g.F, g.N, g.K, nfree, batch, s);           // U[:, K - n:], rowsumH[K - n:]
-            if (fused34)                                                                                               // done by stage 3 ...
+            if (head34)                                                                                                // done by stage 3 ...
                 return rest34 ? launch_rht(g, rht_args(g, R + head34 * g.sV, H + head34 * g.sH, U + head34 * g.sU, rowsumH + (long)head34 * g.Kp, rest34, xa, conc), s)
                               : GCCNMF_OK;                                                                             // ... but for the rest
 #ifdef GCCNMF_EXPERIMENTS
-            if (split_rht) return launch_rht_split(g, R, H, ws.parts, ws.rowsum_parts, s);
+            if (p.split_rht) return launch_rht_split(g, R, H, ws.parts, ws.rowsum_parts, s);
 #endif
-            if (can_fuse_w_update(g, batch, groups) && !m.unfused_w_update)
+            if (p.w_in_rht)                                                                                            // K4a + K4b
                 return launch_rht_update_w(g, rht_update_w_args(g, R, H, W, colsumW, hscale, batch, xa, conc), s);
             return launch_rht(g, rht_args(g, R, H, U, rowsumH, batch, xa, conc), s);
         case 5:
             if (semi) return gccnmf_klnmf_semi_update_w_launch(W, U, rowsumH, colsumW, hscale, g.F, g.K, nfree, batch, s);
-            if (split_rht)      // (the parts are sized as one launch: no file groups beside a single file)
+            if (p.split_rht)      // (the parts are sized as one launch: no file groups beside a single file)
                 return launch_update_w(update_w_args(g, W, g.sW, ws.parts, g.sU, ws.rowsum_parts, colsumW, hscale, g.Kp), batch, 1, s, gccnmf_tune_rht_splits,
                                        g.sU, (long)g.Kp, nullptr, 0, 0);
-            if (can_fuse_w_update(g, batch, groups) && !m.unfused_w_update && !fused34) return GCCNMF_OK;     // done by stage 4's epilogue
+            if (p.w_in_rht) return GCCNMF_OK;                                                                          // done by stage 4's epilogue
             return launch_update_w(update_w_args(g, W, g.sW, U, g.sU, rowsumH, colsumW, hscale, g.Kp), batch, groups, s, 1, 0, 0, nullptr, 0, 0);
         case 6:
             hipLaunchKernelGGL(nmf_scale_h_kernel, dim3(batch * g.K), dim3(256), 0, s, H, hscale, (long)g.Kp, g.K, g.sH, g.ld, g.Np);
@@ -1179,12 +1185,12 @@ static int zero_chain_counters(const KlnmfWorkspace& ws, hipStream_t s) {
 // The end of every iterating call: W and H become NaN if a chained launch of this call failed to hand over (the call is never silent about it),
 // then stage 6 materialises the pending row scale of H.
 static int finish_call(bool chained, const float* V, float* W, float* H, const KlnmfWorkspace& ws, const NmfGeom& g, int batch, float alpha, float eps,
-                       const KlnmfMode& m, hipStream_t s) {
+                       const KlnmfMode& m, const KlnmfPlan& p, hipStream_t s) {
     if (chained) {
         hipLaunchKernelGGL(nmf_chain_poison_kernel, dim3(64), dim3(256), 0, s, ws.status, W, H, (long)batch * g.sW, (long)batch * g.sH);
         GCCNMF_CHECK_LAUNCH();
     }
-    return klnmf_stage(6, V, W, H, ws, g, batch, alpha, eps, m, s);
+    return klnmf_stage(6, V, W, H, ws, g, batch, alpha, eps, m, p, s);
 }
 
 // Which launches gccnmf_klnmf would use for this problem under the current tuning: bit 0 the direct latency kernels, bit 1 the fused
@@ -1196,11 +1202,10 @@ int gccnmf_klnmf_plan(int F, int N, int K, int batch, int flags) {
     if (F < 2 || N < 1 || K < 1 || batch < 1) return -1;
     KlnmfMode m;
     if (decode_mode(flags, F, K, m)) return -1;
-    if (m.fixed_w) return gccnmf_klnmf_fixed_supported(F, K) ? 16 : -1;
-    if (m.free_atoms) return 32;
-    const NmfGeom g = make_geom(F, N, K);
-    return (direct_path(g, batch, m.groups) ? 1 : 0) | (fused_wh_updh(g, batch, m) ? 2 : 0) | (fused_whdiv_rht_files(g, batch, m) > 0 ? 4 : 0) |
-           ((chain_stages(g, batch, m) || short_chain_group(g, batch, m)) ? 8 : 0);
+    const KlnmfPlan p = plan_klnmf(make_geom(F, N, K), batch, m);
+    if (p.kind == KLNMF_FIXED_W) return gccnmf_klnmf_fixed_supported(F, K) ? 16 : -1;
+    if (p.kind == KLNMF_FREE_ATOMS) return 32;
+    return (p.direct ? 1 : 0) | (p.fused12 ? 2 : 0) | (p.head34 > 0 ? 4 : 0) | ((p.chain || p.short_group) ? 8 : 0);
 }
 
 int gccnmf_klnmf_stage(const float* V, float* W, float* H, float* workspace, int F, int N, int K, int batch,
@@ -1213,7 +1218,7 @@ int gccnmf_klnmf_stage(const float* V, float* W, float* H, float* workspace, int
     // (a fixed dictionary -- one W for every file -- exists for stage 7 alone: the divergence against it; the iteration stages have no such form)
     if (m.fixed_w && (stage != 7 || m.h_ones)) return GCCNMF_ERR_ARG;
     const NmfGeom g = make_geom(F, N, K);
-    return klnmf_stage(stage, V, W, H, carve(workspace, g, batch, false), g, batch, sparsity_alpha, epsilon, m, (hipStream_t)stream);
+    return klnmf_stage(stage, V, W, H, carve(workspace, g, batch, false), g, batch, sparsity_alpha, epsilon, m, plan_klnmf(g, batch, m), (hipStream_t)stream);
 }
 
 int gccnmf_klnmf(const float* V, float* W, float* H, float* workspace, int F, int N, int K, int batch, int iterations,
@@ -1226,28 +1231,28 @@ int gccnmf_klnmf(const float* V, float* W, float* H, float* workspace, int F, in
     int rc;
     if ((rc = decode_mode(flags, F, K, m))) return rc;
     const NmfGeom g = make_geom(F, N, K);
+    const KlnmfPlan p = plan_klnmf(g, batch, m);
     const KlnmfWorkspace ws = carve(workspace, g, batch, false);
     const float alpha = sparsity_alpha, eps = epsilon;
-    if (m.free_atoms) {
+    if (p.kind == KLNMF_FREE_ATOMS) {
         // semi-supervised: the dictionary in W[:, :K - n] of every file stays as it is, the n free atoms behind it and all of H are learned.
         // Plain launches (klnmf_stage keeps R materialised); nothing chains.
         if ((rc = clear_chain_status(ws, s))) return rc;
-        if ((rc = klnmf_stage(0, V, W, H, ws, g, batch, alpha, eps, m, s))) return rc;
+        if ((rc = klnmf_stage(0, V, W, H, ws, g, batch, alpha, eps, m, p, s))) return rc;
         for (int it = 0; it < iterations; ++it)
             for (int stage = 1; stage <= 5; ++stage)
-                if ((rc = klnmf_stage(stage, V, W, H, ws, g, batch, alpha, eps, m, s))) return rc;
-        return finish_call(false, V, W, H, ws, g, batch, alpha, eps, m, s);
+                if ((rc = klnmf_stage(stage, V, W, H, ws, g, batch, alpha, eps, m, p, s))) return rc;
+        return finish_call(false, V, W, H, ws, g, batch, alpha, eps, m, p, s);
     }
-    if (m.fixed_w) {
+    if (p.kind == KLNMF_FIXED_W) {
         // fixed dictionary: W is read only, H holds the initial coefficients (or, with H_ONES, is output only); one launch runs every
         // iteration (and leaves H materialised).  Nothing chains.
         if (!gccnmf_klnmf_fixed_supported(F, K) || gccnmf_klnmf_fixed_workspace_floats(F, K) > ws.scratch_floats) return GCCNMF_ERR_UNSUPPORTED;
         if ((rc = clear_chain_status(ws, s))) return rc;
         return gccnmf_klnmf_fixed_launch(V, W, H, workspace, F, N, K, batch, iterations, alpha, eps, m.h_ones, s);
     }
-    if ((rc = klnmf_stage(0, V, W, H, ws, g, batch, alpha, eps, m, s))) return rc;
-    const int chained = chain_stages(g, batch, m);          // 0 | 2: K1 | K2 in one launch | 4: the whole iteration | 8: the whole call
-    const int short_group = chained ? 0 : short_chain_group(g, batch, m);      // K <= 128: the three launches of every iteration as one chained launch
+    if ((rc = klnmf_stage(0, V, W, H, ws, g, batch, alpha, eps, m, p, s))) return rc;
+    const int chained = p.chain, short_group = p.short_group;      // (at most one of the two)
     const bool chains = (chained || short_group) && iterations > 0;
     if (!chained && !short_group && (rc = clear_chain_status(ws, s))) return rc;
     if (chains && (rc = zero_chain_counters(ws, s))) return rc;
@@ -1261,10 +1266,10 @@ int gccnmf_klnmf(const float* V, float* W, float* H, float* workspace, int F, in
         for (int it = 0; it < iterations; ++it) {
             if (chained && (rc = launch_klnmf_chain(chained, g, V, W, H, ws, alpha, eps, batch, m, it, 1, s, nullptr))) return rc;
             for (int stage = chained + 1; stage <= 5; ++stage)
-                if ((rc = klnmf_stage(stage, V, W, H, ws, g, batch, alpha, eps, m, s))) return rc;
+                if ((rc = klnmf_stage(stage, V, W, H, ws, g, batch, alpha, eps, m, p, s))) return rc;
         }
     }
-    return finish_call(chains, V, W, H, ws, g, batch, alpha, eps, m, s);
+    return finish_call(chains, V, W, H, ws, g, batch, alpha, eps, m, p, s);
 }
 
 // Did the chained launches of the LAST gccnmf_klnmf / gccnmf_klnmf_ragged call on this workspace hand over cleanly?  (The call itself is
@@ -1316,7 +1321,8 @@ int gccnmf_klnmf_ragged(const float* V, float* W, float* H, float* workspace, in
     const NmfGeom g = make_geom(F, Nmax, K);
     // a ragged batch exists only as a chained launch (the plain launches take one N for the whole batch): where that form is not available
     // -- short dictionaries, a handful of files -- the caller runs the files of each length as a batch of their own
-    if (!gccnmf_tune_chain || !chain_capable(g, batch, m, true) || (gccnmf_tune_tile_policy != 1 && tiles < 256)) return GCCNMF_ERR_UNSUPPORTED;
+    const KlnmfPlan p = plan_klnmf(g, batch, m);      // (of a uniform batch of the longest file: stages 0 and 6 are all that is run by it)
+    if (!chain_capable(g, batch, m, p.direct, tiles)) return GCCNMF_ERR_UNSUPPORTED;
     // deal the files out to the eight lists: longest first, each to the list with the fewest column tiles so far (ties: the lower list)
     RaggedPlan rg = {};
     rg.n = N;
@@ -1344,14 +1350,14 @@ int gccnmf_klnmf_ragged(const float* V, float* W, float* H, float* workspace, in
     rg.d_n = ws.ragged_tables;
     rg.d_lists = ws.ragged_tables + batch;
     int rc;
-    if ((rc = klnmf_stage(0, V, W, H, ws, g, batch, sparsity_alpha, epsilon, m, s))) return rc;
+    if ((rc = klnmf_stage(0, V, W, H, ws, g, batch, sparsity_alpha, epsilon, m, p, s))) return rc;
     if (iterations > 0) {
         if ((rc = zero_chain_counters(ws, s))) return rc;
         for (int it0 = 0; it0 < iterations; it0 += GCCNMF_CHAIN_MAX_ITERATIONS)
             if ((rc = launch_klnmf_chain(4, g, V, W, H, ws, sparsity_alpha, epsilon, batch, m, it0, std::min(GCCNMF_CHAIN_MAX_ITERATIONS, iterations - it0), s, &rg)))
                 return rc;
     }
-    return finish_call(iterations > 0, V, W, H, ws, g, batch, sparsity_alpha, epsilon, m, s);
+    return finish_call(iterations > 0, V, W, H, ws, g, batch, sparsity_alpha, epsilon, m, p, s);
 }
 
 // ---- shared dictionary (one W for every file / rank) ------------------------------------------

@@ -56,9 +56,9 @@ def _tuning(keys):
 
 
 class Form(object):
-    """The launch form a call takes, restated by hand from klnmf_stage (csrc/nmf.hip: direct_path, fused_wh_updh, fused_whdiv_rht_files,
-    can_fuse_w_update, launch_rht_update_w): which stage produces what.  `direct`, `f12` and `f34` are asserted against gccnmf_klnmf_plan,
-    so they cannot go stale unnoticed.  `fw` has no plan bit: a wrong value fails through the ownership check (stage 4 or stage 5 would
+    """The launch form a call takes, restated by hand from plan_klnmf (csrc/nmf.hip; its fields direct, fused12, head34 and w_in_rht are
+    `direct`, `f12`, `f34` and `fw` here) and launch_rht_update_w: which stage produces what.  `direct`, `f12` and `f34` are asserted against
+    gccnmf_klnmf_plan, so they cannot go stale unnoticed.  `fw` has no plan bit: a wrong value fails through the ownership check (stage 4 or stage 5 would
     write what the case says it does not own), not by name.  Which kernel carries the W update -- `dma_updw` for the fused one, the
     branch of launch_update_w for stage 5 -- is observable nowhere: it is restated here and in the case comments only, and a change of
     those rules in the library has to be followed here by hand."""

@@ -332,6 +332,27 @@ def test_klnmf_plan_is_a_pure_function_of_shape_batch_and_tuning():
         lib.gccnmf_set_tuning(17, 1)
 
 
+def test_klnmf_plan_bits_exclude_each_other_as_the_launch_forms_do():
+    """What the library's launch plan (plan_klnmf, csrc/nmf.hip) makes structural, over every shape class, batch 1 ... 130 and the flag words of a
+    blind call at default tuning: the direct kernels exclude every other form; a short dictionary (K <= 128) chains only where both fused launches
+    take every file; a longer one never takes the short-dictionary launches; only a call that runs alone, on XCD-affine lists and with the W update
+    fused, chains."""
+    from gcc_nmf_amd import _hip
+    plan = _hip.lib().gccnmf_klnmf_plan
+    checked = 0
+    for flags in (0, 1, 2, 3, 4 | (2 << 8), 4 | (3 << 8), 4 | (5 << 8)):
+        for F in (2, 17, 65, 129, 257, 500, 513, 577, 641, 1025, 2049):
+            for N in (1, 63, 64, 244, 1244, 2486, 4096):
+                for K in (1, 16, 32, 64, 96, 128, 129, 256, 300, 320, 384, 1024):
+                    for batch in range(1, 131):
+                        p = plan(F, N, K, batch, flags)
+                        ok = (0 <= p < 16 and (not p & 1 or p == 1) and (not p & 8 or flags == 0)
+                              and (not p & 8 or p == 14 if K <= 128 else not p & 6))
+                        assert ok, 'plan(%d, %d, %d, %d, %#x) = %d' % (F, N, K, batch, flags, p)
+                        checked += 1
+    assert checked == 840840
+
+
 def test_no_cpu_fallback():
     import torch
     if torch.cuda.is_available():
