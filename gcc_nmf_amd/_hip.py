@@ -302,11 +302,67 @@ def check_free_atoms(numFreeAtoms, K_fixed, F=None):
     return n
 
 
-def klnmf(V, W, H, ws, F, N, K, batch, iterations, alpha, eps, fixed_w=False, h_ones=False, groups=1, flags=0, free_atoms=0, stream=None):
-    """``iterations`` KL-NMF iterations on W and H in place.  groups > 1: this call is one of that many concurrent ones
+DIVERGENCES = ('kl', 'is', 'euclidean')        # beta = 1, 0, 2
+GCCNMF_FLAG_DIVERGENCE_IS = 1 << 26            # include/gccnmf_hip.h: Itakura-Saito NMF (bits 26-27 of the flags of gccnmf_klnmf / _stage / _plan)
+GCCNMF_FLAG_DIVERGENCE_EUCLIDEAN = 2 << 26     # include/gccnmf_hip.h: Euclidean NMF
+DIVERGENCE_FLAGS = {'kl': 0, 'is': GCCNMF_FLAG_DIVERGENCE_IS, 'euclidean': GCCNMF_FLAG_DIVERGENCE_EUCLIDEAN}
+DIVERGENCE_MAX_ATOMS, DIVERGENCE_MAX_BINS = 1024, 2049      # the envelope of the IS / Euclidean call
+_BETA_NAMES = {0: 'is', 1: 'kl', 2: 'euclidean'}
+
+
+def check_divergence(divergence, F=None, K=None):
+    """The ``divergence`` keyword of the engines, klnmf, klnmf_stage and klnmf_divergence, and the ``beta`` of performBetaNMF /
+    getBetaDivergence; no device needed.  Takes 'kl', 'is' or 'euclidean', or beta = 1, 0 or 2 (a whole number, not a bool), and returns
+    the name; ValueError otherwise -- a real-valued beta is not available -- and, for 'is' / 'euclidean' with F or K given, outside
+    2 <= F <= 2049, 1 <= K <= 1024."""
+    d = divergence
+    if isinstance(d, str):
+        if d not in DIVERGENCES:
+            raise ValueError("divergence must be 'kl', 'is' or 'euclidean' (or beta = 1, 0, 2), got %r" % (d,))
+    elif isinstance(d, bool) or not isinstance(d, numbers.Real) or d not in _BETA_NAMES:
+        raise ValueError("divergence must be 'kl', 'is' or 'euclidean' (or beta = 1, 0, 2), got %r" % (d,))
+    else:
+        d = _BETA_NAMES[int(d)]
+    if d != 'kl':
+        if F is not None and not 2 <= F <= DIVERGENCE_MAX_BINS:
+            raise ValueError('the %s iteration takes 2 to %d bins, got %r' % (d, DIVERGENCE_MAX_BINS, F))
+        if K is not None and not 1 <= K <= DIVERGENCE_MAX_ATOMS:
+            raise ValueError('the %s iteration takes 1 to %d atoms, got %r' % (d, DIVERGENCE_MAX_ATOMS, K))
+    return d
+
+
+def klnmf_divergence_extra_floats(Fp, Kp, Np, batch):
+    """GCCNMF_KLNMF_DIVERGENCE_WORKSPACE_FLOATS(Fp, Kp, Np, batch) of include/gccnmf_hip.h: the floats an IS / Euclidean call needs behind
+    the KL layout -- Q [batch][Fp][Np] | Ud [batch][Fp][Kp]."""
+    return batch * Fp * (Np + Kp)
+
+
+def klnmf_divergence_workspace_floats(F, N, K, batch, divergence='kl'):
+    """Floats of the workspace of gccnmf_klnmf / gccnmf_klnmf_stage for this divergence: gccnmf_klnmf_workspace_floats, for 'is' and
+    'euclidean' followed by the extra blocks above."""
+    n = lib().gccnmf_klnmf_workspace_floats(F, N, K, batch)
+    if check_divergence(divergence) == 'kl' or n < 0:
+        return n
+    return n + klnmf_divergence_extra_floats(-(-F // 16) * 16, -(-K // 64) * 64, -(-N // 64) * 64, batch)
+
+
+def _divergence_flags(divergence, fixed_w=False, h_ones=False, groups=1, flags=0, free_atoms=0):
+    """The flag bits of ``divergence``; 'is' / 'euclidean' combine with none of the other forms of the call."""
+    d = check_divergence(divergence)
+    if d != 'kl' and (fixed_w or h_ones or groups > 1 or free_atoms or flags & 6):
+        raise ValueError('divergence=%r cannot be combined with a fixed dictionary, the all-ones start, free atoms, file groups or the '
+                         'unfused W update' % (d,))
+    return DIVERGENCE_FLAGS[d]
+
+
+def klnmf(V, W, H, ws, F, N, K, batch, iterations, alpha, eps, fixed_w=False, h_ones=False, groups=1, flags=0, free_atoms=0, stream=None,
+          divergence='kl'):
+    """``iterations`` NMF iterations on W and H in place -- KL, or with divergence='is' / 'euclidean' Itakura-Saito / Euclidean (the
+    workspace is then klnmf_divergence_workspace_floats(..., divergence) floats).  groups > 1: this call is one of that many concurrent ones
     (GCCNMF_FLAG_GROUPS(n) = 4 | n << 8: launch forms are chosen for all groups together); flags: further low flag bits.
     free_atoms = n > 0: semi-supervised -- columns [0, K - n) of every file's W are a dictionary that stays as it is, the last n atoms
     and all of H are learned (GCCNMF_FLAG_FREE_ATOMS(n))."""
+    flags |= _divergence_flags(divergence, fixed_w, h_ones, groups, flags, free_atoms)
     if free_atoms:
         if fixed_w or h_ones or groups > 1 or flags & 6:
             raise ValueError('free atoms cannot be combined with a fixed dictionary, the all-ones start, file groups or the unfused W update')
@@ -315,12 +371,22 @@ def klnmf(V, W, H, ws, F, N, K, batch, iterations, alpha, eps, fixed_w=False, h_
     _stage('gccnmf_klnmf', V, W, H, ws, F, N, K, batch, iterations, alpha, eps, flags, stream=stream)
 
 
-def klnmf_divergence(V, W, H, ws, F, N, K, batch, fixed=False, stream=None):
-    """One stage-7 launch of gccnmf_klnmf_stage: D(V || W.H) of every file of a padded batch.  Returns the (batch,) float64 DEVICE
+def klnmf_stage(V, W, H, ws, F, N, K, batch, alpha, eps, stage, flags=0, free_atoms=0, stream=None, divergence='kl'):
+    """One stage (0-7) of the iteration through gccnmf_klnmf_stage; flags: low flag bits, free_atoms / divergence as for klnmf."""
+    flags |= _divergence_flags(divergence, flags=flags, free_atoms=free_atoms)
+    if free_atoms:
+        flags |= GCCNMF_FLAG_FREE_ATOMS(check_free_atoms(free_atoms, K - free_atoms, F))
+    _stage('gccnmf_klnmf_stage', V, W, H, ws, F, N, K, batch, alpha, eps, flags, int(stage), stream=stream)
+
+
+def klnmf_divergence(V, W, H, ws, F, N, K, batch, fixed=False, stream=None, divergence='kl'):
+    """One stage-7 launch of gccnmf_klnmf_stage: D(V || W.H) of every file of a padded batch -- the KL divergence, or with
+    divergence='is' / 'euclidean' the Itakura-Saito divergence over the elements with V > 0 / half the squared Euclidean distance.  Returns the (batch,) float64 DEVICE
     view of the result inside the workspace `ws` (valid until the workspace is used again); asynchronous.  fixed: W is one shared
     [Fp][Kp] dictionary."""
     Fp, Np = -(-F // 16) * 16, -(-N // 64) * 64
-    _stage('gccnmf_klnmf_stage', V, W, H, ws, F, N, K, batch, 0.0, 0.0, GCCNMF_FLAG_FIXED_W if fixed else 0, GCCNMF_STAGE_DIVERGENCE,
+    _stage('gccnmf_klnmf_stage', V, W, H, ws, F, N, K, batch, 0.0, 0.0, (GCCNMF_FLAG_FIXED_W if fixed else 0) | _divergence_flags(divergence, fixed_w=fixed),
+           GCCNMF_STAGE_DIVERGENCE,
            stream=stream, what='gccnmf_klnmf_stage (divergence)')
     at = batch * Fp * Np
     return ws[at:at + 2 * batch].view(torch.float64)

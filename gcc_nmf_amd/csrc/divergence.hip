@@ -33,6 +33,14 @@ struct KlDivArgs {
     long s_partials;
 };
 
+// TERM: which divergence the epilogue sums -- 0 KL (gccnmf_kl_term), 1 Itakura-Saito (gccnmf_is_term; a V = 0 element contributes nothing),
+// 2 Euclidean (gccnmf_euclidean_term); the GEMM, the masks and the order of the sums are the same for all three.
+template <int TERM>
+__device__ __forceinline__ float kl_divergence_term(float v, float r) {
+    return TERM == 1 ? gccnmf_is_term(v, r) : TERM == 2 ? gccnmf_euclidean_term(v, r) : gccnmf_kl_term(v, r);
+}
+
+template <int TERM>
 __global__ __launch_bounds__(KLD_NT, 2) void kl_divergence_tile_kernel(KlDivArgs p) {
     constexpr int BM = KLD_BM, BN = KLD_BN, BK = KLD_BK, NT = KLD_NT;
     constexpr int LDA = BK + 1;
@@ -131,12 +139,12 @@ __global__ __launch_bounds__(KLD_NT, 2) void kl_divergence_tile_kernel(KlDivArgs
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const bool ok = (row_base + (r & 3) + 8 * (r >> 2)) < p.F;
-            if (ok && ok_a) sum += (double)gccnmf_kl_term(va[r], acc[0][0][r]);
+            if (ok && ok_a) sum += (double)kl_divergence_term<TERM>(va[r], acc[0][0][r]);
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const bool ok = (row_base + (r & 3) + 8 * (r >> 2)) < p.F;
-            if (ok && ok_b) sum += (double)gccnmf_kl_term(vb[r], acc[0][1][r]);
+            if (ok && ok_b) sum += (double)kl_divergence_term<TERM>(vb[r], acc[0][1][r]);
         }
     }
 #pragma unroll
@@ -165,7 +173,8 @@ __global__ __launch_bounds__(256) void kl_divergence_sum_kernel(const double* __
 int gccnmf_kl_divergence_tiles(int F, int N) { return gccnmf_ceil_div(F, KLD_BM) * gccnmf_ceil_div(N, KLD_BN); }
 
 int gccnmf_kl_divergence_launch(const float* V, const float* W, long sW, const float* H, int F, int N, int K, int Fp, int Kp, int Np,
-                                int batch, double* partials, long s_partials, double* out, hipStream_t stream) {
+                                int batch, double* partials, long s_partials, double* out, hipStream_t stream, int divergence) {
+    if (divergence < 0 || divergence > 2) return GCCNMF_ERR_ARG;
     if (!V || !W || !H || !partials || !out || F < 1 || N < 1 || K < 1 || batch < 1) return GCCNMF_ERR_ARG;
     if ((Kp & 3) || (Np & 3) || Fp < F || Kp < gccnmf_round_up(K, KLD_BK) || Np < gccnmf_round_up(N, 4)) return GCCNMF_ERR_ARG;      // float4 staging inside the pitches
     KlDivArgs p = {};
@@ -179,7 +188,10 @@ int gccnmf_kl_divergence_launch(const float* V, const float* W, long sW, const f
     p.partials = partials; p.s_partials = s_partials;
     const long tiles = (long)p.tiles_m * p.tiles_n;
     if (tiles > s_partials || tiles * batch > 0x7fffffffL) return GCCNMF_ERR_ARG;
-    hipLaunchKernelGGL(kl_divergence_tile_kernel, dim3((unsigned)(tiles * batch)), dim3(KLD_NT), 0, stream, p);
+    const dim3 grid((unsigned)(tiles * batch)), block(KLD_NT);
+    if (divergence == 1) hipLaunchKernelGGL(kl_divergence_tile_kernel<1>, grid, block, 0, stream, p);
+    else if (divergence == 2) hipLaunchKernelGGL(kl_divergence_tile_kernel<2>, grid, block, 0, stream, p);
+    else hipLaunchKernelGGL(kl_divergence_tile_kernel<0>, grid, block, 0, stream, p);
     GCCNMF_CHECK_LAUNCH();
     hipLaunchKernelGGL(kl_divergence_sum_kernel, dim3(batch), dim3(256), 0, stream, (const double*)partials, s_partials, (int)tiles, out);
     GCCNMF_CHECK_LAUNCH();

@@ -27,6 +27,10 @@ bool gccnmf_klnmf_semi_supported(int F, int K, int nfree);
 int gccnmf_klnmf_semi_rht_launch(const float* R, const float* H, float* U, float* rowsumH, int F, int N, int K, int nfree, int batch, hipStream_t s);
 int gccnmf_klnmf_semi_update_w_launch(float* W, const float* U, const float* rowsumH, float* colsumW, float* hscale, int F, int K, int nfree,
                                       int batch, hipStream_t s);
+// Itakura-Saito / Euclidean NMF (GCCNMF_FLAG_DIVERGENCE_IS / _EUCLIDEAN), nmf_beta.hip: stages 1-5 of that iteration
+bool gccnmf_klnmf_beta_supported(int F, int K);
+int gccnmf_klnmf_beta_stage_launch(int stage, int divergence, const float* V, float* W, float* H, float* R, float* Q, float* Un, float* Ud,
+                                   float* colsumW, float* hscale, int F, int N, int K, int batch, float alpha, float eps, hipStream_t s);
 #include "../../include/gccnmf_hip.h"
 
 #include <atomic>
@@ -456,11 +460,14 @@ struct KlnmfMode {
     int groups;                 // GCCNMF_FLAG_GROUPS: file groups that run this call side by side on separate streams, launch forms sized for all (1 = alone)
     bool fixed_w, h_ones;       // GCCNMF_FLAG_FIXED_W, GCCNMF_FLAG_H_ONES
     int free_atoms;             // GCCNMF_FLAG_FREE_ATOMS(n): the last n atoms of every file's W are learned beside a dictionary (0 = not semi-supervised)
+    int divergence;             // bits 26-27: 0 = KL, 1 = GCCNMF_FLAG_DIVERGENCE_IS, 2 = GCCNMF_FLAG_DIVERGENCE_EUCLIDEAN
 };
 // ... with the argument rules of the flag combinations, decided before anything is launched: GCCNMF_OK = a valid word.
 //   fixed dictionary: GCCNMF_FLAG_FIXED_W alone or with GCCNMF_FLAG_H_ONES, nothing else (H_ONES without FIXED_W: GCCNMF_ERR_ARG)
 //   free atoms: not with the concurrent-groups or the unfused-W-update bit, n <= 128, n < K (GCCNMF_ERR_ARG); (K - n) % 16 == 0, K <= 1024,
 //   F <= 2049 (GCCNMF_ERR_UNSUPPORTED)
+//   IS / Euclid: one of the two bits, not with a fixed dictionary, the all-ones start, free atoms, concurrent groups or the unfused W update
+//   (GCCNMF_ERR_ARG); F <= 2049, K <= 1024 (GCCNMF_ERR_UNSUPPORTED)
 static int decode_mode(int flags, int F, int K, KlnmfMode& m) {
     const int n = (flags & (GCCNMF_FLAG_GROUPS(255) & ~GCCNMF_FLAG_CONCURRENT_GROUPS)) / (GCCNMF_FLAG_GROUPS(1) & ~GCCNMF_FLAG_CONCURRENT_GROUPS);
     m.xcd_affine = !(flags & GCCNMF_FLAG_NO_XCD_AFFINITY);
@@ -469,6 +476,11 @@ static int decode_mode(int flags, int F, int K, KlnmfMode& m) {
     m.fixed_w = (flags & GCCNMF_FLAG_FIXED_W) != 0;
     m.h_ones = (flags & GCCNMF_FLAG_H_ONES) != 0;
     m.free_atoms = (flags & GCCNMF_FLAG_FREE_ATOMS(255)) / GCCNMF_FLAG_FREE_ATOMS(1);
+    m.divergence = (flags >> 26) & 3;
+    if (m.divergence) {
+        if (m.divergence == 3 || m.fixed_w || m.h_ones || m.free_atoms || (flags & GCCNMF_FLAG_CONCURRENT_GROUPS) || m.unfused_w_update) return GCCNMF_ERR_ARG;
+        return gccnmf_klnmf_beta_supported(F, K) ? GCCNMF_OK : GCCNMF_ERR_UNSUPPORTED;
+    }
     if (m.fixed_w || m.h_ones) return m.fixed_w && !(flags & ~(GCCNMF_FLAG_FIXED_W | GCCNMF_FLAG_H_ONES)) ? GCCNMF_OK : GCCNMF_ERR_ARG;
     if (!m.free_atoms) return GCCNMF_OK;
     if (m.groups > 1 || m.unfused_w_update || m.free_atoms > 128 || m.free_atoms >= K) return GCCNMF_ERR_ARG;
@@ -815,6 +827,18 @@ static KlnmfWorkspace carve(float* workspace, const NmfGeom& g, int batch, bool 
     ws.floats = end;
     return ws;
 }
+// An IS / Euclidean call's workspace is the KL carve above followed by GCCNMF_KLNMF_DIVERGENCE_WORKSPACE_FLOATS more floats: Q [batch][Fp][Np] |
+// Ud [batch][Fp][Kp] (the KL carve is a multiple of 32 floats: both blocks start 16-byte aligned).  R, U (= Un), colsumW, hscale, the status words
+// and stage 7's float64 partials and results sit where the KL call keeps them.
+struct BetaWorkspace {
+    float *Q, *Ud;
+};
+static BetaWorkspace carve_beta(float* workspace, const KlnmfWorkspace& ws, const NmfGeom& g, int batch) {
+    BetaWorkspace b;
+    b.Q = workspace + ws.floats;
+    b.Ud = b.Q + batch * g.sV;
+    return b;
+}
 static bool workspace_aligned(const void* workspace) { return ((uintptr_t)workspace & 15) == 0; }
 
 // The lists of a chained launch (tuning key 23): 1 = whole files per XCD (hand-over through that XCD's L2), 2 = the file-major tile list cut into equal
@@ -855,7 +879,7 @@ static bool chain_rule(int batch, const KlnmfMode& m) {
 }
 // ---- which launches a per-file-dictionary call is made of, decided ONCE at the entry point (gccnmf_klnmf / _stage / _plan / _ragged) ---------
 // plan_klnmf is the only code that reads the form-selecting tuning keys and shape rules; klnmf_stage and the call loops test these fields and no rule.
-enum KlnmfKind { KLNMF_BLIND, KLNMF_FIXED_W, KLNMF_FREE_ATOMS };      // W learned | one given W (GCCNMF_FLAG_FIXED_W) | free atoms beside a dictionary
+enum KlnmfKind { KLNMF_BLIND, KLNMF_FIXED_W, KLNMF_FREE_ATOMS, KLNMF_BETA };      // W learned | one given W (GCCNMF_FLAG_FIXED_W) | free atoms beside a dictionary | IS / Euclid
 struct KlnmfPlan {
     KlnmfKind kind;
     bool direct;            // every stage on the direct latency kernels (direct.hip)
@@ -874,6 +898,10 @@ static KlnmfPlan plan_klnmf(const NmfGeom& g, int batch, const KlnmfMode& m) {
     KlnmfPlan p = {};
     p.kind = m.fixed_w ? KLNMF_FIXED_W : m.free_atoms ? KLNMF_FREE_ATOMS : KLNMF_BLIND;
     if (p.kind == KLNMF_FIXED_W) return p;      // one launch runs every iteration (nmf_fixed.hip); of the stages only 7 exists, in one form
+    if (m.divergence) {                         // IS / Euclid: five plain launches per iteration in ONE form (nmf_beta.hip), no tuning key is read
+        p.kind = KLNMF_BETA;
+        return p;
+    }
     // Free atoms (semi-supervised): stage 4 reads a materialised R [batch][Fp][Np] with zero padding, so stages 1-3 take the forms that leave
     // one in the workspace whatever the tuning keys say -- never the direct kernels (they keep Rt), never the K3 + K4a slab launch.  K1 + K2
     // fused stays: stage 3 rewrites R.  Stages 4 and 5 are nmf_semi.hip's, on the free columns alone.  Nothing chains.
@@ -1095,7 +1123,20 @@ static int klnmf_stage(int stage, const float* V, float* W, float* H, const Klnm
         // D(V || W.H) of the current (materialised) factors, divergence.hip: tile partials (float64) in each file's R block, the batch
         // results (float64) at the start of the U region; one launch form whatever the batch or the tuning.  V, W, H are read only.
         // (float64 partials and results: the workspace is 16-byte aligned -- the entry point checked -- and both offsets are multiples of 4096 bytes)
-        return gccnmf_kl_divergence_launch(V, W, p.kind == KLNMF_FIXED_W ? 0 : g.sW, H, g.F, g.N, g.K, g.Fp, g.Kp, g.Np, batch, (double*)R, g.sV / 2, (double*)U, s);
+        return gccnmf_kl_divergence_launch(V, W, p.kind == KLNMF_FIXED_W ? 0 : g.sW, H, g.F, g.N, g.K, g.Fp, g.Kp, g.Np, batch, (double*)R, g.sV / 2, (double*)U, s,
+                                           m.divergence);
+    }
+    if (p.kind == KLNMF_BETA && stage != 6) {      // (stage 6 is the same launch on every path: below)
+        const BetaWorkspace bw = carve_beta(R, ws, g, batch);      // (R is the start of the workspace)
+        if (stage == 0) {
+            // R and Q are zero outside f < F, n < N from here on (stages 1 and 3 rewrite the whole padded blocks); colsumW, hscale = 1 as for KL
+            if (hipMemsetAsync(R, 0, sizeof(float) * batch * g.sV, s) != hipSuccess) return GCCNMF_ERR_LAUNCH;
+            if (hipMemsetAsync(bw.Q, 0, sizeof(float) * batch * g.sV, s) != hipSuccess) return GCCNMF_ERR_LAUNCH;
+            hipLaunchKernelGGL(nmf_prepare_kernel, dim3(batch * (g.Kp / 16)), dim3(256), 0, s, W, colsumW, hscale, g.F, g.Fp, g.Kp);
+            GCCNMF_CHECK_LAUNCH();
+            return GCCNMF_OK;
+        }
+        return gccnmf_klnmf_beta_stage_launch(stage, m.divergence, V, W, H, R, bw.Q, U, bw.Ud, colsumW, hscale, g.F, g.N, g.K, batch, alpha, eps, s);
     }
     const int nfree = m.free_atoms, groups = m.groups;      // (GCCNMF_FLAG_GROUPS: the W update kernel is sized for all groups together)
     const bool semi = p.kind == KLNMF_FREE_ATOMS;
@@ -1196,7 +1237,8 @@ static int finish_call(bool chained, const float* V, float* W, float* H, const K
 // Which launches gccnmf_klnmf would use for this problem under the current tuning: bit 0 the direct latency kernels, bit 1 the fused
 // K1 + K2 launch, bit 2 the fused K3 + K4a slab launch, bit 3 chained launches of the iteration (benchmarks and tests name the kernel they
 // time by this; the engine keeps ONE file group when the library chains), bit 4 the fused fixed-dictionary launch (GCCNMF_FLAG_FIXED_W),
-// bit 5 the semi-supervised iteration (GCCNMF_FLAG_FREE_ATOMS; bits 4 and 5: then no other bit).
+// bit 5 the semi-supervised iteration (GCCNMF_FLAG_FREE_ATOMS), bit 6 the IS / Euclidean iteration (GCCNMF_FLAG_DIVERGENCE_*; bits 4, 5 and 6: then
+// no other bit).
 int gccnmf_klnmf_plan(int F, int N, int K, int batch, int flags) {
     GCCNMF_ENTER();
     if (F < 2 || N < 1 || K < 1 || batch < 1) return -1;
@@ -1205,6 +1247,7 @@ int gccnmf_klnmf_plan(int F, int N, int K, int batch, int flags) {
     const KlnmfPlan p = plan_klnmf(make_geom(F, N, K), batch, m);
     if (p.kind == KLNMF_FIXED_W) return gccnmf_klnmf_fixed_supported(F, K) ? 16 : -1;
     if (p.kind == KLNMF_FREE_ATOMS) return 32;
+    if (p.kind == KLNMF_BETA) return 64;
     return (p.direct ? 1 : 0) | (p.fused12 ? 2 : 0) | (p.head34 > 0 ? 4 : 0) | ((p.chain || p.short_group) ? 8 : 0);
 }
 
@@ -1234,7 +1277,8 @@ int gccnmf_klnmf(const float* V, float* W, float* H, float* workspace, int F, in
     const KlnmfPlan p = plan_klnmf(g, batch, m);
     const KlnmfWorkspace ws = carve(workspace, g, batch, false);
     const float alpha = sparsity_alpha, eps = epsilon;
-    if (p.kind == KLNMF_FREE_ATOMS) {
+    if (p.kind == KLNMF_FREE_ATOMS || p.kind == KLNMF_BETA) {
+        // IS / Euclid: five plain launches per iteration (nmf_beta.hip); nothing chains.
         // semi-supervised: the dictionary in W[:, :K - n] of every file stays as it is, the n free atoms behind it and all of H are learned.
         // Plain launches (klnmf_stage keeps R materialised); nothing chains.
         if ((rc = clear_chain_status(ws, s))) return rc;
@@ -1308,7 +1352,7 @@ int gccnmf_klnmf_ragged(const float* V, float* W, float* H, float* workspace, in
     GCCNMF_ENTER();
     if (!V || !W || !H || !workspace || !N || F < 2 || Nmax < 1 || K < 1 || batch < 1 || iterations < 0) return GCCNMF_ERR_ARG;
     KlnmfMode m;
-    if (decode_mode(flags, F, K, m) || m.fixed_w || m.free_atoms) return GCCNMF_ERR_ARG;
+    if (decode_mode(flags, F, K, m) || m.fixed_w || m.free_atoms || m.divergence) return GCCNMF_ERR_ARG;
     m.groups = 1;      // (intended today: the concurrent-groups bit is masked off -- a ragged batch exists in ONE form, whatever runs beside it)
     if (!workspace_aligned(workspace)) return GCCNMF_ERR_ARG;
     if (batch > GCCNMF_RAGGED_MAX_BATCH) return GCCNMF_ERR_UNSUPPORTED;

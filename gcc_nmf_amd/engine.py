@@ -260,7 +260,13 @@ class GCCNMFEngine(object):
     (converge_klnmf states the rule; a rise stops a file too, which is intended for sparsityAlpha > 0).  ``get_iterations()`` (batch,),
     ``get_divergence_trace()`` (checks + 1, batch).  A file's factors and count depend on that file alone; they agree with a
     single call of the same count to round-off, not to the bit.  ``tolerance=None`` is the single call, bit for bit.
-    ``get_divergence()`` (batch,) float64 works after ``klnmf()`` either way: one launch (gccnmf_klnmf_stage, stage 7)."""
+    ``get_divergence()`` (batch,) float64 works after ``klnmf()`` either way: one launch (gccnmf_klnmf_stage, stage 7).
+
+    ``divergence`` = 'kl' (default) | 'is' | 'euclidean' (DESIGN section 2d): the objective the factorisation minimises -- Itakura-Saito
+    or Euclidean NMF in place of KL (gccnmf_klnmf with GCCNMF_FLAG_DIVERGENCE_*: plain launches, one file group).  V stays the MAGNITUDE
+    spectrogram and everything behind the factors is unchanged; ``tolerance`` / ``get_divergence()`` / ``get_divergence_trace()`` use the
+    chosen divergence (getBetaDivergence states each).  Not with ``dictionaryW`` or ``numFreeAtoms``, nor with the concurrent-groups or
+    unfused-W-update bits of ``klnmf_flags`` (ValueError); at most 1024 atoms and 2049 bins."""
 
     def __new__(cls, n_samples=None, *args, **kwargs):
         if cls is GCCNMFEngine and kwargs.get('lengths') is not None:
@@ -275,8 +281,18 @@ class GCCNMFEngine(object):
                  sparsityAlpha=0, epsilon=1e-16, seedValue=0, batch=1, windowFunction=np.hanning,
                  device='cuda:0', klnmf_flags=0, nmf_groups=None, dictionaryW=None, initialH='random', reconstruction='direct',
                  gccPHATNLEnabled=False, gccPHATNLAlpha=2.0, tdoaTracking=False, localizationWindowSize=None, tolerance=None, checkEvery=10,
-                 numFreeAtoms=0, maxTargets=None, spatialIterations=0):
+                 numFreeAtoms=0, maxTargets=None, spatialIterations=0, divergence='kl'):
         self.autoTargets, numTargets = _hip.check_auto_targets(numTargets, maxTargets, tdoaTracking)
+        self.divergence = _hip.check_divergence(divergence, int(windowSize) // 2 + 1, None if dictionarySize is None else int(dictionarySize))
+        if self.divergence != 'kl':
+            if dictionaryW is not None or numFreeAtoms:
+                raise ValueError('divergence=%r learns every atom: not available with dictionaryW or numFreeAtoms' % (self.divergence,))
+            if klnmf_flags & 6:
+                raise ValueError('divergence=%r cannot be combined with the concurrent-groups or unfused-W-update bits of klnmf_flags'
+                                 % (self.divergence,))
+            if nmf_groups not in (None, 1):
+                raise ValueError('divergence=%r runs as one file group (nmf_groups=1)' % (self.divergence,))
+            nmf_groups = 1
         if initialH not in ('random', 'ones'):
             raise ValueError("initialH must be 'random' or 'ones'")
         self.initialH = initialH
@@ -371,7 +387,7 @@ class GCCNMFEngine(object):
                 self.W0 = padded(self.dictionaryW, (g.Fp, g.Kp), dev)
                 self.W.copy_(self.W0.unsqueeze(0).expand_as(self.W))
             # nmf_groups equal group workspaces (for one group == the whole-batch workspace)
-            self.ws_nmf = z(self.nmf_groups * self.lib.gccnmf_klnmf_workspace_floats(F, g.N, g.K, B // self.nmf_groups))
+            self.ws_nmf = z(self.nmf_groups * _hip.klnmf_divergence_workspace_floats(F, g.N, g.K, B // self.nmf_groups, self.divergence))
             self.nmf_streams = [torch.cuda.Stream(device=dev) for _ in range(self.nmf_groups)] if self.nmf_groups > 1 else []
             # Copy streams of separate_batches, created ONCE and right behind the group streams.  The runtime maps streams onto a
             # few hardware queues in creation order (4 by default), and a queue is in-order: a 244 MB download that shares its queue
@@ -473,13 +489,14 @@ class GCCNMFEngine(object):
         """(batch,) float64 on the device: stage 7 per file group, each in its own workspace."""
         g = self.g
         fixed = self._fixed()
-        out = [klnmf_divergence(self.V[b0], self.W0 if fixed else self.W[b0], self.H[b0], ws, g.F, g.N, g.K, per, fixed)
+        out = [klnmf_divergence(self.V[b0], self.W0 if fixed else self.W[b0], self.H[b0], ws, g.F, g.N, g.K, per, fixed, divergence=self.divergence)
                for b0, per, ws, _ in self._groups()]
         return out[0] if len(out) == 1 else torch.cat(out)
 
     @_on_device
     def get_divergence(self):
-        """(batch,) float64: D(V || W.H) of the factors as they are now (after klnmf()); one launch and a download."""
+        """(batch,) float64: D(V || W.H) of the factors as they are now (after klnmf()), in the engine's ``divergence``; one launch and a
+        download."""
         return self._divergence().cpu().numpy()
 
     def get_iterations(self):
@@ -511,7 +528,8 @@ class GCCNMFEngine(object):
             # (all-half-height tiles, which win for a 32-file launch ALONE, lose here: 152.4 k vs 155.4 k frames/s)
             _hip.klnmf(self.V[b0], self.W0 if fixed else self.W[b0], self.H[b0], ws, g.F, g.N, g.K, per, iters, self.alpha, self.eps,
                        fixed_w=fixed, h_ones=fixed and first and self.initialH == 'ones', groups=self.nmf_groups,
-                       flags=0 if fixed else self.klnmf_flags, free_atoms=self.numFreeAtoms, stream=None if st is None else st.cuda_stream)
+                       flags=0 if fixed else self.klnmf_flags, free_atoms=self.numFreeAtoms, stream=None if st is None else st.cuda_stream,
+                       divergence=self.divergence)
             if st is not None:
                 done = torch.cuda.Event()
                 done.record(st)
@@ -860,7 +878,7 @@ class GCCNMFEnhancementEngine(GCCNMFEngine):
     ``localize()`` picks ONE peak of each file's mean angular spectrum as the talker's direction (with ``tdoaTracking``: one per frame);
     ``targetTDOAIndex`` -- one index, or one per file -- skips the pick.  ``separate()`` returns (batch, 2, 2, L) waveforms ordered
     [talker, noise], and so do ``separate_batches`` and ``separate_pcm16``; ``get_atom_tdoa_indexes()`` (batch, K, T).  Everything in
-    front of the masks is GCCNMFEngine's: ``dictionaryW``, ``numFreeAtoms``, ``tolerance``, ``reconstruction``,
+    front of the masks is GCCNMFEngine's: ``dictionaryW``, ``numFreeAtoms``, ``tolerance``, ``divergence``, ``reconstruction``,
     ``spatialIterations``, ``gccPHATNLEnabled``.
     There is no ``numTargets`` keyword (two outputs), and no ragged form: ``lengths=`` raises ValueError."""
 
@@ -950,14 +968,22 @@ class RaggedGCCNMFEngine(object):
     (gccnmf_klnmf_ragged: padding to the 64-column tile only, the files dealt out to the XCDs by length).  The one-shot stages (STFT,
     localisation, masks, reconstruction, iSTFT) run per distinct length, on the ordinary engine of that length.  A file's results are bit
     for bit those it gets in an equal-length batch.  Where the library has no chained form for the shape (GCCNMF_ERR_UNSUPPORTED: short
-    dictionaries, a handful of files) the files of each length run their KL-NMF as a batch of their own."""
+    dictionaries, a handful of files) the files of each length run their KL-NMF as a batch of their own -- and so they do with
+    ``divergence`` = 'is' / 'euclidean' (GCCNMFEngine states the keyword), which has no ragged launch."""
 
     def __init__(self, lengths, sampleRate=16000, windowSize=1024, hopSize=256, numTDOAs=128, microphoneSeparationInMetres=1.0,
                  numTargets=3, dictionarySize=None, numIterations=100, sparsityAlpha=0, epsilon=1e-16, seedValue=0,
                  windowFunction=np.hanning, device='cuda:0', klnmf_flags=0, dictionaryW=None, initialH='random', reconstruction='direct',
                  gccPHATNLEnabled=False, gccPHATNLAlpha=2.0, tdoaTracking=False, localizationWindowSize=None, tolerance=None, checkEvery=10,
-                 maxTargets=None, spatialIterations=0):
+                 maxTargets=None, spatialIterations=0, divergence='kl'):
         self.tolerance, self.checkEvery, numIterations = _hip.check_convergence(tolerance, checkEvery, numIterations)
+        self.divergence = _hip.check_divergence(divergence, int(windowSize) // 2 + 1, None if dictionarySize is None else int(dictionarySize))
+        if self.divergence != 'kl':
+            if dictionaryW is not None:
+                raise ValueError('divergence=%r learns every atom: not available with dictionaryW or numFreeAtoms' % (self.divergence,))
+            if klnmf_flags & 6:
+                raise ValueError('divergence=%r cannot be combined with the concurrent-groups or unfused-W-update bits of klnmf_flags'
+                                 % (self.divergence,))
         self.autoTargets, slots = _hip.check_auto_targets(numTargets, maxTargets, tdoaTracking)
         self.reconstruction = check_reconstruction(reconstruction, slots)
         self.spatialIterations = _hip.check_spatial_iterations(spatialIterations, self.reconstruction)
@@ -979,7 +1005,8 @@ class RaggedGCCNMFEngine(object):
                   windowFunction=windowFunction, device=device, klnmf_flags=klnmf_flags, dictionaryW=dictionaryW, initialH=initialH,
                   reconstruction=reconstruction, gccPHATNLEnabled=gccPHATNLEnabled, gccPHATNLAlpha=gccPHATNLAlpha,
                   tdoaTracking=tdoaTracking, localizationWindowSize=localizationWindowSize,     # (each file's windows end at its own T)
-                  tolerance=tolerance, checkEvery=checkEvery, maxTargets=maxTargets, spatialIterations=spatialIterations)
+                  tolerance=tolerance, checkEvery=checkEvery, maxTargets=maxTargets, spatialIterations=spatialIterations,
+                  divergence=self.divergence)
         # one ordinary engine per distinct length: its files (caller's indexes, ascending) are its batch
         self.files_of = {}
         for i, n in enumerate(self.lengths):
@@ -992,8 +1019,9 @@ class RaggedGCCNMFEngine(object):
         with torch.cuda.device(self.device):
             z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=self.device)
             self.ragged = None
-            # a fixed dictionary: each length's engine runs its own one-launch call; a tolerance: each length's files converge as a batch of their own
-            if len(self.sub) > 1 and dictionaryW is None and self.tolerance is None:
+            # a fixed dictionary: each length's engine runs its own one-launch call; a tolerance: each length's files converge as a batch of their
+            # own; IS / Euclid: the ragged launch is KL only, each length runs as a batch of its own
+            if len(self.sub) > 1 and dictionaryW is None and self.tolerance is None and self.divergence == 'kl':
                 ws = self.lib.gccnmf_klnmf_ragged_workspace_floats(g.F, g.N, g.K, self.batch)
                 if ws > 0:
                     self.ragged = dict(V=z(self.batch, g.Fp, g.Np), W=z(self.batch, g.Fp, g.Kp), H=z(self.batch, g.Kp, g.Np), ws=z(ws),

@@ -109,6 +109,37 @@ def performKLNMF(V, dictionarySize, numIterations, sparsityAlpha, epsilon=1e-16,
     return W, H
 
 
+def performBetaNMF(V, dictionarySize, numIterations, beta, sparsityAlpha=0, epsilon=1e-16, seedValue=0):
+    """NMF under one of the three classic beta-divergences (not in the reference, whose performKLNMF is beta = 1):
+    ``beta`` = 0 or 'is' (Itakura-Saito), 1 or 'kl' (Kullback-Leibler), 2 or 'euclidean'.  Plain multiplicative updates in
+    performKLNMF's structure -- with P = W.H:  H <- H o W^T(V o P^(beta-2)) / (W^T P^(beta-1) + sparsityAlpha + epsilon), the same for W
+    without alpha and epsilon, then the unit-norm atoms and the compensating scale of H (gccNMFFunctions.py:75-81).  The initial factors
+    are those performKLNMF draws (with its side effect on NumPy's global generator); beta = 1 IS performKLNMF, bit for bit.
+    V is any non-negative (F, N) matrix: a magnitude spectrogram as everywhere in GCC-NMF, or -- the local Gaussian model behind
+    Itakura-Saito NMF -- the power spectrogram |X|^2; that choice is the caller's.  IS needs V > 0 where the model is to fit (a zero of V
+    pulls nothing: R = 0 there).  Returns float32 (W, H).  beta = 0, 2: F <= 2049, dictionarySize <= 1024, at most LARGE_N_COLUMNS
+    columns (ValueError otherwise: the column-block path of a larger V is KL only)."""
+    V = np.asarray(V)
+    if V.ndim != 2:
+        raise ValueError('V must be (F, N)')
+    F, N = V.shape
+    K = int(dictionarySize)
+    d = _hip.check_divergence(beta, F, K)
+    if d == 'kl':
+        return performKLNMF(V, dictionarySize, numIterations, sparsityAlpha, epsilon, seedValue)
+    if N > LARGE_N_COLUMNS:
+        raise ValueError('performBetaNMF with beta = %r runs V as one call: at most %d columns, got %d (the column-block path is KL only)'
+                         % (beta, LARGE_N_COLUMNS, N))
+    lib, dev = _hip.lib(), _device()
+    init = _klnmf_initial_factors(F, N, K, epsilon, seedValue, dev)
+    with _staging.Scope(dev) as sc:
+        dV, dW, dH, ws = _klnmf_buffers(sc, lib, V, K, init, d)
+        _hip.klnmf(dV, dW, dH, ws, F, N, K, 1, int(numIterations), float(sparsityAlpha), float(epsilon), divergence=d)
+        W = sc.remember(sc.download(dW[:F, :K]), 'W', dict(W=dW), dict(F=F, K=K))
+        H = sc.download(dH[:K, :N])
+    return W, H
+
+
 def _klnmf_initial_factors(F, N, K, epsilon, seedValue, dev):
     """Device images of performKLNMF's initial W and H (gccNMF/gccNMFFunctions.py:70-73), with the reference's side effect on the
     GLOBAL generator."""
@@ -131,8 +162,8 @@ def _klnmf_initial_factors(F, N, K, epsilon, seedValue, dev):
     return init
 
 
-def _klnmf_buffers(sc, lib, V, K, init):
-    """The padded device buffers of one batch-1 KL-NMF call, loaded with V and the initial factors: (dV, dW, dH, workspace)."""
+def _klnmf_buffers(sc, lib, V, K, init, divergence='kl'):
+    """The padded device buffers of one batch-1 NMF call, loaded with V and the initial factors: (dV, dW, dH, workspace)."""
     F, N = V.shape
     g = Geometry(F, 1, K)
     Np = -(-N // 64) * 64
@@ -140,7 +171,7 @@ def _klnmf_buffers(sc, lib, V, K, init):
     dV = sc.dev('V', (g.Fp, Np), corner=(F, N))
     dW = sc.dev('W', (g.Fp, g.Kp), corner=(F, K))
     dH = sc.dev('H', (g.Kp, Np), corner=(K, N))
-    ws = sc.dev('ws_klnmf', (lib.gccnmf_klnmf_workspace_floats(F, N, K, 1),))
+    ws = sc.dev('ws_klnmf', (_hip.klnmf_divergence_workspace_floats(F, N, K, 1, divergence),))
     dV[:F, :N].copy_(sc.upload(V, 'V', float32))
     dW[:F, :K].copy_(init['W'])
     dH[:K, :N].copy_(init['H'])
@@ -157,24 +188,40 @@ def performKLNMFUntilConverged(V, dictionarySize, maxIterations, sparsityAlpha, 
     may go up.  A non-finite D stops nothing.  Returns (W, H, info), info = {'iterations': n, 'divergences': [(iteration, D), ...]}
     starting with (0, D of the initial factors).  W and H agree with performKLNMF(V, dictionarySize, n, ...) to round-off, not to the
     bit (H is rescaled by the atom norms in place between chunks instead of lazily).  One call's worth of columns only: V of more
-    than LARGE_N_COLUMNS columns raises NotImplementedError."""
+    than LARGE_N_COLUMNS columns raises NotImplementedError.  (performBetaNMFUntilConverged is the same under the Itakura-Saito or the
+    Euclidean divergence.)"""
+    return _nmf_until_converged(V, dictionarySize, maxIterations, sparsityAlpha, tolerance, checkEvery, epsilon, seedValue, 'kl',
+                                'performKLNMFUntilConverged', 'performKLNMF')
+
+
+def performBetaNMFUntilConverged(V, dictionarySize, maxIterations, beta, sparsityAlpha=0, tolerance=1e-4, checkEvery=10, epsilon=1e-16,
+                                 seedValue=0):
+    """performKLNMFUntilConverged under the divergence ``beta`` names (performBetaNMF states the values): performBetaNMF's updates, stopped
+    by THAT divergence (getBetaDivergence; for Itakura-Saito over the elements with V > 0) under the same rule.  beta = 1 is
+    performKLNMFUntilConverged.  Returns (W, H, info) likewise."""
+    return _nmf_until_converged(V, dictionarySize, maxIterations, sparsityAlpha, tolerance, checkEvery, epsilon, seedValue,
+                                _hip.check_divergence(beta, np.shape(V)[0] if np.ndim(V) == 2 else None, int(dictionarySize)),
+                                'performBetaNMFUntilConverged', 'performBetaNMF')
+
+
+def _nmf_until_converged(V, dictionarySize, maxIterations, sparsityAlpha, tolerance, checkEvery, epsilon, seedValue, divergence, name, fixed_name):
     tolerance, checkEvery, maxIterations = _hip.check_convergence(tolerance, checkEvery, maxIterations)
     if tolerance is None:
-        raise ValueError('performKLNMFUntilConverged needs a tolerance; performKLNMF runs a fixed number of iterations')
+        raise ValueError('%s needs a tolerance; %s runs a fixed number of iterations' % (name, fixed_name))
     V = np.asarray(V)
     F, N = V.shape
     K = int(dictionarySize)
     if N > LARGE_N_COLUMNS:
-        raise NotImplementedError('performKLNMFUntilConverged runs V as one call: at most %d columns, got %d (performKLNMF takes such a V '
-                                  'as column blocks, without a stopping rule)' % (LARGE_N_COLUMNS, N))
+        raise NotImplementedError('%s runs V as one call: at most %d columns, got %d (performKLNMF takes such a V '
+                                  'as column blocks, without a stopping rule)' % (name, LARGE_N_COLUMNS, N))
     lib, dev = _hip.lib(), _device()
     init = _klnmf_initial_factors(F, N, K, epsilon, seedValue, dev)
     with _staging.Scope(dev) as sc:
-        dV, dW, dH, ws = _klnmf_buffers(sc, lib, V, K, init)
+        dV, dW, dH, ws = _klnmf_buffers(sc, lib, V, K, init, divergence)
 
         def launch(n, first):
-            _hip.klnmf(dV, dW, dH, ws, F, N, K, 1, n, float(sparsityAlpha), float(epsilon))
-        iterations, trace = converge_klnmf(launch, lambda: klnmf_divergence(dV, dW, dH, ws, F, N, K, 1).cpu().numpy(),
+            _hip.klnmf(dV, dW, dH, ws, F, N, K, 1, n, float(sparsityAlpha), float(epsilon), divergence=divergence)
+        iterations, trace = converge_klnmf(launch, lambda: klnmf_divergence(dV, dW, dH, ws, F, N, K, 1, divergence=divergence).cpu().numpy(),
                                            [dW.unsqueeze(0), dH.unsqueeze(0)], maxIterations, tolerance, checkEvery)
         W = sc.remember(sc.download(dW[:F, :K]), 'W', dict(W=dW), dict(F=F, K=K))
         H = sc.download(dH[:K, :N])
@@ -216,9 +263,21 @@ def getKLDivergence(V, W, H):
     """The objective of performKLNMF, which the reference never evaluates: D(V || W.H) = sum V log(V / WH) - V + WH over every element
     (a zero of V contributes WH alone), as a float64 scalar.  W.H runs in float32 on the matrix cores and is never stored; the terms
     are summed in float64 (gccnmf_klnmf_stage, stage 7: csrc/divergence.hip).  V (F, N), W (F, K), H (K, N)."""
+    return _beta_divergence(V, W, H, 'kl', 'getKLDivergence')
+
+
+def getBetaDivergence(V, W, H, beta):
+    """The objective of performBetaNMF as a float64 scalar, with R = W.H in float32 on the matrix cores (never stored) and the terms
+    summed in float64 (gccnmf_klnmf_stage, stage 7).  ``beta`` = 1 / 'kl': getKLDivergence.  0 / 'is': sum of V / R - log(V / R) - 1 over
+    the elements with V > 0 -- IS is +infinity at a zero of V, so such an element contributes NOTHING and the value is the divergence over
+    the support of V.  2 / 'euclidean': sum of (V - R)^2 / 2.  V (F, N), W (F, K), H (K, N)."""
+    return _beta_divergence(V, W, H, _hip.check_divergence(beta), 'getBetaDivergence')
+
+
+def _beta_divergence(V, W, H, divergence, name):
     V, H = np.asarray(V), np.asarray(H)
     if V.ndim != 2 or np.ndim(W) != 2 or H.ndim != 2 or np.shape(W) != (V.shape[0], H.shape[0]) or H.shape[1] != V.shape[1]:
-        raise ValueError('getKLDivergence takes V (F, N), W (F, K) and H (K, N), got %s, %s, %s' % (V.shape, np.shape(W), H.shape))
+        raise ValueError('%s takes V (F, N), W (F, K) and H (K, N), got %s, %s, %s' % (name, V.shape, np.shape(W), H.shape))
     F, N = V.shape
     K = H.shape[0]
     lib, dev = _hip.lib(), _device()
@@ -231,7 +290,7 @@ def getKLDivergence(V, W, H):
         dV[:F, :N].copy_(sc.upload(V, 'V', float32))
         dH[:K, :N].copy_(sc.upload(H, 'H', float32))
         dW = _device_W(sc, W, g, dev)                      # the image behind W if performKLNMF returned it (resident mode)
-        out = sc.download(klnmf_divergence(dV, dW, dH, ws, F, N, K, 1))
+        out = sc.download(klnmf_divergence(dV, dW, dH, ws, F, N, K, 1, divergence=divergence))
     return np.float64(out[0])
 
 

@@ -74,6 +74,34 @@ extern "C" {
                                           * bits (GCCNMF_ERR_ARG); gccnmf_klnmf_plan returns bit 5 alone, or -1 for a call these rules reject;
                                           * gccnmf_klnmf_stage takes the same bits (see there) */
 
+/* bits 26-27: the divergence that gccnmf_klnmf / gccnmf_klnmf_stage minimise.  Both clear = Kullback-Leibler: every call that existed before
+ * launches exactly what it launched.  ITAKURA-SAITO (beta = 0) and EUCLIDEAN (beta = 2) NMF, one file's iteration -- plain multiplicative
+ * updates (exponent 1) in the structure of gccNMFFunctions.py:75-81, csrc/nmf_beta.hip:
+ *     P = W.H                                    f32 on the matrix cores (v_mfma_f32_32x32x2_f32), as everywhere
+ *     IS: Q = 1 / P, R = (V * Q) * Q             Euclid: Q = P, R = V              (KL would be R = V / P, Q = 1)
+ *     H <- H o ((W^T R) / ((W^T Q + alpha) + eps))
+ *     P, R, Q again with the new H
+ *     W <- W o ((R H^T) / (Q H^T))               no eps, as in the KL W update
+ *     s = sqrt(sum_f W^2);  W /= s;  H *= s      (:79-81)
+ * Every element-wise operation is a float32 operation rounded on its own in the order written (IEEE quotients and square root; sum_f W^2 an
+ * fmaf chain); every GEMM element is ONE fma chain over its reduction index in ascending order, so every sum is in an order fixed by
+ * (F, N, K) alone: one launch form whatever the batch and the tuning keys, and a file's factors are bit for bit the same alone, in any batch
+ * and at any place in it.  R and Q are exactly zero outside f < F, n < N (1 / P of a padded element never reaches a reduction), the padding
+ * of W and H stays exactly zero; inside the matrix P = 0 propagates Inf / NaN as IEEE says, like KL's V / 0, and V = 0 gives R = 0.  V is any
+ * non-negative matrix: magnitudes or powers are the caller's choice.
+ * Five plain launches per iteration (the numerator and denominator GEMMs of a half share one); nothing chains, the chain-status words are
+ * cleared; gccnmf_klnmf_plan returns bit 6 alone.  Decided before anything is launched -- GCCNMF_ERR_ARG: both bits; either bit together with
+ * GCCNMF_FLAG_FIXED_W, GCCNMF_FLAG_H_ONES, GCCNMF_FLAG_FREE_ATOMS, GCCNMF_FLAG_CONCURRENT_GROUPS or GCCNMF_FLAG_UNFUSED_W_UPDATE; either bit on
+ * gccnmf_klnmf_ragged.  GCCNMF_ERR_UNSUPPORTED: F > 2049 or K > 1024 (the envelope: 2 <= F <= 2049, 1 <= K <= 1024, any N >= 1, any batch).
+ * The workspace of such a call is LARGER than the KL call's: gccnmf_klnmf_workspace_floats(F, N, K, batch) floats laid out as for KL,
+ * followed by GCCNMF_KLNMF_DIVERGENCE_WORKSPACE_FLOATS(Fp, Kp, Np, batch) more (see gccnmf_klnmf_stage for what sits where). */
+#define GCCNMF_FLAG_DIVERGENCE_IS (1 << 26)
+#define GCCNMF_FLAG_DIVERGENCE_EUCLIDEAN (2 << 26)
+/* floats an IS / Euclidean call needs BEHIND the gccnmf_klnmf_workspace_floats(F, N, K, batch) floats of the KL layout: Q [batch][Fp][Np] |
+ * Ud [batch][Fp][Kp].  A multiple of 64 floats (Kp and Np are multiples of 64); the KL layout is a multiple of 32 floats, so both blocks
+ * start 16-byte aligned when the workspace does (it must: GCCNMF_ERR_ARG otherwise). */
+#define GCCNMF_KLNMF_DIVERGENCE_WORKSPACE_FLOATS(Fp, Kp, Np, batch) ((long)(batch) * (Fp) * ((long)(Np) + (Kp)))
+
 int gccnmf_version(void);
 
 /* Tuning knobs: process-global atomics; every library call works on a snapshot taken at its entry.  Results stay valid (and, where a
@@ -188,8 +216,9 @@ int gccnmf_klnmf_chain_status(const float* workspace, int F, int N, int K, int b
 /* Which launches gccnmf_klnmf uses for this problem under the current tuning: bit 0 = the direct latency kernels (a handful of files),
  * bit 1 = K1 + K2 as one launch of column tiles (tuning key 16), bit 2 = K3 + K4a as one launch of 64-bin slabs (key 17), bit 3 = the whole
  * call as one chained launch (key 21), bit 4 = the fused fixed-dictionary launch (GCCNMF_FLAG_FIXED_W; then no other bit), bit 5 = the semi-supervised
- * iteration (GCCNMF_FLAG_FREE_ATOMS; then no other bit).  -1 on bad arguments (a flag combination gccnmf_klnmf rejects, or a fixed-dictionary
- * or semi-supervised shape outside its envelope).
+ * iteration (GCCNMF_FLAG_FREE_ATOMS; then no other bit), bit 6 = the Itakura-Saito / Euclidean iteration (GCCNMF_FLAG_DIVERGENCE_*; then no other
+ * bit).  -1 on bad arguments (a flag combination gccnmf_klnmf rejects, or a fixed-dictionary, semi-supervised or IS / Euclidean shape outside
+ * its envelope).
  * (Benchmarks and tests name the kernel they time by this; the result of gccnmf_klnmf does not depend on it beyond round-off.) */
 int gccnmf_klnmf_plan(int F, int N, int K, int batch, int flags);
 
@@ -233,7 +262,25 @@ int gccnmf_klnmf_plan(int F, int N, int K, int batch, int flags);
  * without it, but stages 1-3 always take forms that leave R [batch][Fp][Np], zero padded, in the workspace (K1 + K2 fused included: stage 3
  * rewrites R; never the direct kernels or the K3 + K4a slab launch); stage 4 writes U[:, K - n : K] and rowsumH[K - n : K] only, at their ordinary
  * places, stage 5 updates W[:, K - n : K], hscale[K - n : K] and colsumW[K - n : K] only: what belongs to the fixed atoms is not written (hscale
- * stays 1 and colsumW what stage 0 computed).  A call without the bits launches exactly what it launched before they existed. */
+ * stays 1 and colsumW what stage 0 computed).  A call without the bits launches exactly what it launched before they existed.
+ * With GCCNMF_FLAG_DIVERGENCE_IS or GCCNMF_FLAG_DIVERGENCE_EUCLIDEAN in flags (same argument rules as gccnmf_klnmf, decided first; one launch
+ * form, csrc/nmf_beta.hip) the stages are, with the lazy scale s = hscale as above:
+ *     0: colsumW = sum_f W, s = 1, R = Q = 0 | 1: R, Q from P = W.(s * H) | 2: H <- (s * H) * ((W^T.R) / ((W^T.Q + alpha) + eps)) |
+ *     3: R, Q from P = W.H | 4: Un = R.H^T, Ud = Q.H^T | 5: Wt = W * (Un / Ud), s = sqrt(sum_f Wt^2), W = Wt / s, colsumW = sum_f W |
+ *     6: H *= s | 7: that divergence of the current factors, per file, float32 terms summed in float64 in stage 7's order, same places:
+ *          IS      sum over the elements with V > 0 of x - log1p(x), x = (V - R) / R, R = W.H (= V / R - log(V / R) - 1; its series for
+ *                  |x| < 1/8: no cancellation near V = R).  A V = 0 element contributes NOTHING: IS is +infinity there, so the value is
+ *                  the divergence over the support of V
+ *          Euclid  sum of 1/2 (V - R)^2
+ *   with  IS: Q = 1 / P, R = (V * Q) * Q    Euclid: Q = P, R = V.   Where the intermediates sit (floats from `workspace`; KL = the value of
+ *   gccnmf_klnmf_workspace_floats(F, N, K, batch)):
+ *     R        [batch][Fp][Np]      at 0, as for KL; stages 1 and 3 write the whole padded block, exact zeros outside f < F, n < N
+ *     Un       [batch][Fp][Kp]      at batch * Fp * Np: KL's U
+ *     colsumW, rowsumH (not used), hscale [batch][Kp] each, behind Un as for KL; then the rest of the KL layout, of which the status words
+ *                                   alone are used
+ *     Q        [batch][Fp][Np]      at KL; zero padded like R
+ *     Ud       [batch][Fp][Kp]      at KL + batch * Fp * Np
+ *   The padding of Un and Ud is nobody's operand and keeps whatever the workspace held. */
 int gccnmf_klnmf_stage(const float* V, float* W, float* H, float* workspace, int F, int N, int K, int batch,
                        float sparsity_alpha, float epsilon, int flags, int stage, void* stream);
 
