@@ -24,9 +24,9 @@ __global__ __launch_bounds__(FFT_NT) void stft_stereo_kernel(const float* __rest
                                                              int logN, int hop, int T, const float* __restrict__ window,
                                                              const float2* __restrict__ twiddle, float2* __restrict__ X,
                                                              float* __restrict__ V, float* __restrict__ CC, int F, int Fp,
-                                                             int Np, int Tp, int ps) {
+                                                             int Np, int Tp) {
     extern __shared__ __attribute__((aligned(16))) float2 fft_smem[];
-    const int zstride = N + (N >> ps) + FFT_ZPAD;
+    const int zstride = fft_row_floats2(N);
     float2* z = fft_smem;
     float2* tw = fft_smem + TB * zstride;
     const int groups = (T + TB - 1) / TB;
@@ -65,13 +65,13 @@ __global__ __launch_bounds__(FFT_NT) void stft_stereo_kernel(const float* __rest
                     if (PCM16) v = make_float2(w[j] * ((float)q[j].x / 32768.f), w[j] * ((float)q[j].y / 32768.f));
                     else v = make_float2(w[j] * xa[j], w[j] * xb[j]);
                 }
-                z[tb * zstride + fft_pad(bitrev(n, logN), ps)] = v;
+                z[tb * zstride + fft_pad(bitrev(n, logN))] = v;
             }
         }
     }
     __syncthreads();
 #if !(FFT_ABL & 1)
-    fft_stages_any<false, TB>(z, tw, N, logN, zstride, ps);
+    fft_stages_r16<false, TB>(z, tw, N, logN, zstride);
 #endif
 #if FFT_ABL & 2
     if (z[threadIdx.x].x != 123.456f) return;       // timing experiment: no output stage
@@ -83,8 +83,8 @@ __global__ __launch_bounds__(FFT_NT) void stft_stereo_kernel(const float* __rest
         const int f = idx / TB, tb = idx - f * TB;
         const int t = t0 + tb;
         if (t >= T) continue;
-        const float2 zk = z[tb * zstride + fft_pad(f, ps)];
-        const float2 zn = z[tb * zstride + fft_pad((N - f) & (N - 1), ps)];
+        const float2 zk = z[tb * zstride + fft_pad(f)];
+        const float2 zn = z[tb * zstride + fft_pad((N - f) & (N - 1))];
         // reference stores the CONJUGATE of the FFT (librosaSTFT.py:176-179)
         const float2 XL = make_float2(0.5f * (zk.x + zn.x), -0.5f * (zk.y - zn.y));
         const float2 XR = make_float2(0.5f * (zk.y + zn.y), 0.5f * (zk.x - zn.x));
@@ -118,9 +118,9 @@ template <int TB>
 __global__ __launch_bounds__(FFT_NT) void istft_frames_kernel(const float2* __restrict__ spec, int nsig, int N, int logN, int T,
                                                               const float* __restrict__ window,
                                                               const float2* __restrict__ twiddle, float* __restrict__ frames,
-                                                              int F, int Fp, int Tp, int ps) {
+                                                              int F, int Fp, int Tp) {
     extern __shared__ __attribute__((aligned(16))) float2 fft_smem[];
-    const int zstride = N + (N >> ps) + FFT_ZPAD;
+    const int zstride = fft_row_floats2(N);
     float2* z = fft_smem;
     float2* tw = fft_smem + TB * zstride;
     const int groups = (T + TB - 1) / TB;
@@ -162,13 +162,13 @@ __global__ __launch_bounds__(FFT_NT) void istft_frames_kernel(const float2* __re
                     fb.y = 0.f;
                 }
                 float2* zz = z + tb * zstride;
-                zz[fft_pad(bitrev(f, logN), ps)] = make_float2(fa.x - fb.y, fa.y + fb.x);
-                if (f != 0 && f != N / 2) zz[fft_pad(bitrev(N - f, logN), ps)] = make_float2(fa.x + fb.y, fb.x - fa.y);
+                zz[fft_pad(bitrev(f, logN))] = make_float2(fa.x - fb.y, fa.y + fb.x);
+                if (f != 0 && f != N / 2) zz[fft_pad(bitrev(N - f, logN))] = make_float2(fa.x + fb.y, fb.x - fa.y);
             }
         }
     }
     __syncthreads();
-    fft_stages_any<true, TB>(z, tw, N, logN, zstride, ps);
+    fft_stages_r16<true, TB>(z, tw, N, logN, zstride);
 
     const float invN = 1.0f / (float)N;
     float* Fa = frames + (((long)b * nsig + 2 * pr) * T) * N;
@@ -177,7 +177,7 @@ __global__ __launch_bounds__(FFT_NT) void istft_frames_kernel(const float2* __re
         const int tb = idx / N, n = idx - tb * N;
         const int t = t0 + tb;
         if (t >= T) continue;
-        const float2 v = z[tb * zstride + fft_pad(n, ps)];
+        const float2 v = z[tb * zstride + fft_pad(n)];
         const float w = window[n];
         Fa[(long)t * N + n] = w * (v.x * invN);
         Fb[(long)t * N + n] = w * (v.y * invN);
@@ -236,11 +236,11 @@ extern int gccnmf_trace_blocks;
 #endif
 __global__ __launch_bounds__(FFT_NT, 2) void istft_fused_kernel(const float2* __restrict__ spec, int nsig, int N, int logN, int hop, int T,
                                                              const float* __restrict__ window, const float2* __restrict__ twiddle,
-                                                             int F, int Fp, int Tp, int trim, int L, float gain, float* __restrict__ y, int ps, long long* trace) {
+                                                             int F, int Fp, int Tp, int trim, int L, float gain, float* __restrict__ y, long long* trace) {
     extern __shared__ __attribute__((aligned(16))) float2 fft_smem[];
     constexpr int TB = ISTFT_TB, G = ISTFT_TB * ISTFT_SUB;
     ISTFT_TRACE_BEGIN();
-    const int zstride = N + (N >> ps) + FFT_ZPAD;
+    const int zstride = fft_row_floats2(N);
     float2* z = fft_smem;
     float2* tw = fft_smem + TB * zstride;
     const int span = N + hop * (TB - 1);                  // samples one sub-batch touches
@@ -328,8 +328,8 @@ __global__ __launch_bounds__(FFT_NT, 2) void istft_fused_kernel(const float2* __
                 fb.y = 0.f;
             }
             float2* zz = z + tb * zstride;
-            zz[fft_pad(bitrev(f, logN), ps)] = make_float2(fa.x - fb.y, fa.y + fb.x);
-            if (f != 0 && f != N / 2) zz[fft_pad(bitrev(N - f, logN), ps)] = make_float2(fa.x + fb.y, fb.x - fa.y);
+            zz[fft_pad(bitrev(f, logN))] = make_float2(fa.x - fb.y, fa.y + fb.x);
+            if (f != 0 && f != N / 2) zz[fft_pad(bitrev(N - f, logN))] = make_float2(fa.x + fb.y, fb.x - fa.y);
         };
         // Every fetch of the thread is issued before the first placement (clamped addresses, masked afterwards: a conditional load ends a basic
         // block and its wait).  Left as one loop, the compiler's code was fetch - wait - place per trip: nine dependent round trips to the memory
@@ -367,7 +367,7 @@ __global__ __launch_bounds__(FFT_NT, 2) void istft_fused_kernel(const float2* __
         }
         __syncthreads();
         ISTFT_TRACE(1);
-        fft_stages_any<true, TB>(z, tw, N, logN, zstride, ps);
+        fft_stages_r16<true, TB>(z, tw, N, logN, zstride);
         ISTFT_TRACE(2);
         // every thread owns the accumulator positions i = tid, tid + NT, ...: frames added in ascending order, no hazards.  Branch-free reads
         // (clamped indexes, the window from LDS) so that the reads of all positions can be in flight together; the additions are masked.
@@ -382,7 +382,7 @@ __global__ __launch_bounds__(FFT_NT, 2) void istft_fused_kernel(const float2* __
 #pragma unroll
             for (int tb = 0; tb < TB; ++tb) {
                 const int nc = min(max(ic - tb * hop, 0), N - 1);
-                v[tb] = z[tb * zstride + fft_pad(nc, ps)];
+                v[tb] = z[tb * zstride + fft_pad(nc)];
                 w[tb] = s_win[nc];
             }
 #pragma unroll
@@ -457,8 +457,7 @@ static inline long long* istft_trace(int grid) {
     return nullptr;
 #endif
 }
-static inline int fft_ps() { return gccnmf_tune_fft_r16 ? 4 : FFT_NOPAD; }
-static inline size_t fft_rows_bytes(int tb, int n_fft, int ps) { return sizeof(float2) * ((size_t)tb * fft_row_floats2(n_fft, ps) + n_fft / 2); }
+static inline size_t fft_rows_bytes(int tb, int n_fft) { return sizeof(float2) * ((size_t)tb * fft_row_floats2(n_fft) + n_fft / 2); }
 
 extern "C" {
 
@@ -470,10 +469,9 @@ static int launch_stft(const void* x, long x_stride, int n_samples, int n_fft, i
     const int F = n_fft / 2 + 1;
     GccNmfPitches p = gccnmf_make_pitches(F, T, 1);
     // eight frames per workgroup; four when eight no longer fit the 160 KB of LDS (n_fft = 4096)
-    const int ps = fft_ps();
-    const bool small_tb = fft_rows_bytes(FFT_TB, n_fft, ps) > 160 * 1024;
+    const bool small_tb = fft_rows_bytes(FFT_TB, n_fft) > 160 * 1024;
     const int tb = small_tb ? FFT_TB / 2 : FFT_TB;
-    const size_t lds = fft_rows_bytes(tb, n_fft, ps);
+    const size_t lds = fft_rows_bytes(tb, n_fft);
     if (lds > 160 * 1024) return GCCNMF_ERR_UNSUPPORTED;
     const void* fn = pcm16 ? (small_tb ? (const void*)stft_stereo_kernel<true, FFT_TB / 2> : (const void*)stft_stereo_kernel<true, FFT_TB>)
                            : (small_tb ? (const void*)stft_stereo_kernel<false, FFT_TB / 2> : (const void*)stft_stereo_kernel<false, FFT_TB>);
@@ -483,7 +481,7 @@ static int launch_stft(const void* x, long x_stride, int n_samples, int n_fft, i
     const int groups = gccnmf_ceil_div(T, tb);
 #define GCCNMF_LAUNCH_STFT(P_, TB_)                                                                                                       \
     hipLaunchKernelGGL((stft_stereo_kernel<P_, TB_>), dim3(batch * groups), dim3(FFT_NT), lds, (hipStream_t)stream, (const float*)x, x_stride, \
-                       n_samples, n_fft, logN, hop, T, window, (const float2*)twiddle, (float2*)X, V, CC, F, p.Fp, p.Np, p.Tp, ps)
+                       n_samples, n_fft, logN, hop, T, window, (const float2*)twiddle, (float2*)X, V, CC, F, p.Fp, p.Np, p.Tp)
     if (pcm16) {
         if (small_tb) GCCNMF_LAUNCH_STFT(true, FFT_TB / 2);
         else GCCNMF_LAUNCH_STFT(true, FFT_TB);
@@ -515,7 +513,6 @@ int gccnmf_istft_ola(const float* spec, int nsig, int n_fft, int hop, int T, int
     if (!spec || !window || !twiddle || !y || logN < 6 || logN > 12 || hop < 1 || T < 1 || batch < 1 || nsig < 2 || (nsig & 1))
         return GCCNMF_ERR_ARG;
     const int F = n_fft / 2 + 1;
-    const int ps = fft_ps();
     GccNmfPitches p = gccnmf_make_pitches(F, T, 1);
     const int trim = center ? n_fft / 2 : 0;
     const int L = n_fft + hop * (T - 1) - 2 * trim;
@@ -526,20 +523,20 @@ int gccnmf_istft_ola(const float* spec, int nsig, int n_fft, int hop, int T, int
         // hop > n_fft leaves hop - n_fft samples between consecutive frames that no frame touches: the sliding accumulator covers a
         // sub-batch's span only, so the gap behind every ISTFT_TB-th frame would never be written (the two-kernel form writes 0 there)
         if (hop > n_fft) return GCCNMF_ERR_UNSUPPORTED;
-        const size_t lds = fft_rows_bytes(ISTFT_TB, n_fft, ps) + sizeof(float) * (2 * span + n_fft);
+        const size_t lds = fft_rows_bytes(ISTFT_TB, n_fft) + sizeof(float) * (2 * span + n_fft);
         if (lds > 64 * 1024) {
             if (hipFuncSetAttribute((const void*)istft_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
                 return GCCNMF_ERR_LAUNCH;
         }
         const int groups = gccnmf_ceil_div(T, ISTFT_TB * ISTFT_SUB);
         hipLaunchKernelGGL(istft_fused_kernel, dim3(batch * (nsig / 2) * groups), dim3(FFT_NT), lds, (hipStream_t)stream, (const float2*)spec,
-                           nsig, n_fft, logN, hop, T, window, (const float2*)twiddle, F, p.Fp, p.Tp, trim, L, gain, y, ps, istft_trace(batch * (nsig / 2) * groups));
+                           nsig, n_fft, logN, hop, T, window, (const float2*)twiddle, F, p.Fp, p.Tp, trim, L, gain, y, istft_trace(batch * (nsig / 2) * groups));
         GCCNMF_CHECK_LAUNCH();
         return GCCNMF_OK;
     }
-    const bool small_tb = fft_rows_bytes(FFT_TB, n_fft, ps) > 160 * 1024;
+    const bool small_tb = fft_rows_bytes(FFT_TB, n_fft) > 160 * 1024;
     const int tb = small_tb ? FFT_TB / 2 : FFT_TB;
-    const size_t lds = fft_rows_bytes(tb, n_fft, ps);
+    const size_t lds = fft_rows_bytes(tb, n_fft);
     if (lds > 160 * 1024) return GCCNMF_ERR_UNSUPPORTED;
     if (lds > 64 * 1024) {
         const void* fn = small_tb ? (const void*)istft_frames_kernel<FFT_TB / 2> : (const void*)istft_frames_kernel<FFT_TB>;
@@ -549,10 +546,10 @@ int gccnmf_istft_ola(const float* spec, int nsig, int n_fft, int hop, int T, int
     hipStream_t s = (hipStream_t)stream;
     if (small_tb)
         hipLaunchKernelGGL(istft_frames_kernel<FFT_TB / 2>, dim3(batch * (nsig / 2) * groups), dim3(FFT_NT), lds, s, (const float2*)spec, nsig,
-                           n_fft, logN, T, window, (const float2*)twiddle, frames, F, p.Fp, p.Tp, ps);
+                           n_fft, logN, T, window, (const float2*)twiddle, frames, F, p.Fp, p.Tp);
     else
         hipLaunchKernelGGL(istft_frames_kernel<FFT_TB>, dim3(batch * (nsig / 2) * groups), dim3(FFT_NT), lds, s, (const float2*)spec, nsig,
-                           n_fft, logN, T, window, (const float2*)twiddle, frames, F, p.Fp, p.Tp, ps);
+                           n_fft, logN, T, window, (const float2*)twiddle, frames, F, p.Fp, p.Tp);
     GCCNMF_CHECK_LAUNCH();
     hipLaunchKernelGGL(istft_ola_kernel, dim3(gccnmf_ceil_div(L, 256), nsig, batch), dim3(256), 0, s, frames, n_fft, hop, T, L,
                        trim, gain, y);

@@ -20,7 +20,7 @@
 // kernel (128 x 64, gemm_ring.h): 240 workgroups instead of 60 -- reconstruction 191 -> ~40 us, scores 83 -> ~25 us, angular
 // spectrogram (three 128 x 256 workgroups before) 148 -> ~40 us for one file.
 static bool gcc_small_launch(int batch, int M, int N, int Kd) {
-    if (!gccnmf_tune_ring || !gccnmf_ring_supports(Kd) || gccnmf_tune_tile_policy == 1) return false;
+    if (!gccnmf_ring_supports(Kd) || gccnmf_tune_tile_policy == 1) return false;
     if (gccnmf_tune_tile_policy == 2) return true;
     return (long)batch * gccnmf_ceil_div(M, 512) * gccnmf_ceil_div(N, 64) < 256;
 }
@@ -497,7 +497,7 @@ int gccnmf_target_scores_masks(const float* CC, const float* trig, const int* td
     a.C = scores; a.sC = (long)p.Kp * ncol; a.ldc = ncol;
     int rc;
     if (gcc_small_launch(batch, a.M, a.N, a.Kd)) rc = gccnmf_launch_gemm_ring<false, false, EPI_STORE, false>(a, s);
-    else if (K > 128 && gccnmf_tune_dma && gccnmf_tune_ablate != 128) rc = gccnmf_launch_gemm_dma<false, false, EPI_STORE, false>(a, s);
+    else if (K > 128 && gccnmf_tune_dma) rc = gccnmf_launch_gemm_dma<false, false, EPI_STORE, false>(a, s);
     else rc = (K > 128) ? gccnmf_launch_gemm<4, 1, false, false, EPI_STORE, false>(a, s)
                         : gccnmf_launch_gemm<1, 4, false, false, EPI_STORE, false>(a, s);
     if (rc) return rc;
@@ -595,7 +595,7 @@ int gccnmf_reconstruct(const float* W, const float* H, const unsigned char* argm
         return tail ? gccnmf_launch_gemm_ring<true, false, EPI_PHASE, true>(a, s) : gccnmf_launch_gemm_ring<true, false, EPI_PHASE, false>(a, s);
     const bool tall = a.M > 128;
     // batch scale: the LDS-DMA throughput tile (main loop of K1) with the generic phase epilogue
-    if (tall && gccnmf_tune_dma && gccnmf_tune_ablate != 128)
+    if (tall && gccnmf_tune_dma)
         return tail ? gccnmf_launch_gemm_dma<true, false, EPI_PHASE, true>(a, s) : gccnmf_launch_gemm_dma<true, false, EPI_PHASE, false>(a, s);
     if (tall) return tail ? gccnmf_launch_gemm<4, 1, true, false, EPI_PHASE, true>(a, s)
                           : gccnmf_launch_gemm<4, 1, true, false, EPI_PHASE, false>(a, s);

@@ -62,14 +62,6 @@ __device__ __forceinline__ void gemm_dma16_masked(const float* wave_uniform_base
 
 __device__ __forceinline__ int gemm_swz(int row) { return (row >> 2) & 3; }
 
-// The thread index through an asm statement the compiler cannot see through: values derived from it are recomputed where they are
-// needed instead of being kept in registers as loop invariants.
-__device__ __forceinline__ int gemm_opaque_tid() {
-    int t;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"(threadIdx.x));
-    return t;
-}
-
 // MFMA fragment reads as inline asm: the compiler neither sees them as LDS reads (so it does not drain the LDS-DMA queue
 // in front of them) nor waits for them -- every use is preceded by gemm_wait_lds() + gemm_tie() on the destination.
 typedef float gemm_f32x4 __attribute__((ext_vector_type(4)));
@@ -142,10 +134,6 @@ struct GemmFrag<true, NT, ROWS> {
 #pragma unroll
         for (int m = 0; m < NT; ++m) gemm_tie(v[m]);
     }
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int m = 0; m < NT; ++m) v[m] = gemm_f32x4{0.f, 0.f, 0.f, 0.f};
-    }
     __device__ __forceinline__ float get(int m, int e) const { return v[m][e]; }
     __device__ __forceinline__ void scale(const gemm_f32x4& s) {
 #pragma unroll
@@ -169,12 +157,6 @@ struct GemmFrag<false, NT, ROWS> {
         for (int e = 0; e < 4; ++e)
 #pragma unroll
             for (int h = 0; h < NT / 2; ++h) gemm_tie(v[e][h]);
-    }
-    __device__ __forceinline__ void clear() {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-            for (int h = 0; h < NT / 2; ++h) v[e][h] = gemm_f32x2{0.f, 0.f};
     }
     __device__ __forceinline__ float get(int m, int e) const { return v[e][m >> 1][m & 1]; }
     __device__ __forceinline__ void scale(const gemm_f32x4& s) {
@@ -394,8 +376,7 @@ __device__ __forceinline__ void gemm_epilogue_update_w_full(const GemmArgs& p, i
 
 // ---- the work list of a launch ---------------------------------------------------------------------------------------------
 // A launch is an ORDERED list of work items per XCD (GemmArgs.lists = 8: XCD x = blockIdx & 7 serves list x; 1: one list), taken in
-// order by the hardware dispatcher (workgroup b takes item b >> 3 of list b & 7; the experiment build can also hand them out to
-// resident workgroups through a ticket counter).  An item is one output tile, computed by ONE workgroup in the fixed k order, so a
+// order by the hardware dispatcher (workgroup b takes item b >> 3 of list b & 7).  An item is one output tile, computed by ONE workgroup in the fixed k order, so a
 // file's bits depend neither on who takes an item nor on the form it has.  Three kinds, longest first:
 //   wide    512 x 64   items 0 .. len - split - 1 of a list: its chunk [list * cw, ...) of the file-major list of wide tiles
 //                      (files in the class order 0, 8, 16, ... | 1, 9, ... so that a file's tiles share one XCD's L2)
@@ -518,21 +499,17 @@ __host__ __device__ __forceinline__ bool gemm_dma_item(const GemmArgs& p, int li
 
 // The throughput tile: 512 x 64 per workgroup, 128 x 64 per wave (TM = 4 MFMA row tiles x 2 column blocks).
 // NARROW: the instantiation also carries the 512 x 32 form of the main loop (items with nw = 1).
-// PERSISTENT grid (p.tickets != nullptr): 64 resident workgroups per list (two per CU) pull items through a ticket counter until the list
-// is empty -- work-conserving whatever the items cost; the ticket of the NEXT item is taken at the start of the current one, and the
-// next tile's first LDS-DMA pieces are issued BEFORE the current tile's epilogue (p.prefetch), so a workgroup's matrix pipe does not
-// wait for a prologue between two tiles.  The last workgroup to leave resets the counters (the next launch on the stream finds zeros).
 // LDS of one workgroup of the throughput tile: two staging buffers (A | B | A tail-row chunk | B row-scale chunk), the lean epilogue's row
-// factors, the split barrier's counter, the persistent grid's ticket slots
+// factors, the split barrier's counter
 template <int TM>
 struct GemmDmaLds {
     static constexpr int SBUF = 128 * TM * 16 + 64 * 16 + 16 + 16;
 };
 
-// One workgroup of the throughput tile: items t, (persistent grid: further tickets) of list `list`.
+// One workgroup of the throughput tile: item t of list `list` (nothing to do where the list is shorter).
 template <bool A_KC, bool B_KC, int EPI, bool TAIL, int TM, bool NARROW>
 __device__ __forceinline__ void gemm_dma_workgroup(const GemmArgs& p, float* const smem, float* const s_rowvec, unsigned* const s_arrivals_p,
-                                                   int* const s_ticket, const int list, int t, const GemmSync& sync, const int sync_it = 0,
+                                                   const int list, const int t, const GemmSync& sync, const int sync_it = 0,
                                                    const bool trace_on = true) {
     static_assert(TM == 4 || TM == 2, "");
     static_assert(TM == 4 || EPI != EPI_UPDW, "the fused W update owns all rows of its atoms: full-height tiles only");
@@ -545,21 +522,14 @@ __device__ __forceinline__ void gemm_dma_workgroup(const GemmArgs& p, float* con
     constexpr bool SCALE = !B_KC && (EPI == EPI_DIV || EPI == EPI_STORE);   // K1 (R = V / (W.(s*H))) carries a lazy row scale on its B operand
     unsigned& s_arrivals = *s_arrivals_p;            // split barrier of the main loop: 4 arrivals per k-tile
 
-    // Per-lane values are RE-DERIVED per item from an opaque copy of the thread index (gemm_opaque_tid): as loop invariants of the item
-    // loop they would stay live across the epilogue, whose 128 accumulators + two tile pairs of inputs leave no registers for them.
-    int tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // wave-uniform in an SGPR: LDS-DMA bases derive from it
     const int wm = wave, wn = 0;
-    int l31 = lane & 31, hh = lane >> 5;
-#ifdef GCCNMF_EXPERIMENTS
-    const bool persistent = p.tickets != nullptr;
-#else
-    constexpr bool persistent = false;          // the resident-workgroup form is an experiment build (make EXPERIMENTS=1): measured slower, see LABBOOK.md
-#endif
+    const int l31 = lane & 31, hh = lane >> 5;
 
-    // ---- per-item state (set by take_item) ----
-    int nkt = (p.Kd + BK - 1) / BK;                 // (per item in a ragged K4: the file's own reduction length)
-    int n_item = p.N;                               // columns of the item's file (per item in a ragged K1 - K3)
+    // ---- the item (set by take_item) ----
+    int nkt = (p.Kd + BK - 1) / BK;                 // (in a ragged K4: the file's own reduction length)
+    int n_item = p.N;                               // columns of the item's file (its own in a ragged K1 - K3)
     int n_sync = p.N;                               // the file's column count in the GEMMs that hand over per column tile (what a consumer's wait is sized by)
     int file = 0, tm = 0, col0 = 0, nw = 2, row0 = 0;
     const float* __restrict__ A = nullptr;
@@ -570,9 +540,9 @@ __device__ __forceinline__ void gemm_dma_workgroup(const GemmArgs& p, float* con
     unsigned long long tail_mask = 0, scale_mask = 0;                 // lane masks of wave 0's side-chunk pieces (0 = no-op)
     bool wave_active = false, do_tail = false, do_rowsum = false;
     unsigned offA[NA], offB = 0;                                       // per-lane source offsets (bytes from the wave-uniform k-tile origin) of this wave's DMA pieces
-    auto take_item = [&](const int ticket) -> bool {
+    auto take_item = [&]() -> bool {
         int f_, tm_, c_, nw_;
-        if (!gemm_dma_item(p, list, ticket, f_, tm_, c_, nw_)) return false;
+        if (!gemm_dma_item(p, list, t, f_, tm_, c_, nw_)) return false;
         // (the integer divisions of the decode run on the VALU: without the readfirstlanes every value derived from file / tile -- all
         // row pointers, descriptors and scalar offsets below -- stays in VGPRs and each buffer access becomes a waterfall loop)
         file = __builtin_amdgcn_readfirstlane(f_);
@@ -598,7 +568,7 @@ __device__ __forceinline__ void gemm_dma_workgroup(const GemmArgs& p, float* con
         scale_src = bscale != nullptr ? bscale : A;              // (never dereferenced under a zero mask; kept a valid address anyway)
         return true;
     };
-    auto set_offsets = [&](const int lane) {                           // this wave's DMA source offsets for the current item
+    auto set_offsets = [&]() {                                         // this wave's DMA source offsets for the item
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             const int piece = wave * NA + i;                               // 1 KB pieces of the A tile
@@ -670,11 +640,7 @@ __device__ __forceinline__ void gemm_dma_workgroup(const GemmArgs& p, float* con
     // per-lane byte offsets inside a staging buffer (q = 0 / q = 1 chunk of this lane half)
     unsigned oA0 = 0, oA1 = 0, oB0 = 0, oB1 = 0, oTB = 0, oRS = 0;
     const int tg = wave;                                           // tail row: 4 thread groups (= waves) x 4 reduction steps each
-    auto set_lane_constants = [&](const int tid_) {
-        tid = tid_;
-        lane = tid_ & 63;
-        l31 = lane & 31;
-        hh = lane >> 5;
+    auto set_lane_constants = [&]() {
         const int arow = wm * RW + l31, bcol = wn * 64 + l31, tj = lane;
         side_off = 16u * (unsigned)(lane & 3);
         oA0 = A_KC ? 4 * (arow * 16 + 4 * ((0 + hh) ^ gemm_swz(arow))) : 4 * (4 * (0 + hh) * BM + arow);
@@ -682,7 +648,7 @@ __device__ __forceinline__ void gemm_dma_workgroup(const GemmArgs& p, float* con
         oB0 = 4 * SA + (B_KC ? 4 * (bcol * 16 + 4 * ((0 + hh) ^ gemm_swz(bcol))) : 4 * (4 * (0 + hh) * BN + bcol));
         oB1 = 4 * SA + (B_KC ? 4 * (bcol * 16 + 4 * ((2 + hh) ^ gemm_swz(bcol))) : 4 * (4 * (2 + hh) * BN + bcol));
         oTB = 4 * SA + (B_KC ? 4 * (tj * 16 + 4 * (tg ^ gemm_swz(tj))) : 4 * (4 * tg * BN + tj));
-        oRS = 4 * SA + 4 * ((tid_ >> 2) * 16 + 4 * (tid_ & 3));   // row sums: 4 threads per atom row, one chunk each
+        oRS = 4 * SA + 4 * ((tid >> 2) * 16 + 4 * (tid & 3));   // row sums: 4 threads per atom row, one chunk each
     };
 
     auto read_group0 = [&](const unsigned lds) {                    // lds = byte address of the staging buffer
@@ -765,7 +731,7 @@ __device__ __forceinline__ void gemm_dma_workgroup(const GemmArgs& p, float* con
     // re-fetch the last tile (valid addresses, never read): cheaper than a branch around every piece.
 #ifdef GEMM_DMA_PROBE
     // build-time instrumentation (make variant X=-DGEMM_DMA_PROBE, scripts/ktrace.py --probe): shader-clock cycles per
-    // phase of the k-tile, summed over the main loops of all items of the workgroup, per wave
+    // phase of the k-tile, summed over the main loop of the workgroup's item, per wave
     unsigned long long probe[7] = {0, 0, 0, 0, 0, 0, 0};
 #define GEMM_PROBE(i_) const unsigned long long pt##i_ = __builtin_amdgcn_s_memtime()
 #define GEMM_PROBE_DECL(i_) unsigned long long pt##i_ = 0
@@ -892,37 +858,26 @@ __device__ __forceinline__ void gemm_dma_workgroup(const GemmArgs& p, float* con
     if (SCALE) {
         if (!p.bscale && tid < 2 * BK) smem[(tid >> 4) * SBUF + SA + SB + BK + (tid & 15)] = 1.f;       // no row scale: both chunks stay 1
     }
-    bool have = take_item(t);
-    if (have) set_offsets(lane);
-    bool prefetched = false;                           // the first k-tile of the current item is already on its way into buffer 0
-    int it = 0;                                        // items done by this workgroup (ticket slot = it & 1)
+    bool have = take_item();
+    if (have) set_offsets();
     long long* trace_row = nullptr;
+    // ONE trip.  Written as a loop for the compiler: out of a loop it hoists the item's invariants -- the epilogue's row and column addresses, its
+    // kernel arguments -- in front of the prologue, where they are computed under the first LDS-DMA round trip.  As straight-line code the same
+    // statements compile to kernels that need no scratch but run the benchmark 0.4 % slower (LABBOOK.md, the entry on the removed lab paths).
     while (have) {
         const int vb = p.lists == 8 ? 8 * t + list : t;                 // the item's index in the classic grid (= its trace row)
         trace_row = (trace_on && p.trace && vb < p.trace_rows) ? p.trace + 8 * (long)vb : nullptr;
         if (trace_row && tid == 0) {
             trace_row[0] = trace_row[1] = __builtin_amdgcn_s_memrealtime();
             trace_row[4] = (long long)((__builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u) << 16 | (__builtin_amdgcn_s_getreg((31 << 11) | 4) & 0xffffu));
-            trace_row[7] = (long long)blockIdx.x << 16 | (long long)it;
+            trace_row[7] = (long long)blockIdx.x << 16;
         }
-#ifdef GCCNMF_EXPERIMENTS
-        set_lane_constants(gemm_opaque_tid());
-        if (it > 0) set_offsets(lane);
-        // every fragment register starts an item defined: a conditional read followed by an unconditional tie would otherwise keep the
-        // previous item's values alive across the epilogue (76 registers the epilogue does not have)
-        a0.clear(); a1.clear(); b0.clear(); b1.clear();
-        sc0 = sc1 = t4 = tb4 = ts4 = rs4 = zero4;
-        tbxy = tbzw = gemm_f32x2{0.f, 0.f};
-#else
-        set_lane_constants(tid);
-#endif
+        set_lane_constants();
         gemm_sync_wait(sync, file, col0, tid, sync_it, list, n_sync);   // chained launch: this item's operands come from an earlier stage of the same launch
         if (trace_row && tid == 0) trace_row[1] = __builtin_amdgcn_s_memrealtime();      // [1] - [0] = time spent waiting for a producer
-        // ---- prologue: tile 0 -> buffer 0 (unless the previous item's epilogue already sent it), group 0 of tile 0 into registers
-        if (!prefetched) {
+        // ---- prologue: tile 0 -> buffer 0, group 0 of tile 0 into registers
 #pragma unroll
-            for (int i = 0; i < NPIECES; ++i) dma_piece(i, 0, 0);
-        }
+        for (int i = 0; i < NPIECES; ++i) dma_piece(i, 0, 0);
 #pragma unroll
         for (int m = 0; m < TM; ++m)
 #pragma unroll
@@ -943,11 +898,7 @@ __device__ __forceinline__ void gemm_dma_workgroup(const GemmArgs& p, float* con
                 }
             }
         }
-        if (tid == 0) {
-            s_arrivals = 0;
-            // the ticket of the NEXT item, taken now: its round trip is hidden by this item, and the epilogue can already fetch for it
-            if (persistent) s_ticket[it & 1] = p.wpl + (int)__hip_atomic_fetch_add(p.tickets + list, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        if (tid == 0) s_arrivals = 0;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         read_group0(lds0);
@@ -962,110 +913,86 @@ __device__ __forceinline__ void gemm_dma_workgroup(const GemmArgs& p, float* con
         __syncthreads();                      // the epilogues reuse the staging buffers
         if (trace_row && tid == 0) trace_row[2] = __builtin_amdgcn_s_memrealtime();
 
-        // ---- the finished item's coordinates move aside; the next item's operands are set up (and requested) before the epilogue
-        const int e_file = file, e_row0 = row0, e_col0 = col0, e_nw = nw, e_n = n_item;
-        const bool e_active = wave_active, e_tail = do_tail, e_rowsum = do_rowsum;
-        have = false;
-        prefetched = false;
-        if (persistent) {
-            t = __builtin_amdgcn_readfirstlane(s_ticket[it & 1]);
-            have = take_item(t);
-            if (have && p.prefetch) {
-                set_offsets(gemm_opaque_tid() & 63);           // (computed again at the top of the next item: not kept across the epilogue)
-#pragma unroll
-                for (int i = 0; i < NPIECES; ++i) dma_piece(i, 0, 0);
-                prefetched = true;
-            }
-        }
-        float* const scratch = smem + SBUF;             // epilogue scratch: buffer 1 (buffer 0 may be receiving the next item's first tile)
+        float* const scratch = smem + SBUF;             // epilogue scratch: buffer 1
 
         if constexpr (EPI == EPI_UPDW) {
             // launch_rht_update_w guarantees M % 128 == 0 and N % 64 == 0 (a second, generic variant in this kernel would
             // double the live ranges of the accumulators and spill the main loop)
-            if constexpr (TM == 4) gemm_epilogue_update_w_full<TAIL>(p, e_file, e_col0, tid, wm, l31, hh, e_active, acc, tail_acc, rowsum_acc, scratch);
+            if constexpr (TM == 4) gemm_epilogue_update_w_full<TAIL>(p, file, col0, tid, wm, l31, hh, wave_active, acc, tail_acc, rowsum_acc, scratch);
         } else {
-            if (e_active) {
-                const int row_w = e_row0 + wm * RW;                           // wave-uniform
+            if (wave_active) {
+                const int row_w = row0 + wm * RW;                           // wave-uniform
                 bool lean = false;
                 if constexpr (EPI == EPI_STORE || EPI == EPI_DIV || EPI == EPI_UPDH) {
                     lean = row_w + RW <= p.M;                               // all tile pairs of the wave have all their rows
                     if (lean) {
                         GemmEpiloguePair<EPI, BM> e0, e1;
-                        const int ca = e_col0 + l31, tr = wm * RW;
-                        const bool oka = ca < e_n, okb = (!NARROW || e_nw == 2) && ca + 32 < e_n;
+                        const int ca = col0 + l31, tr = wm * RW;
+                        const bool oka = ca < n_item, okb = (!NARROW || nw == 2) && ca + 32 < n_item;
                         const long cb = 4L * p.ldc * (p.M + (TAIL ? 1 : 0));
                         float ba = 0.f, bb = 0.f;
-                        e0.load(p, e_file, row_w, hh, ca, cb);
-                        e1.load(p, e_file, row_w + 32, hh, ca, cb);
+                        e0.load(p, file, row_w, hh, ca, cb);
+                        e1.load(p, file, row_w + 32, hh, ca, cb);
                         if (EPI != EPI_DIV && p.ktailA) {
-                            ba = p.ktailB[e_file * p.s_ktailB + min(ca, e_n - 1)];
-                            bb = p.ktailB[e_file * p.s_ktailB + min(ca + 32, e_n - 1)];
+                            ba = p.ktailB[file * p.s_ktailB + min(ca, n_item - 1)];
+                            bb = p.ktailB[file * p.s_ktailB + min(ca + 32, n_item - 1)];
                         }
-                        e0.finish(p, e_file, row_w, tr, hh, ca, ba, bb, s_rowvec, acc[0][0], acc[0][1], oka, okb, cb);
+                        e0.finish(p, file, row_w, tr, hh, ca, ba, bb, s_rowvec, acc[0][0], acc[0][1], oka, okb, cb);
                         if (trace_row && tid == 0) trace_row[5] = __builtin_amdgcn_s_memrealtime();
-                        if constexpr (TM == 4) e0.load(p, e_file, row_w + 64, hh, ca, cb);
-                        e1.finish(p, e_file, row_w + 32, tr + 32, hh, ca, ba, bb, s_rowvec, acc[1][0], acc[1][1], oka, okb, cb);
+                        if constexpr (TM == 4) e0.load(p, file, row_w + 64, hh, ca, cb);
+                        e1.finish(p, file, row_w + 32, tr + 32, hh, ca, ba, bb, s_rowvec, acc[1][0], acc[1][1], oka, okb, cb);
                         if constexpr (TM == 4) {
-                            e1.load(p, e_file, row_w + 96, hh, ca, cb);
-                            e0.finish(p, e_file, row_w + 64, tr + 64, hh, ca, ba, bb, s_rowvec, acc[2][0], acc[2][1], oka, okb, cb);
-                            e1.finish(p, e_file, row_w + 96, tr + 96, hh, ca, ba, bb, s_rowvec, acc[3][0], acc[3][1], oka, okb, cb);
+                            e1.load(p, file, row_w + 96, hh, ca, cb);
+                            e0.finish(p, file, row_w + 64, tr + 64, hh, ca, ba, bb, s_rowvec, acc[2][0], acc[2][1], oka, okb, cb);
+                            e1.finish(p, file, row_w + 96, tr + 96, hh, ca, ba, bb, s_rowvec, acc[3][0], acc[3][1], oka, okb, cb);
                         }
                         if (trace_row && tid == 0) trace_row[6] = __builtin_amdgcn_s_memrealtime();
                     }
                 }
                 if (!lean) {
                     GemmArgs pq = p;              // (the generic epilogues read the column count from the arguments: the file's own in a ragged batch)
-                    pq.N = e_n;
+                    pq.N = n_item;
 #pragma unroll
                     for (int m = 0; m < TM; ++m)
-                        gemm_epilogue_pair<EPI>(pq, e_file, row_w + m * 32 + 4 * hh, e_col0 + wn * 64 + l31, acc[m][0], acc[m][1], !NARROW || e_nw == 2);
+                        gemm_epilogue_pair<EPI>(pq, file, row_w + m * 32 + 4 * hh, col0 + wn * 64 + l31, acc[m][0], acc[m][1], !NARROW || nw == 2);
                 }
             }
             if (TAIL) {
-                if (e_tail) {
+                if (do_tail) {
                     scratch[tid] = tail_acc;
                     __syncthreads();
-                    if (tid < (NARROW && e_nw == 1 ? 32 : BN)) {
+                    if (tid < (NARROW && nw == 1 ? 32 : BN)) {
                         const float s = (scratch[tid] + scratch[BN + tid]) + (scratch[2 * BN + tid] + scratch[3 * BN + tid]);
-                        const int col = e_col0 + tid;
-                        if (EPI == EPI_PHASE ? gemm_col_valid<EPI>(p, col) : col < e_n) gemm_epilogue<EPI>(p, e_file, p.tail_row, col, s);
+                        const int col = col0 + tid;
+                        if (EPI == EPI_PHASE ? gemm_col_valid<EPI>(p, col) : col < n_item) gemm_epilogue<EPI>(p, file, p.tail_row, col, s);
                     }
                 }
             }
             if (B_KC) {
-                if (e_rowsum) {
+                if (do_rowsum) {
                     float s = rowsum_acc;
                     s += __shfl_xor(s, 1);
                     s += __shfl_xor(s, 2);
                     const int j = tid >> 2;
-                    if ((tid & 3) == 0 && (e_col0 + j) < e_n && (!NARROW || e_nw == 2 || j < 32)) p.rowsumB[e_file * p.s_rowsumB + e_col0 + j] = s;
+                    if ((tid & 3) == 0 && (col0 + j) < n_item && (!NARROW || nw == 2 || j < 32)) p.rowsumB[file * p.s_rowsumB + col0 + j] = s;
                 }
             }
         }
         if (trace_row) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // (also waits for a prefetched first tile: timeline builds only)
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
             if (tid == 0) trace_row[3] = __builtin_amdgcn_s_memrealtime();
         }
-        gemm_sync_signal(sync, e_file, e_col0, e_nw, tid);  // chained launch: this item's output is complete in the XCD's L2
-        ++it;
-        if (have) __syncthreads();            // s_rowvec, the scratch and s_arrivals are rewritten for the next item
+        gemm_sync_signal(sync, file, col0, nw, tid);  // chained launch: this item's output is complete in the XCD's L2
+        have = false;
     }
 #ifdef GEMM_DMA_PROBE
     if (p.trace && lane == 0 && (long)p.trace_grid + 4L * blockIdx.x + 4 <= p.trace_rows) {
 #pragma unroll
         for (int i = 0; i < 7; ++i) p.trace[8 * ((long)p.trace_grid + blockIdx.x * 4 + wave) + i] = (long long)probe[i];
-        p.trace[8 * ((long)p.trace_grid + blockIdx.x * 4 + wave) + 7] = it;
+        p.trace[8 * ((long)p.trace_grid + blockIdx.x * 4 + wave) + 7] = 1;      // items of this workgroup
     }
 #endif
-    if (persistent && tid == 0) {
-        // the last workgroup to leave zeroes the counters: every other workgroup has taken its last ticket before it counted itself out
-        const unsigned gone = __hip_atomic_fetch_add(p.tickets + 8, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (gone == gridDim.x - 1) {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) __hip_atomic_store(p.tickets + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
 }
 
 // The classic launch: one GEMM, workgroup b takes item b >> 3 of list b & 7 (one list: item b).
@@ -1074,11 +1001,10 @@ __global__ __launch_bounds__(256, 2) void gccnmf_gemm_dma_kernel(GemmArgs p) {
     __shared__ __attribute__((aligned(16))) float smem[2 * GemmDmaLds<TM>::SBUF];
     __shared__ __attribute__((aligned(16))) float s_rowvec[(EPI == EPI_STORE || EPI == EPI_UPDH) ? 2 * 128 * TM : 4];   // lean epilogue row factors
     __shared__ unsigned s_arrivals;
-    __shared__ int s_ticket[2];
     const int list = p.lists == 8 ? (int)(blockIdx.x & 7) : 0;
-    const int t = p.lists == 8 ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;      // first item: static (the counter starts behind the resident workgroups)
+    const int t = p.lists == 8 ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
     GemmSync none = {};
-    gemm_dma_workgroup<A_KC, B_KC, EPI, TAIL, TM, NARROW>(p, smem, s_rowvec, &s_arrivals, s_ticket, list, t, none);
+    gemm_dma_workgroup<A_KC, B_KC, EPI, TAIL, TM, NARROW>(p, smem, s_rowvec, &s_arrivals, list, t, none);
 }
 
 // The chained launch of a KL-NMF iteration (or its first STAGES GEMMs): stage 0 = K1 (R = V / (W.(s*H))), 1 = K2 (H update), 2 = K3
@@ -1097,7 +1023,6 @@ __global__ __launch_bounds__(256, 2) void gccnmf_gemm_chain_kernel(GemmArgs p0, 
     __shared__ __attribute__((aligned(16))) float smem[2 * GemmDmaLds<4>::SBUF];
     __shared__ __attribute__((aligned(16))) float s_rowvec[2 * 512];
     __shared__ unsigned s_arrivals;
-    __shared__ int s_ticket[2];
     const int list = (int)(blockIdx.x & 7);
     int pos = (int)(blockIdx.x >> 3), it = ch.it0;
     if (ch.iterations > 1) {
@@ -1107,23 +1032,19 @@ __global__ __launch_bounds__(256, 2) void gccnmf_gemm_chain_kernel(GemmArgs p0, 
     }
     const bool tr = it == ch.trace_it;
     if (pos < ch.first[1]) {
-        gemm_dma_workgroup<true, false, EPI_DIV, TAIL, 4, true>(p0, smem, s_rowvec, &s_arrivals, s_ticket, list, pos, ch.sync[0], it, tr);
+        gemm_dma_workgroup<true, false, EPI_DIV, TAIL, 4, true>(p0, smem, s_rowvec, &s_arrivals, list, pos, ch.sync[0], it, tr);
     } else if (pos < ch.first[2]) {
-        gemm_dma_workgroup<false, false, EPI_UPDH, false, TM1, TM1 == 4>(p1, smem, s_rowvec, &s_arrivals, s_ticket, list, pos - ch.first[1], ch.sync[1], it, tr);
+        gemm_dma_workgroup<false, false, EPI_UPDH, false, TM1, TM1 == 4>(p1, smem, s_rowvec, &s_arrivals, list, pos - ch.first[1], ch.sync[1], it, tr);
     } else if constexpr (STAGES == 4) {
         if (pos < ch.first[3]) {
-            gemm_dma_workgroup<true, false, EPI_DIV, TAIL, 4, true>(p2, smem, s_rowvec, &s_arrivals, s_ticket, list, pos - ch.first[2], ch.sync[2], it, tr);
+            gemm_dma_workgroup<true, false, EPI_DIV, TAIL, 4, true>(p2, smem, s_rowvec, &s_arrivals, list, pos - ch.first[2], ch.sync[2], it, tr);
         } else {
-            gemm_dma_workgroup<true, true, EPI_UPDW, TAIL, 4, false>(p3, smem, s_rowvec, &s_arrivals, s_ticket, list, pos - ch.first[3], ch.sync[3], it, tr);
+            gemm_dma_workgroup<true, true, EPI_UPDW, TAIL, 4, false>(p3, smem, s_rowvec, &s_arrivals, list, pos - ch.first[3], ch.sync[3], it, tr);
         }
     }
 }
 
 // ---- host side: the plan of a launch -----------------------------------------------------------------------------------------
-#ifdef GCCNMF_EXPERIMENTS
-unsigned* gccnmf_ticket_block(hipStream_t stream);
-#endif
-
 // The work lists of one launch of TM-high tiles over the files [a.file0, a.file0 + a.batch).  narrow_capable: the kernel instantiation
 // carries the 512 x 32 loop.  Returns the size of the classic grid (items of the longest list x lists), -1 on overflow.
 //   key 9 = 0: wide tiles only | 1 (default): a file's ragged last column tile (at most 32 of its 64 columns exist) becomes a narrow item
@@ -1177,21 +1098,7 @@ static int gccnmf_launch_gemm_dma_tm(GemmArgs a, hipStream_t stream) {
     a.trace = gccnmf_trace_buf;
     a.trace_rows = gccnmf_trace_buf ? gccnmf_trace_blocks : 0;
     a.trace_grid = classic_grid;
-    a.tickets = nullptr;
-    a.prefetch = 0;
-    a.wpl = 0;
-    int grid = classic_grid;
-#ifdef GCCNMF_EXPERIMENTS
-    a.prefetch = gccnmf_tune_prefetch;
-    if (gccnmf_tune_persistent && TM == 4 && classic_grid > 512) {
-        a.tickets = gccnmf_ticket_block(stream);
-        if (a.tickets) {
-            grid = 512;
-            a.wpl = 512 / a.lists;
-        }
-    }
-#endif
-    hipLaunchKernelGGL((gccnmf_gemm_dma_kernel<A_KC, B_KC, EPI, TAIL, TM, NARROW>), dim3(grid), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((gccnmf_gemm_dma_kernel<A_KC, B_KC, EPI, TAIL, TM, NARROW>), dim3(classic_grid), dim3(256), 0, stream, a);
     GCCNMF_CHECK_LAUNCH();
     return GCCNMF_OK;
 }
@@ -1209,7 +1116,6 @@ template <bool A_KC, bool B_KC, int EPI, bool TAIL>
 static int gccnmf_launch_gemm_dma(GemmArgs a, hipStream_t stream) {
     if (!a.A || !a.B || !a.C || a.M < 1 || a.N < 1 || a.Kd < 1 || a.batch < 1) return GCCNMF_ERR_ARG;
     if ((a.lda & 3) || (a.ldb & 3)) return GCCNMF_ERR_ARG;
-    a.ablate = gccnmf_tune_ablate;
     a.exact_div = gccnmf_tune_exact_div;
     if constexpr (EPI != EPI_UPDW) {
         if ((a.M <= 256 && gccnmf_tune_tail_split != 0) || gccnmf_tune_tail_split == 3) return gccnmf_launch_gemm_dma_tm<A_KC, B_KC, EPI, TAIL, 2>(a, stream);

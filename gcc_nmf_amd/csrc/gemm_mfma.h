@@ -65,9 +65,7 @@ struct GemmArgs {
                                //     in all, the tile is chosen for their files together): keep the throughput tile, its partial round runs beside
                                //     the other groups' kernels
     int file0;                 // first file of this launch (a launch over a sub-range of the batch: strides are applied to file0 + index)
-    int kparts;                // ring kernel only: > 0 = the `batch` "files" are kparts balanced parts of ONE reduction of Kd (split-K, partial outputs sC apart)
     int exact_div;             // LDS-DMA kernel, EPI_DIV: 1 = IEEE division instead of v_rcp_f32 + one Newton step (tuning key 7)
-    int ablate;                // timing experiments: 1 no global loads, 2 no LDS stores, 4 no k-loop barrier, 8 no tail row, 16 no epilogue (results invalid)
     const float* bscale;       // optional per-reduction-index scale applied to B while staging (non-KC B only)
     long s_bscale;
     int tail_row;              // TAIL: index of the extra VALU-computed output row
@@ -104,8 +102,6 @@ struct GemmArgs {
     const int* ragged_lists;   // [8][GEMM_RAGGED_LMAX + 1]: per list the number of files, then their indexes in list order
     int ragged_kd;
     int narrow_ok;             // the instantiation carries the narrow loop and the tuning allows narrow items: a file's ragged last column tile is one
-    int wpl, prefetch;         // persistent grid: resident workgroups per list; 1 = the next item's first k-tile is requested before the epilogue
-    unsigned* tickets;         // persistent grid: [0..7] next-item counters per list, [8] workgroups gone; nullptr = classic grid
     int trace_rows, trace_grid;   // rows of the trace buffer; items of the classic grid (the per-wave probe rows start behind them)
 };
 
@@ -157,7 +153,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, int file, int r
 // clamped (always in-bounds) addresses, then the arithmetic, then the predicated stores: a per-element
 // load -> use -> store chain would serialise 128 memory round trips per lane (the in-place H update cannot
 // be reordered by the compiler) and cost as much as the whole k-loop.
-template <int EPI>
+// PHASE_HALVES (EPI_PHASE): the register-staged kernel, whose staging registers are still live in front of its epilogue, fetches X and V of a
+// tile eight rows at a time (all 16 at once spilled 18 - 22 VGPRs there); every other caller has the registers for 16.
+template <int EPI, bool PHASE_HALVES = false>
 __device__ __forceinline__ void gemm_epilogue_pair(const GemmArgs& p, int file, int row_base, int col_a, const f32x16& acc_in_a,
                                                    const f32x16& acc_in_b, bool allow_b = true) {
     const int col_b = col_a + 32;
@@ -265,27 +263,55 @@ __device__ __forceinline__ void gemm_epilogue_pair(const GemmArgs& p, int file, 
             const int ic = min(col / p.Tp, nic - 1);
             const int t = min(col - (col / p.Tp) * p.Tp, p.T - 1);
             const int c = ic & 1;
-            float2 x[16];
-            float v[16];
+            if constexpr (PHASE_HALVES) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int rc = min(row_base + (r & 3) + 8 * (r >> 2), p.M - 1);
-                x[r] = X[((long)c * p.Fp + rc) * p.Tp + t];
-                v[r] = V[(long)rc * p.ldv + c * p.T + t];
-            }
+                for (int r0 = 0; r0 < 16; r0 += 8) {
+                    float2 x[8];
+                    float v[8];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = row_base + (r & 3) + 8 * (r >> 2);
-                const float a = half ? acc_b[r] : acc_a[r];
-                float2 o;
-                if (v[r] > 0.f) {
-                    o.x = a * (x[r].x / v[r]);
-                    o.y = a * (x[r].y / v[r]);
-                } else {           // numpy.angle(0) == 0 -> exp(0j) == 1
-                    o.x = a;
-                    o.y = 0.f;
+                    for (int q = 0; q < 8; ++q) {
+                        const int r = r0 + q, rc = min(row_base + (r & 3) + 8 * (r >> 2), p.M - 1);
+                        x[q] = X[((long)c * p.Fp + rc) * p.Tp + t];
+                        v[q] = V[(long)rc * p.ldv + c * p.T + t];
+                    }
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) {
+                        const int r = r0 + q, row = row_base + (r & 3) + 8 * (r >> 2);
+                        const float a = half ? acc_b[r] : acc_a[r];
+                        float2 o;
+                        if (v[q] > 0.f) {
+                            o.x = a * (x[q].x / v[q]);
+                            o.y = a * (x[q].y / v[q]);
+                        } else {
+                            o.x = a;
+                            o.y = 0.f;
+                        }
+                        if (ok && row < p.M) C[((long)ic * p.Fp + row) * p.Tp + t] = o;
+                    }
                 }
-                if (ok && row < p.M) C[((long)ic * p.Fp + row) * p.Tp + t] = o;
+            } else {
+                float2 x[16];
+                float v[16];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int rc = min(row_base + (r & 3) + 8 * (r >> 2), p.M - 1);
+                    x[r] = X[((long)c * p.Fp + rc) * p.Tp + t];
+                    v[r] = V[(long)rc * p.ldv + c * p.T + t];
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = row_base + (r & 3) + 8 * (r >> 2);
+                    const float a = half ? acc_b[r] : acc_a[r];
+                    float2 o;
+                    if (v[r] > 0.f) {
+                        o.x = a * (x[r].x / v[r]);
+                        o.y = a * (x[r].y / v[r]);
+                    } else {           // numpy.angle(0) == 0 -> exp(0j) == 1
+                        o.x = a;
+                        o.y = 0.f;
+                    }
+                    if (ok && row < p.M) C[((long)ic * p.Fp + row) * p.Tp + t] = o;
+                }
             }
         }
     }
@@ -523,7 +549,7 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void gccnmf_gemm_kernel(GemmArgs p)
     const float* __restrict__ bscale = (!B_KC && p.bscale) ? p.bscale + file * p.s_bscale : nullptr;
 
     const bool wave_active = (row0 + wm * WT) < p.M;
-    const bool do_tail = TAIL && (tm == 0) && !(p.ablate & 8);
+    const bool do_tail = TAIL && (tm == 0);
     const bool do_rowsum = B_KC && (p.rowsumB != nullptr || EPI == EPI_UPDW) && (tm == 0);
 
     f32x16 acc[TM][2];
@@ -588,8 +614,8 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void gccnmf_gemm_kernel(GemmArgs p)
         const int cur = kt & 1;
         // tile kt+1 (in registers since the previous iteration) -> the other buffer; tile kt+2 -> registers.
         // One barrier per tile: buffer cur^1 was last read in iteration kt-1, which every wave has left.
-        if (kt + 1 < nkt && !(p.ablate & 2)) GEMM_STORE_TILE(cur ^ 1);
-        if (kt + 2 < nkt && !(p.ablate & 1)) GEMM_LOAD_TILE((kt + 2) * BK);
+        if (kt + 1 < nkt) GEMM_STORE_TILE(cur ^ 1);
+        if (kt + 2 < nkt) GEMM_LOAD_TILE((kt + 2) * BK);
 
         const float* __restrict__ sA = smem + cur * SBUF;
         const float* __restrict__ sB = sA + SA;
@@ -637,7 +663,7 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void gccnmf_gemm_kernel(GemmArgs p)
                 }
             }
         }
-        if (!(p.ablate & 4)) __syncthreads();   // ablate: timing experiments only
+        __syncthreads();
     }
 #undef GEMM_LOAD_TILE
 #undef GEMM_STORE_TILE
@@ -648,19 +674,10 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void gccnmf_gemm_kernel(GemmArgs p)
         if constexpr (TM == 4) gemm_epilogue_update_w<TAIL>(p, file, col0, tid, wm, l31, hh, acc, tail_acc, rowsum_acc, smem);
         return;
     }
-    if (p.ablate & 16) {   // timing experiment: keep the accumulators alive, store one value per lane
-        float keep = 0.f;
+    if (wave_active) {
 #pragma unroll
         for (int m = 0; m < TM; ++m)
-#pragma unroll
-            for (int n = 0; n < 2; ++n)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) keep += acc[m][n][r];
-        if (wave_active && keep == 123.456f) p.C[file * p.sC] = keep;
-    } else if (wave_active) {
-#pragma unroll
-        for (int m = 0; m < TM; ++m)
-            gemm_epilogue_pair<EPI>(p, file, row0 + wm * WT + m * 32 + 4 * hh, col0 + wn * 64 + l31, acc[m][0], acc[m][1]);
+            gemm_epilogue_pair<EPI, true>(p, file, row0 + wm * WT + m * 32 + 4 * hh, col0 + wn * 64 + l31, acc[m][0], acc[m][1]);
     }
     if (TAIL) {
         if (do_tail) {   // block-uniform
@@ -693,7 +710,6 @@ static int gccnmf_launch_gemm(GemmArgs a, hipStream_t stream) {
     constexpr int BM = WM * 32 * TM, BN = WN * 64, NT = WM * WN * 64;
     if (!a.A || !a.B || !a.C || a.M < 1 || a.N < 1 || a.Kd < 1 || a.batch < 1) return GCCNMF_ERR_ARG;
     if ((a.lda & 3) || (a.ldb & 3)) return GCCNMF_ERR_ARG;   // float4 staging
-    a.ablate = gccnmf_tune_ablate;
     a.tiles_m = gccnmf_ceil_div(a.M, BM);
     a.tiles_n = gccnmf_ceil_div(a.N, BN);
     const int tiles = a.tiles_m * a.tiles_n;

@@ -66,20 +66,10 @@ __global__ __launch_bounds__(256, 2) void gccnmf_gemm_ring_kernel(GemmArgs p) {
         p.trace[8 * blockIdx.x + 0] = __builtin_amdgcn_s_memrealtime();
         p.trace[8 * blockIdx.x + 4] = (long long)((__builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u) << 16 | (__builtin_amdgcn_s_getreg((31 << 11) | 4) & 0xffffu));
     }
-    // split-K (kparts > 0): "file" is the part index; all parts read the same operands, each its own balanced range of k-tiles
-    // [kb, kb + nkt) (the first (total % kparts) parts take one more), and writes its own partial output (C + part * sC)
-    const bool split = p.kparts > 0;
-    int kb = 0, nkt = (p.Kd + BK - 1) / BK;
-    if (split) {
-        const int q = nkt / p.kparts, r = nkt - q * p.kparts;
-        kb = file * q + min(file, r);
-        nkt = q + (file < r ? 1 : 0);
-    }
-    kb = __builtin_amdgcn_readfirstlane(kb);
-    nkt = __builtin_amdgcn_readfirstlane(nkt);
-    const float* __restrict__ A = p.A + (split ? 0 : file * p.sA) + (A_KC ? (long)kb * BK : (long)kb * BK * p.lda);
-    const float* __restrict__ B = p.B + (split ? 0 : file * p.sB) + (B_KC ? (long)kb * BK : (long)kb * BK * p.ldb);
-    const float* __restrict__ bscale = (SCALE && p.bscale) ? p.bscale + (split ? 0 : file * p.s_bscale) + kb * BK : nullptr;
+    const int nkt = __builtin_amdgcn_readfirstlane((p.Kd + BK - 1) / BK);
+    const float* __restrict__ A = p.A + file * p.sA;
+    const float* __restrict__ B = p.B + file * p.sB;
+    const float* __restrict__ bscale = (SCALE && p.bscale) ? p.bscale + file * p.s_bscale : nullptr;
     const bool side_wg = (tm == 0);                                // the row-0 workgroups carry the tail row and the row sums
     const bool do_rowsum = B_KC && (p.rowsumB != nullptr) && side_wg;
     const int nside = (nkt * BK + 255) & ~255;                     // floats per reduction-index vector in LDS (whole 1 KB pieces)
@@ -473,7 +463,6 @@ template <bool A_KC, bool B_KC, int EPI, bool TAIL>
 static int gccnmf_launch_gemm_ring(GemmArgs a, hipStream_t stream) {
     if (!a.A || !a.B || !a.C || a.M < 1 || a.N < 1 || a.Kd < 1 || a.batch < 1) return GCCNMF_ERR_ARG;
     if ((a.lda & 3) || (a.ldb & 3) || !gccnmf_ring_supports(a.Kd)) return GCCNMF_ERR_ARG;
-    a.ablate = 0;
     a.tiles_m = gccnmf_ceil_div(a.M, 128);
     a.tiles_n = gccnmf_ceil_div(a.N, 64);
     a.xcd_affine = 0;

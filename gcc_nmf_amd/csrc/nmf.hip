@@ -15,9 +15,6 @@
 #include "direct.h"
 #include "update_w.h"
 #include "divergence.h"
-#ifdef GCCNMF_EXPERIMENTS
-int gccnmf_launch_gemm_stream(GemmArgs a, hipStream_t stream);       // the LDS-free throughput tile (direct.hip)
-#endif
 int gccnmf_klnmf_fixed_launch(const float* V, const float* W, float* H, float* workspace, int F, int N, int K, int batch, int iterations,
                               float alpha, float eps, bool ones, hipStream_t s);      // fixed dictionary, every iteration in one launch (nmf_fixed.hip)
 bool gccnmf_klnmf_fixed_supported(int F, int K);
@@ -39,35 +36,37 @@ int gccnmf_klnmf_beta_stage_launch(int stage, int divergence, const float* V, fl
 #define GCCNMF_SHARED_STREAMS 4
 #define GCCNMF_CHAIN_MAX_ITERATIONS gccnmf_tune_chain_chunk   // iterations per chained launch (tuning key 24, default 2048: the grid stays far below 2^30 workgroups)
 #define GCCNMF_RAGGED_MAX_BATCH 248   // files of a ragged batch: 8 lists of at most GEMM_RAGGED_LMAX
-#define GCCNMF_SPLITS 4           // parts of the round-3 single-file split-K (experiment builds); the workspace layout keeps room for them
+#define GCCNMF_SPLITS 4           // the one-file workspace layouts keep a RESERVED block of this many partial products (the room of a removed split-K path: nothing
+                                  // reads or writes it; the sizes are part of what callers see, so the block stays where it is)
 #define GCCNMF_DIRECT_MAX_BATCH 8    // workspaces of at most this many files carry the transposed copies of the direct path (key 12 selects up to here; from 8 files on
                                      // the ring / throughput kernels win anyway: 8 files 41.5 against 41.3 ms, 12 files 61.9 against 59.3)
-// The tuning table (common.h documents the keys): default, lowest and highest value, experiment-only.
+// The tuning table (common.h documents the keys): default, lowest and highest value, experiment-only.  An unused slot has an EMPTY range (lo > hi: no
+// value is accepted); it is kept so that the numbers of the other keys stay what tests, scripts and callers use.
 struct GccNmfKnob {
     int def, lo, hi, experiment;
 };
 static const GccNmfKnob gccnmf_knobs[GCCNMF_TUNE_KEYS] = {
-    {0, 0, 0, 1},                       //  0 (unused)
-    {0, 0, 1 << 30, 1},                 //  1 ablate
+    {0, 1, 0, 0},                       //  0 (unused)
+    {0, 1, 0, 0},                       //  1 (unused)
     {0, 0, 2, 0},                       //  2 tile_policy
     {1, 0, 1, 0},                       //  3 dma
-    {1, 0, 1, 1},                       //  4 ring
-    {3, 1, 4, 1},                       //  5 wh_splits
-    {4, 1, 4, 1},                       //  6 rht_splits
+    {0, 1, 0, 0},                       //  4 (unused)
+    {0, 1, 0, 0},                       //  5 (unused)
+    {0, 1, 0, 0},                       //  6 (unused)
     {1, 0, 1, 0},                       //  7 exact_div: the IEEE quotient since round 5 (measured cost on K1 / K3: 0.0 %, profiles/r05b_kbench_exact_div.txt)
     {3, 1, GCCNMF_SHARED_STREAMS, 0},   //  8 shared_groups
     {1, 0, 3, 0},                       //  9 tail_split (3 = half-height tiles everywhere: tests / measurements)
     {1, 0, 1, 0},                       // 10 direct
-    {0, 0, 8, 1},                       // 11 direct_tile
+    {0, 1, 0, 0},                       // 11 (unused)
     {4, 1, GCCNMF_DIRECT_MAX_BATCH, 0}, // 12 direct_batch (measured, K = 1024: 4 files 21.8 ms against 25.8 on the ring kernel, 8 files 41.5 / 41.3)
-    {0, 0, 4, 1},                       // 13 direct_depth (0, 2..4)
-    {1, 0, 1, 1},                       // 14 short_updh
-    {1, 0, 1, 1},                       // 15 fft_r16
+    {0, 1, 0, 0},                       // 13 (unused)
+    {0, 1, 0, 0},                       // 14 (unused)
+    {0, 1, 0, 0},                       // 15 (unused)
     {1, 0, 2, 0},                       // 16 fused_k12
     {1, 0, 2, 0},                       // 17 fused_k34
-    {0, 0, 1, 1},                       // 18 persistent
-    {1, 0, 1, 1},                       // 19 prefetch
-    {1, 0, 1, 1},                       // 20 wide_update_w
+    {0, 1, 0, 0},                       // 18 (unused)
+    {0, 1, 0, 0},                       // 19 (unused)
+    {0, 1, 0, 0},                       // 20 (unused)
     {1, 0, 8, 0},                       // 21 chain: 1 = the whole call as one chained launch where the rule in plan_klnmf says so; 0 off; forced forms (tests, A/B):
                                         //    2 = K1 | K2, 4 = K1 | K2 | K3 | K4 per iteration, 8 = every iteration of the call
     {0, 0, 1, 1},                       // 22 chain_solo: chained launches with one workgroup per CU (the freedom-from-deadlock test)
@@ -111,51 +110,14 @@ int gccnmf_set_tuning(int key, int value) {
     if (key < 1 || key >= GCCNMF_TUNE_KEYS) return GCCNMF_ERR_ARG;
     const GccNmfKnob& k = gccnmf_knobs[key];
 #ifndef GCCNMF_EXPERIMENTS
-    if (k.experiment) return GCCNMF_ERR_ARG;                 // the product build carries none of the code these select
+    if (k.experiment) return GCCNMF_ERR_ARG;                 // the test hooks of experiment builds
 #endif
-    if (value < k.lo || value > k.hi || (key == 13 && value == 1) || (key == 21 && value != 0 && value != 1 && value != 2 && value != 4 && value != 8)) return GCCNMF_ERR_ARG;
+    if (value < k.lo || value > k.hi || (key == 21 && value != 0 && value != 1 && value != 2 && value != 4 && value != 8)) return GCCNMF_ERR_ARG;
     gccnmf_knob_value[key].store(value, std::memory_order_relaxed);      // takes effect at the next library call (GccNmfCall)
     return GCCNMF_OK;
 }
 
 }  // extern "C"
-
-#ifdef GCCNMF_EXPERIMENTS
-// Ticket blocks of the persistent throughput-tile launches (gemm_dma.h): 16 counters per (device, stream), zero between launches (the last
-// workgroup of a launch resets them).  Launches on one stream are serialised, so a stream's launches share a block; every stream has its own.
-// nullptr (pool exhausted, allocation refused -- e.g. inside a stream capture) = the launch falls back to the classic grid.
-unsigned* gccnmf_ticket_block(hipStream_t stream) {
-    constexpr int MAX_DEV = 16, PER_DEV = 128;
-    struct Entry { hipStream_t s; };
-    static std::mutex mu;
-    static unsigned* pool[MAX_DEV] = {};
-    static Entry entries[MAX_DEV][PER_DEV];
-    static int used[MAX_DEV] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEV) return nullptr;
-    std::lock_guard<std::mutex> lock(mu);
-    for (int i = 0; i < used[dev]; ++i)
-        if (entries[dev][i].s == stream) return pool[dev] + 16 * i;
-    if (used[dev] == PER_DEV) return nullptr;
-    if (!pool[dev]) {
-        static const unsigned zeros[16 * PER_DEV] = {};
-        unsigned* p = nullptr;
-        if (hipMalloc((void**)&p, sizeof(zeros)) != hipSuccess) {
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        if (hipMemcpy(p, zeros, sizeof(zeros), hipMemcpyHostToDevice) != hipSuccess) {      // blocking: the counters are zero before any launch reads them
-            (void)hipGetLastError();
-            (void)hipFree(p);
-            return nullptr;
-        }
-        pool[dev] = p;
-    }
-    entries[dev][used[dev]].s = stream;
-    return pool[dev] + 16 * used[dev]++;
-}
-
-#endif
 
 extern "C" {
 #ifdef GCCNMF_EXPERIMENTS
@@ -234,14 +196,11 @@ __global__ __launch_bounds__(256) void nmf_prepare_kernel(const float* __restric
 // grid = batch * Kp/AT, 256 threads = AT atoms x 256/AT row phases; W and U are read twice (L2-resident) instead of
 // keeping F*AT/256 values per thread in registers.  AT = 64 for big batches (256-byte row segments); AT = 16 when the
 // launch would otherwise be a handful of workgroups (single file: 16 -> 64 workgroups, 4x shorter row loops).
-// nsplit > 1 (single-file split-K, below): U and rowsumH arrive as nsplit partial sums, sSplitU / sSplitR floats apart,
-// and are added in ascending split order wherever they are read.
 template <int AT>
 __global__ __launch_bounds__(256) void nmf_update_w_kernel(float* __restrict__ W, const float* __restrict__ U,
                                                            const float* __restrict__ rowsumH, float* __restrict__ colsumW,
                                                            float* __restrict__ hscale, int F, int Fp, int K, int Kp,
-                                                           long sW, long sU, long sVec, long sRowsum, int nsplit, long sSplitU,
-                                                           long sSplitR) {
+                                                           long sW, long sU, long sVec, long sRowsum) {
     constexpr int PH = 256 / AT;
     __shared__ float red[256];
     __shared__ float s_norm[AT];
@@ -252,20 +211,11 @@ __global__ __launch_bounds__(256) void nmf_update_w_kernel(float* __restrict__ W
     const bool valid = k < K;          // padded atoms stay exactly zero
     float* Wb = W + b * sW;
     const float* Ub = U + b * sU;
-    float rs = 1.f;
-    if (valid) {
-        rs = rowsumH[b * sRowsum + k];
-        for (int sp = 1; sp < nsplit; ++sp) rs += rowsumH[b * sRowsum + sp * sSplitR + k];
-    }
-    auto u_at = [&](long i) {
-        float u = Ub[i];
-        for (int sp = 1; sp < nsplit; ++sp) u += Ub[sp * sSplitU + i];
-        return u;
-    };
+    const float rs = valid ? rowsumH[b * sRowsum + k] : 1.f;
     float ss = 0.f;
     if (valid)
         for (int f = q; f < F; f += PH) {
-            const float wt = Wb[(long)f * Kp + k] * (u_at((long)f * Kp + k) / rs);
+            const float wt = Wb[(long)f * Kp + k] * (Ub[(long)f * Kp + k] / rs);
             ss = fmaf(wt, wt, ss);
         }
     red[threadIdx.x] = ss;
@@ -282,7 +232,7 @@ __global__ __launch_bounds__(256) void nmf_update_w_kernel(float* __restrict__ W
     if (valid)
         for (int f = q; f < F; f += PH) {
             const long i = (long)f * Kp + k;
-            const float wn = (Wb[i] * (u_at(i) / rs)) / norm;
+            const float wn = (Wb[i] * (Ub[i] / rs)) / norm;
             Wb[i] = wn;
             cs += wn;
         }
@@ -297,49 +247,36 @@ __global__ __launch_bounds__(256) void nmf_update_w_kernel(float* __restrict__ W
     }
 }
 
-// The same update in ONE pass for launches of a few files (the two-pass kernel above re-reads W and every U partial, 64 dependent
+// The same update in ONE pass for launches of a few files (the two-pass kernel above re-reads W and U, 64 dependent
 // round trips per thread: 50 us for one file at K = 1024): 16 atoms per workgroup as float4 columns x 64 row phases, the
 // R <= 17 rows of a thread stay in registers between the norm and the store, all loads of a thread are independent.
 // Column reductions: xor-shuffles over the 16 row phases of a wave, then 4 waves through LDS (fixed order: deterministic).
-template <int AT, int NSPLIT>
+template <int AT>
 __global__ __launch_bounds__(256) void nmf_update_w_onepass_kernel(float* __restrict__ W, const float* __restrict__ U,
                                                                    const float* __restrict__ rowsumH, float* __restrict__ colsumW,
                                                                    float* __restrict__ hscale, int F, int K, int Kp, long sW, long sU,
-                                                                   long sVec, long sRowsum, long sSplitU, long sSplitR, float* __restrict__ Wt,
-                                                                   long sWt, int ldwt) {
+                                                                   long sVec, long sRowsum, float* __restrict__ Wt, long sWt, int ldwt) {
     __shared__ __attribute__((aligned(16))) float smem[5 * AT];
     const int chunks = Kp / AT;
     const int b = blockIdx.x / chunks, ch = blockIdx.x - b * chunks;
-    nmf_update_w_onepass_item<AT, NSPLIT>(W, U, rowsumH, colsumW, hscale, F, K, Kp, sW, sU, sVec, sRowsum, sSplitU, sSplitR, Wt, sWt, ldwt, b, ch, smem, (int)threadIdx.x);
+    nmf_update_w_onepass_item<AT>(W, U, rowsumH, colsumW, hscale, F, K, Kp, sW, sU, sVec, sRowsum, Wt, sWt, ldwt, b, ch, smem, (int)threadIdx.x);
 }
 
 // `a`: the factors and their strides (direct.h; update_w_args below fills it); what it does not hold: the files of this launch, the file groups that
-// run it side by side, split-K partials (nsplit > 1) and the transposed copy of W the direct path keeps (Wt, or nullptr)
-static int launch_update_w(const UpdateWArgs& a, int batch, int groups, hipStream_t s, int nsplit, long sSplitU, long sSplitR, float* Wt, long sWt,
-                           int ldwt) {
+// run it side by side and the transposed copy of W the direct path keeps (Wt, or nullptr)
+static int launch_update_w(const UpdateWArgs& a, int batch, int groups, hipStream_t s, float* Wt, long sWt, int ldwt) {
     const int Kp = a.Kp;
     const long sized = (long)batch * groups;           // files of every group that runs this launch side by side: the kernel is chosen for all of them
-    if (sized * (Kp / 64) < 256 && gccnmf_tune_ring && a.F <= 64 * 9 && (nsplit == 1 || nsplit == 2 || nsplit == 4)) {
+    if (sized * (Kp / 64) < 256 && a.F <= 64 * 9) {
         // 16 atoms per workgroup (64-byte row segments); 8 (twice the workgroups, 32-byte segments) measured slower: 13.0 vs 11.4 us for one
-        // file at K = 1024 -- kept selectable for experiments (tuning key 1 = 64)
-#define GCCNMF_ONEPASS(AT_, NS_) hipLaunchKernelGGL((nmf_update_w_onepass_kernel<AT_, NS_>), dim3(batch * (Kp / AT_)), dim3(256), 0, s, a.W, a.U, a.rowsumH, \
-                                                    a.colsumW, a.hscale, a.F, a.K, Kp, a.sW, a.sU, a.sVec, a.sRowsum, sSplitU, sSplitR, Wt, sWt, ldwt)
-        const bool narrow = gccnmf_tune_ablate == 64;
+        // file at K = 1024
+#define GCCNMF_ONEPASS(AT_) hipLaunchKernelGGL((nmf_update_w_onepass_kernel<AT_>), dim3(batch * (Kp / AT_)), dim3(256), 0, s, a.W, a.U, a.rowsumH, \
+                                               a.colsumW, a.hscale, a.F, a.K, Kp, a.sW, a.sU, a.sVec, a.sRowsum, Wt, sWt, ldwt)
         // short dictionaries at batch scale (64 files, K = 128: the launch between the two fused GEMM launches): 32 atoms per workgroup =
         // whole 128-byte lines per row and workgroup -- with 16 atoms every line of W and U is fetched by two workgroups (17 us for 51 MB).
         // Only for K <= 128, where the launch forms follow the batch size anyway (a file's bits are batch-independent for K > 128).
-        const bool wide = !narrow && nsplit == 1 && !Wt && a.K <= 128 && sized * (Kp / 32) >= 256 && gccnmf_tune_wide_update_w;
-        if (wide) {
-            GCCNMF_ONEPASS(32, 1);
-        } else if (narrow) {
-            if (nsplit == 1) GCCNMF_ONEPASS(8, 1);
-            else if (nsplit == 2) GCCNMF_ONEPASS(8, 2);
-            else GCCNMF_ONEPASS(8, 4);
-        } else {
-            if (nsplit == 1) GCCNMF_ONEPASS(16, 1);
-            else if (nsplit == 2) GCCNMF_ONEPASS(16, 2);
-            else GCCNMF_ONEPASS(16, 4);
-        }
+        if (!Wt && a.K <= 128 && sized * (Kp / 32) >= 256) GCCNMF_ONEPASS(32);
+        else GCCNMF_ONEPASS(16);
 #undef GCCNMF_ONEPASS
         GCCNMF_CHECK_LAUNCH();
         return GCCNMF_OK;
@@ -347,10 +284,10 @@ static int launch_update_w(const UpdateWArgs& a, int batch, int groups, hipStrea
     const int Fp = gccnmf_round_up(a.F, 16);
     if (sized * (Kp / 64) >= 256) {
         hipLaunchKernelGGL(nmf_update_w_kernel<64>, dim3(batch * (Kp / 64)), dim3(256), 0, s, a.W, a.U, a.rowsumH, a.colsumW, a.hscale, a.F, Fp, a.K,
-                           Kp, a.sW, a.sU, a.sVec, a.sRowsum, nsplit, sSplitU, sSplitR);
+                           Kp, a.sW, a.sU, a.sVec, a.sRowsum);
     } else {
         hipLaunchKernelGGL(nmf_update_w_kernel<16>, dim3(batch * (Kp / 16)), dim3(256), 0, s, a.W, a.U, a.rowsumH, a.colsumW, a.hscale, a.F, Fp, a.K,
-                           Kp, a.sW, a.sU, a.sVec, a.sRowsum, nsplit, sSplitU, sSplitR);
+                           Kp, a.sW, a.sU, a.sVec, a.sRowsum);
     }
     GCCNMF_CHECK_LAUNCH();
     if (Wt) return gccnmf_transpose_launch(a.W, a.sW, Kp, Wt, sWt, ldwt, a.F, Kp, batch, s);      // (the one-pass kernel writes it itself)
@@ -422,9 +359,9 @@ static int dispatch_gemm(const GemmArgs& a, bool tail, hipStream_t s) {
     const bool tall = a.M > 128;
     // The H update of a SMALL dictionary (K <= 128 atoms = output rows: the reference driver's default, runGCCNMF.py:41) used to ride the
     // register-staged wide tile (128 x 256 per workgroup, one k-tile prefetched): 154 us per launch for 64 files at K = 128 = 0.43 of the
-    // matrix peak.  The LDS-DMA ring kernel's 128 x 64 tiles (six stages in flight, image-layout epilogue) take it instead (key 14).
-    const bool short_updh = !tall && EPI == EPI_UPDH && gccnmf_tune_short_updh && gccnmf_tune_tile_policy != 1 && a.N >= 256;
-    const bool ring = (small_batch_tile(a) || short_updh) && gccnmf_tune_ring && gccnmf_ring_supports(a.Kd);   // (longer reductions: the register-staged tile)
+    // matrix peak.  The LDS-DMA ring kernel's 128 x 64 tiles (six stages in flight, image-layout epilogue) take it instead.
+    const bool short_updh = !tall && EPI == EPI_UPDH && gccnmf_tune_tile_policy != 1 && a.N >= 256;
+    const bool ring = (small_batch_tile(a) || short_updh) && gccnmf_ring_supports(a.Kd);   // (longer reductions: the register-staged tile)
     const GemmFamily family = ring ? GEMM_RING : small_batch_tile(a) ? GEMM_SMALL_BATCH : !tall ? GEMM_WIDE : gccnmf_tune_dma ? GEMM_DMA : GEMM_TALL;
     if (tail && !A_KC) return GCCNMF_ERR_ARG;      // the VALU tail row needs a reduction-contiguous A
     return tail ? launch_gemm_family<A_KC, B_KC, EPI, A_KC>(family, a, s) : launch_gemm_family<A_KC, B_KC, EPI, false>(family, a, s);
@@ -566,96 +503,6 @@ static int launch_rht_update_w(const NmfGeom& g, const GemmArgs& a, hipStream_t 
     return g.tail ? gccnmf_launch_gemm<4, 1, true, true, EPI_UPDW, true>(a, s) : gccnmf_launch_gemm<4, 1, true, true, EPI_UPDW, false>(a, s);
 }
 
-#ifdef GCCNMF_EXPERIMENTS
-// ------------------------------------------------------------------------------------------
-// One file alone (BASELINE config 2 as a single mixture): split-K
-// ------------------------------------------------------------------------------------------
-// A launch over ONE file has 64-80 small-batch tiles for 256 CUs, each a 64..78-step dependent chain: latency-bound.  The two
-// long reductions are therefore cut into GCCNMF_SPLITS equal parts that run as independent "files" of the batched kernel
-// (operand base + part * length, partial outputs side by side): W.H over the atoms, R.H^T over the columns.  The parts
-// are added in ascending order by the consumer -- nmf_div_partials_kernel (R = V / sum) and nmf_update_w_kernel -- so the
-// result does not depend on scheduling.  Zero padding makes the parts equal: Kp and Np are multiples of 64.
-
-// R[f][n] = V[f][n] / (P_0 + P_1 + ... )[f][n] on the valid F x N region only (R's padding must stay zero)
-// one float4 per thread; columns >= N of the last float4 are written as 0 (not 0/0)
-__global__ __launch_bounds__(256) void nmf_div_partials_kernel(const float* __restrict__ V, const float* __restrict__ P, long sP,
-                                                               int nsplit, int F, int N, int Np, float* __restrict__ R) {
-    const int n4 = Np / 4;
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long)F * n4) return;
-    const int f = (int)(idx / n4), n = 4 * (int)(idx - (long)f * n4);
-    if (n >= N) return;
-    const long i = (long)f * Np + n;
-    float4 d = *(const float4*)(P + i);
-    for (int sp = 1; sp < nsplit; ++sp) {
-        const float4 t = *(const float4*)(P + sp * sP + i);
-        d.x += t.x; d.y += t.y; d.z += t.z; d.w += t.w;
-    }
-    const float4 v = *(const float4*)(V + i);
-    *(float4*)(R + i) = make_float4(v.x / d.x, n + 1 < N ? v.y / d.y : 0.f, n + 2 < N ? v.z / d.z : 0.f, n + 3 < N ? v.w / d.w : 0.f);
-}
-
-// reduction length (padded) worth cutting: at least 8 k-tiles per part
-static bool single_file_split(const NmfGeom& g, int batch, int reduction, int splits) {
-    const bool ring = gccnmf_tune_ring && gccnmf_ring_supports(reduction);        // balances unequal parts itself
-    return batch == 1 && splits > 1 && gccnmf_tune_tile_policy != 1 && g.Fm > 128 && reduction >= GCCNMF_SPLITS * 128 &&
-           (ring || (reduction / 16) % splits == 0);
-}
-
-// P_part = W[:, part] . (hscale * H)[part, :]   (EPI_STORE incl. the VALU tail row), then R = V / sum_part P_part
-static int launch_wh_div_split(const NmfGeom& g, const float* V, const float* W, const float* H, const float* hscale, float* P, float* R,
-                               hipStream_t s) {
-    const int nsplit = gccnmf_tune_wh_splits;
-    const bool ring = gccnmf_tune_ring && gccnmf_ring_supports(g.Kp);
-    const int len = g.Kp / nsplit;                           // atoms per part (multiple of 16) -- equal parts for the register-staged kernel
-    GemmArgs a = {};
-    a.A = W; a.sA = len; a.lda = g.Kp; a.a_clamp = g.Fp - 1;
-    a.B = H; a.sB = (long)len * g.Np; a.ldb = g.Np; a.b_clamp = g.Np - 4;
-    a.M = g.Fm; a.N = g.N; a.Kd = len;
-    a.batch = nsplit; a.xcd_affine = 0;
-    a.bscale = hscale; a.s_bscale = len;
-    if (ring) {                                              // the ring kernel balances the k-tiles itself (parts need not be equal: 3 parts of 64 tiles)
-        a.kparts = nsplit;
-        a.Kd = g.Kp;
-    }
-    a.tail_row = g.F - 1;
-    a.C = P; a.sC = g.sV; a.ldc = g.Np;
-    int rc;
-    if (ring)
-        rc = g.tail ? gccnmf_launch_gemm_ring<true, false, EPI_STORE, true>(a, s) : gccnmf_launch_gemm_ring<true, false, EPI_STORE, false>(a, s);
-    else
-        rc = g.tail ? gccnmf_launch_gemm<4, 1, true, false, EPI_STORE, true, 1>(a, s) : gccnmf_launch_gemm<4, 1, true, false, EPI_STORE, false, 1>(a, s);
-    if (rc) return rc;
-    hipLaunchKernelGGL(nmf_div_partials_kernel, dim3((unsigned)(((long)g.F * (g.Np / 4) + 255) / 256)), dim3(256), 0, s, V, P, g.sV, nsplit, g.F,
-                       g.N, g.Np, R);
-    GCCNMF_CHECK_LAUNCH();
-    return GCCNMF_OK;
-}
-
-// U_part = R[:, part] . H[:, part]^T, rowsum_part = sum_{n in part} H   (consumed by nmf_update_w_kernel with nsplit parts)
-static int launch_rht_split(const NmfGeom& g, const float* R, const float* H, float* Upart, float* rowsum_part, hipStream_t s) {
-    const int nsplit = gccnmf_tune_rht_splits;
-    const bool ring = gccnmf_tune_ring && gccnmf_ring_supports(g.Np);
-    const int len = g.Np / nsplit;                           // columns per part (multiple of 16; beyond N both operands are zero)
-    GemmArgs a = {};
-    a.A = R; a.sA = len; a.lda = g.Np; a.a_clamp = g.Fp - 1;
-    a.B = H; a.sB = len; a.ldb = g.Np; a.b_clamp = g.Kp - 1;
-    a.M = g.Fm; a.N = g.K; a.Kd = len;
-    a.batch = nsplit; a.xcd_affine = 0;
-    if (ring) {                                              // balanced k-tile ranges over the N valid columns only (78 tiles, not 80)
-        a.kparts = nsplit;
-        a.Kd = g.N;
-    }
-    a.tail_row = g.F - 1;
-    a.rowsumB = rowsum_part; a.s_rowsumB = g.Kp;
-    a.C = Upart; a.sC = g.sU; a.ldc = g.Kp;
-    if (ring)
-        return g.tail ? gccnmf_launch_gemm_ring<true, true, EPI_STORE, true>(a, s) : gccnmf_launch_gemm_ring<true, true, EPI_STORE, false>(a, s);
-    return g.tail ? gccnmf_launch_gemm<4, 1, true, true, EPI_STORE, true, 1>(a, s) : gccnmf_launch_gemm<4, 1, true, true, EPI_STORE, false, 1>(a, s);
-}
-
-#endif  // GCCNMF_EXPERIMENTS (single-file split-K)
-
 // ------------------------------------------------------------------------------------------
 // The direct path (csrc/direct.hip): launches that cannot fill the chip -- one mixture alone, the shape behind the reference's
 // own function names (runGCCNMF.py:41 -> performKLNMF(V, dictionarySize, 100, 0))
@@ -705,7 +552,7 @@ static int direct_wh_div(const NmfGeom& g, const DirectBufs& d, const float* V, 
     if (transposed) {
         a.Ct = d.Rt; a.sCt = d.sRt; a.ldct = d.ldrt;
     }
-    return gccnmf_direct_launch(a, transposed ? DEPI_DIVT : DEPI_DIV, gccnmf_tune_direct_tile, s);
+    return gccnmf_direct_launch(a, transposed ? DEPI_DIVT : DEPI_DIV, 0, s);
 }
 
 static int direct_update_h(const NmfGeom& g, const DirectBufs& d, const float* W, const float* R, float* H, const float* hscale,
@@ -724,7 +571,7 @@ static int direct_update_h(const NmfGeom& g, const DirectBufs& d, const float* W
     a.E1 = hscale; a.sE1 = g.Kp;
     a.E2 = colsumW; a.sE2 = g.Kp;
     a.alpha = alpha; a.eps = eps;
-    return gccnmf_direct_launch(a, DEPI_UPDH, gccnmf_tune_direct_tile, s);
+    return gccnmf_direct_launch(a, DEPI_UPDH, 0, s);
 }
 
 static int direct_rht(const NmfGeom& g, const DirectBufs& d, const float* R, float* U, float* rowsumH, int batch, hipStream_t s) {
@@ -737,7 +584,7 @@ static int direct_rht(const NmfGeom& g, const DirectBufs& d, const float* R, flo
     }
     a.rowsumB = rowsumH; a.s_rowsumB = g.Kp;
     a.C = U; a.sC = g.sU; a.ldc = g.Kp;
-    return gccnmf_direct_launch(a, DEPI_STORE, gccnmf_tune_direct_tile, s);
+    return gccnmf_direct_launch(a, DEPI_STORE, 0, s);
 }
 
 // The operands of the short-dictionary launches (plan_klnmf says where they run).  K1 + K2 in one launch:
@@ -774,14 +621,14 @@ static UpdateWArgs update_w_args(const NmfGeom& g, float* W, long sW, const floa
 }
 
 // ---- the workspace of gccnmf_klnmf / gccnmf_klnmf_ragged, carved in ONE place ---------------------------------------------------------
-// R [batch][Fp][Np] | U [batch][Fp][Kp] | colsumW, rowsumH, hscale [batch][Kp] each | (batch == 1) the split-K partials: GCCNMF_SPLITS x
-// max(Fp*Np, Fp*Kp) (W.H parts and R.H^T parts use the same memory at different stages) + GCCNMF_SPLITS x Kp | (batch <= GCCNMF_DIRECT_MAX_BATCH)
+// R [batch][Fp][Np] | U [batch][Fp][Kp] | colsumW, rowsumH, hscale [batch][Kp] each | (batch == 1) a reserved block, unused: GCCNMF_SPLITS x
+// max(Fp*Np, Fp*Kp) + GCCNMF_SPLITS x Kp floats | (batch <= GCCNMF_DIRECT_MAX_BATCH)
 // the transposed copies of the direct path: Wt [batch][Kp][Fp], Ht [batch][Np][Kp], Rt [batch][Np][Fp] | the ready counters of the chained
 // launches (tuning key 21; gemm_dma.h: GemmSync, gccnmf_gemm_chain_kernel) | the status words | (a ragged batch) its tables.
 // Counters of one file group: c12 [batch][tiles_n] (K1 -> K2, in 32-column blocks), c23 [batch][tiles_n] (K2 -> K3), c34 [batch] (K3 -> K4, items),
 // c41 [batch] (K4 -> the next iteration's K1, items).  Zeroed once per gccnmf_klnmf call; iteration `it` waits for (it + 1) x the per-iteration count,
 // so nothing is reset between launches.  (The short-dictionary chain keeps its [3][batch] counters at the same place.)
-// The ready counters are rounded up to a 128-byte line (32 words), the GCCNMF_STATUS_WORDS status words follow: error [1], 7 unused, tickets [8], XCCs
+// The ready counters are rounded up to a 128-byte line (32 words), the GCCNMF_STATUS_WORDS status words follow: error [1], 15 unused, XCCs
 // seen per list [8] (from GCCNMF_STATUS_XCC_SEEN on), 8 unused.  Every block in front of the counters is a multiple of 64 floats, so the workspace is
 // one too (a ragged batch's, with its tables: of 4) -- workspaces carved back to back out of ONE allocation (the engine's file groups) all start
 // 16-byte aligned when the first does, which the float4 / LDS-DMA accesses to R, U, Wt, Ht, Rt rely on (the entry points reject a workspace that is
@@ -790,7 +637,6 @@ static UpdateWArgs update_w_args(const NmfGeom& g, float* W, long sW, const floa
 #define GCCNMF_STATUS_XCC_SEEN 16
 struct KlnmfWorkspace {
     float *R, *U, *colsumW, *rowsumH, *hscale;
-    float *parts, *rowsum_parts;            // split-K partials (batch == 1: experiment builds use them, the product build keeps the room)
     float* direct_base;                     // Wt | Ht | Rt (direct_bufs)
     unsigned *c12, *c23, *c34, *c41;        // ready counters
     unsigned *status, *xcc_seen;
@@ -809,9 +655,7 @@ static KlnmfWorkspace carve(float* workspace, const NmfGeom& g, int batch, bool 
     ws.colsumW = take((long)batch * g.Kp);
     ws.rowsumH = take((long)batch * g.Kp);
     ws.hscale = take((long)batch * g.Kp);
-    const long splits = batch == 1 ? GCCNMF_SPLITS : 0;
-    ws.parts = take(splits * (g.sV > g.sU ? g.sV : g.sU));
-    ws.rowsum_parts = take(splits * g.Kp);
+    if (batch == 1) take(GCCNMF_SPLITS * ((g.sV > g.sU ? g.sV : g.sU) + (long)g.Kp));      // the reserved block
     ws.direct_base = take(direct_floats(g, batch));
     ws.scratch_floats = end;
     const long tn = gccnmf_ceil_div(g.N, 64);
@@ -888,11 +732,6 @@ struct KlnmfPlan {
     bool w_in_rht;          // the W update rides in stage 4's epilogue: stage 5 has nothing to do
     int chain;              // 0 | 2: K1 | K2 in one chained launch | 4: the whole iteration | 8: the whole call
     int short_group;        // K <= 128: the three launches of every iteration as one chained launch -- atoms per W-update group (16 | 32), 0 = no chain
-#ifdef GCCNMF_EXPERIMENTS
-    bool split_wh, split_rht;      // the round-3 latency path: one file's reductions (W.H over the atoms, R.H^T over the columns) as parts
-#else
-    static constexpr bool split_wh = false, split_rht = false;      // the split-K path is compiled out of the product library
-#endif
 };
 static KlnmfPlan plan_klnmf(const NmfGeom& g, int batch, const KlnmfMode& m) {
     KlnmfPlan p = {};
@@ -910,10 +749,6 @@ static KlnmfPlan plan_klnmf(const NmfGeom& g, int batch, const KlnmfMode& m) {
     const bool latency = direct_path(g, batch, groups);
     const int want = gccnmf_tune_chain;
     p.direct = latency && !semi;
-#ifdef GCCNMF_EXPERIMENTS
-    p.split_wh = !semi && !latency && single_file_split(g, batch, g.Kp, gccnmf_tune_wh_splits);
-    p.split_rht = !semi && !latency && single_file_split(g, batch, g.Np, gccnmf_tune_rht_splits);
-#endif
     // the shapes of the short-dictionary kernels (direct.hip), and of them those whose W rows fit the registers of the K3 + K4a slab workgroups
     const bool short_shape = gccnmf_tune_tile_policy == 0 && !latency && batch >= 2 && g.tail && g.Fm >= 64 && g.Fm <= 512 && (g.Fm % 64) == 0 && g.K <= 128;
     const bool slab_shape = short_shape && (g.Fm / 64) * 16 >= 32 * gccnmf_ceil_div(g.K, 32);
@@ -955,7 +790,7 @@ static KlnmfPlan plan_klnmf(const NmfGeom& g, int batch, const KlnmfMode& m) {
     }
     // K4a + K4b in one launch (launch_rht_update_w): the fused epilogue needs the tall tile; tiny launches prefer the small-batch tile and two launches
     const bool tall_tile = gccnmf_tune_tile_policy == 1 || (gccnmf_tune_tile_policy == 0 && (long)batch * groups * gccnmf_ceil_div(g.K, 64) >= 256);
-    p.w_in_rht = g.Fm > 128 && g.Fm <= 512 && tall_tile && !m.unfused_w_update && !p.head34 && !semi && !p.direct && !p.split_rht;
+    p.w_in_rht = g.Fm > 128 && g.Fm <= 512 && tall_tile && !m.unfused_w_update && !p.head34 && !semi && !p.direct;
 
     // The chained launches: bit for bit the plain call, which is why they are derived from the fields above.  K > 128: a plain launch of a few files
     // takes the two-launch W update -- other kernels, other summation order -- so the call chains only where the plain one has the W update in K4's
@@ -969,11 +804,11 @@ static KlnmfPlan plan_klnmf(const NmfGeom& g, int batch, const KlnmfMode& m) {
     // chained the same way (direct.hip: gccnmf_short_chain_kernel).  Shapes both fused kernels and the one-pass W update take; the same batch
     // rule as the throughput chain.  short_group: the atoms per W-update group (16 / 32: what the plain launch would use at this batch).
     if (!p.chain && !semi && (want == 1 || want == 8) && slab_shape && gccnmf_tune_fused_k12 && gccnmf_tune_fused_k34 && m.xcd_affine &&
-        !m.unfused_w_update && batch >= 8 && g.F <= 64 * 9 && gccnmf_tune_ring && (long)batch * (g.Kp / 64) < 256 && gccnmf_tune_ablate != 64) {
+        !m.unfused_w_update && batch >= 8 && g.F <= 64 * 9 && (long)batch * (g.Kp / 64) < 256) {
         // by rule: only where the plain call runs the SAME three item programs for every file (both fused launches, no files left to the two-launch
         // form) -- the chained call is then bit for bit the plain one, and a file's bits keep following the batch size exactly as before
         if (want == 8 || (chain_rule(batch, m) && p.fused12 && p.head34 == batch))
-            p.short_group = ((long)batch * (g.Kp / 32) >= 256 && gccnmf_tune_wide_update_w) ? 32 : 16;
+            p.short_group = (long)batch * (g.Kp / 32) >= 256 ? 32 : 16;
     }
     return p;
 }
@@ -997,7 +832,7 @@ static int launch_klnmf_chain(int stages, const NmfGeom& g, const float* V, floa
                      update_h_args(g, W, g.sW, ws.R, H, ws.hscale, g.Kp, ws.colsumW, g.Kp, alpha, eps, batch, 1, concurrent),
                      wh_div_args(g, V, W, g.sW, H, nullptr, 0, ws.R, batch, 1, concurrent),
                      rht_update_w_args(g, ws.R, H, W, ws.colsumW, ws.hscale, batch, 1, concurrent)};
-    for (GemmArgs& x : a) x.ablate = gccnmf_tune_ablate, x.exact_div = gccnmf_tune_exact_div;
+    for (GemmArgs& x : a) x.exact_div = gccnmf_tune_exact_div;
     const int tm1 = g.K <= 256 ? 2 : 4;            // K2's outputs are the K atoms: at most 256 rows -> half-height tiles, as in a plain launch
     GemmChain ch = {};
     for (int i = 0; i < 4; ++i) {
@@ -1156,7 +991,7 @@ static int klnmf_stage(int stage, const float* V, float* W, float* H, const Klnm
             case 2: return direct_update_h(g, d, W, R, H, hscale, colsumW, alpha, eps, batch, s);
             case 3: return direct_wh_div(g, d, V, W, H, nullptr, R, true, batch, s);
             case 4: return direct_rht(g, d, R, U, rowsumH, batch, s);
-            case 5: return launch_update_w(update_w_args(g, W, g.sW, U, g.sU, rowsumH, colsumW, hscale, g.Kp), batch, groups, s, 1, 0, 0, d.Wt, d.sWt, d.ldwt);
+            case 5: return launch_update_w(update_w_args(g, W, g.sW, U, g.sU, rowsumH, colsumW, hscale, g.Kp), batch, groups, s, d.Wt, d.sWt, d.ldwt);
             default: return GCCNMF_ERR_ARG;
         }
     }
@@ -1170,9 +1005,6 @@ static int klnmf_stage(int stage, const float* V, float* W, float* H, const Klnm
             break;
         case 1:
             if (p.fused12) return gccnmf_wh_updh_launch(wh_updh_args(g, V, W, H, hscale, colsumW, alpha, eps, batch), s);    // K1 + K2
-#ifdef GCCNMF_EXPERIMENTS
-            if (p.split_wh) return launch_wh_div_split(g, V, W, H, hscale, ws.parts, R, s);
-#endif
             return launch_wh_div(g, wh_div_args(g, V, W, g.sW, H, hscale, g.Kp, R, batch, xa, conc), s);
         case 2:
             if (p.fused12) return GCCNMF_OK;                                                                             // done by stage 1
@@ -1183,28 +1015,19 @@ static int klnmf_stage(int stage, const float* V, float* W, float* H, const Klnm
                 if (rc || !rest34) return rc;
                 return launch_wh_div(g, wh_div_args(g, V + head34 * g.sV, W + head34 * g.sW, g.sW, H + head34 * g.sH, nullptr, 0, R + head34 * g.sV, rest34, xa, conc), s);
             }
-#ifdef GCCNMF_EXPERIMENTS
-            if (p.split_wh) return launch_wh_div_split(g, V, W, H, nullptr, ws.parts, R, s);
-#endif
             return launch_wh_div(g, wh_div_args(g, V, W, g.sW, H, nullptr, 0, R, batch, xa, conc), s);
         case 4:
             if (semi) return gccnmf_klnmf_semi_rht_launch(R, H, U, rowsumH, g.F, g.N, g.K, nfree, batch, s);           // U[:, K - n:], rowsumH[K - n:]
             if (head34)                                                                                                // done by stage 3 ...
                 return rest34 ? launch_rht(g, rht_args(g, R + head34 * g.sV, H + head34 * g.sH, U + head34 * g.sU, rowsumH + (long)head34 * g.Kp, rest34, xa, conc), s)
                               : GCCNMF_OK;                                                                             // ... but for the rest
-#ifdef GCCNMF_EXPERIMENTS
-            if (p.split_rht) return launch_rht_split(g, R, H, ws.parts, ws.rowsum_parts, s);
-#endif
             if (p.w_in_rht)                                                                                            // K4a + K4b
                 return launch_rht_update_w(g, rht_update_w_args(g, R, H, W, colsumW, hscale, batch, xa, conc), s);
             return launch_rht(g, rht_args(g, R, H, U, rowsumH, batch, xa, conc), s);
         case 5:
             if (semi) return gccnmf_klnmf_semi_update_w_launch(W, U, rowsumH, colsumW, hscale, g.F, g.K, nfree, batch, s);
-            if (p.split_rht)      // (the parts are sized as one launch: no file groups beside a single file)
-                return launch_update_w(update_w_args(g, W, g.sW, ws.parts, g.sU, ws.rowsum_parts, colsumW, hscale, g.Kp), batch, 1, s, gccnmf_tune_rht_splits,
-                                       g.sU, (long)g.Kp, nullptr, 0, 0);
             if (p.w_in_rht) return GCCNMF_OK;                                                                          // done by stage 4's epilogue
-            return launch_update_w(update_w_args(g, W, g.sW, U, g.sU, rowsumH, colsumW, hscale, g.Kp), batch, groups, s, 1, 0, 0, nullptr, 0, 0);
+            return launch_update_w(update_w_args(g, W, g.sW, U, g.sU, rowsumH, colsumW, hscale, g.Kp), batch, groups, s, nullptr, 0, 0);
         case 6:
             hipLaunchKernelGGL(nmf_scale_h_kernel, dim3(batch * g.K), dim3(256), 0, s, H, hscale, (long)g.Kp, g.K, g.sH, g.ld, g.Np);
             break;
@@ -1408,15 +1231,15 @@ int gccnmf_klnmf_ragged(const float* V, float* W, float* H, float* workspace, in
 // A rank's columns come as SHARDS: `batch` files of N columns each, either whole padded matrices back to back
 // ([batch][Fp][Np] / [batch][Kp][Np], ld = 0) or -- ld > 0 -- column blocks of ONE matrix with row pitch ld (file b = columns
 // [b*N, b*N+N) of V [Fp][ld], H [Kp][ld]; N a multiple of 64 unless batch == 1): the frame windows of one long mixture need no
-// gather / scatter that way.  Per shard scratch: R (same layout as V) | Upart [batch][Fp][Kp] | rowsum_part [batch][Kp].
+// gather / scatter that way.  Per shard scratch: R (same layout as V) | Upart [batch][Fp][Kp] | rowsum_part [batch][Kp] | (one file in the
+// plain layout) a reserved block, unused: GCCNMF_SPLITS x (max(Fp*Np, Fp*Kp) + Kp) floats | the direct path's Wt, Ht, Rt.
 // Shared by all shards of a rank: W, vec = colsumW [Kp] | hscale [Kp], partial = num [Fp][Kp] | den [Kp].
 struct SharedShard {
     const float* V;
     float *H, *R, *Upart, *rowsum_part;
-    float *parts, *rowsum_parts;      // one file in the plain layout: scratch of the latency path's split-K partials, else nullptr
-    bool latency;                     // ... and the current tuning sends it down that path
-    bool direct;                      // ... on the direct-to-register kernels (round 4), else the round-3 split-K launches
-    DirectBufs d;                     // transposed copies (Wt, Ht, Rt) of such a shard, behind the split-K scratch
+    bool single_file;                 // one file in the plain layout: its scratch carries the direct path's buffers
+    bool direct;                      // ... and the current tuning sends it down that path: the direct-to-register kernels (direct.hip)
+    DirectBufs d;                     // transposed copies (Wt, Ht, Rt) of such a shard, behind the reserved block
     NmfGeom g;
     int batch;
     long r_floats;
@@ -1431,24 +1254,16 @@ static bool shared_shard_ok(int F, int N, int K, int batch, int ld) {
 }
 
 // A shard that is ONE file in the plain layout (a rank's whole, short column range: at eight ranks a 160 s mixture leaves 20 s each)
-// is latency-bound exactly like one mixture alone: it takes that path's split-K launches (W.H over the atoms, R.H^T over the columns,
-// csrc/nmf.hip "One file alone") instead of 64-80 workgroup launches with 64-78-step chains.
+// is latency-bound exactly like one mixture alone: it takes that path's direct kernels instead of 64-80 workgroup launches with 64-78-step chains.
 static bool shared_single_file_layout(const NmfGeom& g, int batch, int ld) { return batch == 1 && (ld == 0 || ld == g.Np); }   // sizes the scratch
-static bool shared_latency_shard(const NmfGeom& g, int batch, int ld) {                                                        // decides per call
-#ifdef GCCNMF_EXPERIMENTS
-    return shared_single_file_layout(g, batch, ld) && single_file_split(g, 1, g.Kp, gccnmf_tune_wh_splits) &&
-           single_file_split(g, 1, g.Np, gccnmf_tune_rht_splits);
-#else
-    return false;           // the product's latency path is the direct one (sh.direct); the split-K launches are an experiment build's
-#endif
-}
-static long shared_split_floats(const NmfGeom& g) { return GCCNMF_SPLITS * ((g.sV > g.sU ? g.sV : g.sU) + (long)g.Kp) + direct_floats(g, 1); }
+static long shared_reserved_floats(const NmfGeom& g) { return GCCNMF_SPLITS * ((g.sV > g.sU ? g.sV : g.sU) + (long)g.Kp); }
+static long shared_single_file_floats(const NmfGeom& g) { return shared_reserved_floats(g) + direct_floats(g, 1); }
 
 static SharedShard make_shard(const float* V, float* H, float* ws, int F, int N, int K, int batch, int ld) {
     SharedShard sh;
     sh.g = make_geom(F, N, K);
-    sh.direct = shared_single_file_layout(sh.g, batch, ld) && direct_path(sh.g, 1, 1);
-    sh.latency = sh.direct || shared_latency_shard(sh.g, batch, ld);
+    sh.single_file = shared_single_file_layout(sh.g, batch, ld);
+    sh.direct = sh.single_file && direct_path(sh.g, 1, 1);
     if (ld > 0) {
         sh.g.ld = ld;
         sh.g.sV = sh.g.sH = N;              // the next file is the next column block
@@ -1458,12 +1273,9 @@ static SharedShard make_shard(const float* V, float* H, float* ws, int F, int N,
     sh.R = ws;
     sh.Upart = sh.R + sh.r_floats;
     sh.rowsum_part = sh.Upart + (long)batch * sh.g.sU;
-    sh.parts = sh.rowsum_parts = nullptr;
-    if (shared_single_file_layout(sh.g, batch, ld)) {
+    if (sh.single_file) {
         sh.g = make_geom(F, N, K);              // (ld == Np: the plain single-file geometry; strides are irrelevant for one file)
-        sh.parts = sh.rowsum_part + (long)batch * sh.g.Kp;
-        sh.rowsum_parts = sh.parts + GCCNMF_SPLITS * (sh.g.sV > sh.g.sU ? sh.g.sV : sh.g.sU);
-        sh.d = direct_bufs(sh.g, sh.rowsum_parts + GCCNMF_SPLITS * (long)sh.g.Kp, 1);
+        sh.d = direct_bufs(sh.g, sh.rowsum_part + (long)batch * sh.g.Kp + shared_reserved_floats(sh.g), 1);
     }
     return sh;
 }
@@ -1473,7 +1285,7 @@ static int shared_begin(const SharedShard* sh, int n, const float* W, float* col
     for (int i = 0; i < n; ++i) {    // R's padding (rows >= F, columns >= N) is a reduction operand of K2 and K4a: zero
         if (hipMemsetAsync(sh[i].R, 0, sizeof(float) * sh[i].r_floats, s) != hipSuccess) return GCCNMF_ERR_LAUNCH;
         // ... and so are the rows n >= N of Ht / Rt and the columns f >= F of Wt on the direct path
-        if (sh[i].parts && hipMemsetAsync(sh[i].d.Wt, 0, sizeof(float) * direct_floats(sh[i].g, 1), s) != hipSuccess) return GCCNMF_ERR_LAUNCH;
+        if (sh[i].single_file && hipMemsetAsync(sh[i].d.Wt, 0, sizeof(float) * direct_floats(sh[i].g, 1), s) != hipSuccess) return GCCNMF_ERR_LAUNCH;
     }
     hipLaunchKernelGGL(nmf_prepare_kernel, dim3(g.Kp / 16), dim3(256), 0, s, W, colsumW, hscale, g.F, g.Fp, g.Kp);
     GCCNMF_CHECK_LAUNCH();
@@ -1534,14 +1346,6 @@ static int shared_gemms(const SharedShard& sh, const float* W, const float* cols
         if ((rc = direct_wh_div(g, sh.d, sh.V, W, sh.H, nullptr, sh.R, true, 1, s))) return rc;
         return direct_rht(g, sh.d, sh.R, sh.Upart, sh.rowsum_part, 1, s);
     }
-#ifdef GCCNMF_EXPERIMENTS
-    if (sh.latency) {                           // one file alone: the split-K launches of the round-3 latency path
-        if ((rc = launch_wh_div_split(g, sh.V, W, sh.H, hscale, sh.parts, sh.R, s))) return rc;
-        if ((rc = launch_update_h(update_h_args(g, W, 0, sh.R, sh.H, hscale, 0, colsumW, 0, alpha, eps, 1, 0, 0), s))) return rc;
-        if ((rc = launch_wh_div_split(g, sh.V, W, sh.H, nullptr, sh.parts, sh.R, s))) return rc;
-        return launch_rht_split(g, sh.R, sh.H, sh.parts, sh.rowsum_parts, s);
-    }
-#endif
     // files are independent inside K1-K3 and per file inside K4a: keep every tile of a file on one XCD (its H / R panels are shared
     // through that XCD's L2), exactly as the per-file-dictionary path does
     if ((rc = launch_wh_div(g, wh_div_args(g, sh.V, W, 0, sh.H, hscale, 0, sh.R, sh.batch, xa, conc), s))) return rc;
@@ -1554,14 +1358,9 @@ static int shared_gemms(const SharedShard& sh, const float* W, const float* cols
 // partial (+)= [sum_files Upart || sum_files rowsum_part], files in ascending order (deterministic)
 static int shared_reduce(const SharedShard& sh, float* partial, int accumulate, hipStream_t s) {
     const NmfGeom& g = sh.g;
-    // (one file alone: the "files" are the parts of its split R.H^T reduction, added in ascending order)
-    const bool split = sh.latency && !sh.direct;
-    const float* U = split ? sh.parts : sh.Upart;
-    const float* rowsum = split ? sh.rowsum_parts : sh.rowsum_part;
-    const int n = split ? gccnmf_tune_rht_splits : sh.batch;
-    hipLaunchKernelGGL(nmf_reduce_files_kernel, dim3((unsigned)((g.sU + 255) / 256)), dim3(256), 0, s, U, g.sU, n, g.sU, partial, accumulate);
+    hipLaunchKernelGGL(nmf_reduce_files_kernel, dim3((unsigned)((g.sU + 255) / 256)), dim3(256), 0, s, sh.Upart, g.sU, sh.batch, g.sU, partial, accumulate);
     GCCNMF_CHECK_LAUNCH();
-    hipLaunchKernelGGL(nmf_reduce_files_kernel, dim3(gccnmf_ceil_div(g.Kp, 256)), dim3(256), 0, s, rowsum, (long)g.Kp, n, (long)g.Kp,
+    hipLaunchKernelGGL(nmf_reduce_files_kernel, dim3(gccnmf_ceil_div(g.Kp, 256)), dim3(256), 0, s, sh.rowsum_part, (long)g.Kp, sh.batch, (long)g.Kp,
                        partial + g.sU, accumulate);
     GCCNMF_CHECK_LAUNCH();
     return GCCNMF_OK;
@@ -1608,7 +1407,7 @@ static int shared_step_a_all(const SharedShard* sh, int n, const float* W, const
 
 static int shared_step_b(float* W, const float* partial, float* colsumW, float* hscale, int F, int K, hipStream_t s) {
     NmfGeom g = make_geom(F, 1, K);
-    return launch_update_w(update_w_args(g, W, 0, partial, 0, partial + g.sU, colsumW, hscale, 0), 1, 1, s, 1, 0, 0, nullptr, 0, 0);
+    return launch_update_w(update_w_args(g, W, 0, partial, 0, partial + g.sU, colsumW, hscale, 0), 1, 1, s, nullptr, 0, 0);
 }
 
 static int shared_finish(const SharedShard* sh, int n, float* hscale, int K, hipStream_t s) {
@@ -1625,21 +1424,21 @@ static int shared_finish(const SharedShard* sh, int n, float* hscale, int K, hip
 
 // the four-call protocol's workspace: one default-layout shard's scratch | colsumW [Kp] | hscale [Kp]
 static float* legacy_vec(const SharedShard& sh) {
-    return sh.parts ? sh.rowsum_parts + GCCNMF_SPLITS * (long)sh.g.Kp + direct_floats(sh.g, 1) : sh.rowsum_part + (long)sh.batch * sh.g.Kp;
+    return sh.single_file ? sh.d.Wt + direct_floats(sh.g, 1) : sh.rowsum_part + (long)sh.batch * sh.g.Kp;
 }
 
 long gccnmf_klnmf_shared_workspace_floats(int F, int N, int K, int batch) {
     GCCNMF_ENTER();
     if (!shared_shard_ok(F, N, K, batch, 0)) return -1;
     NmfGeom g = make_geom(F, N, K);
-    return (long)batch * (g.sV + g.sU + g.Kp) + (shared_single_file_layout(g, batch, 0) ? shared_split_floats(g) : 0) + 2L * g.Kp;
+    return (long)batch * (g.sV + g.sU + g.Kp) + (shared_single_file_layout(g, batch, 0) ? shared_single_file_floats(g) : 0) + 2L * g.Kp;
 }
 
 long gccnmf_klnmf_shared_shard_workspace_floats(int F, int N, int K, int batch, int ld) {
     GCCNMF_ENTER();
     if (!shared_shard_ok(F, N, K, batch, ld)) return -1;
     NmfGeom g = make_geom(F, N, K);
-    return shared_r_floats(g, batch, ld) + (long)batch * (g.sU + g.Kp) + (shared_single_file_layout(g, batch, ld) ? shared_split_floats(g) : 0);
+    return shared_r_floats(g, batch, ld) + (long)batch * (g.sU + g.Kp) + (shared_single_file_layout(g, batch, ld) ? shared_single_file_floats(g) : 0);
 }
 
 long gccnmf_klnmf_shared_partial_floats(int F, int K) {
@@ -1786,11 +1585,7 @@ int gccnmf_debug_gemm(const float* A, const float* B, float* C, int M, int N, in
     a.rowsumB = rowsumB; a.s_rowsumB = N;
     a.C = C; a.sC = sC; a.ldc = ldc;
     hipStream_t s = (hipStream_t)stream;
-#ifdef GCCNMF_EXPERIMENTS
-    if (layout & 32) return (layout & 31) ? GCCNMF_ERR_ARG : gccnmf_launch_gemm_stream(a, s);      // the LDS-free throughput tile (direct.hip)
-#else
-    if (layout & 32) return GCCNMF_ERR_UNSUPPORTED;
-#endif
+    if (layout & 32) return GCCNMF_ERR_UNSUPPORTED;      // (once a kernel that is gone)
     const bool wide = layout & 8;
     if (!wide && gccnmf_tune_dma) {       // the throughput tile's default staging path (tuning key 3)
         switch (layout & 3) {

@@ -5,12 +5,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-template <int AT, int NSPLIT>
+template <int AT>
 __device__ __forceinline__ void nmf_update_w_onepass_item(float* __restrict__ W, const float* __restrict__ U, const float* __restrict__ rowsumH,
                                                           float* __restrict__ colsumW, float* __restrict__ hscale, int F, int K, int Kp, long sW,
-                                                          long sU, long sVec, long sRowsum, long sSplitU, long sSplitR, float* __restrict__ Wt,
-                                                          long sWt, int ldwt, const int b, const int ch, float* const smem, const int tid) {
-    constexpr int nsplit = NSPLIT;
+                                                          long sU, long sVec, long sRowsum, float* __restrict__ Wt, long sWt, int ldwt, const int b, const int ch, float* const smem, const int tid) {
     constexpr int L4 = AT / 4;                 // float4 lanes per row segment
     constexpr int PH = 256 / L4;               // row phases per workgroup (PH / 4 per wave)
     constexpr int R = (64 * 9 + PH - 1) / PH;  // rows per thread for F <= 576
@@ -21,12 +19,7 @@ __device__ __forceinline__ void nmf_update_w_onepass_item(float* __restrict__ W,
     const bool v0 = k0 < K, v1 = k0 + 1 < K, v2 = k0 + 2 < K, v3 = k0 + 3 < K;      // padded atoms stay exactly zero
     float* Wb = W + b * sW;
     const float* Ub = U + b * sU;
-    float4 rs = *(const float4*)(rowsumH + b * sRowsum + k0);
-#pragma unroll
-    for (int sp = 1; sp < nsplit; ++sp) {
-        const float4 t = *(const float4*)(rowsumH + b * sRowsum + sp * sSplitR + k0);
-        rs.x += t.x; rs.y += t.y; rs.z += t.z; rs.w += t.w;
-    }
+    const float4 rs = *(const float4*)(rowsumH + b * sRowsum + k0);
     // every load of the thread is issued before the first use: rows beyond F re-read row F-1 (clamped, always in bounds) and are
     // masked afterwards -- conditional loads would serialise into R dependent round trips
     float4 wt[R], uu[R];
@@ -36,17 +29,6 @@ __device__ __forceinline__ void nmf_update_w_onepass_item(float* __restrict__ W,
         wt[r] = *(const float4*)(Wb + i);
         uu[r] = *(const float4*)(Ub + i);
     }
-    float4 tt[NSPLIT > 1 ? NSPLIT - 1 : 1][R];          // the partials of a split-K launch: all in flight together, added in ascending order
-#pragma unroll
-    for (int sp = 1; sp < nsplit; ++sp)
-#pragma unroll
-        for (int r = 0; r < R; ++r) tt[sp - 1][r] = *(const float4*)(Ub + sp * sSplitU + (long)min(q + PH * r, F - 1) * Kp + k0);
-#pragma unroll
-    for (int sp = 1; sp < nsplit; ++sp)
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            uu[r].x += tt[sp - 1][r].x; uu[r].y += tt[sp - 1][r].y; uu[r].z += tt[sp - 1][r].z; uu[r].w += tt[sp - 1][r].w;
-        }
     float4 ss = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int r = 0; r < R; ++r) {

@@ -394,7 +394,7 @@ class HipSharedColumns(_SharedRun):
         if block is None:
             if self.ld <= 4096:
                 # a short column range (at eight ranks a 160 s mixture leaves 20 s = 2494 columns each) is latency-bound like one
-                # mixture alone: ONE block, which the library sends down that path's split-K launches (csrc/nmf.hip)
+                # mixture alone: ONE block, which the library sends down that path's direct kernels (csrc/direct.hip)
                 block = self.ld
             else:
                 # R.H^T has Kp/64 workgroups per block: aim at >= 512 (two per CU), blocks of at least 256 columns (16 k-tiles)

@@ -127,10 +127,10 @@ int gccnmf_version(void);
  *  23  lists of a chained launch: 1 (default) = whole files per XCD where they balance, else the tile list in equal eighths with agent-scope hand-over;
  *      0 = the plain launch's lists (batch a multiple of 8); 2 = always spread; 3 = always whole files
  *  24  iterations per chained launch (default 2048; a call of more iterations is several chained launches)
- *   X  1 ablations of the register-staged kernel (results INVALID), 4 ring kernel off, 5 / 6 parts of the round-3 single-file split-K, 11 / 13
- *      fixed tile / pipeline depth of the direct kernels, 14 short H updates off the ring kernel, 15 one FFT stage per LDS round trip, 18 / 19
- *      resident-workgroup grid and its prefetch, 20 the 16-atom W update, 22 chained launches with one workgroup per CU, 25 fault injection into
- *      the chained launches' hand-over (consumers give up at once)
+ *   X  the two test hooks of the lab build: 22 chained launches with one workgroup per CU, 25 fault injection into the chained launches'
+ *      hand-over (consumers give up at once)
+ *   -  0, 1, 4, 5, 6, 11, 13, 14, 15, 18, 19, 20 are unused: they selected measured-and-rejected kernel paths that are gone (LABBOOK.md);
+ *      every build answers GCCNMF_ERR_ARG.  The numbers of the other keys are stable.
  * gccnmf_klnmf_plan reports what a call would launch.  Unknown keys / values: GCCNMF_ERR_ARG. */
 int gccnmf_set_tuning(int key, int value);
 
@@ -183,14 +183,14 @@ int gccnmf_pack_pcm16(const float* y, int groups, int L, unsigned int* peak_scra
  * W, H (:70-73) are drawn on the host and passed in.  W and H are updated in place.
  *   V [batch][Fp][Np], W [batch][Fp][Kp], H [batch][Kp][Np] with Np = round_up(N,64); N = 2T on the
  *   GCC-NMF path but any N >= 1 is accepted (performKLNMF is also called on arbitrary V).
- *   workspace: gccnmf_klnmf_workspace_floats(...) floats of scratch (R, R.H^T, K-vectors; for batch == 1 also the partial
- *   products of the split-K latency path, and at its end the counters and status words of the chained launches).  Always size it with the
+ *   workspace: gccnmf_klnmf_workspace_floats(...) floats of scratch (R, R.H^T, K-vectors; for batch == 1 also a reserved,
+ *   unused block, for up to 8 files the transposed copies of the direct path, and at its end the counters and status words of the chained launches).  Always size it with the
  *   batch of the call it is used with.  The size is a multiple of 4 floats for every valid argument tuple (so is every other
  *   *_workspace_floats of this header), and `workspace` must be 16-byte aligned, else GCCNMF_ERR_ARG before anything is launched -- here, in
  *   gccnmf_klnmf_ragged and in gccnmf_klnmf_stage: its blocks are read with 16-byte vector loads and LDS-DMA.  Workspaces carved back to back
  *   out of one aligned allocation, each of the size this function returns, therefore all qualify.
- *   batch >= 2: a file's result is bit-identical whatever batch it rides in (for equal launch-size decisions); batch == 1
- *   cuts the two long reductions in four parts added in a fixed order (deterministic, summation-order accuracy). */
+ *   batch >= 2: a file's result is bit-identical whatever batch it rides in (for equal launch-size decisions); a file alone
+ *   or among a few takes the direct kernels (csrc/direct.hip), which sum in another fixed order (deterministic, summation-order accuracy). */
 long gccnmf_klnmf_workspace_floats(int F, int N, int K, int batch);
 int gccnmf_klnmf(const float* V, float* W, float* H, float* workspace, int F, int N, int K, int batch,
                  int iterations, float sparsity_alpha, float epsilon, int flags, void* stream);

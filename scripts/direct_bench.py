@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Latency path (one mixture alone): per-stage kernel times of one KL-NMF iteration for the direct kernels (csrc/direct.hip) against
-the round-3 split-K path, per GEMM tile, and the 100-iteration wall time.  usage (GPU box): python scripts/direct_bench.py [K hop [batch]]"""
+the ring kernel (tuning key 10 = 0), and the 100-iteration wall time.  usage (GPU box): python scripts/direct_bench.py [K hop [batch]]"""
 import json
 import os
 import sys
@@ -25,7 +25,6 @@ e = GCCNMFEngine(160000, dictionarySize=K, numIterations=100, batch=B, hopSize=h
 e.upload(xs if B > 1 else xs[0])
 e.stft()
 g = e.g
-TILES = ['auto', '1x1', '1x2', '1x5', '2x2', '2x4', '2x5', '4x4', '4x5']
 
 
 def stage(s):
@@ -82,8 +81,7 @@ def time_klnmf(reps=3):
 out = {'K': K, 'hop': hop, 'batch': B, 'F': g.F, 'N': g.N}
 for direct in (0, 1):
     lib.gccnmf_set_tuning(10, direct)
-    lib.gccnmf_set_tuning(11, 0)
-    name = 'direct' if direct else 'split-K (round 3)'
+    name = 'direct' if direct else 'ring'
     st = {('K1', 'K2', 'K3', 'K4a', 'K4b')[s - 1]: round(time_stage(s), 2) for s in range(1, 6)}
     it = time_iteration()
     ms = time_klnmf()
@@ -91,27 +89,10 @@ for direct in (0, 1):
     out[name] = {'stage_us_back_to_back': st, 'iteration_us': round(it, 2), 'klnmf_100_ms': round(ms, 3)}
     print('%-20s stages (us, same launch repeated) %s | iteration %.1f us | 100 iterations %.3f ms' % (name, st, it, ms), flush=True)
     if direct:
-        print('   W rel diff direct vs split-K after 100 iterations: %.2e' % float(((wf - w_old).norm() / w_old.norm()).item()))
+        print('   W rel diff direct vs ring after 100 iterations: %.2e' % float(((wf - w_old).norm() / w_old.norm()).item()))
     else:
         w_old = wf
-# every tile on every GEMM stage of the direct path
 lib.gccnmf_set_tuning(10, 1)
-sweep = {}
-for t in range(1, 9):
-    lib.gccnmf_set_tuning(11, t)
-    sweep[TILES[t]] = {('K1', 'K2', 'K3', 'K4a')[s - 1]: round(time_stage(s, 20), 2) for s in range(1, 5)}
-    print('tile %-4s %s' % (TILES[t], sweep[TILES[t]]), flush=True)
-lib.gccnmf_set_tuning(11, 0)
-out['tile_sweep_us'] = sweep
-# register sets of the operand pipeline (tuning key 13), tile by the cost model
-depth = {}
-for dpt in (2, 3, 4):
-    lib.gccnmf_set_tuning(13, dpt)
-    depth[dpt] = {('K1', 'K2', 'K3', 'K4a')[s - 1]: round(time_stage(s, 20), 2) for s in range(1, 5)}
-    depth[dpt]['iteration'] = round(time_iteration(), 2)
-    print('pipeline depth %d: %s' % (dpt, depth[dpt]), flush=True)
-lib.gccnmf_set_tuning(13, 0)
-out['depth_sweep_us'] = depth
 # the whole mixture through the engine
 e.run()
 torch.cuda.synchronize()

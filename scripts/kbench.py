@@ -22,14 +22,12 @@ def main():
     ap.add_argument('--T', type=int, default=622)
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--flags', type=int, default=0)
-    ap.add_argument('--ablate', type=int, default=0)
     ap.add_argument('--dma', type=int, default=1)
     a = ap.parse_args()
     import torch
     from gcc_nmf_amd import _hip
     from gcc_nmf_amd.engine import Geometry, _ptr, _stream
     lib = _hip.lib()
-    lib.gccnmf_set_tuning(1, a.ablate)
     lib.gccnmf_set_tuning(3, a.dma)
     F, T, K, B = 513, a.T, a.K, a.files
     g = Geometry(F, T, K)
@@ -62,7 +60,6 @@ def main():
         'K4b W update+normalise': lambda: stage(5),
         'K1 shape, store only (A_KC, tail)': lambda: dbg(W, H, R, F, N, K, g.Kp, g.Np, g.Np, g.Fp - 1, g.Np - 4, 1 | 4, g.Fp * g.Kp, g.Kp * g.Np, g.Fp * g.Np),
         'K2 shape, store only (W^T.R)': lambda: dbg(W, R, G2, K, N, F, g.Kp, g.Np, g.Np, g.Kp - 4, g.Np - 4, 0, g.Fp * g.Kp, g.Fp * g.Np, g.Kp * g.Np),
-        'K2 shape, store only, LDS-free stream tile (direct.hip)': lambda: dbg(W, R, G2, K, N, F - 1, g.Kp, g.Np, g.Np, g.Kp - 4, g.Np - 4, 32, g.Fp * g.Kp, g.Fp * g.Np, g.Kp * g.Np),
         'K2 shape, Kd=512, store only (dma tile)': lambda: dbg(W, R, G2, K, N, F - 1, g.Kp, g.Np, g.Np, g.Kp - 4, g.Np - 4, 0, g.Fp * g.Kp, g.Fp * g.Np, g.Kp * g.Np),
         'K4a shape, store only (KC,KC, tail)': lambda: dbg(R, H, U, F, K, N, g.Np, g.Np, g.Kp, g.Fp - 1, g.Kp - 1, 3 | 4, g.Fp * g.Np, g.Kp * g.Np, g.Fp * g.Kp),
         'K1 shape, store only, ONE H for all files (B L2-resident)': lambda: dbg(W, H, R, F, N, K, g.Kp, g.Np, g.Np, g.Fp - 1, g.Np - 4, 1 | 4, g.Fp * g.Kp, 0, g.Fp * g.Np),
@@ -72,8 +69,6 @@ def main():
         'K1 shape, no tail row (M=512)': lambda: dbg(W, H, G2, 512, N, K, g.Kp, g.Np, g.Np, g.Fp - 1, g.Np - 4, 1, g.Fp * g.Kp, g.Kp * g.Np, max(g.Kp, g.Fp) * g.Np),
         'K4a shape -> R buffer': lambda: dbg(V, H, R, F, K, N, g.Np, g.Np, g.Np, g.Fp - 1, g.Kp - 1, 3 | 4, g.Fp * g.Np, g.Kp * g.Np, g.Fp * g.Np),
     }
-    if not hasattr(lib, 'gccnmf_debug_mfma_peak'):          # the product library: no LDS-free stream tile (debug_gemm layout bit 32 is an experiment build's)
-        cases = {k: v for k, v in cases.items() if 'stream tile' not in k}
     # pure-MFMA probe: 512 blocks x 4 waves x 8 x 4096 MFMAs
     scratch = torch.zeros(16, device=dev)
     for blocks in ((256, 512, 1024) if hasattr(lib, 'gccnmf_debug_mfma_peak') else ()):      # the probe lives in the experiment build

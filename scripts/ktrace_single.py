@@ -14,7 +14,6 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--K', type=int, default=1024)
     ap.add_argument('--stages', default='1,2,3,4')
-    ap.add_argument('--ablate', type=int, default=0)
     a = ap.parse_args()
     import torch
     from gcc_nmf_amd import _hip
@@ -47,7 +46,6 @@ def main():
             stage(s)
     torch.cuda.synchronize()
     nblk = 4096
-    lib.gccnmf_set_tuning(1, a.ablate)
     for st in [int(x) for x in a.stages.split(',')]:
         trace = torch.zeros((nblk, 8), dtype=torch.int64, device=dev)
         for s in (1, 2, 3, 4, 5):          # a warm iteration, then the traced stage in sequence

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""One mixture alone (BASELINE config 2's shape: 10 s, K = 1024, 100 iterations): wall time per file for the tuning variants of the
-latency path.  usage (GPU box): python scripts/single_file.py [--profile]"""
+"""One mixture alone (BASELINE config 2's shape: 10 s, K = 1024, 100 iterations): wall time per file on the direct latency path and on the
+ring kernel (tuning key 10).  usage (GPU box): python scripts/single_file.py [--profile]"""
 import os
 import sys
 import time
@@ -41,22 +41,15 @@ def run(label, reps=3):
     return e.y.clone()
 
 
-for kv in filter(None, os.environ.get('TUNE', '').split(',')):       # e.g. TUNE=5=2,6=4
+for kv in filter(None, os.environ.get('TUNE', '').split(',')):       # e.g. TUNE=12=1,2=0
     key, val = [int(v) for v in kv.split('=')]
     assert lib.gccnmf_set_tuning(key, val) == 0, kv
 if '--profile' in sys.argv:
     run('default', 2)
     sys.exit(0)
 lib.gccnmf_set_tuning(10, 1)
-y_new = run('direct path (round 4)')
+y_new = run('direct path')
 lib.gccnmf_set_tuning(10, 0)
-lib.gccnmf_set_tuning(4, 0)
-y_old = run('register-staged (round 1)')
-print('    waveform rms direct vs register-staged: %.2e' % float(((y_new - y_old) ** 2).mean().sqrt()))
-lib.gccnmf_set_tuning(4, 1)
-for wh in (2, 3, 4):
-    for rht in (4,):
-        lib.gccnmf_set_tuning(5, wh)
-        lib.gccnmf_set_tuning(6, rht)
-        y = run('ring, W.H splits %d, R.H^T splits %d' % (wh, rht))
-        print('    waveform rms vs register-staged: %.2e' % float(((y - y_old) ** 2).mean().sqrt()))
+y_old = run('ring kernel')
+lib.gccnmf_set_tuning(10, 1)
+print('    waveform rms direct vs ring: %.2e' % float(((y_new - y_old) ** 2).mean().sqrt()))

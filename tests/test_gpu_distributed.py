@@ -137,7 +137,7 @@ def test_file_groups_of_different_widths_as_one_training():
 
 
 def test_short_column_range_takes_the_latency_path():
-    """A rank's whole, short column range (one 'file' in the plain layout, K and N >= 512) runs the split-K launches of the
+    """A rank's whole, short column range (one 'file' in the plain layout, K and N >= 512) runs the direct kernels of the
     one-mixture-alone path inside gccnmf_klnmf_shared_run: == performKLNMF, == the column-block form to summation order, and
     repeatable bit for bit."""
     from gcc_nmf_amd.distributed import HipSharedColumns

@@ -11,7 +11,7 @@ Frame counts.  The T edges come from compile-time constants (mirrored in fft_che
 they change): the forward transform and the two-kernel inverse run FFT_TB = 8 frames per workgroup (T = 1, 7, 8, 9, 17: less than one,
 one short of, exactly, one more than one, and two workgroups plus one), 4 at n_fft = 4096 (T = 1, 3, 4, 5); the fused inverse owns
 ISTFT_TB x ISTFT_SUB = 4 x 8 = 32 hops per workgroup, takes frames 4 at a time and starts ceil(n_fft / hop) - 1 frames early (T = 1, 3, 4, 5,
-31, 32, 33, 65).  The product build runs the register-pass FFT; nothing here touches tuning key 15.
+31, 32, 33, 65).  Every build runs the register-pass FFT (fft_core.h).
 """
 import numpy as np
 import pytest

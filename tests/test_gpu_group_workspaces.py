@@ -104,7 +104,7 @@ def test_klnmf_on_the_second_carve_is_bitwise_the_first_and_within_the_oracle_ba
     """gccnmf_klnmf for `per` files on ws[0:] and on ws[ws_per:] of one allocation, same V, W0, H0: W and H bit for bit equal, the first and
     the last file within 1e-4 of the float64 oracle, no word outside the carve in use written, the status words clean.  Every shape has
     `per` odd and ceil(N / 64) even (the 8-byte carve of the old size formula), and gccnmf_klnmf_plan shows the form the case is named for:
-    the direct latency kernels (one file: its workspace also holds the split-K partials; three files), the fused short-dictionary launches
+    the direct latency kernels (one file: its workspace also holds the reserved block of a single file; three files), the fused short-dictionary launches
     (forced: keys 16 / 17), four launches with R materialised on the throughput tile, the small-batch tile, and a geometry without the
     bin-tail (F = 200).
     The throughput (LDS-DMA) tile by rule: at N = 244 neither 9 files at K = 256 nor 17 at K = 1024 reach it -- K1 and K3 take it from

@@ -54,7 +54,6 @@ GEMM_CASES = [
     (3, 200, 64, 150, 1), (3 | 4, 513, 128, 300, 2), (3 | 4, 513, 200, 1244, 8), (3 | 8, 100, 256, 75, 1),
     (3 | 4 | 8, 129, 300, 50, 2),
     (16, 1024, 200, 513, 2), (16 | 8, 128, 300, 33, 9), (16, 300, 100, 17, 1),      # rank-1 reduction tail in the epilogue
-    (32, 1024, 1244, 512, 9), (32, 700, 130, 75, 2), (32, 100, 64, 16, 1),          # the LDS-free throughput tile (direct.hip, experiment)
 ]
 
 
@@ -92,15 +91,13 @@ def test_debug_gemm(hip, layout, M, N, Kd, batch):
     dC = torch.full((batch, M, ldc), -7.0, dtype=torch.float32, device='cuda')
     bscale = None
     dscale = None
-    if not b_kc and not (layout & 16) and not (layout & 32):
+    if not b_kc and not (layout & 16):
         bscale = (rng.rand(Kd16) + 0.5).astype(np.float32)
         dscale = dev(bscale)
     drow = torch.zeros((batch, N), dtype=torch.float32, device='cuda') if b_kc else None
     rc = lib.gccnmf_debug_gemm(dA.data_ptr(), dB.data_ptr(), dC.data_ptr(), M, N, Kd, lda, ldb, ldc, a_clamp, b_clamp, layout,
                                batch, Ad[0].size, Bd[0].size, M * ldc, 0 if dscale is None else dscale.data_ptr(),
                                0 if drow is None else drow.data_ptr(), stream())
-    if (layout & 32) and rc == 3:
-        pytest.skip('the LDS-free stream tile (layout bit 32) exists in experiment builds only: make EXPERIMENTS=1')
     assert rc == 0
     torch.cuda.synchronize()
     C = dC.cpu().numpy()
@@ -233,42 +230,6 @@ def test_stft_stereo(hip, n_fft, hop, n):
     assert np.abs(X - ref).max() < 1e-5 * np.abs(ref).max()
 
 
-@pytest.mark.parametrize('n_fft,hop,n', [(64, 16, 2000), (128, 32, 3000), (256, 100, 3000), (512, 128, 9000), (1024, 256, 40000), (2048, 512, 30000),
-                                         (4096, 1024, 40000)])
-def test_register_pass_fft_is_bitwise_the_stage_per_round_trip_fft(hip, n_fft, hop, n):
-    """Round 4 runs up to four radix-2 stages per LDS round trip (fft_core.h: fft_pass); every butterfly computes the same expression on
-    the same operands, so the STFT (X, V, coherence) and both inverse forms give the SAME BITS as the one-stage-per-round-trip routine
-    (tuning key 15 = 0), at every supported size."""
-    from gcc_nmf_amd.engine import GCCNMFEngine
-    from gcc_nmf_amd.synthetic import synthetic_batch
-    lib = hip.lib()
-    xs = synthetic_batch(3, 2, numSamples=n)
-    outs = []
-    for r16 in (0, 1):
-        if lib.gccnmf_set_tuning(15, r16) != 0:
-            pytest.skip('key 15 (one FFT stage per LDS round trip) exists in experiment builds only: make EXPERIMENTS=1')
-        e = GCCNMFEngine(n, windowSize=n_fft, hopSize=hop, dictionarySize=16, numIterations=2, batch=2, numTargets=2)
-        e.upload(xs)
-        e.stft()
-        X, V, C = e.X.clone(), e.V.clone(), e.CC.clone()
-        # the inverse transform of the mixture spectrogram itself (spec = X for both 'targets'), fused and two-kernel forms
-        e.spec.copy_(torch.stack([e.X[:, 0], e.X[:, 1], e.X[:, 1], e.X[:, 0]], dim=1))
-        ys = []
-        for fused in ([True, False] if e.fused_istft or n_fft + 3 * hop <= 2048 else [False]):
-            e.fused_istft = fused
-            e.istft()
-            ys.append(e.y.clone())
-        outs.append((X, V, C, ys))
-    lib.gccnmf_set_tuning(15, 1)
-    for a, b in zip(outs[0][:3], outs[1][:3]):
-        assert torch.equal(a, b)
-    assert len(outs[0][3]) == len(outs[1][3])
-    for a, b in zip(outs[0][3], outs[1][3]):
-        assert torch.isfinite(a).all() and torch.equal(a, b)
-    if len(outs[1][3]) == 2:
-        assert torch.equal(outs[1][3][0], outs[1][3][1])          # fused == two-kernel form, as before
-
-
 def test_istft_n_fft_4096(hip):
     from gcc_nmf_amd.librosaSTFT import stft, istft
     rng = np.random.RandomState(7)
@@ -389,7 +350,7 @@ def tile_policy(hip, request):
 
 @pytest.mark.parametrize('F,N,K,iters,alpha', [(513, 90, 128, 12, 0), (513, 201, 192, 6, 0.3), (257, 77, 40, 10, 0), (200, 333, 300, 5, 0),
                                                (129, 64, 64, 8, 0), (1025, 50, 64, 4, 0),
-                                               (513, 900, 640, 5, 0)])      # one file: unequal split-K parts (40 k-tiles in 3, 57 in 4)
+                                               (513, 900, 640, 5, 0)])      # one file, a long reduction on both sides (40 and 57 k-tiles)
 def test_klnmf_vs_oracle(hip, F, N, K, iters, alpha, tile_policy):
     from gcc_nmf_amd.gccNMFFunctions import performKLNMF
     rng = np.random.RandomState(F + N + K)
@@ -424,13 +385,10 @@ def test_klnmf_one_big_matrix_takes_the_column_block_path(hip, N, K, iters):
     assert np.allclose(np.linalg.norm(W, axis=0), 1.0, atol=1e-5)
 
 
-def test_klnmf_direct_path_against_the_split_k_path_and_small_batches(hip):
-    """The direct-to-register latency path (csrc/direct.hip) against what key 10 = 0 runs for one mixture -- the round-3 split-K launches
-    in the lab build (key 5 exists there), the LDS-DMA ring kernel in the product library, where the split-K path is compiled out -- and for
+def test_klnmf_direct_path_against_the_ring_kernel_and_small_batches(hip):
+    """The direct-to-register latency path (csrc/direct.hip) against what key 10 = 0 runs for one mixture -- the LDS-DMA ring kernel -- and for
     a handful of files (tuning key 12 lets small batches take the direct path): the same factors to round-off (different summation grouping)."""
     lib = hip.lib()
-    lab = lib.gccnmf_set_tuning(5, 3) == 0              # key 5 (parts of the single-file split-K W.H) is an experiment-build key
-    other = 'split' if lab else 'ring'
     F, T, K, B = 513, 311, 256, 3
     g = hip_geometry(F, T, K)
     rng = np.random.RandomState(3)
@@ -438,7 +396,7 @@ def test_klnmf_direct_path_against_the_split_k_path_and_small_batches(hip):
     from gcc_nmf_amd.engine import klnmf_initial_factors, padded
     W0, H0 = klnmf_initial_factors(F, 2 * T, K)
     res = {}
-    for name, direct, maxb, batch in [(other, 0, 1, 1), ('direct', 1, 1, 1), ('direct-batch', 1, 4, B), ('ring-batch', 0, 1, B)]:
+    for name, direct, maxb, batch in [('ring', 0, 1, 1), ('direct', 1, 1, 1), ('direct-batch', 1, 4, B), ('ring-batch', 0, 1, B)]:
         assert lib.gccnmf_set_tuning(10, direct) == 0 and lib.gccnmf_set_tuning(12, maxb) == 0
         Vd = padded(V[:batch], (batch, g.Fp, g.Np), 'cuda')
         Wd = padded(np.repeat(W0[None], batch, 0), (batch, g.Fp, g.Kp), 'cuda')
@@ -451,12 +409,12 @@ def test_klnmf_direct_path_against_the_split_k_path_and_small_batches(hip):
     lib.gccnmf_set_tuning(12, 4)
     for b in range(B):
         Wr, Hr = O.performKLNMF(V[b], K, 7, 0)
-        for name in ('direct-batch', 'ring-batch') + ((other, 'direct') if b == 0 else ()):
+        for name in ('direct-batch', 'ring-batch') + (('ring', 'direct') if b == 0 else ()):
             W, H = res[name]
             assert rel(W[b, :F, :K], Wr) < 1e-4 and rel(H[b, :K, :2 * T], Hr) < 1e-4, (name, b)
             # the padding stays exactly zero (it is a reduction operand)
             assert not W[b, F:].any() and not W[b, :, K:].any() and not H[b, K:].any() and not H[b, :, 2 * T:].any(), (name, b)
-    assert rel(res['direct'][0], res[other][0]) < 2e-5
+    assert rel(res['direct'][0], res['ring'][0]) < 2e-5
 
 
 @pytest.mark.parametrize('F,T,K,B,alpha', [(513, 75, 128, 6, 0.0), (513, 40, 200, 9, 0.2), (257, 33, 100, 5, 0.0), (385, 20, 64, 12, 0.0),
@@ -580,12 +538,11 @@ def test_klnmf_batch_is_file_independent(hip):
 
 
 @pytest.mark.parametrize('F,T,K,B,flags', [(513, 622, 64, 26, 0), (513, 330, 512, 50, 0), (513, 200, 1024, 70, 2), (513, 622, 96, 64, 0), (513, 330, 256, 40, 0)])
-def test_narrow_items_and_resident_workgroups_are_bitwise(hip, F, T, K, B, flags):
+def test_throughput_tile_launch_forms_are_bitwise(hip, F, T, K, B, flags):
     """The throughput-tile launch in every form it can take (csrc/gemm_dma.h): full 512 x 64 tiles only (key 9 = 0: the reference form) |
     the launcher's own choice -- half-height tiles for the files of a partial last round and for outputs of at most 256 rows, a narrow
-    item for a file's ragged last column tile (key 9 = 1) | every tile as two narrow halves (key 9 = 2) | in an experiment build, 512
-    resident workgroups pulling items by ticket (key 18), with and without the next item's first k-tile requested under the epilogue (19).
-    Every output element sees the same k order in each of them: W and H are bit for bit those of the reference form.
+    item for a file's ragged last column tile (key 9 = 1) | every tile as two narrow halves (key 9 = 2) | half-height tiles everywhere
+    (key 9 = 3).  Every output element sees the same k order in each of them: W and H are bit for bit those of the reference form.
     (K1/K3 at 26 x 20 = 520 items; the H update at K = 512, 50 x 11 = 550; the unfused R.H^T at K = 1024, 70 x 16 = 1120; 64 files.)"""
     lib = hip.lib()
     from gcc_nmf_amd.engine import Geometry, padded, klnmf_initial_factors
@@ -596,25 +553,20 @@ def test_narrow_items_and_resident_workgroups_are_bitwise(hip, F, T, K, B, flags
     W0, H0 = klnmf_initial_factors(F, N, K)
     dV = padded(V, (B, g.Fp, g.Np), 'cuda')
     outs = []
-    forms = [(0, 0, 0), (1, 0, 0), (2, 0, 0), (3, 0, 0)]          # (3: half-height tiles everywhere)
-    experiments = lib.gccnmf_set_tuning(18, 0) == 0    # an experiment build (make EXPERIMENTS=1) also carries the resident-workgroup grid
-    if experiments:
-        forms += [(0, 1, 0), (1, 1, 1), (2, 1, 1), (1, 1, 0)]
+    forms = [0, 1, 2, 3]          # key 9
     try:
-        for narrow, resident, prefetch in forms:
+        for narrow in forms:
             assert lib.gccnmf_set_tuning(9, narrow) == 0
-            if experiments:
-                assert lib.gccnmf_set_tuning(18, resident) == 0 and lib.gccnmf_set_tuning(19, prefetch) == 0
             assert lib.gccnmf_set_tuning(16, 0) == 0 and lib.gccnmf_set_tuning(17, 0) == 0          # K <= 128: the four-launch form, on the throughput tile
             dW = padded(np.repeat(W0[None], B, 0), (B, g.Fp, g.Kp), 'cuda')
             dH = padded(np.repeat(H0[None], B, 0), (B, g.Kp, g.Np), 'cuda')
             ws = torch.zeros(lib.gccnmf_klnmf_workspace_floats(F, N, K, B), dtype=torch.float32, device='cuda')
             assert lib.gccnmf_klnmf(dV.data_ptr(), dW.data_ptr(), dH.data_ptr(), ws.data_ptr(), F, N, K, B, 3, 0.1, 1e-16, flags, stream()) == 0
             outs.append((dW.cpu().numpy(), dH.cpu().numpy()))
-            # once more on the same stream: a resident-workgroup launch finds the ticket counters as the previous one left them
+            # once more on the same stream and workspace
             assert lib.gccnmf_klnmf(dV.data_ptr(), dW.data_ptr(), dH.data_ptr(), ws.data_ptr(), F, N, K, B, 1, 0.1, 1e-16, flags, stream()) == 0
     finally:
-        for key, value in ((9, 1), (18, 0), (19, 1), (16, 1), (17, 1)):
+        for key, value in ((9, 1), (16, 1), (17, 1)):
             lib.gccnmf_set_tuning(key, value)
     for form, (Wq, Hq) in zip(forms[1:], outs[1:]):
         assert np.array_equal(outs[0][0], Wq) and np.array_equal(outs[0][1], Hq), form
@@ -872,10 +824,9 @@ def test_chained_launch_completes_with_one_workgroup_per_cu(hip):
 
 
 def test_wide_one_pass_w_update_at_batch_scale(hip):
-    """K <= 128 with at least 256 workgroups of 32 atoms (64 files at K = 128): the W update runs as nmf_update_w_onepass_kernel<32, 1> -- two
+    """K <= 128 with at least 256 workgroups of 32 atoms (64 files at K = 128): the W update runs as nmf_update_w_onepass_kernel<32> -- two
     18-row register sets per thread (190 VGPRs, 2 waves per SIMD, no spill: -Rpass-analysis=kernel-resource-usage), norms and column sums summed in
-    another order than the 16-atom form of smaller batches.  Against the oracle on the first and the last file, and -- lab build, key 20 --
-    against the 16-atom form to round-off."""
+    another order than the 16-atom form of smaller batches.  Against the oracle on the first and the last file."""
     lib = hip.lib()
     from gcc_nmf_amd.engine import klnmf_initial_factors
     B, F, T, K, iters = 64, 513, 40, 128, 6
@@ -888,12 +839,6 @@ def test_wide_one_pass_w_update_at_batch_scale(hip):
         Wr, Hr = O.performKLNMF(V[b], K, iters, 0)
         assert rel(W[b, :F, :K].cpu().numpy(), Wr) < 1e-4 and rel(H[b, :K, :N].cpu().numpy(), Hr) < 1e-4
     assert torch.allclose(torch.linalg.norm(W[:, :F, :K], dim=1), torch.ones_like(W[:, 0, :K]), atol=1e-5)
-    if lib.gccnmf_set_tuning(20, 0) == 0:                      # experiment build: the 16-atom form at the same batch
-        try:
-            W16, H16 = _klnmf_run(lib, V, W0, H0, F, N, K, B, iters)
-        finally:
-            lib.gccnmf_set_tuning(20, 1)
-        assert rel(W.cpu().numpy(), W16.cpu().numpy()) < 1e-5 and rel(H.cpu().numpy(), H16.cpu().numpy()) < 1e-5
 
 
 @pytest.mark.parametrize('B,T,K,iters,alpha', [(64, 622, 128, 5, 0.0), (40, 311, 100, 6, 0.2), (24, 330, 64, 6, 0.0), (27, 100, 32, 4, 0.0)])

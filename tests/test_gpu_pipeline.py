@@ -318,7 +318,7 @@ def test_benchmark_shape_properties():
       - KL divergence D(V || W.H) after 30 iterations is below the value after 5 (multiplicative updates descend)
       - unit-L2 atoms, non-negative factors, untouched zero padding
       - every file of the batch equals its own run in another batch: bit for bit when both runs use the same GEMM tile (the
-        result does not depend on the batch position or size), and to 1e-6 of the signal RMS for the file ALONE (split-K
+        result does not depend on the batch position or size), and to 1e-6 of the signal RMS for the file ALONE (the direct
         latency path, and the small-batch tile sums each 16-deep k-tile in a different order than the LDS-DMA tile)."""
     from gcc_nmf_amd.synthetic import synthetic_batch
     xs = synthetic_batch(100, 8)
@@ -368,7 +368,7 @@ def test_benchmark_shape_properties():
         finally:
             lib.gccnmf_set_tuning(2, 0)
         assert np.array_equal(y2[1], y8[5]), policy
-        if policy == 1:                   # forcing the throughput tile also switches the single-file split-K off
+        if policy == 1:                   # forcing the throughput tile also switches the single-file latency path off
             assert np.array_equal(y1[0], y8[5])
 
 
@@ -477,7 +477,7 @@ def test_separate_batches_overlaps_transfers_and_matches_separate():
 def test_klnmf_repeats_are_bitwise_identical():
     """Race detector for the hand-synchronised GEMM main loop (LDS-DMA, inline-asm fragment reads, LDS-counter split barrier):
     the same KL-NMF run repeated on the throughput tile gives bit-identical factors every time, as does the single-file
-    split-K path."""
+    latency path."""
     from gcc_nmf_amd.synthetic import synthetic_batch
     xs = synthetic_batch(500, 16)
     e = engine(160000, dictionarySize=1024, numIterations=8, batch=16)

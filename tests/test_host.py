@@ -42,8 +42,10 @@ def test_library_exports_every_declared_symbol(flavor):
         for n in _hip.EXPERIMENT_SIGNATURES:
             assert not hasattr(handle, n), 'the product library must not carry %s' % n
         assert handle.gccnmf_set_tuning(18, 0) != 0 and handle.gccnmf_set_tuning(1, 0) != 0          # experiment keys are rejected
+        for key, default in ((1, 0), (4, 1), (5, 3), (6, 4), (11, 0), (13, 0), (14, 1), (15, 1), (18, 0), (19, 1), (20, 1)):
+            assert handle.gccnmf_set_tuning(key, default) != 0, 'key %d selected a path that is gone: an unused slot' % key
     else:
-        assert handle.gccnmf_set_tuning(18, 0) == 0
+        assert handle.gccnmf_set_tuning(22, 0) == 0
     assert _hip.lib().gccnmf_version() >= 100
 
 
@@ -62,7 +64,7 @@ def test_pitches_and_workspace_sizes():
     chain = lambda batch: -(-(batch * (2 * 20 + 2)) // 32) * 32 + 32
     assert lib.gccnmf_klnmf_workspace_floats(513, 1244, 1024, 2) == 2 * (base + direct) + chain(2)
     assert lib.gccnmf_klnmf_workspace_floats(513, 1244, 1024, 64) == 64 * base + chain(64)               # (a handful of files at most)
-    assert lib.gccnmf_klnmf_workspace_floats(513, 1244, 1024, 1) == base + 4 * (528 * 1280 + 1024) + direct + chain(1)      # + the split-K partials of one file alone
+    assert lib.gccnmf_klnmf_workspace_floats(513, 1244, 1024, 1) == base + 4 * (528 * 1280 + 1024) + direct + chain(1)      # + the reserved block of one file alone (once split-K partials)
     assert lib.gccnmf_klnmf_workspace_floats(513, 0, 1024, 1) == -1
     assert lib.gccnmf_klnmf_workspace_floats(513, 1244, 128, 64) == 64 * (528 * 1280 + 528 * 128 + 3 * 128) + chain(64)     # (the fused short-dictionary launches need no scratch)
     # argument checking happens before any HIP call, so it is testable without a GPU
@@ -123,7 +125,7 @@ def test_every_workspace_size_is_a_multiple_of_four_floats():
 
 
 def test_klnmf_workspace_sizes_follow_the_layout_in_closed_form():
-    """The KL-NMF workspace is R | U | colsumW, rowsumH, hscale | split-K scratch (one file) | Wt, Ht, Rt (up to 8 files) | ready counters,
+    """The KL-NMF workspace is R | U | colsumW, rowsumH, hscale | a reserved block (one file) | Wt, Ht, Rt (up to 8 files) | ready counters,
     rounded up to 32 words | 32 status words, and for a ragged batch the tables behind them (the files' column counts + 8 lists of 32 words,
     rounded up to 4): both size functions agree with that layout written out here, for every tuple of the sweep."""
     from gcc_nmf_amd import _hip
@@ -177,8 +179,8 @@ def test_shared_run_argument_checks_and_workspace_sizes():
     assert lib.gccnmf_klnmf_shared_shard_workspace_floats(513, 640, 1024, 31, 20032) == Fp * 20032 + 31 * (Fp * Kp + Kp)
     # whole padded files back to back
     assert lib.gccnmf_klnmf_shared_shard_workspace_floats(513, 1244, 1024, 64, 0) == 64 * (Fp * 1280 + Fp * Kp + Kp)
-    # ONE file in the plain layout also carries the scratch of the latency path: the split-K partials (4 x max(Fp*Np, Fp*Kp) + 4 x Kp)
-    # and the transposed copies Wt | Ht | Rt of the direct kernels
+    # ONE file in the plain layout also carries the scratch of the latency path: a reserved block (4 x max(Fp*Np, Fp*Kp) + 4 x Kp: once the
+    # partials of a split-K path, unused now) and the transposed copies Wt | Ht | Rt of the direct kernels
     one = Fp * 1280 + Fp * Kp + Kp
     lat = 4 * (Fp * 1280 + Kp) + Kp * Fp + 1280 * Kp + 1280 * Fp
     assert lib.gccnmf_klnmf_shared_shard_workspace_floats(513, 1244, 1024, 1, 0) == one + lat
