@@ -48,7 +48,9 @@ extern "C" {
                                           * read only (bit-identical after the call); H [batch][Kp][Np] holds the initial coefficients on entry and
                                           * the result on exit (h <- h o W^T(v / Wh) / (colsum W + alpha + eps), every iteration of the call in one
                                           * launch, csrc/nmf_fixed.hip).  V, workspace, sparsity_alpha and epsilon as for the blind call; the
-                                          * chain-status words are left cleared.  F <= 2049 and K <= 1024, else GCCNMF_ERR_UNSUPPORTED.  Not
+                                          * chain-status words are left cleared.  Of the workspace the call writes only its head, den [Kp] (colsum W +
+                                          * alpha + eps; 1 for a padding atom) | Wt [Kp][round_up(F, 32)] (W^T, zero outside F x K), and the
+                                          * chain-status words.  F <= 2049 and K <= 1024, else GCCNMF_ERR_UNSUPPORTED.  Not
                                           * combinable with bits 0-15 (GCCNMF_ERR_ARG); gccnmf_klnmf_stage (but for its stage 7) / gccnmf_klnmf_ragged reject it */
 #define GCCNMF_FLAG_H_ONES (1 << 17)    /* with GCCNMF_FLAG_FIXED_W only (else GCCNMF_ERR_ARG): the initial H is all ones (the streaming
                                           * processor's h0 = 1); H is output only and is not read */

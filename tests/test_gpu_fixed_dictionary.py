@@ -182,3 +182,192 @@ def test_ragged_with_dictionary():
         y = e.separate(np.stack([xs[i] for i in idx]))
         for k, i in enumerate(idx):
             assert np.array_equal(out[i], y[k])
+
+
+# ---- the fused launch element by element, at every wave shape (tests/fixed_dictionary_restatement.py derives the bars and the table) ------------
+# Through the C ABI, on a workspace and an H padding pre-filled with NaN.  Every comparison prints its worst share of the bar before it
+# asserts; every call is held to the ownership rules (Call).
+import ctypes                                      # noqa: E402
+import functools                                   # noqa: E402
+
+import fixed_dictionary_restatement as R           # noqa: E402
+import klnmf_stages_restatement as S               # noqa: E402
+
+ALPHA, EPS = float(S.ALPHA), float(S.EPS)
+POOL = 5                                           # files per shape; a case takes the first `files` of them, or those it picks
+STATUS_WORDS = 32                                  # the chain-status words: the last 32 floats of the workspace
+
+
+@functools.lru_cache(maxsize=None)
+def _problem(F, N, K, frame=False):
+    return R.problem(F, N, K, POOL, frame)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.int32)
+
+
+class Call(object):
+    """One gccnmf_klnmf(..., GCCNMF_FLAG_FIXED_W [| GCCNMF_FLAG_H_ONES]) of V (B, F, N), W (F, K), H0 (B, K, N) or None.  On entry V and W are
+    zero padded, the padding of H (H0 None: all of H) and the whole workspace hold NaN.  Checked on every call: V and all of W bit for bit
+    unchanged; every workspace float behind the documented head den [Kp] | Wt [Kp][round_up(F, 32)] still its NaN bits, but for the
+    chain-status words, which are cleared and report 0; the padding of H (rows >= K, columns >= N, up to Kp x Np) bit for bit +0."""
+
+    def __init__(self, V, W, H0, iterations, alpha=ALPHA, eps=EPS, ones=False, label=''):
+        lib = _lib()
+        B, F, N = V.shape
+        K = W.shape[1]
+        Fp, Kp, Np = _geom(F, N, K)
+        Fq = -(-F // 32) * 32
+        self.shape, self.label = (B, F, N, K, Kp, Fq), label
+        Vd = torch.zeros((B, Fp, Np), dtype=torch.float32, device='cuda')
+        Vd[:, :F, :N] = torch.from_numpy(np.array(V)).cuda()
+        Wd = torch.zeros((Fp, Kp), dtype=torch.float32, device='cuda')
+        Wd[:F, :K] = torch.from_numpy(np.array(W)).cuda()
+        Hd = torch.full((B, Kp, Np), float('nan'), dtype=torch.float32, device='cuda')
+        if H0 is not None:
+            Hd[:, :K, :N] = torch.from_numpy(np.array(H0, dtype=np.float32)).cuda()
+        floats = lib.gccnmf_klnmf_workspace_floats(F, N, K, B)
+        ws = torch.full((floats,), float('nan'), dtype=torch.float32, device='cuda')
+        V_in, W_in, ws_in = Vd.cpu().numpy(), Wd.cpu().numpy(), ws.cpu().numpy()
+        assert np.isnan(ws_in).all()
+        rc = lib.gccnmf_klnmf(Vd.data_ptr(), Wd.data_ptr(), Hd.data_ptr(), ws.data_ptr(), F, N, K, B, iterations, alpha, eps,
+                              R.FIXED_W | (R.H_ONES if ones else 0), torch.cuda.current_stream().cuda_stream)
+        assert rc == 0, '%s: gccnmf_klnmf returned %d' % (label, rc)
+        torch.cuda.synchronize()
+        st = ctypes.c_int(-1)
+        assert lib.gccnmf_klnmf_chain_status(ws.data_ptr(), F, N, K, B, ctypes.byref(st)) == 0 and st.value == 0, label
+        self.Hfull, self.ws = Hd.cpu().numpy(), ws.cpu().numpy()
+        self.H = self.Hfull[:, :K, :N]
+        assert np.array_equal(_bits(Vd.cpu().numpy()), _bits(V_in)), '%s: V changed' % label
+        assert np.array_equal(_bits(Wd.cpu().numpy()), _bits(W_in)), '%s: W changed' % label
+        head = Kp * (1 + Fq)
+        assert head <= floats - STATUS_WORDS
+        same = _bits(self.ws[head:floats - STATUS_WORDS]) == _bits(ws_in[head:floats - STATUS_WORDS])
+        assert same.all(), '%s: workspace float %d behind the head was written' % (label, head + int(np.argwhere(~same)[0, 0]))
+        assert not _bits(self.ws[floats - STATUS_WORDS:]).any(), '%s: the chain-status words are not cleared' % label
+        assert not _bits(self.Hfull[:, K:, :]).any() and not _bits(self.Hfull[:, :, N:]).any(), '%s: the padding of H is not +0' % label
+
+    def check_head(self, W, alpha, eps):
+        """den [Kp] | Wt [Kp][round_up(F, 32)] at the start of the workspace -> worst share of den's bar"""
+        B, F, N, K, Kp, Fq = self.shape
+        den, Wt = self.ws[:Kp], self.ws[Kp:Kp * (1 + Fq)].reshape(Kp, Fq)
+        ref_den, ref_Wt = R.prepare(W, np.float32(alpha), np.float32(eps))
+        worst, miss = S.share(den[:K], ref_den, R.bar_den(F))
+        print('%s: den: worst share of the bar (%.0f * 2^-24) %.3f' % (self.label, R.bar_den(F) / S.U24, worst))
+        assert miss is None, '%s: den%s is %r, reference %r' % (self.label, miss, den[miss], ref_den[miss])
+        assert (den[K:] == 1).all(), '%s: den of a padding atom is not 1' % self.label
+        assert np.array_equal(_bits(Wt[:K, :F]), _bits(ref_Wt)), '%s: Wt is not W^T bit for bit' % self.label
+        assert not _bits(Wt[K:, :]).any() and not _bits(Wt[:, F:]).any(), '%s: Wt is not +0 outside F x K' % self.label
+        return worst
+
+
+def _label(F, K, N, files, what):
+    return '(F, K, N) = (%d, %d, %d) x %d, KB = %d, nw = %d, %s' % ((F, K, N, files) + R.fixed_shape(K)[1:] + (what,))
+
+
+@pytest.mark.parametrize('F,K,N,files', R.SHAPES)
+def test_one_iteration_against_the_restatement(F, K, N, files):
+    _, W, H0 = _problem(F, N, K)
+    H0 = H0[:files]
+    dead, bar = R.dead_atom(K), R.bar_iteration(F, K)
+    for alpha, frame in ((ALPHA, False), (0.0, False), (ALPHA, True)):
+        V = _problem(F, N, K, frame)[0][:files]
+        label = _label(F, K, N, files, 'alpha = %g%s' % (alpha, ', a silent frame' if frame else ''))
+        c = Call(V, W, H0, 1, alpha, label=label)
+        assert np.isfinite(c.H).all(), label
+        worst, misses = 0.0, []
+        for b in range(files):
+            ref = R.iteration(V[b], W, H0[b], np.float32(alpha), S.EPS)
+            w, miss = S.share(c.H[b], ref, bar)
+            worst = max(worst, w)
+            if miss is not None:
+                misses.append('file %d element %s: %r, reference %r' % (b, miss, c.H[b][miss], ref[miss]))
+            # the exact zeros the reference holds: the dead atom, the zeros of H0, the silent frame
+            if dead is not None:
+                assert not ref[dead].any() and not c.H[b, dead].any(), label
+            for k, n in R.h_zeros(K, N, b):
+                assert ref[k, n] == 0 and c.H[b, k, n] == 0, label
+            n0 = S.zero_lines(F, N, b)[1]
+            if frame and n0 is not None:
+                assert not ref[:, n0].any() and not c.H[b, :, n0].any(), label
+        print('%s: H: worst share of the bar (%.0f * 2^-24) %.3f' % (label, bar / S.U24, worst))
+        assert not misses, '%s: H misses its bar of %.0f * 2^-24 relative: %s' % (label, bar / S.U24, '; '.join(misses[:4]))
+        c.check_head(W, alpha, EPS)
+
+
+@pytest.mark.parametrize('F,K,N,files', R.SHAPES)
+def test_three_iterations_in_one_call_are_three_calls(F, K, N, files):
+    """the prefetch's wrap to chunk 0 of the next iteration, the LDS buffer toggle across iterations, the register-resident H"""
+    V, W, H0 = _problem(F, N, K)
+    V, H0 = V[:files], H0[:files]
+    label = _label(F, K, N, files, 'three iterations')
+    one = Call(V, W, H0, 3, label=label)
+    H, bar, worst = H0, R.bar_iteration(F, K), 0.0
+    for it in range(3):
+        step = Call(V, W, H, 1, label=label)
+        for b in range(files):                                               # every one of the three against the restatement from ITS input
+            w, miss = S.share(step.H[b], R.iteration(V[b], W, H[b]), bar)
+            worst = max(worst, w)
+            assert miss is None, '%s: call %d, file %d element %s misses its bar' % (label, it, b, miss)
+        H = step.H
+    print('%s: H of each of the three calls: worst share of the bar (%.0f * 2^-24) %.3f' % (label, bar / S.U24, worst))
+    assert np.isfinite(one.H).all() and not np.array_equal(_bits(one.H), _bits(H0)), label
+    assert np.array_equal(_bits(one.Hfull), _bits(step.Hfull)), '%s: one call of 3 iterations differs from 3 calls of one' % label
+
+
+@pytest.mark.parametrize('F,K,N,files', R.SHAPES)
+def test_zero_iterations(F, K, N, files):
+    V, W, H0 = _problem(F, N, K)
+    V, H0 = V[:files], H0[:files]
+    label = _label(F, K, N, files, 'no iteration')
+    c = Call(V, W, H0, 0, label=label)                                       # (Call: the padding, NaN on entry, is +0)
+    assert np.array_equal(_bits(c.H), _bits(H0)), '%s: H changed' % label
+    c = Call(V, W, None, 0, ones=True, label=label)
+    assert np.array_equal(_bits(c.H), _bits(np.ones_like(H0))), '%s: H is not all ones' % label
+
+
+@pytest.mark.parametrize('F,K,N,files', R.SHAPES)
+def test_h_ones_is_an_explicit_all_ones_start(F, K, N, files):
+    V, W, H0 = _problem(F, N, K)
+    V = V[:files]
+    for iterations in (1, 3):
+        label = _label(F, K, N, files, 'H_ONES, %d iterations' % iterations)
+        flag = Call(V, W, None, iterations, ones=True, label=label)          # H is NaN throughout on entry: it is not read
+        explicit = Call(V, W, np.ones_like(H0[:files]), iterations, label=label)
+        assert np.isfinite(flag.H).all(), label
+        assert np.array_equal(_bits(flag.Hfull), _bits(explicit.Hfull)), label
+
+
+BATCH_SHAPES = [s for s in R.SHAPES if s[3] >= 2 and R.fixed_shape(s[1])[1] >= 2]
+
+
+@pytest.mark.parametrize('F,K,N,files', BATCH_SHAPES)
+def test_a_file_has_the_same_bits_alone_in_its_batch_and_in_a_permuted_batch_of_five(F, K, N, files):
+    V, W, H0 = _problem(F, N, K)
+    label = _label(F, K, N, files, 'batch independence')
+    batch = Call(V[:files], W, H0[:files], 3, label=label)
+    perm = [4, 2, 3, 0, 1]
+    five = Call(V[perm], W, H0[perm], 3, label=label)
+    assert np.isfinite(five.H).all(), label
+    for b in range(files):
+        alone = Call(V[b:b + 1], W, H0[b:b + 1], 3, label=label)
+        assert np.array_equal(_bits(alone.Hfull[0]), _bits(batch.Hfull[b])), '%s: file %d alone' % (label, b)
+        assert np.array_equal(_bits(five.Hfull[perm.index(b)]), _bits(batch.Hfull[b])), '%s: file %d in the batch of five' % (label, b)
+
+
+def test_the_batch_independence_cases_cover_kb_2_3_and_4():
+    assert {R.fixed_shape(K)[1] for _, K, _, _ in BATCH_SHAPES} == {2, 3, 4}
+
+
+@pytest.mark.parametrize('F,K,N,files', [(64, 300, 70, 2), (65, 516, 40, 2)])
+def test_inferKLNMFCoefficients_is_the_c_abi_call(F, K, N, files):
+    from gcc_nmf_amd.engine import inferKLNMFCoefficients, klnmf_initial_factors
+    assert (F, K, N, files) in R.SHAPES and R.fixed_shape(K)[1] == (2 if K == 300 else 3)
+    V, W, _ = _problem(F, N, K)
+    V = V[:files]
+    H = inferKLNMFCoefficients(np.array(V), np.array(W), 3)          # (copies: the pool is read-only)
+    H0 = np.broadcast_to(klnmf_initial_factors(F, N, K)[1], (files, K, N))
+    c = Call(V, W, H0, 3, alpha=0.0, eps=1e-16, label=_label(F, K, N, files, 'inferKLNMFCoefficients'))
+    assert H.dtype == np.float32 and H.shape == (files, K, N) and np.isfinite(H).all()
+    assert np.array_equal(_bits(H), _bits(c.H))
