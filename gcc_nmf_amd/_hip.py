@@ -355,28 +355,92 @@ def _divergence_flags(divergence, fixed_w=False, h_ones=False, groups=1, flags=0
     return DIVERGENCE_FLAGS[d]
 
 
+GCCNMF_FLAG_CONTINUITY = 1 << 28               # include/gccnmf_hip.h: temporal-continuity KL-NMF (the weight rides in K and batch)
+GCCNMF_FLAG_CONTINUITY_STEREO = 1 << 29        # include/gccnmf_hip.h: ... inside two column segments [L | R]
+CONTINUITY_MAX_ATOMS, CONTINUITY_MAX_BINS, CONTINUITY_MAX_BATCH = 1024, 2049, 65535      # the envelope of the temporal-continuity call
+
+
+def check_continuity(weight, segments=1):
+    """The ``continuity`` / ``segments`` keywords of klnmf and klnmf_stage, the ``temporalContinuity`` of the engines and of
+    performTemporalKLNMF; no device needed.  Returns (weight as a float, segments as an int); ValueError unless the weight is a real,
+    finite number >= 0 (not a bool) and segments is 1 or 2."""
+    if isinstance(weight, bool) or not isinstance(weight, numbers.Real) or not math.isfinite(weight) or weight < 0:
+        raise ValueError('the temporal-continuity weight must be a finite number >= 0, got %r' % (weight,))
+    if isinstance(segments, bool) or not isinstance(segments, numbers.Integral) or segments not in (1, 2):
+        raise ValueError('the temporal-continuity term runs inside 1 or 2 column segments, got %r' % (segments,))
+    return float(weight), int(segments)
+
+
+def klnmf_continuity_extra_floats(Kp, Np, batch):
+    """GCCNMF_KLNMF_CONTINUITY_WORKSPACE_FLOATS(Kp, Np, batch) of include/gccnmf_hip.h: the floats a temporal-continuity call needs behind
+    the KL layout -- Gm | Gp [batch][Kp][Np] each | E | D [batch][2][Kp] each."""
+    return batch * Kp * (2 * Np + 4)
+
+
+def klnmf_continuity_workspace_floats(F, N, K, batch):
+    """Floats of the workspace of a temporal-continuity gccnmf_klnmf / gccnmf_klnmf_stage call: gccnmf_klnmf_workspace_floats followed
+    by the extra blocks above."""
+    n = lib().gccnmf_klnmf_workspace_floats(F, N, K, batch)
+    return n if n < 0 else n + klnmf_continuity_extra_floats(-(-K // 64) * 64, -(-N // 64) * 64, batch)
+
+
+def continuity_words(K, batch, weight):
+    """(K, batch) arguments of a call with GCCNMF_FLAG_CONTINUITY: the float32 bits of the weight in their upper halves
+    (GCCNMF_CONTINUITY_K / GCCNMF_CONTINUITY_BATCH of include/gccnmf_hip.h), as signed 32-bit values."""
+    bits = ctypes.c_uint32.from_buffer_copy(ctypes.c_float(weight)).value
+    signed = lambda v: ctypes.c_int32(v & 0xffffffff).value
+    return signed(int(K) | (bits & 0xffff0000)), signed(int(batch) | ((bits & 0xffff) << 16))
+
+
+def _continuity_words(continuity, segments, F, N, K, batch, flags, other):
+    """(flags, K, batch) as the library takes them.  A weight of 0 sends the words of a call without the keyword; a weight above 0
+    combines with none of the other forms of the call (``other``) and carries its envelope (ValueError before the library is touched)."""
+    weight, segments = check_continuity(continuity, segments)
+    if weight == 0:
+        return flags, K, batch
+    if other or flags & 6:
+        raise ValueError('temporal continuity cannot be combined with a fixed dictionary, the all-ones start, free atoms, another '
+                         'divergence, file groups or the unfused W update')
+    if not 2 <= F <= CONTINUITY_MAX_BINS or not 1 <= K <= CONTINUITY_MAX_ATOMS or not 1 <= batch <= CONTINUITY_MAX_BATCH:
+        raise ValueError('the temporal-continuity call takes 2 to %d bins, 1 to %d atoms and 1 to %d files, got F = %r, K = %r, batch = %r'
+                         % (CONTINUITY_MAX_BINS, CONTINUITY_MAX_ATOMS, CONTINUITY_MAX_BATCH, F, K, batch))
+    if ctypes.c_float(weight).value in (0.0, float('inf')):
+        raise ValueError('the temporal-continuity weight %r is not a positive finite float32' % (weight,))
+    if segments == 2 and N % 2:
+        raise ValueError('two column segments need an even number of columns, got %d' % N)
+    K, batch = continuity_words(K, batch, weight)
+    return flags | GCCNMF_FLAG_CONTINUITY | (GCCNMF_FLAG_CONTINUITY_STEREO if segments == 2 else 0), K, batch
+
+
 def klnmf(V, W, H, ws, F, N, K, batch, iterations, alpha, eps, fixed_w=False, h_ones=False, groups=1, flags=0, free_atoms=0, stream=None,
-          divergence='kl'):
+          divergence='kl', continuity=0.0, segments=1):
     """``iterations`` NMF iterations on W and H in place -- KL, or with divergence='is' / 'euclidean' Itakura-Saito / Euclidean (the
     workspace is then klnmf_divergence_workspace_floats(..., divergence) floats).  groups > 1: this call is one of that many concurrent ones
     (GCCNMF_FLAG_GROUPS(n) = 4 | n << 8: launch forms are chosen for all groups together); flags: further low flag bits.
     free_atoms = n > 0: semi-supervised -- columns [0, K - n) of every file's W are a dictionary that stays as it is, the last n atoms
-    and all of H are learned (GCCNMF_FLAG_FREE_ATOMS(n))."""
+    and all of H are learned (GCCNMF_FLAG_FREE_ATOMS(n)).
+    continuity = weight > 0: KL-NMF with the temporal-continuity term inside ``segments`` (1 | 2) equal column runs (GCCNMF_FLAG_CONTINUITY;
+    the workspace is then klnmf_continuity_workspace_floats floats); 0 sends exactly the words of a call without the keyword."""
     flags |= _divergence_flags(divergence, fixed_w, h_ones, groups, flags, free_atoms)
+    flags, Kw, batchw = _continuity_words(continuity, segments, F, N, K, batch, flags,
+                                          fixed_w or h_ones or groups > 1 or free_atoms or check_divergence(divergence) != 'kl')
     if free_atoms:
         if fixed_w or h_ones or groups > 1 or flags & 6:
             raise ValueError('free atoms cannot be combined with a fixed dictionary, the all-ones start, file groups or the unfused W update')
         flags |= GCCNMF_FLAG_FREE_ATOMS(check_free_atoms(free_atoms, K - free_atoms, F))
     flags |= (GCCNMF_FLAG_FIXED_W if fixed_w else 0) | (GCCNMF_FLAG_H_ONES if h_ones else 0) | (4 | groups << 8 if groups > 1 else 0)
-    _stage('gccnmf_klnmf', V, W, H, ws, F, N, K, batch, iterations, alpha, eps, flags, stream=stream)
+    _stage('gccnmf_klnmf', V, W, H, ws, F, N, Kw, batchw, iterations, alpha, eps, flags, stream=stream)
 
 
-def klnmf_stage(V, W, H, ws, F, N, K, batch, alpha, eps, stage, flags=0, free_atoms=0, stream=None, divergence='kl'):
-    """One stage (0-7) of the iteration through gccnmf_klnmf_stage; flags: low flag bits, free_atoms / divergence as for klnmf."""
+def klnmf_stage(V, W, H, ws, F, N, K, batch, alpha, eps, stage, flags=0, free_atoms=0, stream=None, divergence='kl', continuity=0.0,
+                segments=1):
+    """One stage (0-7) of the iteration through gccnmf_klnmf_stage; flags: low flag bits, free_atoms / divergence / continuity / segments
+    as for klnmf."""
     flags |= _divergence_flags(divergence, flags=flags, free_atoms=free_atoms)
+    flags, Kw, batchw = _continuity_words(continuity, segments, F, N, K, batch, flags, free_atoms or check_divergence(divergence) != 'kl')
     if free_atoms:
         flags |= GCCNMF_FLAG_FREE_ATOMS(check_free_atoms(free_atoms, K - free_atoms, F))
-    _stage('gccnmf_klnmf_stage', V, W, H, ws, F, N, K, batch, alpha, eps, flags, int(stage), stream=stream)
+    _stage('gccnmf_klnmf_stage', V, W, H, ws, F, N, Kw, batchw, alpha, eps, flags, int(stage), stream=stream)
 
 
 def klnmf_divergence(V, W, H, ws, F, N, K, batch, fixed=False, stream=None, divergence='kl'):

@@ -28,9 +28,16 @@ int gccnmf_klnmf_semi_update_w_launch(float* W, const float* U, const float* row
 bool gccnmf_klnmf_beta_supported(int F, int K);
 int gccnmf_klnmf_beta_stage_launch(int stage, int divergence, const float* V, float* W, float* H, float* R, float* Q, float* Un, float* Ud,
                                    float* colsumW, float* hscale, int F, int N, int K, int batch, float alpha, float eps, hipStream_t s);
+// temporal-continuity KL-NMF (GCCNMF_FLAG_CONTINUITY), nmf_smooth.hip: stages 1-4 of that iteration
+bool gccnmf_klnmf_smooth_supported(int F, int K, int batch);
+int gccnmf_klnmf_smooth_stage_launch(int stage, const float* V, const float* W, float* H, float* R, float* U, float* rowsumH, const float* colsumW,
+                                     const float* hscale, float* Gm, float* Gp, float* E, float* D, int F, int N, int K, int batch, int segments,
+                                     float alpha, float eps, float weight, hipStream_t s);
 #include "../../include/gccnmf_hip.h"
 
 #include <atomic>
+#include <cmath>
+#include <cstring>
 #include <algorithm>
 #include <vector>
 #define GCCNMF_SHARED_STREAMS 4
@@ -398,13 +405,32 @@ struct KlnmfMode {
     bool fixed_w, h_ones;       // GCCNMF_FLAG_FIXED_W, GCCNMF_FLAG_H_ONES
     int free_atoms;             // GCCNMF_FLAG_FREE_ATOMS(n): the last n atoms of every file's W are learned beside a dictionary (0 = not semi-supervised)
     int divergence;             // bits 26-27: 0 = KL, 1 = GCCNMF_FLAG_DIVERGENCE_IS, 2 = GCCNMF_FLAG_DIVERGENCE_EUCLIDEAN
+    int segments;               // GCCNMF_FLAG_CONTINUITY: the column segments the temporal-continuity term runs inside (1 | 2 with _STEREO), 0 = no such term
+    float continuity;           // ... and its weight (unpack_continuity took it out of K and batch)
 };
+// GCCNMF_FLAG_CONTINUITY: the weight's float32 bits ride in the upper halves of K and batch (GCCNMF_CONTINUITY_K / _BATCH); the entry points
+// call this FIRST, so that everything behind it sees the plain K and batch.  Without the bit the words are left alone.  GCCNMF_ERR_ARG:
+// the stereo bit without the continuity bit, a weight that is negative, NaN or Inf, two segments with N odd.
+static int unpack_continuity(int flags, int N, int& K, int& batch, KlnmfMode& m) {
+    m.segments = 0;
+    m.continuity = 0.f;
+    if (!(flags & GCCNMF_FLAG_CONTINUITY)) return (flags & GCCNMF_FLAG_CONTINUITY_STEREO) ? GCCNMF_ERR_ARG : GCCNMF_OK;
+    const unsigned bits = ((unsigned)K & 0xffff0000u) | ((unsigned)batch >> 16);
+    K &= 0xffff;
+    batch &= 0xffff;
+    std::memcpy(&m.continuity, &bits, sizeof(float));
+    m.segments = (flags & GCCNMF_FLAG_CONTINUITY_STEREO) ? 2 : 1;
+    if (!(m.continuity >= 0.f) || std::isinf(m.continuity)) return GCCNMF_ERR_ARG;
+    return m.segments == 2 && (N & 1) ? GCCNMF_ERR_ARG : GCCNMF_OK;
+}
 // ... with the argument rules of the flag combinations, decided before anything is launched: GCCNMF_OK = a valid word.
 //   fixed dictionary: GCCNMF_FLAG_FIXED_W alone or with GCCNMF_FLAG_H_ONES, nothing else (H_ONES without FIXED_W: GCCNMF_ERR_ARG)
 //   free atoms: not with the concurrent-groups or the unfused-W-update bit, n <= 128, n < K (GCCNMF_ERR_ARG); (K - n) % 16 == 0, K <= 1024,
 //   F <= 2049 (GCCNMF_ERR_UNSUPPORTED)
 //   IS / Euclid: one of the two bits, not with a fixed dictionary, the all-ones start, free atoms, concurrent groups or the unfused W update
 //   (GCCNMF_ERR_ARG); F <= 2049, K <= 1024 (GCCNMF_ERR_UNSUPPORTED)
+//   temporal continuity (m.segments, set by unpack_continuity): with none of those, nor IS / Euclid (GCCNMF_ERR_ARG); F <= 2049, K <= 1024
+//   (GCCNMF_ERR_UNSUPPORTED)
 static int decode_mode(int flags, int F, int K, KlnmfMode& m) {
     const int n = (flags & (GCCNMF_FLAG_GROUPS(255) & ~GCCNMF_FLAG_CONCURRENT_GROUPS)) / (GCCNMF_FLAG_GROUPS(1) & ~GCCNMF_FLAG_CONCURRENT_GROUPS);
     m.xcd_affine = !(flags & GCCNMF_FLAG_NO_XCD_AFFINITY);
@@ -414,6 +440,10 @@ static int decode_mode(int flags, int F, int K, KlnmfMode& m) {
     m.h_ones = (flags & GCCNMF_FLAG_H_ONES) != 0;
     m.free_atoms = (flags & GCCNMF_FLAG_FREE_ATOMS(255)) / GCCNMF_FLAG_FREE_ATOMS(1);
     m.divergence = (flags >> 26) & 3;
+    if (m.segments) {
+        if (m.divergence || m.fixed_w || m.h_ones || m.free_atoms || (flags & GCCNMF_FLAG_CONCURRENT_GROUPS) || m.unfused_w_update) return GCCNMF_ERR_ARG;
+        return gccnmf_klnmf_smooth_supported(F, K, 1) ? GCCNMF_OK : GCCNMF_ERR_UNSUPPORTED;
+    }
     if (m.divergence) {
         if (m.divergence == 3 || m.fixed_w || m.h_ones || m.free_atoms || (flags & GCCNMF_FLAG_CONCURRENT_GROUPS) || m.unfused_w_update) return GCCNMF_ERR_ARG;
         return gccnmf_klnmf_beta_supported(F, K) ? GCCNMF_OK : GCCNMF_ERR_UNSUPPORTED;
@@ -683,6 +713,19 @@ static BetaWorkspace carve_beta(float* workspace, const KlnmfWorkspace& ws, cons
     b.Ud = b.Q + batch * g.sV;
     return b;
 }
+// A temporal-continuity call's workspace is the KL carve followed by GCCNMF_KLNMF_CONTINUITY_WORKSPACE_FLOATS more floats: Gm | Gp
+// [batch][Kp][Np] each | E | D [batch][2][Kp] each (segment-major inside a file).
+struct SmoothWorkspace {
+    float *Gm, *Gp, *E, *D;
+};
+static SmoothWorkspace carve_smooth(float* workspace, const KlnmfWorkspace& ws, const NmfGeom& g, int batch) {
+    SmoothWorkspace w;
+    w.Gm = workspace + ws.floats;
+    w.Gp = w.Gm + batch * g.sH;
+    w.E = w.Gp + batch * g.sH;
+    w.D = w.E + (long)batch * 2 * g.Kp;
+    return w;
+}
 static bool workspace_aligned(const void* workspace) { return ((uintptr_t)workspace & 15) == 0; }
 
 // The lists of a chained launch (tuning key 23): 1 = whole files per XCD (hand-over through that XCD's L2), 2 = the file-major tile list cut into equal
@@ -723,7 +766,7 @@ static bool chain_rule(int batch, const KlnmfMode& m) {
 }
 // ---- which launches a per-file-dictionary call is made of, decided ONCE at the entry point (gccnmf_klnmf / _stage / _plan / _ragged) ---------
 // plan_klnmf is the only code that reads the form-selecting tuning keys and shape rules; klnmf_stage and the call loops test these fields and no rule.
-enum KlnmfKind { KLNMF_BLIND, KLNMF_FIXED_W, KLNMF_FREE_ATOMS, KLNMF_BETA };      // W learned | one given W (GCCNMF_FLAG_FIXED_W) | free atoms beside a dictionary | IS / Euclid
+enum KlnmfKind { KLNMF_BLIND, KLNMF_FIXED_W, KLNMF_FREE_ATOMS, KLNMF_BETA, KLNMF_SMOOTH };      // W learned | one given W (GCCNMF_FLAG_FIXED_W) | free atoms beside a dictionary | IS / Euclid | temporal continuity
 struct KlnmfPlan {
     KlnmfKind kind;
     bool direct;            // every stage on the direct latency kernels (direct.hip)
@@ -739,6 +782,10 @@ static KlnmfPlan plan_klnmf(const NmfGeom& g, int batch, const KlnmfMode& m) {
     if (p.kind == KLNMF_FIXED_W) return p;      // one launch runs every iteration (nmf_fixed.hip); of the stages only 7 exists, in one form
     if (m.divergence) {                         // IS / Euclid: five plain launches per iteration in ONE form (nmf_beta.hip), no tuning key is read
         p.kind = KLNMF_BETA;
+        return p;
+    }
+    if (m.segments) {                           // temporal continuity: plain launches in ONE form (nmf_smooth.hip), R materialised, no tuning key is read
+        p.kind = KLNMF_SMOOTH;
         return p;
     }
     // Free atoms (semi-supervised): stage 4 reads a materialised R [batch][Fp][Np] with zero padding, so stages 1-3 take the forms that leave
@@ -973,6 +1020,17 @@ static int klnmf_stage(int stage, const float* V, float* W, float* H, const Klnm
         }
         return gccnmf_klnmf_beta_stage_launch(stage, m.divergence, V, W, H, R, bw.Q, U, bw.Ud, colsumW, hscale, g.F, g.N, g.K, batch, alpha, eps, s);
     }
+    if (p.kind == KLNMF_SMOOTH && stage >= 1 && stage <= 5) {      // (stages 0 and 6 are the KL launches below)
+        if (stage == 5) {      // the two-pass W update on 16 atoms per workgroup, whatever the batch: a file's bits do not follow the launch size
+            hipLaunchKernelGGL(nmf_update_w_kernel<16>, dim3(batch * (g.Kp / 16)), dim3(256), 0, s, W, U, rowsumH, colsumW, hscale, g.F, g.Fp, g.K, g.Kp,
+                               g.sW, g.sU, (long)g.Kp, (long)g.Kp);
+            GCCNMF_CHECK_LAUNCH();
+            return GCCNMF_OK;
+        }
+        const SmoothWorkspace sw = carve_smooth(R, ws, g, batch);      // (R is the start of the workspace)
+        return gccnmf_klnmf_smooth_stage_launch(stage, V, W, H, R, U, rowsumH, colsumW, hscale, sw.Gm, sw.Gp, sw.E, sw.D, g.F, g.N, g.K, batch, m.segments,
+                                                alpha, eps, m.continuity, s);
+    }
     const int nfree = m.free_atoms, groups = m.groups;      // (GCCNMF_FLAG_GROUPS: the W update kernel is sized for all groups together)
     const bool semi = p.kind == KLNMF_FREE_ATOMS;
     const int head34 = p.head34, rest34 = batch - head34;      // files on the slab launch | behind it on the two launches
@@ -1060,26 +1118,29 @@ static int finish_call(bool chained, const float* V, float* W, float* H, const K
 // Which launches gccnmf_klnmf would use for this problem under the current tuning: bit 0 the direct latency kernels, bit 1 the fused
 // K1 + K2 launch, bit 2 the fused K3 + K4a slab launch, bit 3 chained launches of the iteration (benchmarks and tests name the kernel they
 // time by this; the engine keeps ONE file group when the library chains), bit 4 the fused fixed-dictionary launch (GCCNMF_FLAG_FIXED_W),
-// bit 5 the semi-supervised iteration (GCCNMF_FLAG_FREE_ATOMS), bit 6 the IS / Euclidean iteration (GCCNMF_FLAG_DIVERGENCE_*; bits 4, 5 and 6: then
-// no other bit).
+// bit 5 the semi-supervised iteration (GCCNMF_FLAG_FREE_ATOMS), bit 6 the IS / Euclidean iteration (GCCNMF_FLAG_DIVERGENCE_*), bit 7 the
+// temporal-continuity iteration (GCCNMF_FLAG_CONTINUITY; bits 4, 5, 6 and 7: then no other bit).
 int gccnmf_klnmf_plan(int F, int N, int K, int batch, int flags) {
     GCCNMF_ENTER();
-    if (F < 2 || N < 1 || K < 1 || batch < 1) return -1;
     KlnmfMode m;
+    if (unpack_continuity(flags, N, K, batch, m)) return -1;
+    if (F < 2 || N < 1 || K < 1 || batch < 1) return -1;
     if (decode_mode(flags, F, K, m)) return -1;
     const KlnmfPlan p = plan_klnmf(make_geom(F, N, K), batch, m);
     if (p.kind == KLNMF_FIXED_W) return gccnmf_klnmf_fixed_supported(F, K) ? 16 : -1;
     if (p.kind == KLNMF_FREE_ATOMS) return 32;
     if (p.kind == KLNMF_BETA) return 64;
+    if (p.kind == KLNMF_SMOOTH) return 128;
     return (p.direct ? 1 : 0) | (p.fused12 ? 2 : 0) | (p.head34 > 0 ? 4 : 0) | ((p.chain || p.short_group) ? 8 : 0);
 }
 
 int gccnmf_klnmf_stage(const float* V, float* W, float* H, float* workspace, int F, int N, int K, int batch,
                        float sparsity_alpha, float epsilon, int flags, int stage, void* stream) {
     GCCNMF_ENTER();
+    KlnmfMode m;
+    if (const int rc = unpack_continuity(flags, N, K, batch, m)) return rc;
     if (!V || !W || !H || !workspace || F < 2 || N < 1 || K < 1 || batch < 1) return GCCNMF_ERR_ARG;
     if (!workspace_aligned(workspace)) return GCCNMF_ERR_ARG;          // float4 / LDS-DMA accesses to its blocks; stage 7's float64 partials and results
-    KlnmfMode m;
     if (const int rc = decode_mode(flags, F, K, m)) return rc;
     // (a fixed dictionary -- one W for every file -- exists for stage 7 alone: the divergence against it; the iteration stages have no such form)
     if (m.fixed_w && (stage != 7 || m.h_ones)) return GCCNMF_ERR_ARG;
@@ -1090,18 +1151,20 @@ int gccnmf_klnmf_stage(const float* V, float* W, float* H, float* workspace, int
 int gccnmf_klnmf(const float* V, float* W, float* H, float* workspace, int F, int N, int K, int batch, int iterations,
                  float sparsity_alpha, float epsilon, int flags, void* stream) {
     GCCNMF_ENTER();
+    KlnmfMode m;
+    int rc;
+    if ((rc = unpack_continuity(flags, N, K, batch, m))) return rc;
     if (!V || !W || !H || !workspace || F < 2 || N < 1 || K < 1 || batch < 1 || iterations < 0) return GCCNMF_ERR_ARG;
     if (!workspace_aligned(workspace)) return GCCNMF_ERR_ARG;          // R, U, Wt, Ht, Rt are read with float4 loads and LDS-DMA: 16 bytes
     hipStream_t s = (hipStream_t)stream;
-    KlnmfMode m;
-    int rc;
     if ((rc = decode_mode(flags, F, K, m))) return rc;
     const NmfGeom g = make_geom(F, N, K);
     const KlnmfPlan p = plan_klnmf(g, batch, m);
     const KlnmfWorkspace ws = carve(workspace, g, batch, false);
     const float alpha = sparsity_alpha, eps = epsilon;
-    if (p.kind == KLNMF_FREE_ATOMS || p.kind == KLNMF_BETA) {
+    if (p.kind == KLNMF_FREE_ATOMS || p.kind == KLNMF_BETA || p.kind == KLNMF_SMOOTH) {
         // IS / Euclid: five plain launches per iteration (nmf_beta.hip); nothing chains.
+        // temporal continuity: seven plain launches per iteration (nmf_smooth.hip and the two-pass W update); nothing chains.
         // semi-supervised: the dictionary in W[:, :K - n] of every file stays as it is, the n free atoms behind it and all of H are learned.
         // Plain launches (klnmf_stage keeps R materialised); nothing chains.
         if ((rc = clear_chain_status(ws, s))) return rc;
@@ -1174,7 +1237,9 @@ int gccnmf_klnmf_ragged(const float* V, float* W, float* H, float* workspace, in
                         float sparsity_alpha, float epsilon, int flags, void* stream) {
     GCCNMF_ENTER();
     if (!V || !W || !H || !workspace || !N || F < 2 || Nmax < 1 || K < 1 || batch < 1 || iterations < 0) return GCCNMF_ERR_ARG;
+    if (flags & (GCCNMF_FLAG_CONTINUITY | GCCNMF_FLAG_CONTINUITY_STEREO)) return GCCNMF_ERR_ARG;      // (a ragged batch has no temporal-continuity form)
     KlnmfMode m;
+    m.segments = 0;
     if (decode_mode(flags, F, K, m) || m.fixed_w || m.free_atoms || m.divergence) return GCCNMF_ERR_ARG;
     m.groups = 1;      // (intended today: the concurrent-groups bit is masked off -- a ragged batch exists in ONE form, whatever runs beside it)
     if (!workspace_aligned(workspace)) return GCCNMF_ERR_ARG;

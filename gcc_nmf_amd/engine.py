@@ -57,6 +57,28 @@ class ChainHandOverError(RuntimeError):
     """A chained KL-NMF launch of a chunk did not hand over cleanly (gccnmf_klnmf_chain_status): the run is repeated on plain launches."""
 
 
+def check_temporal_continuity(temporalContinuity, dictionaryW, numFreeAtoms, divergence, tolerance, klnmf_flags, nmf_groups, windowSize,
+                              dictionarySize, batch):
+    """The ``temporalContinuity`` keyword of the engines; no device needed.  Returns the weight as a float; ValueError for a weight that is
+    no finite number >= 0 and, for a weight above 0, with anything the temporal-continuity call does not combine with or outside its
+    envelope (at most 2049 bins, 1024 atoms, 65535 files)."""
+    weight = _hip.check_continuity(temporalContinuity, 2)[0]
+    if weight > 0:
+        if dictionaryW is not None or numFreeAtoms:
+            raise ValueError('temporalContinuity learns every atom: not available with dictionaryW or numFreeAtoms')
+        if _hip.check_divergence(divergence) != 'kl':
+            raise ValueError('temporalContinuity is a term of the KL iteration: not available with divergence=%r' % (divergence,))
+        if tolerance is not None:
+            raise ValueError('temporalContinuity has no stopping rule on the penalised objective: not available with tolerance')
+        if klnmf_flags & 6:
+            raise ValueError('temporalContinuity cannot be combined with the concurrent-groups or unfused-W-update bits of klnmf_flags')
+        if nmf_groups not in (None, 1):
+            raise ValueError('temporalContinuity runs as one file group (nmf_groups=1)')
+        _hip._continuity_words(weight, 2, int(windowSize) // 2 + 1, 2, 128 if dictionarySize is None else int(dictionarySize), max(int(batch), 1), 0,
+                               False)
+    return weight
+
+
 def converge_klnmf(launch, divergence, factors, maxIterations, tolerance, checkEvery, failed=None):
     """KL-NMF in chunks of ``checkEvery`` iterations until every file has converged or ``maxIterations`` is reached (plumbing: the
     iterations and the divergence are library calls).
@@ -266,7 +288,12 @@ class GCCNMFEngine(object):
     or Euclidean NMF in place of KL (gccnmf_klnmf with GCCNMF_FLAG_DIVERGENCE_*: plain launches, one file group).  V stays the MAGNITUDE
     spectrogram and everything behind the factors is unchanged; ``tolerance`` / ``get_divergence()`` / ``get_divergence_trace()`` use the
     chosen divergence (getBetaDivergence states each).  Not with ``dictionaryW`` or ``numFreeAtoms``, nor with the concurrent-groups or
-    unfused-W-update bits of ``klnmf_flags`` (ValueError); at most 1024 atoms and 2049 bins."""
+    unfused-W-update bits of ``klnmf_flags`` (ValueError); at most 1024 atoms and 2049 bins.
+    ``temporalContinuity`` = weight >= 0 (default 0: the engine as it was, bit for bit): KL-NMF whose H update carries
+    the temporal-continuity term inside the two column segments [L | R] of V (performTemporalKLNMF states it).  Everything behind the
+    factors is unchanged and ``get_divergence()`` stays the KL divergence; one file group; not with ``dictionaryW``, ``numFreeAtoms``,
+    another ``divergence``, ``tolerance`` or the concurrent-groups / unfused-W-update bits (ValueError before a device is looked for);
+    at most 1024 atoms and 2049 bins."""
 
     def __new__(cls, n_samples=None, *args, **kwargs):
         if cls is GCCNMFEngine and kwargs.get('lengths') is not None:
@@ -281,8 +308,12 @@ class GCCNMFEngine(object):
                  sparsityAlpha=0, epsilon=1e-16, seedValue=0, batch=1, windowFunction=np.hanning,
                  device='cuda:0', klnmf_flags=0, nmf_groups=None, dictionaryW=None, initialH='random', reconstruction='direct',
                  gccPHATNLEnabled=False, gccPHATNLAlpha=2.0, tdoaTracking=False, localizationWindowSize=None, tolerance=None, checkEvery=10,
-                 numFreeAtoms=0, maxTargets=None, spatialIterations=0, divergence='kl'):
+                 numFreeAtoms=0, maxTargets=None, spatialIterations=0, divergence='kl', temporalContinuity=0.0):
         self.autoTargets, numTargets = _hip.check_auto_targets(numTargets, maxTargets, tdoaTracking)
+        self.temporalContinuity = check_temporal_continuity(temporalContinuity, dictionaryW, numFreeAtoms, divergence, tolerance, klnmf_flags,
+                                                            nmf_groups, windowSize, dictionarySize, batch)
+        if self.temporalContinuity > 0:
+            nmf_groups = 1
         self.divergence = _hip.check_divergence(divergence, int(windowSize) // 2 + 1, None if dictionarySize is None else int(dictionarySize))
         if self.divergence != 'kl':
             if dictionaryW is not None or numFreeAtoms:
@@ -387,7 +418,8 @@ class GCCNMFEngine(object):
                 self.W0 = padded(self.dictionaryW, (g.Fp, g.Kp), dev)
                 self.W.copy_(self.W0.unsqueeze(0).expand_as(self.W))
             # nmf_groups equal group workspaces (for one group == the whole-batch workspace)
-            self.ws_nmf = z(self.nmf_groups * _hip.klnmf_divergence_workspace_floats(F, g.N, g.K, B // self.nmf_groups, self.divergence))
+            self.ws_nmf = z(_hip.klnmf_continuity_workspace_floats(F, g.N, g.K, B) if self.temporalContinuity > 0 else
+                            self.nmf_groups * _hip.klnmf_divergence_workspace_floats(F, g.N, g.K, B // self.nmf_groups, self.divergence))
             self.nmf_streams = [torch.cuda.Stream(device=dev) for _ in range(self.nmf_groups)] if self.nmf_groups > 1 else []
             # Copy streams of separate_batches, created ONCE and right behind the group streams.  The runtime maps streams onto a
             # few hardware queues in creation order (4 by default), and a queue is in-order: a 244 MB download that shares its queue
@@ -529,7 +561,7 @@ class GCCNMFEngine(object):
             _hip.klnmf(self.V[b0], self.W0 if fixed else self.W[b0], self.H[b0], ws, g.F, g.N, g.K, per, iters, self.alpha, self.eps,
                        fixed_w=fixed, h_ones=fixed and first and self.initialH == 'ones', groups=self.nmf_groups,
                        flags=0 if fixed else self.klnmf_flags, free_atoms=self.numFreeAtoms, stream=None if st is None else st.cuda_stream,
-                       divergence=self.divergence)
+                       divergence=self.divergence, continuity=self.temporalContinuity, segments=2)
             if st is not None:
                 done = torch.cuda.Event()
                 done.record(st)
@@ -969,14 +1001,16 @@ class RaggedGCCNMFEngine(object):
     localisation, masks, reconstruction, iSTFT) run per distinct length, on the ordinary engine of that length.  A file's results are bit
     for bit those it gets in an equal-length batch.  Where the library has no chained form for the shape (GCCNMF_ERR_UNSUPPORTED: short
     dictionaries, a handful of files) the files of each length run their KL-NMF as a batch of their own -- and so they do with
-    ``divergence`` = 'is' / 'euclidean' (GCCNMFEngine states the keyword), which has no ragged launch."""
+    ``divergence`` = 'is' / 'euclidean' and with ``temporalContinuity`` > 0 (GCCNMFEngine states the keywords), which have no ragged launch."""
 
     def __init__(self, lengths, sampleRate=16000, windowSize=1024, hopSize=256, numTDOAs=128, microphoneSeparationInMetres=1.0,
                  numTargets=3, dictionarySize=None, numIterations=100, sparsityAlpha=0, epsilon=1e-16, seedValue=0,
                  windowFunction=np.hanning, device='cuda:0', klnmf_flags=0, dictionaryW=None, initialH='random', reconstruction='direct',
                  gccPHATNLEnabled=False, gccPHATNLAlpha=2.0, tdoaTracking=False, localizationWindowSize=None, tolerance=None, checkEvery=10,
-                 maxTargets=None, spatialIterations=0, divergence='kl'):
+                 maxTargets=None, spatialIterations=0, divergence='kl', temporalContinuity=0.0):
         self.tolerance, self.checkEvery, numIterations = _hip.check_convergence(tolerance, checkEvery, numIterations)
+        self.temporalContinuity = check_temporal_continuity(temporalContinuity, dictionaryW, 0, divergence, tolerance, klnmf_flags, None,
+                                                            windowSize, dictionarySize, len(lengths))
         self.divergence = _hip.check_divergence(divergence, int(windowSize) // 2 + 1, None if dictionarySize is None else int(dictionarySize))
         if self.divergence != 'kl':
             if dictionaryW is not None:
@@ -1006,7 +1040,7 @@ class RaggedGCCNMFEngine(object):
                   reconstruction=reconstruction, gccPHATNLEnabled=gccPHATNLEnabled, gccPHATNLAlpha=gccPHATNLAlpha,
                   tdoaTracking=tdoaTracking, localizationWindowSize=localizationWindowSize,     # (each file's windows end at its own T)
                   tolerance=tolerance, checkEvery=checkEvery, maxTargets=maxTargets, spatialIterations=spatialIterations,
-                  divergence=self.divergence)
+                  divergence=self.divergence, temporalContinuity=self.temporalContinuity)
         # one ordinary engine per distinct length: its files (caller's indexes, ascending) are its batch
         self.files_of = {}
         for i, n in enumerate(self.lengths):
@@ -1021,7 +1055,7 @@ class RaggedGCCNMFEngine(object):
             self.ragged = None
             # a fixed dictionary: each length's engine runs its own one-launch call; a tolerance: each length's files converge as a batch of their
             # own; IS / Euclid: the ragged launch is KL only, each length runs as a batch of its own
-            if len(self.sub) > 1 and dictionaryW is None and self.tolerance is None and self.divergence == 'kl':
+            if len(self.sub) > 1 and dictionaryW is None and self.tolerance is None and self.divergence == 'kl' and not self.temporalContinuity:
                 ws = self.lib.gccnmf_klnmf_ragged_workspace_floats(g.F, g.N, g.K, self.batch)
                 if ws > 0:
                     self.ragged = dict(V=z(self.batch, g.Fp, g.Np), W=z(self.batch, g.Fp, g.Kp), H=z(self.batch, g.Kp, g.Np), ws=z(ws),

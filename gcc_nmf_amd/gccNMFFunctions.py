@@ -140,6 +140,51 @@ def performBetaNMF(V, dictionarySize, numIterations, beta, sparsityAlpha=0, epsi
     return W, H
 
 
+def performTemporalKLNMF(V, dictionarySize, numIterations, sparsityAlpha, temporalContinuity, numSegments=1, epsilon=1e-16, seedValue=0):
+    """performKLNMF with Virtanen's temporal-continuity term on H (IEEE TASLP 2007; not in the reference): the columns
+    of V are ``numSegments`` (1 | 2: [L | R]) equal runs of frames, and inside each run every atom's gains pay
+    ``temporalContinuity`` * T * sum_t (h_t - h_{t-1})^2 / sum_t h_t^2 -- an ABSOLUTE weight, in units of V -- beside the KL divergence and
+    sparsityAlpha * sum H.  The H update is H <- H o (W^T(V / WH) + b Gm) / (colsum W + sparsityAlpha + b Gp + epsilon) with Gp - Gm the
+    gradient of the cost; the W update and the normalisation are performKLNMF's.  The initial factors are those performKLNMF draws (with
+    its side effect on NumPy's global generator); a weight of 0 IS performKLNMF, bit for bit.  Returns float32 (W, H).  A weight above 0:
+    F <= 2049, dictionarySize <= 1024, an even column count for two segments (ValueError) and at most LARGE_N_COLUMNS columns
+    (NotImplementedError: the column-block path of a larger V is plain KL only)."""
+    V = np.asarray(V)
+    if V.ndim != 2:
+        raise ValueError('V must be (F, N)')
+    F, N = V.shape
+    K = int(dictionarySize)
+    weight, segments = _hip.check_continuity(temporalContinuity, numSegments)
+    if weight == 0:
+        return performKLNMF(V, dictionarySize, numIterations, sparsityAlpha, epsilon, seedValue)
+    if N > LARGE_N_COLUMNS:
+        raise NotImplementedError('performTemporalKLNMF runs V as one call: at most %d columns, got %d (the column-block path is plain KL only)'
+                                  % (LARGE_N_COLUMNS, N))
+    _hip._continuity_words(weight, segments, F, N, K, 1, 0, False)      # the envelope, before a device is looked for
+    lib, dev = _hip.lib(), _device()
+    init = _klnmf_initial_factors(F, N, K, epsilon, seedValue, dev)
+    with _staging.Scope(dev) as sc:
+        dV, dW, dH, ws = _klnmf_buffers(sc, lib, V, K, init, continuity=True)
+        _hip.klnmf(dV, dW, dH, ws, F, N, K, 1, int(numIterations), float(sparsityAlpha), float(epsilon), continuity=weight, segments=segments)
+        W = sc.remember(sc.download(dW[:F, :K]), 'W', dict(W=dW), dict(F=F, K=K))
+        H = sc.download(dH[:K, :N])
+    return W, H
+
+
+def getTemporalContinuity(H, numSegments=1):
+    """The temporal-continuity cost of performTemporalKLNMF, summed over the atoms and segments of H (K, N) on the host in float64:
+    sum of T * sum_t (h_t - h_{t-1})^2 / sum_t h_t^2 with T = N / numSegments; an all-zero row contributes 0."""
+    H = np.asarray(H, np.float64)
+    _, segments = _hip.check_continuity(0.0, numSegments)
+    if H.ndim != 2 or H.shape[1] % segments:
+        raise ValueError('H must be (K, N) with N a multiple of numSegments')
+    K, N = H.shape
+    h = H.reshape(K, segments, N // segments)
+    E = (h * h).sum(2)
+    D = (np.diff(h, axis=2) ** 2).sum(2)
+    return float(((N // segments) * D[E > 0] / E[E > 0]).sum())
+
+
 def _klnmf_initial_factors(F, N, K, epsilon, seedValue, dev):
     """Device images of performKLNMF's initial W and H (gccNMF/gccNMFFunctions.py:70-73), with the reference's side effect on the
     GLOBAL generator."""
@@ -162,7 +207,7 @@ def _klnmf_initial_factors(F, N, K, epsilon, seedValue, dev):
     return init
 
 
-def _klnmf_buffers(sc, lib, V, K, init, divergence='kl'):
+def _klnmf_buffers(sc, lib, V, K, init, divergence='kl', continuity=False):
     """The padded device buffers of one batch-1 NMF call, loaded with V and the initial factors: (dV, dW, dH, workspace)."""
     F, N = V.shape
     g = Geometry(F, 1, K)
@@ -171,7 +216,8 @@ def _klnmf_buffers(sc, lib, V, K, init, divergence='kl'):
     dV = sc.dev('V', (g.Fp, Np), corner=(F, N))
     dW = sc.dev('W', (g.Fp, g.Kp), corner=(F, K))
     dH = sc.dev('H', (g.Kp, Np), corner=(K, N))
-    ws = sc.dev('ws_klnmf', (_hip.klnmf_divergence_workspace_floats(F, N, K, 1, divergence),))
+    ws = sc.dev('ws_klnmf', (_hip.klnmf_continuity_workspace_floats(F, N, K, 1) if continuity else
+                             _hip.klnmf_divergence_workspace_floats(F, N, K, 1, divergence),))
     dV[:F, :N].copy_(sc.upload(V, 'V', float32))
     dW[:F, :K].copy_(init['W'])
     dH[:K, :N].copy_(init['H'])

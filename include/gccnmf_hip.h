@@ -104,6 +104,38 @@ extern "C" {
  * start 16-byte aligned when the workspace does (it must: GCCNMF_ERR_ARG otherwise). */
 #define GCCNMF_KLNMF_DIVERGENCE_WORKSPACE_FLOATS(Fp, Kp, Np, batch) ((long)(batch) * (Fp) * ((long)(Np) + (Kp)))
 
+/* TEMPORAL-CONTINUITY KL-NMF, bits 28-29 of `flags` of gccnmf_klnmf, gccnmf_klnmf_stage and gccnmf_klnmf_plan (csrc/nmf_smooth.hip): KL-NMF
+ * whose H update carries Virtanen's temporal-continuity term (IEEE TASLP 2007) with the ABSOLUTE weight beta >= 0 (in units of V).  The
+ * columns are `segments` equal runs of T = N / segments frames -- 1, or with GCCNMF_FLAG_CONTINUITY_STEREO 2, the GCC-NMF layout [L | R];
+ * nothing couples across a segment boundary or into the padding.  Per file, atom and segment, with h = s * H the materialised gains:
+ *     E = sum_t h_t^2     D = sum_{t >= 1} (h_t - h_{t-1})^2     cost c = T D / E
+ *     Gp_t = 2 T n_t h_t / E                                 n_t = the neighbours inside the segment (2, at the ends 1, T = 1: 0)
+ *     Gm_t = 2 T (h_{t-1} + h_{t+1}) / E + 2 T h_t D / E^2   a missing neighbour adds 0;  E = 0 -> Gp = Gm = 0
+ *     H <- h o ((W^T (V / (W h)) + beta Gm) / (((colsumW + alpha) + beta Gp) + eps))
+ * (Gp - Gm = dc / dh_t; Jacobi: every neighbour is the value from before the stage); the W update, the normalisation and H *= s are KL's.
+ * E, D, Gm and Gp are formed in float64 from the exact products s * H, summed in an order fixed by (N, segments) alone, and rounded once to
+ * float32; every element-wise operation of the H update is a float32 operation rounded on its own in the order written (the file's header
+ * states each).  ONE launch form whatever the batch and the tuning keys, no atomics: a file's factors are bit for bit the same alone, in
+ * any batch and at any place in it.  Seven plain launches per iteration; nothing chains, the chain-status words are cleared;
+ * gccnmf_klnmf_plan returns bit 7 alone.
+ * THE WEIGHT has no argument of its own: with GCCNMF_FLAG_CONTINUITY set -- and only then -- its float32 bits are read from the upper
+ * halves of the K and batch arguments, so pass GCCNMF_CONTINUITY_K(K, bits) and GCCNMF_CONTINUITY_BATCH(batch, bits) there (K and batch
+ * themselves are then at most 65535).  Decided before anything is launched -- GCCNMF_ERR_ARG: the stereo bit without the continuity bit; a
+ * weight that is negative, NaN or Inf; two segments with N odd; either bit together with GCCNMF_FLAG_FIXED_W, GCCNMF_FLAG_H_ONES,
+ * GCCNMF_FLAG_FREE_ATOMS, GCCNMF_FLAG_DIVERGENCE_*, GCCNMF_FLAG_CONCURRENT_GROUPS or GCCNMF_FLAG_UNFUSED_W_UPDATE; either bit on
+ * gccnmf_klnmf_ragged.  GCCNMF_ERR_UNSUPPORTED: F > 2049 or K > 1024 (the envelope: 2 <= F <= 2049, 1 <= K <= 1024, any N >= 1, batch <=
+ * 65535).  The padding of H may hold anything on entry (NaN included) and never reaches a result; the H update writes +0 into the padding
+ * columns of the rows k < K.  The workspace is LARGER than the KL call's: gccnmf_klnmf_workspace_floats(F, N, K, batch) floats laid out as
+ * for KL, followed by GCCNMF_KLNMF_CONTINUITY_WORKSPACE_FLOATS(Kp, Np, batch) more (see gccnmf_klnmf_stage for what sits where).  A call
+ * without bit 28 launches exactly what it launched before the bits existed.  Bit 30 is free. */
+#define GCCNMF_FLAG_CONTINUITY (1 << 28)
+#define GCCNMF_FLAG_CONTINUITY_STEREO (1 << 29)
+#define GCCNMF_CONTINUITY_K(K, weight_bits) ((int)((unsigned)(K) | ((unsigned)(weight_bits) & 0xffff0000u)))
+#define GCCNMF_CONTINUITY_BATCH(batch, weight_bits) ((int)((unsigned)(batch) | ((unsigned)(weight_bits) << 16)))
+/* floats a temporal-continuity call needs BEHIND the KL layout: Gm | Gp [batch][Kp][Np] each | E | D [batch][2][Kp] each.  A multiple of
+ * 4 floats; the KL layout is a multiple of 32 floats, so every block starts 16-byte aligned when the workspace does. */
+#define GCCNMF_KLNMF_CONTINUITY_WORKSPACE_FLOATS(Kp, Np, batch) ((long)(batch) * (Kp) * (2 * (long)(Np) + 4))
+
 int gccnmf_version(void);
 
 /* Tuning knobs: process-global atomics; every library call works on a snapshot taken at its entry.  Results stay valid (and, where a
@@ -219,8 +251,9 @@ int gccnmf_klnmf_chain_status(const float* workspace, int F, int N, int K, int b
  * bit 1 = K1 + K2 as one launch of column tiles (tuning key 16), bit 2 = K3 + K4a as one launch of 64-bin slabs (key 17), bit 3 = the whole
  * call as one chained launch (key 21), bit 4 = the fused fixed-dictionary launch (GCCNMF_FLAG_FIXED_W; then no other bit), bit 5 = the semi-supervised
  * iteration (GCCNMF_FLAG_FREE_ATOMS; then no other bit), bit 6 = the Itakura-Saito / Euclidean iteration (GCCNMF_FLAG_DIVERGENCE_*; then no other
- * bit).  -1 on bad arguments (a flag combination gccnmf_klnmf rejects, or a fixed-dictionary, semi-supervised or IS / Euclidean shape outside
- * its envelope).
+ * bit), bit 7 = the temporal-continuity iteration (GCCNMF_FLAG_CONTINUITY, K and batch carrying the weight as for gccnmf_klnmf; then no other
+ * bit).  -1 on bad arguments (a flag combination gccnmf_klnmf rejects, or a fixed-dictionary, semi-supervised, IS / Euclidean or
+ * temporal-continuity shape outside its envelope).
  * (Benchmarks and tests name the kernel they time by this; the result of gccnmf_klnmf does not depend on it beyond round-off.) */
 int gccnmf_klnmf_plan(int F, int N, int K, int batch, int flags);
 
@@ -282,7 +315,16 @@ int gccnmf_klnmf_plan(int F, int N, int K, int batch, int flags);
  *                                   alone are used
  *     Q        [batch][Fp][Np]      at KL; zero padded like R
  *     Ud       [batch][Fp][Kp]      at KL + batch * Fp * Np
- *   The padding of Un and Ud is nobody's operand and keeps whatever the workspace held. */
+ *   The padding of Un and Ud is nobody's operand and keeps whatever the workspace held.
+ * With GCCNMF_FLAG_CONTINUITY in flags (same argument rules and weight carriage as gccnmf_klnmf, decided first; one launch form,
+ * csrc/nmf_smooth.hip): stages 0, 1, 3, 4, 5, 6 and 7 mean what they mean for KL, always as launches that leave R, U and rowsumH
+ * materialised at their KL places (stages 1 and 3 write the whole padded R block; never the direct, fused or chained forms); stage 2 is the
+ * continuity launch (E, D, Gm, Gp from H and hscale) followed by the H-update launch.  Behind the KL layout (KL = the value of
+ * gccnmf_klnmf_workspace_floats(F, N, K, batch)):
+ *     Gm       [batch][Kp][Np]      at KL; written inside k < K, n < N alone, like Gp
+ *     Gp       [batch][Kp][Np]      at KL + batch * Kp * Np
+ *     E        [batch][2][Kp]       at KL + 2 * batch * Kp * Np; [b][segment][k], the second plane is written with two segments only
+ *     D        [batch][2][Kp]       at KL + 2 * batch * Kp * Np + 2 * batch * Kp */
 int gccnmf_klnmf_stage(const float* V, float* W, float* H, float* workspace, int F, int N, int K, int batch,
                        float sparsity_alpha, float epsilon, int flags, int stage, void* stream);
 
