@@ -631,6 +631,7 @@ class GCCNMFEngine(object):
         self.masks()
         self.reconstruct()
         self.istft()
+        self._scored_y = self.y           # what score() reads: the buffer this run wrote (separate_batches alternates two)
 
     # ---- host <-> device -------------------------------------------------------------------------
     def _checked_samples(self, stereoSamples, one_file=True):
@@ -771,6 +772,41 @@ class GCCNMFEngine(object):
             finally:
                 torch.cuda.synchronize(dev)
                 self.x, self.y = xs[0], ys[0]
+
+    @_on_device
+    def score(self, images, filterLength=512, guardSamples=0):
+        """BSS Eval image criteria (evaluation.bss_eval_images) of the waveforms of the last ``separate()`` (or ``run()``; after
+        ``separate_batches``, of the last batch it ran), scored where they lie on the device -- no download.  ``images``: the true source images (batch, S, 2, n_samples), host array or tensor,
+        on the mixture's time axis: waveform sample y[n] belongs to images[..., n + windowSize // 2].  ``guardSamples`` are cut at both
+        ends of the waveforms first.  Returns (sdr, isr, sir, sar, perm), each (batch, S) indexed by true source: output perm[b][j] is
+        true source j, the assignment with the largest mean SIR.  On the enhancement engine S = 2: talker, noise.
+        ValueError: numTargets='auto' (an empty slot has no image), no separation yet, a wrong shape, guardSamples not a whole number >= 0 or cutting
+        everything, the rules of bss_eval_images, non-finite images or waveforms."""
+        from . import evaluation
+        if self.autoTargets:
+            raise ValueError("score() is not available with numTargets='auto': empty target slots have no image")
+        y = getattr(self, '_scored_y', None)
+        if y is None:
+            raise ValueError('score() needs a separation first: nothing has been separated by this engine yet')
+        g = guardSamples
+        if isinstance(g, bool) or not isinstance(g, (int, np.integer)) or g < 0 or 2 * g >= self.L:
+            raise ValueError('guardSamples must be a whole number >= 0 that leaves samples to score (%d per waveform), got %r' % (self.L, g))
+        want = (self.batch, self.g.S, 2, self.n_samples)
+        if tuple(images.shape) != want:
+            raise ValueError('expected images of shape %s, got %s' % (want, tuple(images.shape)))
+        off, g = self.n_fft // 2 + int(g), int(g)
+        n = self.L - 2 * g
+        evaluation.check_image_shape((self.batch, self.g.S, 2, n), filterLength)
+        if torch.is_tensor(images):
+            S = images[..., off:off + n].to(device=self.device, dtype=torch.float32).contiguous()
+        else:
+            S = torch.from_numpy(np.ascontiguousarray(np.asarray(images)[..., off:off + n], dtype=np.float32)).to(self.device)
+        E = y[..., g:g + n].contiguous()
+        if not (bool(torch.isfinite(S).all()) and bool(torch.isfinite(E).all())):
+            raise ValueError('images or separated waveforms are not finite everywhere')
+        from . import _eval
+        _eval.require_device()
+        return evaluation.score_device(S, E, filterLength)
 
     @_on_device
     def check_pcm_finite(self):
