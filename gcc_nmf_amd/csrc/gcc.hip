@@ -182,16 +182,18 @@ __global__ __launch_bounds__(256) void track_carry_kernel(int T, int Tp, int S, 
     }
 }
 
-// The steering product Re(C e^{-j w tau}) = Cr cos + Ci sin of a thread's four frames, with its roundings written out: frames 0, 2 and 3
-// fma(Cr, cos, Ci * sin), frame 1 the two rounded products added.  That is what the compiler made of `cr * c + ci * sn` while the
-// fixed-index kernel was the only form (its packed-math pairing decides which sums it contracts), and the results of every existing
-// call rest on it; stated explicitly, with contraction off, the fixed-index and the per-frame form share it and give the same bits
-// for the same (cos, sin) whatever a later compiler would have paired.
+// The steering product Re(C e^{-j w tau}) = Cr cos + Ci sin of a thread's four frames, with its roundings written out and the SAME for
+// every frame: fma(Cr, cos, Ci * sin), contraction off, so that neither the fixed-index nor the per-frame form depends on what a compiler
+// would have paired.  A frame's product must not know where the frame sits in its buffer: the frame-sharded separation
+// (distributed.py, mode 3) hands a rank the frames [t0, t1) of a mixture as its frames [0, t1 - t0), and its scores have to be the
+// unsplit run's in every bit.  (Until tests/test_gpu_time_shards.py compared them, frame 1 of every four added two rounded products --
+// what the compiler's packed-math pairing had once made of `cr * c + ci * sn` -- and a shard whose t0 is no multiple of 4 differed from
+// the unsplit run in the last bit of a quarter of its scores.)
 __device__ __forceinline__ float4 gcc_steer4(float4 cr, float4 ci, float4 c, float4 sn) {
 #pragma clang fp contract(off)
     float4 out;
     out.x = fmaf(cr.x, c.x, ci.x * sn.x);
-    out.y = cr.y * c.y + ci.y * sn.y;
+    out.y = fmaf(cr.y, c.y, ci.y * sn.y);
     out.z = fmaf(cr.z, c.z, ci.z * sn.z);
     out.w = fmaf(cr.w, c.w, ci.w * sn.w);
     return out;

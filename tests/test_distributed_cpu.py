@@ -237,3 +237,218 @@ def test_collective_timeout_and_ipc_environment_messages(monkeypatch):
     # a single process (no group) needs no exchange; an unknown route is an error only once a group exists
     hook = D.collective_hook(None)
     assert hook[0] is None and hook[3] == 'single rank'
+
+
+# ---- mode 3 at every seam and split: the host side (tests/test_gpu_time_shards.py replays the same geometries on the device) ---------
+def test_shard_frames_partitions_every_length_and_world():
+    """The ranges of shard_frames partition [0, T) in rank order, sizes differ by at most one and the larger shards come first, for
+    every T in 1..200 and world in 1..9 (T < world: the last ranks are empty, which HipTimeShard's constructor then refuses)."""
+    from gcc_nmf_amd.distributed import shard_frames
+    for T in range(1, 201):
+        for world in range(1, 10):
+            r = [shard_frames(T, world, k) for k in range(world)]
+            assert r[0][0] == 0 and r[-1][1] == T, (T, world, r)
+            assert all(r[k][1] == r[k + 1][0] for k in range(world - 1)), (T, world, r)
+            sizes = [b - a for a, b in r]
+            assert min(sizes) >= 0 and max(sizes) - min(sizes) <= 1, (T, world, sizes)
+            assert sizes == sorted(sizes, reverse=True), (T, world, sizes)
+            for bad in (-1, world, world + 3):
+                with pytest.raises(ValueError):
+                    shard_frames(T, world, bad)
+
+
+def test_time_shard_cases_are_what_they_claim_and_have_three_peaks():
+    """The geometries the device test replays: T, halo and split as tabulated, by the package's own num_frames / shard_frames, and the
+    float64 oracle finds the three peaks recorded for each -- so the device comparison is not one of two runs that found nothing."""
+    import time_shard_cases as C
+    from gcc_nmf_amd.distributed import shard_frames
+    from gcc_nmf_amd.engine import num_frames
+    from oracle import gccnmf_oracle as O
+    assert sorted(C.CASES) == sorted(C.EXPECTED) == sorted(C.PEAKS) and len(C.CASES) == 7
+    for name, (n_fft, hop, world, n, D) in C.CASES.items():
+        T, halo, split = C.describe(name)
+        assert (T, halo, split) == C.EXPECTED[name], name
+        assert T == num_frames(n, n_fft, hop) and split == [b - a for a, b in (shard_frames(T, world, k) for k in range(world))], name
+        assert min(split) >= max(halo, 2) and n <= 2 * 16000, name
+        X = O.computeComplexMixtureSpectrogram(C.mixture(n), n_fft, hop, np.hanning)
+        A = O.getAngularSpectrogram(O.spectralCoherence(X), np.linspace(0, 8000.0, X.shape[1]), 1.0, D)
+        idx = O.estimateTargetTDOAIndexesFromAngularSpectrum(np.mean(A, axis=-1), 1.0, D, C.NUM_TARGETS)
+        assert [int(i) for i in idx] == C.PEAKS[name], (name, idx)
+    assert C.EXPECTED['1024/128 x4'][2][1:] == [C.EXPECTED['1024/128 x4'][1]] * 3             # three shards of exactly `halo` frames
+    assert min(C.EXPECTED['1024/512 x7'][2]) == 2 and C.EXPECTED['1024/512 x7'][1] == 1      # max(halo, 2)
+
+
+def _synthetic_segments(n_fft, hop, T, world, S=2):
+    """What every rank's overlap_add hands to stitch_time_shards, by its documented contract: rank r owns the untrimmed samples
+    [t0 hop, t1 hop) -- the last one up to the end of its last frame -- shifted by the centre trim n_fft // 2.  The sample at global
+    (trimmed) index i holds i + 1 + 2^20 r: never zero, exact in float32, and it names the rank that wrote it."""
+    from gcc_nmf_amd.distributed import shard_frames
+    segs = []
+    for r in range(world):
+        t0, t1 = shard_frames(T, world, r)
+        L = (t1 - t0 - 1) * hop + n_fft if r == world - 1 else (t1 - t0) * hop
+        start = t0 * hop - n_fft // 2
+        v = (np.arange(start, start + L) + 1 + (r << 20)).astype(np.float32)
+        segs.append((np.broadcast_to(v, (S, 2, L)).copy(), start))
+    return segs
+
+
+def test_stitch_writes_every_sample_once_from_the_right_segment():
+    import time_shard_cases as C
+    from gcc_nmf_amd.distributed import stitch_time_shards
+    for name, (n_fft, hop, world, n, _) in C.CASES.items():
+        T = C.describe(name)[0]
+        segs = _synthetic_segments(n_fft, hop, T, world)
+        L = hop * (T - 1)
+        starts = [s for _, s in segs]
+        assert starts[0] == -(n_fft // 2) and starts[-1] + segs[-1][0].shape[2] > L, name       # first starts before 0, last runs past the end
+        assert all(s + seg.shape[2] == nxt for (seg, s), nxt in zip(segs, starts[1:])), name    # the contract's segments tile
+        for order in (segs, segs[::-1]):                                                        # tiles: the order cannot matter
+            y = stitch_time_shards(order, 2, T, hop)
+            assert y.shape == (2, 2, L) and y.dtype == np.float32
+            i = np.arange(L)
+            owner = np.searchsorted(np.array(starts[1:]), i, side='right')                      # the rank whose range holds sample i
+            want = (i + 1 + (owner << 20)).astype(np.float32)
+            bad = np.argwhere(y != want)
+            assert not len(bad), '%s: sample %s holds %r, not %r' % (name, tuple(bad[0]), y[tuple(bad[0])], want[bad[0][2]])
+            assert len(set(owner.tolist())) == world, name                                      # every rank wrote something
+
+
+@pytest.mark.parametrize('world', [3, 8])
+def test_time_shard_initial_factors_reassemble_the_single_rank_draw(world):
+    """Every rank's rows put back into [all left frames | all right frames] are klnmf_initial_factors(F, 2T, K) bit for bit."""
+    from gcc_nmf_amd.distributed import shard_frames, time_shard_initial_factors
+    from gcc_nmf_amd.engine import klnmf_initial_factors
+    F, T, K = 33, 53, 7
+    W, H = klnmf_initial_factors(F, 2 * T, K)
+    got = np.full((K, 2 * T), np.nan, np.float32)
+    for rank in range(world):
+        t0, t1 = shard_frames(T, world, rank)
+        Wr, Hr = time_shard_initial_factors(F, T, K, t0, t1)
+        assert Wr.dtype == np.float32 and Hr.dtype == np.float32 and Hr.shape == (K, 2 * (t1 - t0))
+        assert np.array_equal(Wr.view(np.int32), np.asarray(W, np.float32).view(np.int32)), 'W differs on rank %d' % rank
+        got[:, t0:t1], got[:, T + t0:T + t1] = Hr[:, :t1 - t0], Hr[:, t1 - t0:]
+    bad = np.argwhere(got.view(np.int32) != np.ascontiguousarray(H, np.float32).view(np.int32))
+    assert not len(bad), 'H differs first at %s (T = %d: column %d is frame %d of the %s channel)' % (
+        tuple(bad[0]), T, bad[0][1], bad[0][1] % T, 'right' if bad[0][1] >= T else 'left')
+
+
+def test_time_shard_constructor_guard_counts_the_halo_of_a_non_dividing_hop():
+    """The guard precedes every device call, so it is checked here too: at 1024 / 300 the halo is ceil(1024 / 300) - 1 = 3 frames, and
+    a shard of 2 frames cannot hold the tail its successor needs.  One frame more is no ValueError (without a device the engine then
+    says so; tests/test_gpu_time_shards.py builds it)."""
+    from gcc_nmf_amd import _hip
+    from gcc_nmf_amd.distributed import HipTimeShard
+    x = np.zeros((2, 1024 + 300 * (3 * 2 - 1)), np.float32)               # T = 6, three ranks of 2 frames
+    try:
+        with pytest.raises(ValueError, match=r'2 frames is shorter than the overlap-add halo \(3 frames\)'):
+            HipTimeShard(x, 1, 3, windowSize=1024, hopSize=300, dictionarySize=64, device='cuda:0')
+    except _hip.HipLibraryError:
+        raise AssertionError('a shard of 2 frames got past the guard at 1024 / 300, whose halo is 3 frames (the engine was reached)')
+    x = np.zeros((2, 1024 + 300 * (3 * 3 - 1)), np.float32)               # T = 9, three ranks of 3 frames
+    try:
+        HipTimeShard(x, 1, 3, windowSize=1024, hopSize=300, dictionarySize=64, device='cuda:0')
+    except _hip.HipLibraryError:
+        pass                                                              # no device here: the guard let it through, which is the point
+
+
+class _ThreadGroup(object):
+    """torch.distributed for `world` THREADS of one process, as far as separate_time_sharded and train_shared_dictionary use it: the
+    all-reduce (sum in rank order) and the all-gather played by hand between two barriers."""
+
+    class ReduceOp(object):
+        SUM = 'sum'
+
+    def __init__(self, world):
+        import threading
+        self.world, self.local = world, threading.local()
+        self.barrier = threading.Barrier(world, timeout=300)
+        self.slots = [None] * world
+
+    def is_available(self):
+        return True
+
+    def is_initialized(self):
+        return True
+
+    def get_world_size(self, group=None):
+        return self.world
+
+    def get_rank(self, group=None):
+        return self.local.rank
+
+    def _exchange(self, tensor):
+        self.slots[self.local.rank] = tensor.clone()
+        self.barrier.wait()
+        got = list(self.slots)
+        self.barrier.wait()                                  # nobody overwrites a slot before everybody has read it
+        return got
+
+    def all_reduce(self, tensor, op=None, group=None):
+        assert op == self.ReduceOp.SUM
+        got = self._exchange(tensor)
+        total = got[0].clone()
+        for t in got[1:]:
+            total += t
+        tensor.copy_(total)
+
+    def all_gather(self, out, tensor, group=None):
+        for o, t in zip(out, self._exchange(tensor)):
+            o.copy_(t)
+
+    def run(self, fn):
+        """fn(rank) on every rank's thread -> [result]; the first exception of any rank is re-raised here."""
+        import threading
+        results, errors = [None] * self.world, []
+
+        def work(rank):
+            self.local.rank = rank
+            try:
+                results[rank] = fn(rank)
+            except BaseException as e:                       # noqa: B902 -- re-raised below; the others leave their barrier
+                errors.append(e)
+                self.barrier.abort()
+        threads = [threading.Thread(target=work, args=(r,)) for r in range(self.world)]
+        for t in threads:
+            t.start()
+        for t in threads:
+            t.join()
+        if errors:
+            real = [e for e in errors if not isinstance(e, threading.BrokenBarrierError)]
+            raise (real or errors)[0]
+        return results
+
+
+@pytest.mark.parametrize('name', ['1024/300 x3', '1024/128 x4'])
+def test_time_sharded_oracle_three_and_four_ranks_in_one_process(name, monkeypatch):
+    """separate_time_sharded itself with a middle rank: the NumPy shard at world 3 with a hop that does not divide n_fft, and at world 4
+    with three shards of exactly `halo` frames.  The ranks are threads and the two collectives are played by hand (_ThreadGroup); the
+    stitched waveform equals the one-shard run of the same oracle within the bar of the two-rank gloo test, and the segments tile."""
+    import time_shard_cases as C
+    from gcc_nmf_amd import distributed as D
+    from oracle.time_shard_oracle import NumpyTimeShard
+    n_fft, hop, world, n, numTDOAs = C.CASES[name]
+    T, halo, split = C.describe(name)
+    x = C.mixture(n)
+    kw = dict(windowSize=n_fft, hopSize=hop, numTDOAs=numTDOAs, numTargets=C.NUM_TARGETS, dictionarySize=16)
+    one = NumpyTimeShard(x, 0, 1, **kw)
+    y1 = D.stitch_time_shards([D.separate_time_sharded(one, 5)], C.NUM_TARGETS, T, hop)
+    assert one.idx == C.PEAKS[name] and np.isfinite(y1).all() and np.abs(y1).max() > 0
+
+    group = _ThreadGroup(world)
+    monkeypatch.setattr(D, 'dist', group)
+    shards = [NumpyTimeShard(x, r, world, **kw) for r in range(world)]
+    assert [s.t1 - s.t0 for s in shards] == split and all(s.halo == halo and s.T_total == T for s in shards)
+    parts = group.run(lambda r: D.separate_time_sharded(shards[r], 5))
+    monkeypatch.undo()
+    parts = [(np.array(seg), int(start)) for seg, start in parts]
+    assert all(np.array_equal(shards[0].W, s.W) and s.idx == one.idx for s in shards)
+    assert parts[0][1] == -(n_fft // 2), 'the first segment starts at %d, not at the centre trim -%d' % (parts[0][1], n_fft // 2)
+    for r in range(world - 1):
+        assert parts[r][1] + parts[r][0].shape[2] == parts[r + 1][1], 'segments %d and %d do not tile' % (r, r + 1)
+    assert parts[-1][0].shape[2] == (split[-1] - 1) * hop + n_fft
+    y = D.stitch_time_shards(parts, C.NUM_TARGETS, T, hop)
+    err = np.abs(y - y1).max(axis=(0, 1))
+    print('%s: T %d, halo %d, split %s: max |y - y1| %.3e of max |y1| %.3e' % (name, T, halo, split, err.max(), np.abs(y1).max()))
+    assert err.max() < 1e-5 * np.abs(y1).max(), 'first sample off: %d (seams at %s)' % (int(np.argmax(err >= 1e-5 * np.abs(y1).max())),
+                                                                                       [p[1] for p in parts[1:]])
