@@ -123,3 +123,37 @@ def speech_in_noise_mixture(seed, snrDb, numSamples=64000, sampleRate=16000, del
     scale = 0.1 / np.max(np.abs(x))
     pcm = np.round(x * scale * 32768).astype(np.int16)
     return (pcm.astype('float32') / 32768).astype(np.float32), clean * scale
+
+
+def array_mixture(seed, microphonePositions, azimuthsDeg, numSamples=16000, sampleRate=16000, returnImages=False,
+                  speedOfSound=340.29):
+    """Far-field talkers in front of a microphone array: one low-passed noise source with a syllable-rate on/off envelope per azimuth
+    (as ``reverberant_mixture`` builds its talkers), arriving from the unit vector u = (cos az, sin az, 0).  Microphone m at position
+    r_m hears the talker delayed by -r_m . u / c -- applied as a circular phase ramp in the frequency domain, so fractional delays are
+    exact -- plus a little independent sensor noise; int16-representable float32 samples as in synthetic_mixture.  Returns the mixture
+    (M, numSamples) float32; with ``returnImages`` also the per-talker, per-channel images (J, M, numSamples), float64, on the
+    mixture's scale (they add up to the mixture before the sensor noise and the int16 rounding)."""
+    from scipy.signal import butter, lfilter
+    r = np.asarray(microphonePositions, np.float64)
+    if r.ndim != 2 or r.shape[1] != 3:
+        raise ValueError('microphonePositions must have shape (M, 3), got %s' % (r.shape,))
+    rng = np.random.default_rng(20261021 + seed)
+    t = np.arange(numSamples) / float(sampleRate)
+    freqs = np.fft.rfftfreq(numSamples, 1.0 / sampleRate)
+    b, a = butter(4, 4000.0 / (sampleRate / 2.0))
+    images = []
+    for j, az in enumerate(np.deg2rad(np.asarray(azimuthsDeg, np.float64))):
+        s = lfilter(b, a, rng.standard_normal(numSamples))
+        phi = rng.uniform(0, 2 * np.pi)
+        s = s * (0.5 * (1 + np.sin(2 * np.pi * (2.0 + 0.7 * j) * t + phi))) ** 4
+        u = np.array([np.cos(az), np.sin(az), 0.0])
+        delays = -r.dot(u) / float(speedOfSound)
+        spectrum = np.fft.rfft(s)
+        images.append(np.stack([np.fft.irfft(spectrum * np.exp(-2j * np.pi * freqs * d), numSamples) for d in delays]))
+    images = np.stack(images)
+    x = images.sum(axis=0)
+    x = x + rng.normal(0, 1e-2 * np.std(x), x.shape)
+    scale = 0.1 / np.max(np.abs(x))
+    pcm = np.round(x * scale * 32768).astype(np.int16)
+    x = (pcm.astype('float32') / 32768).astype(np.float32)
+    return (x, images * scale) if returnImages else x
