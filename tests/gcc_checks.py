@@ -41,6 +41,28 @@ def check_gemm_like(got, ref64, absprod, Kd, c=2.0, what='result'):
                              % (what, int(bad.sum()), i, got[i], ref64[i], err[i], bound[i], Kd))
 
 
+def gemm_share(got, ref64, absprod, Kd, c=2.0):
+    """The largest |got - ref64| / gemm_bound(absprod, Kd, c) over the elements (0 / 0 counts as 0, a non-finite element as inf)."""
+    got = np.asarray(got)
+    if got.size == 0:
+        return 0.0
+    if not np.isfinite(got).all():
+        return float('inf')
+    err = np.abs(got.astype(np.complex128 if np.iscomplexobj(got) or np.iscomplexobj(ref64) else np.float64) - np.asarray(ref64))
+    bound = np.broadcast_to(gemm_bound(absprod, Kd, c), err.shape)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        share = np.where(err == 0, 0.0, err / bound)
+    return float(share.max())
+
+
+def report_gemm_like(got, ref64, absprod, Kd, c=2.0, what='result'):
+    """check_gemm_like, which prints the worst share of its bar before it asserts -> that share."""
+    share = gemm_share(got, ref64, absprod, Kd, c)
+    print('%s: worst share of the bar (%d * 2^-24 absprod) %.4f' % (what, c * (Kd + 4), share))
+    check_gemm_like(got, ref64, absprod, Kd, c, what)
+    return share
+
+
 def check_written(got, what='output'):
     """Every element finite: the buffers are NaN-filled before the call, so a NaN left is an element the kernel did not write."""
     bad = ~np.isfinite(np.asarray(got))

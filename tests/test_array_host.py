@@ -1,7 +1,8 @@
 """CPU-only checks of the microphone-array feature: the float64 restatement tests/array_restatement.py against the
-stereo restatements and the oracle at M = 2; the geometry helpers; the restatement's peaks on a synthetic 4-microphone line; planted
-mistakes against the float64 checks the device tests use; the constructor's argument rules (no device needed); header, ctypes table and
-exported symbols of libgccnmf_array.so; every argument rule of its C entry points (decided before any launch, so dummy pointers do)."""
+stereo restatements and the oracle at M = 2; the geometry helpers; the restatement's peaks on a synthetic 4-microphone line and on the
+mixtures of the engine tests at 5 to 8 microphones; planted mistakes against the float64 checks the device tests use, at the stacked cells
+of tests/stacked_pairs.py among them; the constructor's argument rules (no device needed); header, ctypes table and exported symbols of
+libgccnmf_array.so; every argument rule of its C entry points (decided before any launch, so dummy pointers do)."""
 import ctypes
 import os
 import re
@@ -15,6 +16,7 @@ import array_restatement as A
 import fft_checks as K
 import gcc_checks as C
 import ratio_restatement as R
+import stacked_pairs as SP
 from oracle import gccnmf_oracle as O
 
 HEADER = os.path.join(REPO, 'include', 'gccnmf_array.h')
@@ -186,6 +188,95 @@ def test_planted_mistakes_fail_the_float64_checks():
     assert not (np.abs(A.istft(spec[[1, 0, 2, 3]], w, 64, 16, 0.5)[0] - y) <= bar).all()
     ref_y = O.istft(spec[2], 16, 64, w) * 0.5
     assert np.abs(ref_y - y[2]).max() < 1e-5
+
+
+# ---- the stacked cells of tests/test_gpu_stacked_pairs.py see the mistakes they are for --------------------------------------------------------
+def failing(out, f, cell):
+    """The names of the checks of stacked_pairs.checks() -- the functions the device test calls -- that `out` does not pass."""
+    names = []
+    for name, check in SP.checks(out, f, *cell[:6]):
+        try:
+            check()
+        except AssertionError:
+            names.append(name)
+    return names
+
+
+# cells 1, 3 and 4: the ring kernel with a k-tail, a scores reduction beyond the ring, no k-tail
+PLANTED_CELLS = [(8, 33, 33, 3, 70, 5, 1, 2, 1), (7, 257, 33, 3, 64, 5, 1, 2, 1), (6, 41, 200, 4, 129, 65, 1, 1, 1)]
+
+
+@pytest.mark.parametrize('cell', PLANTED_CELLS, ids=['M%d-F%d' % c[:2] for c in PLANTED_CELLS])
+def test_stacked_cells_see_the_mistakes_they_are_for(cell):
+    from gcc_nmf_amd.array import array_steering_tables
+    assert SP.kernels(*cell) == SP.CELLS[cell]
+    M, F, D, S, K, T = cell[:6]
+    Pn, Fp, Fs = SP.shapes(M, F)
+    assert Fp > F, 'a pitch of F differs from the pitch Fp'
+    f = SP.host_file(M, F, D, S, K, T, 7 * F + M)
+    trig = array_steering_tables(SP.frequencies(F), SP.pair_tdoas(M, D), Fp, SP.rup(D, 64))
+    CC, Ws = SP.stacked_operands(f, Fp, SP.rup(K, 64), SP.rup(T, 64))
+    assert CC.shape[1] == Pn * Fp == SP.rup(Fs, 16)
+    run = lambda CC, Ws: failing(SP.evaluate(CC, trig, Ws, f['tdoa'], D, S, K, T), f, cell)
+    assert run(CC, Ws) == [], 'the float64 evaluation of the stacked buffers, rounded to float32, passes every check'
+    both = ['angular', 'steering', 'scores']
+    # 1. two pairs exchanged (the second and the last)
+    a, b = Fp, (Pn - 1) * Fp
+    wrong = CC.copy()
+    wrong[:, a:a + Fp], wrong[:, b:b + Fp] = CC[:, b:b + Fp], CC[:, a:a + Fp]
+    assert run(wrong, Ws) == both
+    # 2. pair blocks pitched by F where Fp is meant: the second block starts in the first one's padding rows (which stay zero in the
+    #    steering products: the steering table is zero there)
+    wrong = np.zeros_like(CC)
+    for p in range(Pn):
+        wrong[:, p * F:(p + 1) * F] = CC[:, p * Fp:p * Fp + F]
+    assert run(wrong, Ws) == both
+    # 3. the last pair's Nyquist bin dropped from the scores (the rank-1 k-tail term where the cell has one)
+    wrong = Ws.copy()
+    wrong[(Pn - 1) * Fp + F - 1] = 0
+    assert run(CC, wrong) == ['scores']
+    # 4. W copied under P - 1 of the P blocks
+    wrong = Ws.copy()
+    wrong[(Pn - 1) * Fp:] = 0
+    assert run(CC, wrong) == ['scores']
+
+
+def test_a_reused_second_accumulator_fails_the_ratio_check_at_five_targets():
+    """tests/test_gpu_array_stages.py at S = 4 ... 7: target 4 of the row that carries targets g and g + 4 takes target 0's numerator."""
+    M, F, T, Kk, S = 3, 33, 20, 16, 5
+    X, W, H, am, masks = random_problem(M, F, T, Kk, S, 9)
+    for form, mk, den in (('one-hot', A.one_hot(am, S), A.denominators(W, H, M, argmax=am, S=S)),
+                          ('soft', masks, A.denominators(W, H, M, masks=masks))):
+        num = A.numerators(W, H, mk, M)
+        ref = A.ratio_one_hot(W, H, am, S, X) if form == 'one-hot' else A.ratio_soft(W, H, masks, X)
+        bound = np.broadcast_to(np.abs(X)[None], ref.shape)
+        assert np.array_equal(X[None] * (num / den[None]), ref)
+        C.check_gemm_like(ref.astype(np.complex64), ref, bound, Kk, what=form)
+        num[4] = num[0]
+        wrong = (X[None] * (num / den[None])).astype(np.complex64)
+        C.check_gemm_like(wrong[:4], ref[:4], bound[:4], Kk, what=form)
+        with pytest.raises(AssertionError):
+            C.check_gemm_like(wrong, ref, bound, Kk, what=form)
+
+
+# ---- the mixtures of the engine tests at 5 to 8 microphones -------------------------------------------------------------------------------------
+CASES_5_TO_8 = [(c, SP.ENGINE_CASES[c], SP.ENGINE_SHAPE) for c in SP.ENGINE_CASES] + [(SP.CORNER_CASE, SP.CORNER_SEED, SP.CORNER_SHAPE)]
+
+
+@pytest.mark.parametrize('case,seed,shape', CASES_5_TO_8, ids=['M%d-b%d-S%d-n_fft%d' % (c + (s['n_fft'],)) for c, _, s in CASES_5_TO_8])
+def test_the_restatement_alone_finds_the_talkers_of_the_engine_mixtures(case, seed, shape):
+    """tests/test_gpu_array_engine.py asserts status == 0 for these files: a condition on the inputs, settled here without a device.  Every
+    chosen peak stands above both neighbours by more than 2 % of the mean spectrum's range -- the float32 spectrogram is within
+    2 (2 P F + 4) 2^-24 of the sum of moduli, a thousand times less."""
+    M, B, S = case
+    tau = SP.pair_tdoas(M, shape['D'])
+    assert len({tuple(np.round(row * 1e9).astype(np.int64)) for row in np.concatenate([tau, -tau])}) == M * (M - 1), 'no two pair vectors are equal'
+    xs = SP.engine_mixtures(M, B, S, seed, shape['n'])
+    assert xs.shape == (B, M, shape['n'])
+    for b in range(B):
+        idx, status, clear = SP.reference_peaks(xs[b], shape['n_fft'], shape['hop'], shape['D'], S)
+        print('M = %d file %d: peaks %s, the least clear one by %.3f of the range' % (M, b, idx, clear))
+        assert status == 0 and idx == [13, 30, 43][:S] and clear > 0.02
 
 
 # ---- the engine's argument rules: ValueError before a device is looked for ------------------------------------------------------------------

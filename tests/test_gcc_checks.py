@@ -72,6 +72,16 @@ def test_gemm_bound_catches(mutate):
     got = mutate(A, B, np.dot(A, B))
     with pytest.raises(AssertionError):
         C.check_gemm_like(got, ref, absprod, A.shape[1])
+    assert C.gemm_share(got, ref, absprod, A.shape[1]) > 1, 'the printed share of the bar says what the check says'
+    with pytest.raises(AssertionError):
+        C.report_gemm_like(got, ref, absprod, A.shape[1])
+
+
+def test_the_printed_share_is_below_one_where_the_check_passes():
+    A, B, ref, absprod = gemm_case()
+    assert 0 < C.report_gemm_like(np.dot(A, B), ref, absprod, A.shape[1]) < 1
+    assert C.gemm_share(ref.astype(np.complex64), ref.astype(np.complex128), absprod, A.shape[1]) < 1
+    assert C.gemm_share(np.zeros((0, 3)), np.zeros((0, 3)), np.zeros((0, 3)), 5) == 0
 
 
 def test_padding_set_to_one_is_caught():

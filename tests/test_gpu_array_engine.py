@@ -5,7 +5,9 @@ nmf_groups=1).  (The stereo engine takes its coherence from the STFT epilogue, w
 array engine's is gccnmf_coherence's arithmetic, so the stereo engine's CC is replaced by that call on its own X before the comparison,
 and whether the epilogue's bits were the same is printed.)
 
-M = 3 (odd: the STFT's spare signal slot, a spare spectrogram slot for odd S M) and M = 4, stage by stage against the float64 restatement
+M = 3 (odd: the STFT's spare signal slot, a spare spectrogram slot for odd S M) and M = 4 on the line LINE, M = 5 ... 8 on an unequally
+spaced eight-microphone line (tests/stacked_pairs.py: no two pair vectors equal, mixtures chosen on the host by tests/test_array_host.py),
+and one call at the corner of the envelope (M = 8, n_fft = 4096), stage by stage against the float64 restatement
 tests/array_restatement.py, every stage fed the device's OWN previous stage, with the element-wise bounds of gcc_checks / fft_checks:
   angular spectrogram   gemm_bound at Kd = 2 P F (cos and sin products of every pair's F bins)
   its mean              check_mean;  peaks: check_peaks, exact
@@ -20,6 +22,7 @@ import pytest
 import array_restatement as A
 import fft_checks as K
 import gcc_checks as C
+import stacked_pairs as SP
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
@@ -70,19 +73,19 @@ def test_two_channels_are_the_stereo_engine_bit_for_bit():
     assert np.array_equal(a.get_C()[:, 0], e.get_C())
 
 
-def run_stages(M, B, S, seed):
+def run_stages(M, B, S, seed, line=LINE, n=4096, n_fft=256, hop=64, Kk=32, D=61, iters=5):
     from gcc_nmf_amd import _hip
     from gcc_nmf_amd.array import GCCNMFArrayEngine, azimuthDirections
     from gcc_nmf_amd.synthetic import array_mixture
-    n, n_fft, hop, Kk, D, iters = 4096, 256, 64, 32, 61, 5
     azimuths = [40, 90, 130][:max(S, 2)]
-    xs = np.stack([array_mixture(seed + b, LINE[:M], azimuths, n, 16000) for b in range(B)])
+    xs = np.stack([array_mixture(seed + b, line[:M], azimuths, n, 16000) for b in range(B)])
     dirs = azimuthDirections(D)
-    e = GCCNMFArrayEngine(n, numChannels=M, microphonePositions=LINE[:M], directions=dirs, speedOfSound=SOUND, windowSize=n_fft,
+    e = GCCNMFArrayEngine(n, numChannels=M, microphonePositions=line[:M], directions=dirs, speedOfSound=SOUND, windowSize=n_fft,
                           hopSize=hop, numTargets=S, dictionarySize=Kk, numIterations=iters, batch=B)
     P, F, T = e.P, e.F, e.T
-    assert (F, T, e.Fs, e.N) == (129, 61, (P - 1) * 144 + 129, M * 61) and e.nsig_pitch == S * M + (S * M) % 2
-    tau = A.pair_tdoas_from_geometry(LINE[:M], A.azimuth_directions(D), SOUND)
+    Fp = -(-F // 16) * 16
+    assert (F, T, e.Fs, e.N) == (n_fft // 2 + 1, 1 + (n - n_fft) // hop, (P - 1) * Fp + F, M * T) and e.nsig_pitch == S * M + (S * M) % 2
+    tau = A.pair_tdoas_from_geometry(line[:M], A.azimuth_directions(D), SOUND)
     assert np.array_equal(e.pairTDOAs, tau)
     y = e.separate(xs)
     what = 'M=%d batch=%d S=%d' % (M, B, S)
@@ -110,20 +113,21 @@ def run_stages(M, B, S, seed):
         assert np.abs(V[b] - ref_V).max() <= K.HYPOT_U * U * np.abs(ref_V).max(), what
         assert np.abs(Cd[b] - ref_C).max() <= (4 + 2 * K.HYPOT_U) * U * (1 + 1e-5) * np.sqrt(2), what
         ref_ang, absprod = A.angular(Cd[b], freqs, tau)
-        C.check_gemm_like(ang[b], ref_ang, absprod, 2 * P * F, what='%s angular spectrogram of file %d' % (what, b))
+        C.report_gemm_like(ang[b], ref_ang, absprod, 2 * P * F, what='%s angular spectrogram of file %d' % (what, b))
         C.check_mean(mean[b], ang[b], '%s mean of file %d' % (what, b))
         C.check_peaks(idx[b], status[b], mean[b], S, '%s peaks of file %d' % (what, b))
         assert status[b] == 0, 'the mixtures are chosen so that every file has its peaks'
         ref_G, absG = A.scores(Cd[b], Wd[b], freqs, tau, idx[b])
-        C.check_gemm_like(sc[b], ref_G, absG, P * F, what='%s scores of file %d' % (what, b))
+        C.report_gemm_like(sc[b], ref_G, absG, P * F, what='%s scores of file %d' % (what, b))
         C.check_argmax(am[b], sc[b], '%s arg-max of file %d' % (what, b))
         ref_spec = A.ratio_one_hot(Wd[b], Hd[b], am[b], S, X[b])
         assert (A.denominators(Wd[b], Hd[b], M, argmax=am[b], S=S) > 0).all()
-        C.check_gemm_like(spec[b], ref_spec, np.broadcast_to(np.abs(X[b])[None], ref_spec.shape), Kk, what='%s spec of file %d' % (what, b))
+        C.report_gemm_like(spec[b], ref_spec, np.broadcast_to(np.abs(X[b])[None], ref_spec.shape), Kk, what='%s spec of file %d' % (what, b))
         slots = torch.view_as_complex(e.spec)[b, :, :F, :T].cpu().numpy()
         ref_y, bar = A.istft(slots, w, n_fft, hop, hop / float(n_fft) * 2)
         got_y = e._y[b].cpu().numpy()
         err = np.abs(got_y - ref_y)
+        print('%s waveforms of file %d: worst share of the bar %.4f' % (what, b, (err / np.maximum(bar, 1e-300)).max()))
         assert (err <= bar).all(), '%s waveforms of file %d: worst share of the bar %.3g' % (what, b, (err / np.maximum(bar, 1e-300)).max())
         assert np.array_equal(got_y[:S * M].reshape(S, M, -1), y[b])
         if e.nsig_pitch > S * M:
@@ -144,6 +148,23 @@ def run_stages(M, B, S, seed):
 @pytest.mark.parametrize('M,B,S', [(4, 2, 3), (3, 1, 3), (3, 3, 2)], ids=['M4-b2-S3', 'M3-b1-S3', 'M3-b3-S2'])
 def test_stage_by_stage_against_float64(M, B, S):
     run_stages(M, B, S, 10 * M + B)
+
+
+@pytest.mark.parametrize('M,B,S', list(SP.ENGINE_CASES), ids=['M%d-b%d-S%d' % c for c in SP.ENGINE_CASES])
+def test_five_to_eight_microphones_stage_by_stage_against_float64(M, B, S):
+    """B M odd at (5, 1, 2): the STFT's spare signal slot; B M and S M odd at (7, 1, 3): the spare spectrogram slot stays zero; at M = 8
+    the stacked calls run at Fs = 4017 bins."""
+    e = run_stages(M, B, S, SP.ENGINE_CASES[(M, B, S)], line=SP.LINE8, **SP.ENGINE_SHAPE)
+    assert e.P == M * (M - 1) // 2 and (M < 8 or e.Fs == 4017)
+    assert e.get_tdoa_indexes().tolist() == [[13, 30, 43][:S]] * B, 'the talkers at 40, 90 and 130 degrees of a 61-point scan'
+
+
+def test_the_corner_of_the_envelope_stage_by_stage_against_float64():
+    """Eight microphones at the longest window: Fs = 57777 stacked bins (grid extent 57792 of 65535), three frames, K = 16, two iterations."""
+    M, B, S = SP.CORNER_CASE
+    e = run_stages(M, B, S, SP.CORNER_SEED, line=SP.LINE8, Kk=16, iters=2, **SP.CORNER_SHAPE)
+    assert (e.F, e.T, e.Fs, e.P * e.Fp) == (2049, 3, 57777, 57792)
+    assert e.get_tdoa_indexes().tolist() == [[13, 30]]
 
 
 def test_the_line_array_finds_its_three_talkers():

@@ -8,7 +8,11 @@ channel 0 is channel c; and it is within gcc_checks.check_gemm_like(Kd = K) of t
 to |X|: num_i and den are chains of at most K fma of non-negative terms (relative error <= K u each, no cancellation; the soft form's
 mask products add one rounding per term, the one-hot form's S - 1 additions of den replace as many fma that a masked-out term makes
 exact), num_i <= den, one quotient and one product: at most (2 K + 4) u |X| <= 2 (K + 4) u |X|, the bound of check_gemm_like with
-absprod = |X|.  A NaN planted in W must come out as NaN exactly where the restatement has NaN."""
+absprod = |X|.  A NaN planted in W must come out as NaN exactly where the restatement has NaN.  The stereo planes of the bit comparison
+meet the same bound themselves, so that the stereo kernel's instantiations for 4 to 7 targets are checked against a reference too.
+
+Every channel count 2 ... 8 (pair indexes up to 27) and every target count 1 ... 8 runs, the latter in both forms; CASES says which row tile
+shapes of the reconstruction (128 rows a tile, the last row of F = 32 n + 1 on the VALU) each F stands for."""
 import numpy as np
 import pytest
 
@@ -64,12 +68,11 @@ def feature_spectra(B, M, F, T, seed):
     return X
 
 
-@pytest.mark.parametrize('T', [2, 64, 67])
-@pytest.mark.parametrize('M', [2, 3, 4])
-def test_features_are_the_stereo_kernels_per_pair_and_channel(libs, M, T):
+def features_case(M, T, F):
     from gcc_nmf_amd import _array, _hip
-    B, F, Fp = 3, 33, 48
+    B, Fp = 3, rup(F, 16)
     Tp, Np, Np2, P = rup(T, 64), rup(M * T, 64), rup(2 * T, 64), M * (M - 1) // 2
+    assert len(A.pairs(M)) == P
     X = feature_spectra(B, M, F, T, 10 * M + T)
     dX = dev(padded_X(X, Fp, Tp))
     V = torch.full((B, Fp, Np), NAN, dtype=torch.float32, device='cuda')
@@ -83,11 +86,14 @@ def test_features_are_the_stereo_kernels_per_pair_and_channel(libs, M, T):
     C.check_zero(blocks[:, :, :, :, T:].cpu().numpy(), 'CC frames >= T')
     C.check_zero(V[:, F:, :].cpu().numpy(), 'V rows >= F')
     C.check_zero(V[:, :, M * T:].cpu().numpy(), 'V columns >= M T')
+    wrong = []
     for p, (a, b) in enumerate(A.pairs(M)):
         Xs = dX[:, [a, b]].contiguous()
         CCs = torch.zeros((B, 2, Fp, Tp), dtype=torch.float32, device='cuda')
         _hip.coherence(Xs, F, T, B, CCs)
-        assert same_bits(blocks[:, :, p, :F, :T], CCs[:, :, :F, :T]), 'pair %d = (%d, %d)' % (p, a, b)
+        if not same_bits(blocks[:, :, p, :F, :T], CCs[:, :, :F, :T]):
+            wrong.append((p, (a, b)))
+    assert not wrong, 'blocks that are not gccnmf_coherence of their pair, as (p, (a, b)): %s' % wrong
     c = blocks[:, :, :, :F, :T].cpu().numpy()
     assert (c[:, :, :, F - 1, T - 1] == 0).all() and (c[:, :, :M - 1, 1, 0] == 0).all(), 'a zero magnitude gives (0, 0)'
     assert np.abs(np.hypot(c[0, 0, 0, 7, 1], c[0, 1, 0, 7, 1]) - 1) < 1e-5, 'a tiny bin keeps its phase'
@@ -108,6 +114,20 @@ def test_features_are_the_stereo_kernels_per_pair_and_channel(libs, M, T):
     assert same_bits(Va[0], V[1]) and same_bits(Ca[0], CC[1]), 'a file alone gives the bits it gives in the batch'
     ref_V, ref_C = A.features(X[1])
     assert np.abs(V[1, :F, :M * T].cpu().numpy() - ref_V).max() <= 4 * 2.0 ** -24 * np.abs(ref_V).max()
+
+
+@pytest.mark.parametrize('T', [2, 64, 67])
+@pytest.mark.parametrize('M', [2, 3, 4, 5, 6, 7, 8])
+def test_features_are_the_stereo_kernels_per_pair_and_channel(libs, M, T):
+    """F = 33: fifteen padding rows (Fp - F = 15) between the pair blocks."""
+    features_case(M, T, 33)
+
+
+@pytest.mark.parametrize('M,T,F', [(8, 67, 48), (3, 2, 32)])
+def test_features_without_padding_rows_between_the_pairs(libs, M, T, F):
+    """F = Fp: pair p + 1 starts in the row after pair p's last bin."""
+    assert F % 16 == 0
+    features_case(M, T, F)
 
 
 # ---- reconstruction ---------------------------------------------------------------------------------------------------------------------------
@@ -155,8 +175,20 @@ def stereo_planes(hip_mod, dW, dH, dA, dM, dX, c, M, F, T, K, S, soft):
     return spec.view(B, S, 2, Fp, Tp, 2)[:, :, 0]
 
 
-# (M, F, K, T, S): every value of each parameter at least once, and the corner (M = 5, F = 33, K = 70, T = 70, S = 8)
-CASES = [(2, 33, 5, 3, 1), (3, 41, 16, 64, 2), (5, 33, 70, 70, 8), (3, 33, 16, 70, 3), (2, 41, 70, 64, 3), (5, 41, 5, 3, 2)]
+# (M, F, K, T, S): every M in 2 ... 8, every S in 1 ... 8 (each in both forms), K in 5 / 16 / 70 and T in 3 / 64 / 70 at least once each, and
+# every row-tile shape of the reconstruction: F = 33 tail, one tile; 41 no tail, one tile; 129 tail, 128 MFMA rows, exactly one tile; 161 tail,
+# 160 MFMA rows, a second tile of 32; 200 no tail, Fp = 208, a partial second tile (the min(row, Fp - 1) clamp); 257 tail, exactly two tiles.
+CASES = [(2, 33, 5, 3, 1),         # the smallest of everything
+         (3, 41, 16, 64, 2),
+         (5, 33, 70, 70, 8),       # both accumulator sets of the tail row in full
+         (3, 33, 16, 70, 3),
+         (2, 41, 70, 64, 3),
+         (5, 41, 5, 3, 2),
+         (4, 129, 16, 3, 4),       # S = 4: the first set full, the second unused; one tile exactly
+         (6, 161, 5, 64, 5),       # S = 5: one target in the second set; a second tile of 32 rows under a tail
+         (7, 200, 70, 3, 6),       # S = 6; the clamp path
+         (3, 257, 16, 64, 7),      # S = 7; two full tiles under a tail
+         (8, 257, 70, 70, 8)]      # the corner
 
 
 @pytest.mark.parametrize('soft', [False, True], ids=['one-hot', 'soft'])
@@ -176,20 +208,24 @@ def test_reconstruct_is_the_stereo_kernel_per_channel_and_within_the_float64_bou
     C.check_zero(planes[:B - 1, :, :, F:].cpu().numpy(), 'rows >= F')
     C.check_zero(planes[:, :, :, :, T:].cpu().numpy(), 'frames >= T')
     C.check_zero(planes[B - 1, :, :, F:].cpu().numpy(), 'rows >= F of the file with the NaN')
+    stereo = torch.empty_like(planes)
     for c in range(M):
-        want = stereo_planes(_hip, dW, dH, dA, dM, dX, c, M, F, T, K, S, soft)
-        assert same_bits(planes[:, :, c], want), 'channel %d' % c
-    got = planes[:, :, :, :F, :T].cpu().numpy()
-    got = (got[..., 0] + 1j * got[..., 1]).astype(np.complex64)
+        stereo[:, :, c] = stereo_planes(_hip, dW, dH, dA, dM, dX, c, M, F, T, K, S, soft)
+        assert same_bits(planes[:, :, c], stereo[:, :, c]), 'channel %d' % c
+    got, got_stereo = [(a[..., 0] + 1j * a[..., 1]).astype(np.complex64) for a in (planes[:, :, :, :F, :T].cpu().numpy(),
+                                                                                    stereo[:, :, :, :F, :T].cpu().numpy())]
     for b in range(B):
         ref = A.ratio_soft(W[b], H[b], masks[b], X[b]) if soft else A.ratio_one_hot(W[b], H[b], am[b], S, X[b])
         nan = np.isnan(ref)
-        assert np.array_equal(np.isnan(got[b]), nan), 'file %d: NaN exactly where the restatement has NaN' % b
         assert nan.any() == (b == B - 1)
         if b == B - 1:
             assert nan[:, :, F // 2, :].all() and not np.delete(nan, F // 2, axis=2).any()
-        C.check_gemm_like(np.where(nan, 0, got[b]), np.where(nan, 0, ref), np.broadcast_to(np.abs(X[b])[None], ref.shape), K,
-                          what='file %d' % b)
+        # (the stereo planes are checked on their own, not through the bit comparison above: they are gcc_ratio_kernel's only float64 check
+        # at 4 to 7 targets)
+        for name, g in (('array', got[b]), ('stereo', got_stereo[b])):
+            assert np.array_equal(np.isnan(g), nan), '%s kernel, file %d: NaN exactly where the restatement has NaN' % (name, b)
+            C.report_gemm_like(np.where(nan, 0, g), np.where(nan, 0, ref), np.broadcast_to(np.abs(X[b])[None], ref.shape), K,
+                               what='%s kernel, file %d' % (name, b))
     assert (got[0, :, M - 1, :, T // 2] == 0).all(), 'den = 0: every target is exactly 0'
     assert (np.abs(got[0, :, M - 1, :, (T // 2 + 1) % T]) > 0).any() or T == 1
     # a file alone, and in another place of the batch
