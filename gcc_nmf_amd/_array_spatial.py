@@ -1,0 +1,78 @@
+"""ctypes binding of libgccnmf_array_spatial.so (include/gccnmf_array_spatial.h): the M x M spatial (multichannel Wiener) filter of
+``array.py`` (``GCCNMFArrayEngine(reconstruction='spatial')``).
+
+A library of its own beside libgccnmf_hip.so and libgccnmf_array.so, with the same conventions: the status codes and ``HipLibraryError``
+of ``_hip``, NO CPU fallback -- a missing library, a missing symbol or a missing device is an error on every call path.  Below ``lib()``:
+one plain function per entry point (pointers are tensors, the stream defaults to torch's current one).
+"""
+import ctypes
+import os
+
+import torch
+
+from ._hip import HipLibraryError, check, _ptr, _stream
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, 'libgccnmf_array_spatial.so')
+
+c_int, c_long, c_void_p = ctypes.c_int, ctypes.c_long, ctypes.c_void_p
+
+MIN_CHANNELS = 2                     # include/gccnmf_array_spatial.h: GCCNMF_ARRAY_SPATIAL_MIN_CHANNELS
+MAX_CHANNELS = 8                     # include/gccnmf_array_spatial.h: GCCNMF_ARRAY_SPATIAL_MAX_CHANNELS
+MAX_TARGETS = 8                      # include/gccnmf_array_spatial.h: GCCNMF_ARRAY_SPATIAL_MAX_TARGETS
+LOADING = 1e-3                       # include/gccnmf_array_spatial.h: GCCNMF_ARRAY_SPATIAL_LOADING
+
+# name -> (restype, argtypes); mirrors include/gccnmf_array_spatial.h declaration by declaration
+SIGNATURES = {
+    'gccnmf_array_spatial_version': (c_int, []),
+    'gccnmf_array_spatial_workspace_floats': (c_long, [c_int, c_int, c_int, c_int]),
+    'gccnmf_array_spatial': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+}
+
+_lib = None
+
+
+def lib():
+    """The loaded shared library with typed prototypes; raises HipLibraryError if it cannot be used."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise HipLibraryError(
+            '%s is missing: build it with `python -c "import __graft_entry__ as g; g.build()"` or '
+            '`make -C gcc_nmf_amd/csrc` (hipcc --offload-arch=gfx950). There is no CPU fallback.' % LIB_PATH)
+    try:
+        handle = ctypes.CDLL(LIB_PATH)
+    except OSError as e:
+        raise HipLibraryError('cannot load %s: %s' % (LIB_PATH, e))
+    for name, (restype, argtypes) in SIGNATURES.items():
+        try:
+            fn = getattr(handle, name)
+        except AttributeError:
+            raise HipLibraryError('%s does not export %s (stale build? re-run make -C gcc_nmf_amd/csrc)' % (LIB_PATH, name))
+        fn.restype = restype
+        fn.argtypes = argtypes
+    _lib = handle
+    return _lib
+
+
+def require_device():
+    """HipLibraryError unless the library loads and a ROCm device is visible."""
+    lib()
+    if not torch.cuda.is_available():
+        raise HipLibraryError('no ROCm device visible: the array spatial filter has no CPU fallback')
+
+
+def workspace_floats(M, F, S, batch):
+    """Floats of ``cov`` [batch][S][Fp][M M]; HipLibraryError for a shape the library rejects."""
+    need = lib().gccnmf_array_spatial_workspace_floats(M, F, S, batch)
+    if need < 0:
+        raise HipLibraryError('gccnmf_array_spatial_workspace_floats rejected M = %d, F = %d, S = %d, batch = %d' % (M, F, S, batch))
+    return need
+
+
+def spatial(X, M, F, T, S, batch, nsig_pitch, cov, spec, stream=None):
+    """The covariance launch and the filter launch: spec [batch][nsig_pitch][Fp][Tp][2] (slot i M + c, the ratio-mode estimates) is
+    overwritten in place with the filtered estimates, cov [batch][S][Fp][M M] is written."""
+    check(lib().gccnmf_array_spatial(_ptr(X), M, F, T, S, batch, nsig_pitch, _ptr(cov), _ptr(spec),
+                                     _stream() if stream is None else stream), 'gccnmf_array_spatial')

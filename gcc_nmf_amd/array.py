@@ -12,11 +12,12 @@ Python here is plumbing only, as in ``engine``: every stage is one call into a l
 import numpy as np
 import torch
 
-from . import _array, _hip
+from . import _array, _array_spatial, _hip
 from .engine import (SPEED_OF_SOUND_IN_METRES_PER_SECOND, _on_device, num_frames, klnmf_initial_factors, fft_twiddles, steering_tables,
                      padded)
 
 MAX_DIRECTIONS = 4096
+RECONSTRUCTIONS = ('ratio', 'spatial')
 
 
 def azimuthDirections(numDirections, startDeg=0.0, stopDeg=180.0):
@@ -100,16 +101,22 @@ class GCCNMFArrayEngine(object):
     The candidate directions are an OPEN one-dimensional sequence: a direction is a peak when its mean SRP-PHAT value is larger than
     that of both neighbours in the sequence, so -- as on the stereo path -- the two end points never qualify as peaks.
 
-    Stages are named as in ``GCCNMFEngine``: upload, stft, klnmf, localize, masks, reconstruct, istft, run, separate.  The
-    reconstruction is the ratio mask (the targets of a channel add up to that channel's mixture); at most 8 targets.  With M = 2 and
-    ``pairTDOAs = tdoasInSeconds[None]`` every buffer holds the bits of ``GCCNMFEngine(reconstruction='ratio', nmf_groups=1)``.
+    Stages are named as in ``GCCNMFEngine``: upload, stft, klnmf, localize, masks, reconstruct, istft, run, separate.  At most 8 targets.
+    ``reconstruction='ratio'`` (the default) is the ratio mask: the targets of a channel add up to that channel's mixture, and a mask
+    weights each channel by a real number.  ``reconstruction='spatial'`` runs the M x M spatial (multichannel Wiener) filter behind it
+    (libgccnmf_array_spatial.so, include/gccnmf_array_spatial.h): a spatial covariance per target and bin from the ratio estimates, then
+    S'_i = v_i R_i (sum_j v_j R_j)^-1 X, which combines the channels; ``get_cov()`` returns the covariances.  With M = 2 and
+    ``pairTDOAs = tdoasInSeconds[None]`` every buffer holds the bits of ``GCCNMFEngine(reconstruction=..., nmf_groups=1)`` in the same mode.
 
     ``separate(x)``: (batch, M, n_samples) float32 -> (batch, S, M, hop * (T - 1)) float32."""
 
     def __init__(self, n_samples, numChannels=2, pairTDOAs=None, microphonePositions=None, directions=None,
                  speedOfSound=SPEED_OF_SOUND_IN_METRES_PER_SECOND, sampleRate=16000, windowSize=1024, hopSize=256, numTargets=3,
                  dictionarySize=128, numIterations=100, sparsityAlpha=0, epsilon=1e-16, seedValue=0, batch=1, windowFunction=np.hanning,
-                 device='cuda:0', klnmf_flags=0):
+                 device='cuda:0', klnmf_flags=0, reconstruction='ratio'):
+        if reconstruction not in RECONSTRUCTIONS:
+            raise ValueError("reconstruction must be 'ratio' or 'spatial', got %r" % (reconstruction,))
+        self.reconstruction = reconstruction
         self.M, self.pairTDOAs, S = check_array_arguments(numChannels, pairTDOAs, microphonePositions, directions, speedOfSound,
                                                           numTargets, windowSize)
         self.P = _array.num_pairs(self.M)
@@ -125,6 +132,8 @@ class GCCNMFArrayEngine(object):
             raise _hip.HipLibraryError('no ROCm device visible: the GCC-NMF HIP path has no CPU fallback')
         self.lib = _hip.lib()
         _array.lib()
+        if reconstruction == 'spatial':
+            _array_spatial.lib()
         self.device = torch.device(device)
         self.iters, self.alpha, self.eps, self.seed = int(numIterations), float(sparsityAlpha), float(epsilon), seedValue
         self.batch = B = int(batch)
@@ -174,6 +183,8 @@ class GCCNMFArrayEngine(object):
             self.scores = z(B, Kp, S * Tp)
             self.argmax = torch.zeros((B, Kp, Tp), dtype=torch.uint8, device=dev)
             self.spec = z(B, self.nsig_pitch, Fp, Tp, 2)              # (the spare slot stays zero: the reconstruction does not touch it)
+            # spatial mode: R~ of every (file, target, bin), M M floats a row (include/gccnmf_array_spatial.h)
+            self.cov = z(_array_spatial.workspace_floats(M, F, S, B)).view(B, S, Fp, M * M) if reconstruction == 'spatial' else None
             self.frames = None
             # the stereo engine's rule: the fused inverse transform + overlap-add where the library has one and the launch is large enough
             self.fused_istft = (self.n_fft + 3 * self.hop <= 2048 and self.hop <= self.n_fft
@@ -225,6 +236,8 @@ class GCCNMFArrayEngine(object):
     def reconstruct(self):
         _array.reconstruct(self.W, self.H, self.argmax, None, self.X, self.M, self.F, self.T, self.K, self.S, self.batch, self.nsig_pitch,
                            self.spec)
+        if self.reconstruction == 'spatial':
+            _array_spatial.spatial(self.X, self.M, self.F, self.T, self.S, self.batch, self.nsig_pitch, self.cov, self.spec)
 
     @_on_device
     def istft(self, keep_frames=False):
@@ -300,6 +313,21 @@ class GCCNMFArrayEngine(object):
 
     def get_argmax(self):
         return self.argmax[:, :self.K, :self.T].cpu().numpy()
+
+    def get_cov(self):
+        """(batch, S, F, M, M) complex64: the loaded spatial covariance R~ of every target and bin, the full Hermitian matrix
+        (spatial mode only)."""
+        if self.cov is None:
+            raise ValueError("get_cov() needs reconstruction='spatial'")
+        M = self.M
+        rows = self.cov[:, :, :self.F].cpu().numpy()
+        R = np.zeros((self.batch, self.S, self.F, M, M), np.complex64)
+        for a in range(M):                                    # a row: the M diagonal entries, then (Re, Im) of the pairs in the library's order
+            R[..., a, a] = rows[..., a]
+        for k, (a, b) in enumerate(_array.pairs(M)):
+            R[..., a, b] = rows[..., M + 2 * k] + 1j * rows[..., M + 2 * k + 1]
+            R[..., b, a] = rows[..., M + 2 * k] - 1j * rows[..., M + 2 * k + 1]
+        return R
 
     def get_spec(self):
         """(batch, S, M, F, T) complex64"""
