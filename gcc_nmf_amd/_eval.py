@@ -9,6 +9,7 @@ import os
 
 import torch
 
+from . import _hip
 from ._hip import STATUS, HipLibraryError, check, _ptr, _stream
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -34,32 +35,14 @@ _lib = None
 def lib():
     """The loaded shared library with typed prototypes; raises HipLibraryError if it cannot be used."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise HipLibraryError(
-            '%s is missing: build it with `python -c "import __graft_entry__ as g; g.build()"` or '
-            '`make -C gcc_nmf_amd/csrc` (hipcc --offload-arch=gfx950). There is no CPU fallback.' % LIB_PATH)
-    try:
-        handle = ctypes.CDLL(LIB_PATH)
-    except OSError as e:
-        raise HipLibraryError('cannot load %s: %s' % (LIB_PATH, e))
-    for name, (restype, argtypes) in SIGNATURES.items():
-        try:
-            fn = getattr(handle, name)
-        except AttributeError:
-            raise HipLibraryError('%s does not export %s (stale build? re-run make -C gcc_nmf_amd/csrc)' % (LIB_PATH, name))
-        fn.restype = restype
-        fn.argtypes = argtypes
-    _lib = handle
+    if _lib is None:
+        _lib = _hip.load_library(LIB_PATH, SIGNATURES)
     return _lib
 
 
 def require_device():
     """HipLibraryError unless the library loads and a ROCm device is visible."""
-    lib()
-    if not torch.cuda.is_available():
-        raise HipLibraryError('no ROCm device visible: the scoring kernels have no CPU fallback')
+    _hip.require_device(lib, 'the scoring kernels have')
 
 
 def workspace_bytes(Ma, Mb, n, L, batch):

@@ -172,6 +172,37 @@ def check_tdoa_tracking(tdoaTracking, localizationWindowSize, numSources):
     return bool(tdoaTracking), L
 
 
+def load_library(path, signatures, optional=(), lenient=False):
+    """``ctypes.CDLL(path)`` with typed prototypes: ``signatures`` and ``optional`` map name -> (restype, argtypes).  HipLibraryError if the
+    file is missing, does not load or lacks a name of ``signatures`` (``lenient``: such a name is skipped and stays uncallable); names of
+    ``optional`` are typed where the library has them.  The one loader of the four binding modules."""
+    if not os.path.exists(path):
+        raise HipLibraryError(
+            '%s is missing: build it with `python -c "import __graft_entry__ as g; g.build()"` or '
+            '`make -C gcc_nmf_amd/csrc` (hipcc --offload-arch=gfx950). There is no CPU fallback.' % path)
+    try:
+        handle = ctypes.CDLL(path)
+    except OSError as e:
+        raise HipLibraryError('cannot load %s: %s' % (path, e))
+    for table, required in ((signatures, not lenient), (dict(optional), False)):
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(handle, name, None)
+            if fn is None:
+                if required:
+                    raise HipLibraryError('%s does not export %s (stale build? re-run make -C gcc_nmf_amd/csrc)' % (path, name))
+                continue
+            fn.restype = restype
+            fn.argtypes = argtypes
+    return handle
+
+
+def require_device(lib_fn, what):
+    """HipLibraryError unless ``lib_fn()`` loads its library and a ROCm device is visible; ``what`` names the kernels in the message."""
+    lib_fn()
+    if not torch.cuda.is_available():
+        raise HipLibraryError('no ROCm device visible: %s no CPU fallback' % what)
+
+
 _lib = None
 
 
@@ -180,28 +211,8 @@ def lib():
     global _lib
     if _lib is not None:
         return _lib
-    if not os.path.exists(LIB_PATH):
-        raise HipLibraryError(
-            '%s is missing: build it with `python -c "import __graft_entry__ as g; g.build()"` or '
-            '`make -C gcc_nmf_amd/csrc` (hipcc --offload-arch=gfx950). There is no CPU fallback.' % LIB_PATH)
-    try:
-        handle = ctypes.CDLL(LIB_PATH)
-    except OSError as e:
-        raise HipLibraryError('cannot load %s: %s' % (LIB_PATH, e))
-    for name, (restype, argtypes) in SIGNATURES.items():
-        try:
-            fn = getattr(handle, name)
-        except AttributeError:
-            if os.environ.get('GCCNMF_HIP_LIB'):      # an A/B build of another revision: entry points it lacks are simply not callable
-                continue
-            raise HipLibraryError('%s does not export %s (stale build? re-run make -C gcc_nmf_amd/csrc)' % (LIB_PATH, name))
-        fn.restype = restype
-        fn.argtypes = argtypes
-    for name, (restype, argtypes) in EXPERIMENT_SIGNATURES.items():
-        fn = getattr(handle, name, None)
-        if fn is not None:
-            fn.restype = restype
-            fn.argtypes = argtypes
+    # GCCNMF_HIP_LIB names an A/B build of another revision: entry points it lacks are simply not callable
+    handle = load_library(LIB_PATH, SIGNATURES, optional=EXPERIMENT_SIGNATURES, lenient=bool(os.environ.get('GCCNMF_HIP_LIB')))
     # A/B runs without code changes: GCCNMF_TUNE="9=2,8=1" applies gccnmf_set_tuning(key, value) pairs at load time
     for kv in filter(None, os.environ.get('GCCNMF_TUNE', '').split(',')):
         key, value = [int(v) for v in kv.split('=')]

@@ -9,6 +9,7 @@
 // so each stage is ONE launch for the whole batch.
 #include "gemm_ring.h"
 #include "ratio.h"
+#include "phat.h"
 #include "spatial.h"
 #include "angular_nl.h"
 #include "atom_tdoa.h"
@@ -283,15 +284,8 @@ __global__ __launch_bounds__(256) void gcc_coherence_kernel(const float2* __rest
     const long plane = (long)Fp * Tp;
     const float2 xl = X[(long)b * 2 * plane + (long)f * Tp + t];
     const float2 xr = X[(long)b * 2 * plane + plane + (long)f * Tp + t];
-    const float aL = hypotf(xl.x, xl.y), aR = hypotf(xr.x, xr.y);
-    float re = xl.x * xr.x + xl.y * xr.y, im = xl.y * xr.x - xl.x * xr.y;
-    if (aL > 0.f && aR > 0.f) {
-        re = re / aL / aR;
-        im = im / aL / aR;
-    } else {
-        re = 0.f;   // a bin that is exactly 0 in f32 carries no phase: it contributes nothing (NaN policy)
-        im = 0.f;
-    }
+    float re, im;
+    phat_coherence(xl, xr, re, im);
     float* Cb = CC + (long)b * 2 * plane + (long)f * Tp + t;
     Cb[0] = re;
     Cb[plane] = im;

@@ -1,4 +1,4 @@
-// Ratio-mask (Wiener) reconstruction, one fused launch (ratio.hip).
+// Ratio-mask (Wiener) reconstruction, one fused launch (ratio.hip: the kernel of ratio_kernel.h at two channels).
 #pragma once
 #include "common.h"
 

@@ -38,7 +38,7 @@ int gccnmf_array_version(void);
  *   V  [batch][Fp][Np]:          V[f][c T + t] = hypotf(re, im) of channel c (the operation of gccnmf_magnitude); every padding element
  *                                (rows >= F, columns >= M T) is written as 0.
  *   CC [batch][2][P Fp][Tp]      (Re plane, then Im plane): row p Fp + f of pair p = (a, b) is X_a conj(X_b) / |X_a| / |X_b|, exactly
- *                                the arithmetic of gccnmf_coherence with channel 0 = X_a, channel 1 = X_b, including its rule that a bin
+ *                                the arithmetic of gccnmf_coherence (csrc/phat.h) with channel 0 = X_a, channel 1 = X_b, including its rule that a bin
  *                                whose magnitude is zero in either channel gives (0, 0); every other element of both planes is written as 0.
  * Either output may be NULL.  A file's output does not depend on the batch it is in.
  * GCCNMF_ERR_ARG: M outside 2..8, X null, both outputs null, F < 2, T < 1, batch < 1.
@@ -56,7 +56,8 @@ int gccnmf_array_features(const float* X, int M, int F, int T, int batch, float*
  *                = sum_k W[f,k] H_c[k,t]              soft form, the same chain
  *     spec[i M + c] = X_c * (num_i / den)             the IEEE quotient, then one real x complex product; 0 for every i where den <= 0
  * Every element of the S M written slots is stored: rows >= F and frames >= T as zeros.  One tile shape whatever F, K, S and the batch:
- * a file's output does not depend on the batch or on its place in it.  At M = 2 the output is gccnmf_reconstruct's, bit for bit.
+ * a file's output does not depend on the batch or on its place in it.  At M = 2 the output is gccnmf_reconstruct's, bit for bit: both libraries
+ * instantiate the one kernel of csrc/ratio_kernel.h.
  * GCCNMF_ERR_ARG: a null W, H, X or spec, argmax and masks both null, M outside 2..8, F < 2, T < 1, K < 1, batch < 1, nsig_pitch < S M.
  * GCCNMF_ERR_UNSUPPORTED: S outside 1..8, M batch above 65535, M T within 64 of 2^31. */
 int gccnmf_array_reconstruct(const float* W, const float* H, const unsigned char* argmax, const float* masks, const float* X, int M, int F,

@@ -556,7 +556,7 @@ int gccnmf_magnitude(const float* X, int F, int T, int batch, float* V, void* st
  *   `masks` != NULL, arbitrary float masks [batch][S][Kp][Tp] (the reference signature accepts any array)
  *   spec [batch][S*2][Fp][Tp] complex out (index i*2+c); workspace: gccnmf_reconstruct_workspace_floats
  * Ratio-mask (Wiener-like) mode: pass S | GCCNMF_RECONSTRUCT_RATIO (the mode rides above the low byte of S, which the score stage
- * limits to 255 anyway; any other bit above the low byte: GCCNMF_ERR_ARG).  One fused launch (csrc/ratio.hip), 1 <= S <= 8, else
+ * limits to 255 anyway; any other bit above the low byte: GCCNMF_ERR_ARG).  One fused launch (csrc/ratio.hip, the kernel of csrc/ratio_kernel.h), 1 <= S <= 8, else
  * GCCNMF_ERR_UNSUPPORTED; with H_c = H[:, c*T:(c+1)*T]:
  *   num_i[f,t]  = sum_k W[f,k] H_c[k,t] M_i[k,t]                   (f32 fma chain in k order)
  *   den[f,t]    = num_0 + num_1 + ... + num_{S-1}                  one-hot form (`masks` == NULL, M_i = [argmax == i])

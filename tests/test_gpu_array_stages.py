@@ -4,12 +4,14 @@ gccnmf_array_features: block p of CC is, bit for bit, gccnmf_coherence of the st
 bit for bit, gccnmf_magnitude of each channel; every padding element is written as zero; a file alone gives the bits it gives in a batch.
 
 gccnmf_array_reconstruct: plane (i, c) is, bit for bit, plane (i, 0) of gccnmf_reconstruct in ratio mode on the stereo problem whose
-channel 0 is channel c; and it is within gcc_checks.check_gemm_like(Kd = K) of the float64 restatement tests/array_restatement.py, relative
+channel 0 is channel c.  Both libraries instantiate the one kernel of csrc/ratio_kernel.h, so this checks its M / nsig_pitch / c T
+addressing -- the (file, channel) of a workgroup, the columns of H_c, the slot i M + c of a plane -- at M channels against M = 2, not that
+two kernels agree.  And it is within gcc_checks.check_gemm_like(Kd = K) of the float64 restatement tests/array_restatement.py, relative
 to |X|: num_i and den are chains of at most K fma of non-negative terms (relative error <= K u each, no cancellation; the soft form's
 mask products add one rounding per term, the one-hot form's S - 1 additions of den replace as many fma that a masked-out term makes
 exact), num_i <= den, one quotient and one product: at most (2 K + 4) u |X| <= 2 (K + 4) u |X|, the bound of check_gemm_like with
 absprod = |X|.  A NaN planted in W must come out as NaN exactly where the restatement has NaN.  The stereo planes of the bit comparison
-meet the same bound themselves, so that the stereo kernel's instantiations for 4 to 7 targets are checked against a reference too.
+meet the same bound themselves, so that the separation library's instantiations for 4 to 7 targets are checked against a reference too.
 
 Every channel count 2 ... 8 (pair indexes up to 27) and every target count 1 ... 8 runs, the latter in both forms; CASES says which row tile
 shapes of the reconstruction (128 rows a tile, the last row of F = 32 n + 1 on the VALU) each F stands for."""
@@ -220,8 +222,8 @@ def test_reconstruct_is_the_stereo_kernel_per_channel_and_within_the_float64_bou
         assert nan.any() == (b == B - 1)
         if b == B - 1:
             assert nan[:, :, F // 2, :].all() and not np.delete(nan, F // 2, axis=2).any()
-        # (the stereo planes are checked on their own, not through the bit comparison above: they are gcc_ratio_kernel's only float64 check
-        # at 4 to 7 targets)
+        # (the stereo planes are checked on their own, not through the bit comparison above: they are the only float64 check of the
+        # separation library's ratio_kernel instantiations at 4 to 7 targets)
         for name, g in (('array', got[b]), ('stereo', got_stereo[b])):
             assert np.array_equal(np.isnan(g), nan), '%s kernel, file %d: NaN exactly where the restatement has NaN' % (name, b)
             C.report_gemm_like(np.where(nan, 0, g), np.where(nan, 0, ref), np.broadcast_to(np.abs(X[b])[None], ref.shape), K,
