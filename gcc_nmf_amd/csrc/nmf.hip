@@ -659,8 +659,8 @@ static UpdateWArgs update_w_args(const NmfGeom& g, float* W, long sW, const floa
 // c41 [batch] (K4 -> the next iteration's K1, items).  Zeroed once per gccnmf_klnmf call; iteration `it` waits for (it + 1) x the per-iteration count,
 // so nothing is reset between launches.  (The short-dictionary chain keeps its [3][batch] counters at the same place.)
 // The ready counters are rounded up to a 128-byte line (32 words), the GCCNMF_STATUS_WORDS status words follow: error [1], 15 unused, XCCs
-// seen per list [8] (from GCCNMF_STATUS_XCC_SEEN on), 8 unused.  Every block in front of the counters is a multiple of 64 floats, so the workspace is
-// one too (a ragged batch's, with its tables: of 4) -- workspaces carved back to back out of ONE allocation (the engine's file groups) all start
+// seen per list [8] (from GCCNMF_STATUS_XCC_SEEN on), 8 unused.  Every block in front of the counters is a multiple of 64 floats, the counter and status
+// block one of 32, so the workspace is a multiple of 32 (a ragged batch's, with its tables: of 4) -- workspaces carved back to back out of ONE allocation (the engine's file groups) all start
 // 16-byte aligned when the first does, which the float4 / LDS-DMA accesses to R, U, Wt, Ht, Rt rely on (the entry points reject a workspace that is
 // not 16-byte aligned).  Everything that locates a block -- the size functions included: `floats` of a carve of no memory -- takes it from here.
 #define GCCNMF_STATUS_WORDS 32

@@ -146,7 +146,13 @@ THROUGHPUT_SHAPES = [(513, 96, 65), (513, 97, 65), (641, 96, 70), (200, 130, 130
 SHORT_SHAPES = [(129, 65, 20), (513, 1, 128), (513, 130, 128), (257, 64, 33), (129, 65, 33)]
 UPDATE_W_SHAPES = [(513, 16, 50), (40, 16, 50)]
 DMA_UPDW_SHAPE = (513, 96, 128)          # Fm a multiple of 128 and K of 64: the one shape class whose fused W update runs in the LDS-DMA kernel
-ALL_SHAPES = DIRECT_SHAPES + THROUGHPUT_SHAPES + SHORT_SHAPES + UPDATE_W_SHAPES + [DMA_UPDW_SHAPE]
+# the smallest shapes chain_capable (csrc/nmf.hip) admits -- F in {257, 385, 513}, K a multiple of 128 from 256 on -- on the PLAIN launches the chained
+# ones are pinned to bit for bit (tests/test_gpu_chained_small_shapes.py):
+#   (257, 70, 256)  K2's outputs are 256 rows: half-height tiles; Fm = 256: two row blocks of the fused W update, four atom tiles
+#   (385, 96, 384)  K2 of 384 rows: one full-height row tile with an idle wave; Fm = 384; the last column tile has exactly 32 columns (the narrow item)
+#   (513, 33, 640)  two row tiles of K2, the second a quarter full; ten atom tiles of the W update; ONE column tile; K1 / K3 reduce over 640
+CHAIN_SHAPES = [(257, 70, 256), (385, 96, 384), (513, 33, 640)]
+ALL_SHAPES = DIRECT_SHAPES + THROUGHPUT_SHAPES + SHORT_SHAPES + UPDATE_W_SHAPES + [DMA_UPDW_SHAPE] + CHAIN_SHAPES
 NO_XCD_AFFINITY, UNFUSED_W_UPDATE = 1, 2                    # GCCNMF_FLAG_* of include/gccnmf_hip.h
 
 

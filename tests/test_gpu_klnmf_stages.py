@@ -1,6 +1,7 @@
 """Every stage of the KL-NMF iteration (gccnmf_klnmf_stage, stages 0-6) in the launch forms the stage entry point dispatches to -- the direct
 kernels, the small-batch and the throughput tile (LDS-DMA and register-staged; full, narrow and half-height items), K1 + K2 and K3 + K4a
-fused, the W update in the R.H^T epilogue of either GEMM kernel, the three W-update kernels -- each element of each output against the
+fused, the W update in the R.H^T epilogue of either GEMM kernel, the three W-update kernels, the plain launches at the smallest shapes the chained
+launches exist for -- each element of each output against the
 float64 restatement of that stage (tests/klnmf_stages_restatement.py, which derives the bars) evaluated on the state the device held
 BEFORE the stage -- rounding never compounds from stage to stage, and one wrong bin, frame or atom cannot hide in a norm.
 
@@ -372,6 +373,24 @@ def test_w_update_in_the_lds_dma_epilogue(dma, B):
     F, N, K = S.DMA_UPDW_SHAPE
     run = _run(F, N, K, B, 0, keys={2: 1, 3: dma}, want=dict(direct=False, f12=False, f34=False, fw=True, dma_updw=dma == 1))
     assert 'stage 4 W (K4a + K4b)' in run.shares and 'stage 5 W' not in run.shares
+
+
+# ---- the smallest chain-capable shapes (S.CHAIN_SHAPES: F in {257, 385, 513}, K a multiple of 128 from 256 on) on the plain launches -------------------
+# What the chained and ragged launches are pinned to bit for bit at these shapes (tests/test_gpu_chained_small_shapes.py), here element by element:
+#   (257, 70, 256)  K2 on half-height tiles (256 rows); the fused W update at Fm = 256 with four atom tiles
+#   (385, 96, 384)  K2's 384 rows: one row tile; Fm = 384; the last column tile of exactly 32 columns; six atom tiles
+#   (513, 33, 640)  K2's 640 rows: two row tiles; ONE column tile; K1 / K3 with a reduction of 640; ten atom tiles
+# Key 9 decides the item form of K1 / K2 / K3 in the LDS-DMA launcher: 1 (default) prices a launch this small onto half-height tiles; 0 is full-height
+# wide tiles only -- K2 at K > 256 as a chained launch runs it --; 2 every tile as two narrow halves of a full-height tile.  The first two (dma, split)
+# pairs are the default form in both staging kernels, the last two the full-height forms.  The W update rides the LDS-DMA epilogue with key 3 = 1
+# (Fm a multiple of 128, K of 64), the register-staged kernel's with key 3 = 0.
+@pytest.mark.parametrize('B', [2, 9])
+@pytest.mark.parametrize('dma,split', [(1, 1), (0, 1), (1, 0), (1, 2)])
+@pytest.mark.parametrize('F,N,K', S.CHAIN_SHAPES)
+def test_chain_capable_shapes_on_the_plain_launches(F, N, K, dma, split, B):
+    keys = {2: 1, 3: dma} if split == 1 else {2: 1, 3: dma, 9: split}
+    run = _run(F, N, K, B, 0, keys=keys, want=dict(direct=False, f12=False, f34=False, fw=True, dma_updw=dma == 1))
+    assert {'stage 1 R', 'stage 2 H', 'stage 3 R', 'stage 4 W (K4a + K4b)'} <= set(run.shares) and 'stage 5 W' not in run.shares
 
 
 # ---- short dictionaries: K1 + K2 and K3 + K4a as one launch each (tuning keys 16 / 17 = 2; key 10 = 0 keeps two files off the direct kernels) -------
