@@ -175,7 +175,7 @@ def check_tdoa_tracking(tdoaTracking, localizationWindowSize, numSources):
 def load_library(path, signatures, optional=(), lenient=False):
     """``ctypes.CDLL(path)`` with typed prototypes: ``signatures`` and ``optional`` map name -> (restype, argtypes).  HipLibraryError if the
     file is missing, does not load or lacks a name of ``signatures`` (``lenient``: such a name is skipped and stays uncallable); names of
-    ``optional`` are typed where the library has them.  The one loader of the four binding modules."""
+    ``optional`` are typed where the library has them.  The one loader of the five binding modules."""
     if not os.path.exists(path):
         raise HipLibraryError(
             '%s is missing: build it with `python -c "import __graft_entry__ as g; g.build()"` or '

@@ -12,7 +12,7 @@ Python here is plumbing only, as in ``engine``: every stage is one call into a l
 import numpy as np
 import torch
 
-from . import _array, _array_spatial, _hip
+from . import _array, _array_em, _array_spatial, _hip
 from .engine import (SPEED_OF_SOUND_IN_METRES_PER_SECOND, _on_device, num_frames, klnmf_initial_factors, fft_twiddles, steering_tables,
                      padded)
 
@@ -105,18 +105,23 @@ class GCCNMFArrayEngine(object):
     ``reconstruction='ratio'`` (the default) is the ratio mask: the targets of a channel add up to that channel's mixture, and a mask
     weights each channel by a real number.  ``reconstruction='spatial'`` runs the M x M spatial (multichannel Wiener) filter behind it
     (libgccnmf_array_spatial.so, include/gccnmf_array_spatial.h): a spatial covariance per target and bin from the ratio estimates, then
-    S'_i = v_i R_i (sum_j v_j R_j)^-1 X, which combines the channels; ``get_cov()`` returns the covariances.  With M = 2 and
-    ``pairTDOAs = tdoasInSeconds[None]`` every buffer holds the bits of ``GCCNMFEngine(reconstruction=..., nmf_groups=1)`` in the same mode.
+    S'_i = v_i R_i (sum_j v_j R_j)^-1 X, which combines the channels; ``get_cov()`` returns the covariances.
+    ``spatialIterations=n`` (0 to 255, default 0; 'spatial' only) runs n iterations of the local Gaussian model EM between the two
+    (libgccnmf_array_em.so, include/gccnmf_array_em.h): a full-rank M x M covariance per target and bin and the powers are re-estimated
+    against each other, and the filter runs on the refined ones; ``get_cov()`` then returns the refined covariances.  With M = 2 and
+    ``pairTDOAs = tdoasInSeconds[None]`` every buffer holds the bits of ``GCCNMFEngine(reconstruction=..., spatialIterations=..., nmf_groups=1)``
+    in the same mode.
 
     ``separate(x)``: (batch, M, n_samples) float32 -> (batch, S, M, hop * (T - 1)) float32."""
 
     def __init__(self, n_samples, numChannels=2, pairTDOAs=None, microphonePositions=None, directions=None,
                  speedOfSound=SPEED_OF_SOUND_IN_METRES_PER_SECOND, sampleRate=16000, windowSize=1024, hopSize=256, numTargets=3,
                  dictionarySize=128, numIterations=100, sparsityAlpha=0, epsilon=1e-16, seedValue=0, batch=1, windowFunction=np.hanning,
-                 device='cuda:0', klnmf_flags=0, reconstruction='ratio'):
+                 device='cuda:0', klnmf_flags=0, reconstruction='ratio', spatialIterations=0):
         if reconstruction not in RECONSTRUCTIONS:
             raise ValueError("reconstruction must be 'ratio' or 'spatial', got %r" % (reconstruction,))
         self.reconstruction = reconstruction
+        self.spatialIterations = _hip.check_spatial_iterations(spatialIterations, reconstruction)
         self.M, self.pairTDOAs, S = check_array_arguments(numChannels, pairTDOAs, microphonePositions, directions, speedOfSound,
                                                           numTargets, windowSize)
         self.P = _array.num_pairs(self.M)
@@ -134,6 +139,8 @@ class GCCNMFArrayEngine(object):
         _array.lib()
         if reconstruction == 'spatial':
             _array_spatial.lib()
+        if self.spatialIterations:
+            _array_em.lib()
         self.device = torch.device(device)
         self.iters, self.alpha, self.eps, self.seed = int(numIterations), float(sparsityAlpha), float(epsilon), seedValue
         self.batch = B = int(batch)
@@ -184,7 +191,14 @@ class GCCNMFArrayEngine(object):
             self.argmax = torch.zeros((B, Kp, Tp), dtype=torch.uint8, device=dev)
             self.spec = z(B, self.nsig_pitch, Fp, Tp, 2)              # (the spare slot stays zero: the reconstruction does not touch it)
             # spatial mode: R~ of every (file, target, bin), M M floats a row (include/gccnmf_array_spatial.h)
-            self.cov = z(_array_spatial.workspace_floats(M, F, S, B)).view(B, S, Fp, M * M) if reconstruction == 'spatial' else None
+            # with the EM refinement the same rows open its workspace, and the powers v [batch][S][Fp][Tp] follow them (include/gccnmf_array_em.h)
+            self.cov = self.ws_em = self.powers = None
+            if self.spatialIterations:
+                self.ws_em = z(_array_em.workspace_floats(M, F, T, S, B))
+                self.cov = self.ws_em[:B * S * Fp * M * M].view(B, S, Fp, M * M)
+                self.powers = self.ws_em[B * S * Fp * M * M:].view(B, S, Fp, Tp)
+            elif reconstruction == 'spatial':
+                self.cov = z(_array_spatial.workspace_floats(M, F, S, B)).view(B, S, Fp, M * M)
             self.frames = None
             # the stereo engine's rule: the fused inverse transform + overlap-add where the library has one and the launch is large enough
             self.fused_istft = (self.n_fft + 3 * self.hop <= 2048 and self.hop <= self.n_fft
@@ -236,7 +250,9 @@ class GCCNMFArrayEngine(object):
     def reconstruct(self):
         _array.reconstruct(self.W, self.H, self.argmax, None, self.X, self.M, self.F, self.T, self.K, self.S, self.batch, self.nsig_pitch,
                            self.spec)
-        if self.reconstruction == 'spatial':
+        if self.spatialIterations:
+            _array_em.em(self.X, self.M, self.F, self.T, self.S, self.batch, self.nsig_pitch, self.spatialIterations, self.ws_em, self.spec)
+        elif self.reconstruction == 'spatial':
             _array_spatial.spatial(self.X, self.M, self.F, self.T, self.S, self.batch, self.nsig_pitch, self.cov, self.spec)
 
     @_on_device
@@ -316,7 +332,7 @@ class GCCNMFArrayEngine(object):
 
     def get_cov(self):
         """(batch, S, F, M, M) complex64: the loaded spatial covariance R~ of every target and bin, the full Hermitian matrix
-        (spatial mode only)."""
+        (spatial mode only; after ``spatialIterations`` EM iterations, the refined one)."""
         if self.cov is None:
             raise ValueError("get_cov() needs reconstruction='spatial'")
         M = self.M

@@ -267,15 +267,31 @@ struct ArraySpatialVec<2> {
 };
 __device__ __forceinline__ float2 array_spatial_get(const float2 v, int) { return v; }
 __device__ __forceinline__ float2 array_spatial_get(const float4 v, int fr) { return fr ? make_float2(v.z, v.w) : make_float2(v.x, v.y); }
+// v = (sum_c |E_c|^2) / M of frame fr of the loaded estimates: the channels ascending, then the IEEE quotient
+template <int M, int FR>
+__device__ __forceinline__ float array_spatial_power(const typename ArraySpatialVec<FR>::type (&e)[M], int fr) {
+#pragma clang fp contract(off)
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < M; ++c) {
+        const float2 a = array_spatial_get(e[c], fr);
+        const float term = a.x * a.x + a.y * a.y;
+        s = c == 0 ? term : s + term;
+    }
+    return s / (float)M;
+}
 __device__ __forceinline__ void array_spatial_put(float2* p, const float2 (&o)[1]) { *p = o[0]; }
 __device__ __forceinline__ void array_spatial_put(float2* p, const float2 (&o)[2]) {
     *(float4*)p = make_float4(o[0].x, o[0].y, o[1].x, o[1].y);
 }
 
 // grid = (Fp / 4, batch), 4 waves a workgroup: wave w of workgroup x owns row 4 x + w (< Fp: Fp is a multiple of 16)
-template <int M, int S>
-__global__ __launch_bounds__(256) void array_spatial_filter_kernel(const float2* __restrict__ X, const float* __restrict__ cov, int nsig_pitch,
-                                                                   int F, int Fp, int T, int Tp, float2* spec) {
+// WS: the powers come from the workspace of the EM refinement (array_spatial_em.hip; [batch][S][Fp][Tp], frames < T) instead of the
+// estimates in spec, which is then only written.
+template <int M, int S, bool WS>
+__global__ __launch_bounds__(256) void array_spatial_filter_kernel(const float2* __restrict__ X, const float* __restrict__ cov,
+                                                                   const float* __restrict__ powers, int nsig_pitch, int F, int Fp, int T,
+                                                                   int Tp, float2* spec) {
 #pragma clang fp contract(off)
     constexpr int MM = M * M, FR = M <= 4 ? 2 : 1;
     typedef typename ArraySpatialVec<FR>::type vec;
@@ -306,25 +322,27 @@ __global__ __launch_bounds__(256) void array_spatial_filter_kernel(const float2*
     const float* __restrict__ r = sR[wave];
     for (int t = FR * lane; t < Tp; t += 64 * FR) {            // frames t ... t + FR - 1 < Tp
         float v[FR][S], xr[FR][M], xi[FR][M];
+        if constexpr (WS) {
+            const float* __restrict__ P = powers + (long)b * S * plane + (long)f * Tp + t;
 #pragma unroll
-        for (int i = 0; i < S; ++i) {
-            vec e[M];
+            for (int i = 0; i < S; ++i) {
 #pragma unroll
-            for (int c = 0; c < M; ++c) e[c] = *(const vec*)(O + (i * M + c) * plane + t);
+                for (int fr = 0; fr < FR; ++fr) v[fr][i] = t + fr < T ? P[i * plane + fr] : 0.f;
+            }
+        } else {
 #pragma unroll
-            for (int fr = 0; fr < FR; ++fr) {
-                if constexpr (M == 2) {
-                    const float2 a = array_spatial_get(e[0], fr), c = array_spatial_get(e[1], fr);
-                    v[fr][i] = spatial_power(a.x, a.y, c.x, c.y);
-                } else {
-                    float s = 0.f;
+            for (int i = 0; i < S; ++i) {
+                vec e[M];
 #pragma unroll
-                    for (int c = 0; c < M; ++c) {
-                        const float2 a = array_spatial_get(e[c], fr);
-                        const float term = a.x * a.x + a.y * a.y;
-                        s = c == 0 ? term : s + term;
+                for (int c = 0; c < M; ++c) e[c] = *(const vec*)(O + (i * M + c) * plane + t);
+#pragma unroll
+                for (int fr = 0; fr < FR; ++fr) {
+                    if constexpr (M == 2) {
+                        const float2 a = array_spatial_get(e[0], fr), c = array_spatial_get(e[1], fr);
+                        v[fr][i] = spatial_power(a.x, a.y, c.x, c.y);
+                    } else {
+                        v[fr][i] = array_spatial_power<M, FR>(e, fr);
                     }
-                    v[fr][i] = s / (float)M;
                 }
             }
         }
@@ -380,28 +398,42 @@ __global__ __launch_bounds__(256) void array_spatial_filter_kernel(const float2*
     }
 }
 
-template <int M, int S>
-static void array_spatial_filter_launch(const float* X, const float* cov, int nsig_pitch, int F, int Fp, int T, int Tp, int batch, float* spec,
-                                        hipStream_t s) {
-    hipLaunchKernelGGL((array_spatial_filter_kernel<M, S>), dim3(Fp / 4, batch), dim3(256), 0, s, (const float2*)X, cov, nsig_pitch, F, Fp, T,
-                       Tp, (float2*)spec);
+// WS is the caller's: a library holds only the form it launches (powers is null, and not read, at WS = false)
+template <int M, int S, bool WS>
+static void array_spatial_filter_launch(const float* X, const float* cov, const float* powers, int nsig_pitch, int F, int Fp, int T, int Tp,
+                                        int batch, float* spec, hipStream_t s) {
+    hipLaunchKernelGGL((array_spatial_filter_kernel<M, S, WS>), dim3(Fp / 4, batch), dim3(256), 0, s, (const float2*)X, cov, powers, nsig_pitch,
+                       F, Fp, T, Tp, (float2*)spec);
+}
+
+// The two launches on their own, for the EM refinement between them (array_spatial_em.hip)
+template <int M>
+static void array_spatial_cov_launch(int nsig_pitch, int F, int Fp, int T, int Tp, int S, int batch, const float* spec, float* cov,
+                                     hipStream_t s) {
+    hipLaunchKernelGGL(array_spatial_cov_kernel<M>, dim3(gccnmf_ceil_div(F * (M >= 6 ? 2 : 1), 4), S, batch), dim3(256), 0, s, (const float2*)spec, nsig_pitch, F,
+                       Fp, T, Tp, S, cov);
+}
+
+template <int M, bool WS>
+static void array_spatial_filter_dispatch(const float* X, const float* cov, const float* powers, int nsig_pitch, int F, int Fp, int T, int Tp,
+                                          int S, int batch, float* spec, hipStream_t s) {
+    switch (S) {
+        case 1: array_spatial_filter_launch<M, 1, WS>(X, cov, powers, nsig_pitch, F, Fp, T, Tp, batch, spec, s); break;
+        case 2: array_spatial_filter_launch<M, 2, WS>(X, cov, powers, nsig_pitch, F, Fp, T, Tp, batch, spec, s); break;
+        case 3: array_spatial_filter_launch<M, 3, WS>(X, cov, powers, nsig_pitch, F, Fp, T, Tp, batch, spec, s); break;
+        case 4: array_spatial_filter_launch<M, 4, WS>(X, cov, powers, nsig_pitch, F, Fp, T, Tp, batch, spec, s); break;
+        case 5: array_spatial_filter_launch<M, 5, WS>(X, cov, powers, nsig_pitch, F, Fp, T, Tp, batch, spec, s); break;
+        case 6: array_spatial_filter_launch<M, 6, WS>(X, cov, powers, nsig_pitch, F, Fp, T, Tp, batch, spec, s); break;
+        case 7: array_spatial_filter_launch<M, 7, WS>(X, cov, powers, nsig_pitch, F, Fp, T, Tp, batch, spec, s); break;
+        default: array_spatial_filter_launch<M, 8, WS>(X, cov, powers, nsig_pitch, F, Fp, T, Tp, batch, spec, s); break;
+    }
 }
 
 template <int M>
 static void array_spatial_launch(const float* X, int nsig_pitch, int F, int Fp, int T, int Tp, int S, int batch, float* cov, float* spec,
                                  hipStream_t s) {
-    hipLaunchKernelGGL(array_spatial_cov_kernel<M>, dim3(gccnmf_ceil_div(F * (M >= 6 ? 2 : 1), 4), S, batch), dim3(256), 0, s, (const float2*)spec, nsig_pitch, F,
-                       Fp, T, Tp, S, cov);
-    switch (S) {
-        case 1: array_spatial_filter_launch<M, 1>(X, cov, nsig_pitch, F, Fp, T, Tp, batch, spec, s); break;
-        case 2: array_spatial_filter_launch<M, 2>(X, cov, nsig_pitch, F, Fp, T, Tp, batch, spec, s); break;
-        case 3: array_spatial_filter_launch<M, 3>(X, cov, nsig_pitch, F, Fp, T, Tp, batch, spec, s); break;
-        case 4: array_spatial_filter_launch<M, 4>(X, cov, nsig_pitch, F, Fp, T, Tp, batch, spec, s); break;
-        case 5: array_spatial_filter_launch<M, 5>(X, cov, nsig_pitch, F, Fp, T, Tp, batch, spec, s); break;
-        case 6: array_spatial_filter_launch<M, 6>(X, cov, nsig_pitch, F, Fp, T, Tp, batch, spec, s); break;
-        case 7: array_spatial_filter_launch<M, 7>(X, cov, nsig_pitch, F, Fp, T, Tp, batch, spec, s); break;
-        default: array_spatial_filter_launch<M, 8>(X, cov, nsig_pitch, F, Fp, T, Tp, batch, spec, s); break;
-    }
+    array_spatial_cov_launch<M>(nsig_pitch, F, Fp, T, Tp, S, batch, spec, cov, s);
+    array_spatial_filter_dispatch<M, false>(X, cov, nullptr, nsig_pitch, F, Fp, T, Tp, S, batch, spec, s);
 }
 
 static bool array_spatial_shape_ok(int M, int F, int S, int batch) {
@@ -409,6 +441,7 @@ static bool array_spatial_shape_ok(int M, int F, int S, int batch) {
            F >= 2 && batch >= 1 && (long)M * batch <= 65535;
 }
 
+#ifndef ARRAY_SPATIAL_KERNELS_ONLY                             // (array_spatial_em.hip includes this file for its kernels and launches)
 extern "C" {
 
 int gccnmf_array_spatial_version(void) { return ARRAY_SPATIAL_VERSION; }
@@ -442,3 +475,4 @@ int gccnmf_array_spatial(const float* X, int M, int F, int T, int S, int batch, 
 }
 
 }  // extern "C"
+#endif

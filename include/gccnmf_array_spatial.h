@@ -2,7 +2,7 @@
  * (gfx950): the second stage of mask-based separation under the local Gaussian model, run behind gccnmf_array_reconstruct
  * (include/gccnmf_array.h) on its ratio-mode estimates, in place.  The M-channel form of the spatial mode of gccnmf_reconstruct
  * (include/gccnmf_hip.h); gcc_nmf_amd/csrc/array_spatial.hip, gcc_nmf_amd/array.py (GCCNMFArrayEngine(reconstruction='spatial')).
- * DESIGN section 4j.  The EM refinement of the stereo path (spatialIterations) has no M-channel form yet.
+ * DESIGN section 4j.  The EM refinement (spatialIterations) runs between the two launches: include/gccnmf_array_em.h.
  *
  * A library of its own beside libgccnmf_hip.so and libgccnmf_array.so, with their conventions -- every pointer is a DEVICE pointer
  * aligned to 16 bytes, every call is asynchronous on `stream` (a hipStream_t passed as void*), every function returns a status code
